@@ -16,10 +16,20 @@ LOCAL_RANK / WORLD_SIZE / MASTER_* set, relays rank 0's JSON line and exits non-
 Training configs: one step = forward + CE/aux-CE loss + backward + (RCCL gradient all-reduce when N > 1) + global-norm clip +
 SGD-momentum + weight re-pack on a synthetic batch that is already resident in HBM.  cfg5: one step = one 1024x1024 image =
 16 windows of 256x256 evaluated as ONE batch through the fp16 model + the window glue kernels, replayed from a hipGraph.
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...); everything else it can measure takes runs of its own and comes with --full:
   roofline       -- the dominant kernel family of the step (MFMA implicit-GEMM convolutions), algorithmic FLOPs / HIP-event time
   roofline_msda  -- the deformable-attention gather kernel (encoder call of THIS config) against the HBM roofline
   cpu_baseline   -- the oracle (torch-CPU fp32 restatement of the reference) timed on the host cores, rank 0, N = 1 only
+  other_configs  -- the default command only: cfg3, cfg5 and cfg2 in fp32 as short runs in child processes
+Without --full these keys are null (other_configs absent).  --dump-calls also runs the per-kernel timing step (it is what the file holds).
+--dump-outputs DIR writes what the timed path computes (rank 0), as float32 .npy files.  cfg5: the predicted mask of the image from the last
+timed step (pred.npy; the weights do not change from step to step).  Train configs: a training step advances the weights, and its reductions
+(fp32 atomics) leave the last bits free, which K steps of training amplify far beyond rounding.  So after the timed steps the training state
+(weights, momentum, BatchNorm statistics, step counter, dropout seed) is put back to the seeded state it had before the first step, and the
+timed path -- the captured step -- runs once more on the same batch: loss.npy, and a fixed seeded sample of the flat fp32 master weights after
+that step, of what the step changed in them and of the BatchNorm running statistics (weights.npy, weight_update.npy, bn_buffers.npy).  Inputs
+and initial weights are seeded: the same arguments give the same inputs, and outputs equal to rounding, in every run.
 """
 import argparse
 import json
@@ -405,7 +415,7 @@ def _ride_along(args, key, steps, warm, extra=()):
     the child could not be run -- the caller then measures in-process.  The launcher's rank environment is not passed on (the child is a plain one-process run)."""
     import subprocess
     # (CPU baseline of a ride-along: 3 timed steps, median -- BASELINE.md 3's protocol; round 5 took one)
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", key, "--steps", str(steps), "--warmup", str(warm), "--no-other-configs", "--cpu-steps", "3"] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", key, "--steps", str(steps), "--warmup", str(warm), "--full", "--no-other-configs", "--cpu-steps", "3"] + list(extra)
     if args.no_cpu_baseline and "--no-cpu-baseline" not in cmd:
         cmd.append("--no-cpu-baseline")
     if args.cpu_threads:
@@ -576,6 +586,11 @@ def main():
     ap.add_argument("--inprocess-others", action="store_true", help="A/B: measure the ride-along configs in this process instead of in child processes")
     ap.add_argument("--cpu-steps", type=int, default=0, help="timed steps of the CPU baseline (0 = the config's default)")
     ap.add_argument("--keep-gc", action="store_true", help="A/B: leave Python's garbage collector enabled during the timed steps (default: collected before, paused during)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline number does not need: the per-kernel timing step and its "
+                    "rooflines, the CPU baseline and (default command) the ride-along configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write outputs of the timed path to DIR/<name>.npy (float32, at most 64 MB). cfg5: the last timed "
+                    "step's mask. Train configs: ONE captured step replayed after the timed steps from the seeded initial state, not step W + K "
+                    "(fp32 atomics make K steps of training irreproducible)")
     ap.add_argument("--dry-run", action="store_true", help="--gpus N without a GPU: start the N ranks, rendezvous over gloo, and check rank environment, "
                     "gradient-exchange ranges, SyncBatchNorm group membership and tile sharding; prints a JSON plan, launches no kernel")
     args = ap.parse_args()
@@ -601,12 +616,13 @@ def main():
         cfg["size"] = args.size
     dtype_name = args.dtype or cfg["dtype"]
     run = run_infer if cfg["mode"] == "infer" else run_train
-    result = run(args, args.config, cfg, dtype_name, env, args.steps, args.warmup, cpu=not args.no_cpu_baseline, dump=args.dump_calls, cpu_steps=args.cpu_steps or None)
-    # The driver only ever runs the default command: the other two single-GPU configurations of BASELINE.json ride along as short runs
+    result = run(args, args.config, cfg, dtype_name, env, args.steps, args.warmup, cpu=args.full and not args.no_cpu_baseline, dump=args.dump_calls,
+                 cpu_steps=args.cpu_steps or None, outputs=args.dump_outputs)
+    # --full on the default command: the other two single-GPU configurations of BASELINE.json ride along as short runs
     # (metric / config / value above stay configs[1]'s).  Not at N > 1, not for experiments that changed the workload.
     default_workload = (args.config == "cfg2" and not args.batch and not args.size and not args.dtype and not args.no_graph and not args.overlap
                         and not args.two_phase)
-    if world == 1 and default_workload and not args.no_other_configs:
+    if args.full and world == 1 and default_workload and not args.no_other_configs:
         others = {}
         # (30 timed steps after 8 warm-up steps each: round 4's 12-step mean moved 18 % on ONE stalled step in the driver's run)
         for key, steps, warm in (("cfg3", 30, 8), ("cfg5", 30, 8)):
@@ -642,7 +658,70 @@ def main():
         print(json.dumps(result), flush=True)
 
 
-def run_train(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump=None, cpu_steps=None):
+def profiled_train_step(model, opt, loss_fn, images, labels, world, dtype_name, cfg_key, B, S, dump):
+    """--full (or --dump-calls): live per-kernel timing -- one extra eager step with a HIP event pair around every C-ABI launch -> (roofline, roofline_msda)."""
+    from emrt_amd.engine import TrainEngine
+    eng_prof = TrainEngine(model, opt, loss_fn, 1, use_graph=False, overlap=False)   # serialised: per-kernel durations
+    eng_prof.reducer = None
+    # (the profiled step is serialised on ONE stream: the recorded launches are replayed without the fork / join events of the step prologue's
+    # side stream, so that prologue runs on the main stream here)
+    from emrt_amd.runtime import ctx as _ctx
+    _side_was, _ctx().prologue_side = _ctx().prologue_side, False
+    try:
+        calls = timed_replay(lambda: eng_prof._eager_step(images, labels) if world == 1 else eng_prof._fwd_bwd(images, labels))
+    finally:
+        _ctx().prologue_side = _side_was
+    if dump:
+        dump_calls(dump, calls, 4 if dtype_name == "fp32" else 2)
+    roofline, roofline_msda, lines = rooflines(calls, dtype_name, cfg_key if (B, S) == (CONFIGS[cfg_key]["batch"], CONFIGS[cfg_key]["size"]) else "custom", True)
+    for ln in lines:
+        log(ln)
+    return roofline, roofline_msda
+
+
+def _training_state(model, opt):
+    """The device tensors a training step reads and advances: fp32 master weights, gradient, momentum, BatchNorm running statistics, the
+    clip / learning-rate scalars, the device step counter (learning rate, dropout streams) and the dropout seed."""
+    from emrt_amd.runtime import ctx
+    st, c = model.store, ctx()
+    return [st.master, st.grad, st.velocity, st.buffers, opt.clip_state, opt.lr_dev, c.step_counter, c._seed]
+
+
+def snapshot_training_state(model, opt):
+    torch.cuda.synchronize()
+    return {"tensors": [t.clone() for t in _training_state(model, opt)], "lr_epoch": opt._learning_rate.last_epoch}
+
+
+def restore_training_state(model, opt, snap):
+    """Back to the snapshot, in place (the captured graphs hold these addresses); the compute-dtype mirror is re-packed from the master
+    weights by the next step (ParamStore.dirty)."""
+    torch.cuda.synchronize()
+    for t, t0 in zip(_training_state(model, opt), snap["tensors"]):
+        t.copy_(t0)
+    opt._learning_rate.last_epoch = snap["lr_epoch"]
+    model.store.dirty = True
+    torch.cuda.synchronize()
+
+
+OUTPUT_SAMPLE = 1 << 21     # elements per dumped array at most (8 MB of float32; four arrays stay below the 64 MB cap)
+
+
+def dump_outputs(out_dir, arrays, sample=OUTPUT_SAMPLE):
+    """--dump-outputs: each device tensor as DIR/<name>.npy in float32 -- whole when it has at most `sample` elements, else the elements at a
+    fixed seeded set of `sample` sorted flat indices (a function of the array's length only: two builds sample the same positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > sample:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(20240607))[:sample].sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.float().cpu().numpy())
+    log("[bench] outputs of the last timed step written to %s: %s" % (out_dir, ", ".join(sorted(arrays))))
+
+
+def run_train(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump=None, cpu_steps=None, outputs=None):
     """One training configuration: W warm-up + K timed steps (barrier + synchronize on both sides, max over ranks) -> rank 0's result dict."""
     if dtype_name == "fp16":
         raise SystemExit("fp16 is inference-only (include/emrt_hip.h); training configs run in bf16 or fp32")
@@ -670,6 +749,7 @@ def run_train(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump
         _ctx().sync_always = False
     if args.exchange_noop and eng.reducer is not None:
         eng.reducer.noop = True
+    initial = snapshot_training_state(model, opt) if outputs else None
     g = torch.Generator().manual_seed(1234 + rank)
     images = torch.randn(B, 3, S, S, generator=g).to(dev)
     labels = torch.randint(0, ncls, (B, S, S), generator=g)
@@ -732,6 +812,16 @@ def run_train(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump
                   "steps_taken": eng.calls, "decreasing_checked": decreasing_checked, "ok": bool(loss_ok)}
     if not loss_ok:
         raise SystemExit("[bench] loss check failed (on this or another rank): %r" % (loss_check,))
+    if outputs:      # every rank (the step may hold collectives), before anything below takes another step
+        # NOT step W + K's outputs: the captured step once more, from the seeded state before the first step (module docstring: fp32 atomics
+        # make the state after K steps differ from run to run far beyond rounding; one step from a fixed state agrees to rounding)
+        st = model.store
+        restore_training_state(model, opt, initial)
+        loss_t = eng.step(images, labels)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(outputs, {"loss": loss_t, "weights": st.master[:st.n_train], "weight_update": st.master[:st.n_train] - initial["tensors"][0][:st.n_train],
+                                   "bn_buffers": st.buffers})
     probe = exposed = None
     if world > 1 and eng.reducer is not None and not args.exchange_noop:
         # what the gradient exchange costs the step: the same structure (graphs, SyncBatchNorm cuts, optimizer graph) with the all-reduce
@@ -761,22 +851,9 @@ def run_train(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump
 
     result = None
     if rank == 0:
-        # ---- live per-kernel timing: one extra eager step with a HIP event pair around every C-ABI launch --------------
-        eng_prof = TrainEngine(model, opt, loss_fn, 1, use_graph=False, overlap=False)   # serialised: per-kernel durations
-        eng_prof.reducer = None
-        # (the profiled step is serialised on ONE stream: the recorded launches are replayed without the fork / join events of the step prologue's
-        # side stream, so that prologue runs on the main stream here)
-        from emrt_amd.runtime import ctx as _ctx
-        _side_was, _ctx().prologue_side = _ctx().prologue_side, False
-        try:
-            calls = timed_replay(lambda: eng_prof._eager_step(images, labels) if world == 1 else eng_prof._fwd_bwd(images, labels))
-        finally:
-            _ctx().prologue_side = _side_was
-        if dump:
-            dump_calls(dump, calls, 4 if dtype_name == "fp32" else 2)
-        roofline, roofline_msda, lines = rooflines(calls, dtype_name, cfg_key if (B, S) == (CONFIGS[cfg_key]["batch"], CONFIGS[cfg_key]["size"]) else "custom", True)
-        for ln in lines:
-            log(ln)
+        roofline = roofline_msda = None
+        if args.full or dump:
+            roofline, roofline_msda = profiled_train_step(model, opt, loss_fn, images, labels, world, dtype_name, cfg_key, B, S, dump)
         cpu_baseline = None
         if world == 1 and cpu:
             cpu_baseline = run_cpu_baseline_train(B, S, ncls, args.cpu_threads, timed_steps=cpu_steps or (3 if cfg_key == "cfg2" else 2))
@@ -812,7 +889,7 @@ def _window_grid(n):
     return r, n // r
 
 
-def run_infer(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump=None, cpu_steps=None):
+def run_infer(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump=None, cpu_steps=None, outputs=None):
     """cfg5: sliding-window inference of 1024x1024 images (replicas only: --gpus N runs N independent replicas, no collective)."""
     from emrt_amd.runtime import BF16, F16, F32
     from emrt_amd.src.api.infer import SlidingWindowEngine, slide_inference
@@ -865,12 +942,16 @@ def run_infer(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump
     result = None
     if rank == 0:
         assert tuple(pred.shape) == (1, 1, img_h, img_w) and pred.dtype == torch.int32
-        calls = timed_replay(lambda: slide_inference(model, [img], (crop, crop), (crop, crop), ncls))
-        if dump:
-            dump_calls(dump, calls, 4 if dtype_name == "fp32" else 2)
-        roofline, roofline_msda, lines = rooflines(calls, dtype_name, cfg_key if nwin == CONFIGS[cfg_key]["batch"] else "custom", False)
-        for ln in lines:
-            log(ln)
+        if outputs:
+            dump_outputs(outputs, {"pred": pred})
+        roofline = roofline_msda = None
+        if args.full or dump:
+            calls = timed_replay(lambda: slide_inference(model, [img], (crop, crop), (crop, crop), ncls))
+            if dump:
+                dump_calls(dump, calls, 4 if dtype_name == "fp32" else 2)
+            roofline, roofline_msda, lines = rooflines(calls, dtype_name, cfg_key if nwin == CONFIGS[cfg_key]["batch"] else "custom", False)
+            for ln in lines:
+                log(ln)
         cpu_baseline = None
         if world == 1 and cpu:
             cpu_baseline = run_cpu_baseline_infer(ncls, crop, nwin, args.cpu_threads, timed=cpu_steps or 3)
@@ -892,12 +973,17 @@ def run_infer(args, cfg_key, cfg, dtype_name, env, steps, warmup, cpu=True, dump
     return result
 
 
+def cpu_budget():
+    """Host threads of the CPU baseline: the OMP_NUM_THREADS cap of the run when one is set, else the cores this process may run on (at most 64)."""
+    return min(int(os.environ.get("OMP_NUM_THREADS") or 0) or len(os.sched_getaffinity(0)) or os.cpu_count() or 1, 64)
+
+
 def run_cpu_baseline_train(B, S, ncls, threads, timed_steps=3):
     """The oracle's train step (fwd + loss + bwd + clip + SGD-momentum) on the host cores: 1 warm-up + `timed_steps` timed
     steps, the MEDIAN step time is reported (>= 3 timed steps for the headline config)."""
     from oracle.emrt_torch import EMRT as OracleEMRT
     from oracle import train_ref
-    n = threads or min(os.cpu_count() or 1, 64)
+    n = threads or cpu_budget()
     torch.set_num_threads(n)
     torch.manual_seed(1234)
     ref = OracleEMRT(ncls, "resnet50").train()
@@ -922,7 +1008,7 @@ def run_cpu_baseline_infer(ncls, crop, nwin, threads, timed=3):
     sample: at most 32 windows are evaluated (the rate per window does not depend on how many more there are)."""
     nwin = min(nwin, 32)
     from oracle.emrt_torch import EMRT as OracleEMRT
-    n = threads or min(os.cpu_count() or 1, 64)
+    n = threads or cpu_budget()
     torch.set_num_threads(n)
     torch.manual_seed(1234)
     ref = OracleEMRT(ncls, "resnet50").eval()

@@ -1,4 +1,10 @@
 """Helpers for the -m gpu parity tests: host<->device layout conversion and a tiny parameter store for single layers."""
+import contextlib
+import fcntl
+import os
+import tempfile
+
+import pytest
 import torch
 import torch.nn as tnn
 
@@ -102,3 +108,27 @@ def close_gemm(name, got, ref, dtype, out_bits=None):
         idx = torch.nonzero(bad)[0].tolist()
         raise AssertionError("%s: %d/%d elements beyond the contraction-derived bound; max |diff| %.4g at rms(ref) %.4g; first at %s got %.6g ref %.6g" % (
             name, int(bad.sum()), bad.numel(), err.max().item(), rms, idx, got[tuple(idx)].item(), ref[tuple(idx)].item()))
+
+
+# Processes that may hold the GPU at one time while the suite runs: the test workers (each one opens the device) and the rank processes of a
+# multi-rank test together (every rank of these tests runs on GPU 0).  The GPU test hosts stop a run in which more than 6 processes hold a
+# GPU at once, hence the default cap; EMRT_TEST_MAX_GPU_PROCS sets another where the host allows more.  Rank processes of different tests
+# never overlap (a lock file shared by the workers of this user), and a test whose ranks do not fit beside the workers under the cap skips
+# before it starts any of them.
+MAX_GPU_PROCS = int(os.environ.get("EMRT_TEST_MAX_GPU_PROCS", "6"))
+
+
+@contextlib.contextmanager
+def rank_processes(world):
+    """Wraps the start and the whole lifetime of one test's `world` rank processes."""
+    workers = max(1, int(os.environ.get("PYTEST_XDIST_WORKER_COUNT", "1")))
+    if workers + world > MAX_GPU_PROCS:
+        pytest.skip("%d rank processes on GPU 0 beside %d test worker(s) would hold the GPU in %d processes at once, above the cap of %d "
+                    "(EMRT_TEST_MAX_GPU_PROCS)" % (world, workers, workers + world, MAX_GPU_PROCS))
+    path = os.path.join(tempfile.gettempdir(), "emrt_test_rank_processes.%d.lock" % os.getuid())
+    with open(path, "a") as f:
+        fcntl.flock(f, fcntl.LOCK_EX)
+        try:
+            yield
+        finally:
+            fcntl.flock(f, fcntl.LOCK_UN)

@@ -316,8 +316,6 @@ WGRAD_8P = [
 def test_wgrad_8phase_kernel_bf16_vs_torch(case, slab, split):
     from emrt_amd import _lib
     L_ = _lib.lib()
-    if split and case[1] * case[2] * case[3] > 100000:
-        pytest.skip("forced slice counts are exercised on the small cases")
     old = [(k, L_.set_tuning(k, v)) for k, v in (("wgrad8p_force", 1), ("pair_max", 0), ("wgrad8p_slab", slab), ("wgrad_split", split))]
     try:
         _conv_case_vs_torch(case, dilation=case[10] or 1)

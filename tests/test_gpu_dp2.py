@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests.hip_utils import rank_processes
+
 pytestmark = pytest.mark.gpu
 
 
@@ -218,24 +220,26 @@ def _identity_worker(rank, world, port, q):
 
 
 def _run_workers(fn, world=2, timeout=900, extra=()):
-    port = _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=fn, args=(r, world, port, q) + tuple(extra)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(timeout)
-    for p in procs:
-        if p.is_alive():
-            p.kill()          # (exactly the processes started here)
-    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
-    return sorted(q.get(timeout=5) for _ in range(world))
+    with rank_processes(world):
+        port = _free_port()
+        ctx = mp.get_context("spawn")
+        q = ctx.Queue()
+        procs = [ctx.Process(target=fn, args=(r, world, port, q) + tuple(extra)) for r in range(world)]
+        for p in procs:
+            p.start()
+        for p in procs:
+            p.join(timeout)
+        for p in procs:
+            if p.is_alive():
+                p.kill()          # (exactly the processes started here)
+        assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+        return sorted(q.get(timeout=5) for _ in range(world))
 
 
 # BASELINE configs[3] is 8 ranks (one per GPU of the node): the partitioning -- flat-gradient mean, SyncBatchNorm group, three-range early
 # exchange, bit-identical weights on every rank -- is run at its real rank count (and at 4, the driver's other scaling point) with the ranks
 # sharing the one GPU of the box over gloo.  train.py:116-123 (paddle.DataParallel), src/utils/dataloader.py:38-41.
+# (A rank count that does not fit beside the test workers under tests/hip_utils.MAX_GPU_PROCS skips: rank_processes.)
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_n_ranks_equal_one_rank_on_the_concatenated_batch(world):
     got = _run_workers(_identity_worker, world)

@@ -9,6 +9,8 @@ import sys
 
 import pytest
 
+from tests.hip_utils import rank_processes
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,8 +22,9 @@ def _env():
 
 
 def test_bench_gpus_2_starts_two_ranks_itself():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
+    with rank_processes(2):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                           cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -32,8 +35,9 @@ def test_bench_gpus_2_starts_two_ranks_itself():
 
 
 def test_train_gpus_2_starts_two_ranks_itself(tmp_path):
-    r = subprocess.run([sys.executable, "-m", "emrt_amd.train", "--gpus", "2", "--iters", "4", "--no-eval", "--dtype", "fp32",
-                        "--save_dir", str(tmp_path)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
+    with rank_processes(2):
+        r = subprocess.run([sys.executable, "-m", "emrt_amd.train", "--gpus", "2", "--iters", "4", "--no-eval", "--dtype", "fp32",
+                            "--save_dir", str(tmp_path)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "Total params" in r.stdout
     assert os.path.exists(os.path.join(str(tmp_path), "iter_4_model_state.pdparams"))
