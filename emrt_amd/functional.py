@@ -527,6 +527,50 @@ def conv2d(x, w, stride=1, pad=0, relu=False, residual=None, out=None, out_f32=F
     return out
 
 
+def gconv2d(x, w, stride=1, relu=False, out=None, need_dx=True, bn_stats=None, out_scale=None, out_shift=None):
+    """Grouped 3x3 convolution, pad 1 (emrt_gconv2d): x [N,H,W,C] view -> [N,OH,OW,OC], w a GemmWeight with .groups > 1 whose forward operand is
+    [OC][3][3][C / groups].  A PendingBN input is materialised first.  Backward: emrt_gconv2d_bwd (dx handed to the tape, dW += and dbias +=)."""
+    c = ctx()
+    if isinstance(x, PendingBN):
+        x = x.materialize()
+    N, H, W, C, ldin, in_bs = _check_map(x)
+    assert C == w.C * w.groups and w.KH == w.KW == 3, (C, w.C, w.groups, w.KH)
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = c.empty((N, OH, OW, w.OC))
+    _, oh_, ow_, oc_, ldout, out_bs = _check_map(out)
+    assert (oh_, ow_, oc_) == (OH, OW, w.OC), ((oh_, ow_, oc_), (OH, OW, w.OC))
+    assert out_scale is None or c.tape is None, "BatchNorm folding is inference only"
+    _L().call("emrt_gconv2d", P(x), ctypes.c_void_p(w.fwd_ptr), P(out), P(out_shift) if out_scale is not None else P(w.bias), N, H, W, C, ldin, in_bs,
+              OH, OW, w.OC, ldout, out_bs, stride, w.groups, int(relu), P(bn_stats), P(out_scale), c.dtype, c.stream)
+    tape = c.tape
+    if tape is not None:
+        def bwd():
+            dy = tape.pop_grad(out)
+            if dy is None:
+                return
+            if relu:
+                assert dy.is_contiguous() and out.is_contiguous()
+                dm = c.empty(tuple(dy.shape), dy.dtype)
+                _L().call("emrt_mask_bwd", P(dy), P(out), P(dm), dy.numel(), 0.0, None, 0, 0, 1, 1, c.dtype, c.stream)
+                dy = dm
+            _, _, _, _, lddy, dy_bs = _check_map(dy)
+            w.grad_is_zero = False
+            dx = slot = None
+            lddx = dx_bs = 0
+            if need_dx:
+                slot = tape.grad_slot(x)          # accumulate straight into an existing gradient / a slice of the base buffer
+                dx = slot if slot is not None else c.empty(tuple(x.shape))
+                _, _, _, _, lddx, dx_bs = _check_map(dx)
+            _L().call("emrt_gconv2d_bwd", P(x), P(dy), ctypes.c_void_p(w.fwd_ptr), P(dx), lddx, dx_bs, int(slot is not None), P(w.grad),
+                      P(w.bias_grad) if w.bias is not None else None, N, H, W, C, ldin, in_bs, OH, OW, w.OC, lddy, dy_bs, stride, w.groups,
+                      c.dtype, c.stream)
+            if need_dx and slot is None:
+                tape.add_grad(x, dx, owned=True)
+        tape.record(bwd)
+    return out
+
+
 def linear(x, w, relu=False, out_f32=False, need_dx=True, drop=None):
     """x [B, L, C] or [M, C] (strided rows allowed) -> [..., OC]: a 1x1 convolution over the row axis."""
     return conv2d(x, w, 1, 0, relu=relu, out_f32=out_f32, need_dx=need_dx, drop=drop)
@@ -773,6 +817,14 @@ def conv_bn(conv, bn, x, relu=False, residual=None, out=None, defer=False):
     defer="conv" (training, when the only consumer is a conv2d / conv_bn): the same; that convolution applies the BatchNorm with its operand loads
     (emrt_conv2d_bna) or, when its kernel has no such form, launches emrt_bn_apply itself (PendingBN.materialize)."""
     c = ctx()
+    if getattr(conv, "groups", 1) > 1:
+        # grouped 3x3 (ResNeXt): its own kernel, statistics in its epilogue, the same BatchNorm tail
+        if c.fold_live and not c.training and c.tape is None and (conv.gw.bias is None or bn.state.fold_conv is conv):
+            assert residual is None, "a grouped convolution's folded BatchNorm takes no residual"
+            return gconv2d(x, conv.gw, conv.stride, relu=relu, out=out, need_dx=False, out_scale=bn.state.fold_scale, out_shift=bn.state.fold_shift)
+        sums = c.zeros_f64(BN_REPLICAS * 2 * bn.C) if c.training else None
+        y = gconv2d(x, conv.gw, conv.stride, need_dx=conv.need_dx, bn_stats=sums)
+        return _bn_tail(y, bn, sums, relu, residual, out, defer)
     if c.fold_live and not c.training and c.tape is None and (conv.gw.bias is None or bn.state.fold_conv is conv):
         scale, shift = bn.state.fold_scale, bn.state.fold_shift      # ParamStore.fold_bn(): refreshed at the top of every eval forward
         return conv2d(x, conv.gw, conv.stride, conv.padding, relu=relu, residual=residual, out=out, need_dx=False,

@@ -247,22 +247,35 @@ class HipLayer(tnn.Module):
 
 
 class Conv2D(HipLayer):
-    def __init__(self, cin, cout, k, stride=1, padding=0, bias=True, need_dx=True, dilation=1, pad_cin=None):
+    def __init__(self, cin, cout, k, stride=1, padding=0, bias=True, need_dx=True, dilation=1, pad_cin=None, groups=1):
         """pad_cin: the layer is fed maps with pad_cin >= cin channels whose extra channels are zero (the image as an 8-channel
-        map, Fn.nchw_to_nhwc(c_out=)); its weights are stored with that many input channels (ParamStore.padded_cin)."""
+        map, Fn.nchw_to_nhwc(c_out=)); its weights are stored with that many input channels (ParamStore.padded_cin).
+        groups > 1: a grouped 3x3 convolution with padding 1 (ResNeXt), weight [cout, cin / groups, 3, 3], run by Fn.gconv2d."""
         super().__init__()
         self.cin, self.cout, self.k, self.stride, self.padding, self.need_dx = cin, cout, k, stride, padding, need_dx
         self.dilation = dilation
+        self.groups = groups
+        if groups > 1 and not (k == 3 and padding == 1 and dilation == 1 and pad_cin is None and cin % groups == 0 and cout % groups == 0):
+            raise NotImplementedError("grouped convolutions are 3x3 with padding 1 (emrt_gconv2d)")
         self.pad_cin = pad_cin if pad_cin and pad_cin > cin else None
-        self.weight = tnn.Parameter(torch.empty(cout, cin, k, k))
+        self.weight = tnn.Parameter(torch.empty(cout, cin // groups, k, k))
         self.bias = tnn.Parameter(torch.zeros(cout)) if bias else None
         self.gw = None
 
     def bind(self, store, prefix):
+        if self.groups > 1:
+            # the forward operand [OC][3][3][Cg] (the compute-dtype mirror in bf16 / fp16) also serves the data gradient: no transposed copy
+            self.gw = store.make_gemm(store.offsets[prefix + "weight"], self.cout, self.cin // self.groups, 3, 3,
+                                      store.offsets[prefix + "bias"] if self.bias is not None else None, need_bwd=False)
+            self.gw.groups = self.groups
+            return
         self.gw = store.make_gemm(store.offsets[prefix + "weight"], self.cout, store.padded_cin.get(prefix + "weight", self.cin), self.k, self.k,
                                   store.offsets[prefix + "bias"] if self.bias is not None else None, need_bwd=self.need_dx)
 
     def forward(self, x, relu=False, residual=None, out=None, out_f32=False):
+        if self.groups > 1:
+            assert residual is None and not out_f32
+            return Fn.gconv2d(x, self.gw, self.stride, relu=relu, out=out, need_dx=self.need_dx)
         return Fn.conv2d(x, self.gw, self.stride, self.padding, relu=relu, residual=residual, out=out, out_f32=out_f32, need_dx=self.need_dx,
                          dilation=self.dilation)
 

@@ -26,7 +26,7 @@ from ... import functional as Fn
 from ... import nn as hnn
 from ...runtime import ctx, Tape, F32
 
-NOGRAD_PARAMS = ("backbone.fc.weight", "backbone.fc.bias", "model.tgt_embed.weight")
+NOGRAD_PARAMS = ("backbone.fc.weight", "backbone.fc.bias", "model.tgt_embed.weight", "backbone.out.weight", "backbone.out.bias")   # (out: ResNeXt's)
 # parameters whose gradient is only final after the ops recorded before the tape's split mark (ResNet.forward) have run
 # backward; everything else can be exchanged between ranks while those run (engine.TrainEngine, two-phase step)
 # The image enters the network as an 8-channel NHWC map (channels 3..7 zero) and the three convolutions that read it (ResNet stem,
@@ -205,6 +205,78 @@ class ResNetV1c(hnn.HipLayer):  # backbones/resnet.py:102-221 with deep_stem=Tru
             if (layer is self.layer3 or layer is self.layer4) and ctx().tape is not None:
                 ctx().tape.splits.append(len(ctx().tape.ops))
             for blk in layer._modules.values():
+                x = blk(x)
+            feats.append(x)
+        return feats
+
+
+# ---------------------------------------------------------------------------------------------------
+# ResNeXt-50 64x4d (backbones/resnext.py:153-279, cardinality 64; module names as Paddle's structured names)
+# ---------------------------------------------------------------------------------------------------
+class ConvBNLayer(hnn.HipLayer):  # :33-70 (conv without bias -> BatchNorm; the activation is applied by the caller's conv_bn)
+    def __init__(self, cin, cout, k, stride=1, groups=1, need_dx=True, pad_cin=None):
+        super().__init__()
+        self._conv = hnn.Conv2D(cin, cout, k, stride, (k - 1) // 2, bias=False, need_dx=need_dx, pad_cin=pad_cin, groups=groups)
+        self._batch_norm = hnn.BatchNorm2D(cout)
+
+
+class ResNeXtBlock(hnn.HipLayer):  # BottleneckBlock, :92-150
+    def __init__(self, cin, width, stride, shortcut, cardinality):
+        super().__init__()
+        self.conv0 = ConvBNLayer(cin, width, 1)
+        self.conv1 = ConvBNLayer(width, width, 3, stride, groups=cardinality)
+        self.conv2 = ConvBNLayer(width, width, 1)
+        self.short = None if shortcut else ConvBNLayer(cin, width, 1, stride)
+
+    def forward(self, x):
+        c0, c1, c2, sh = self.conv0, self.conv1, self.conv2, self.short
+        pair = None
+        if sh is not None:
+            # conv0 and the shortcut conv read the same x: one grouped forward launch (Fn.conv_bn_pair), as in BottleneckBlock
+            pair = Fn.conv_bn_pair([(c0._conv, c0._batch_norm, True, "conv"), (sh._conv, sh._batch_norm, False, "join")], x)
+        if pair is not None:
+            y, identity = pair
+        else:
+            y = Fn.conv_bn(c0._conv, c0._batch_norm, x, relu=True, defer="conv")       # (the grouped conv materialises it: PendingBN.materialize)
+            identity = None
+        y = Fn.conv_bn(c1._conv, c1._batch_norm, y, relu=True, defer="conv")           # grouped 3x3 (emrt_gconv2d); its BatchNorm + ReLU go into conv2's loads
+        if identity is None:
+            identity = x if sh is None else Fn.conv_bn(sh._conv, sh._batch_norm, x, defer="join")
+        return Fn.conv_bn(c2._conv, c2._batch_norm, y, relu=True, residual=identity)
+
+
+class ResNeXt(hnn.HipLayer):  # :153-250 with layers=50, cardinality=64
+    depth = (3, 4, 6, 3)
+    # the early gradient exchange (engine.TrainEngine) is keyed by parameter-name prefixes: this backbone's names for LATE_GRAD_PREFIXES /
+    # GRAD_SEGMENT_PREFIXES (split marks before stages 3 and 4, i.e. bb_2_* and bb_3_*)
+    late_grad_prefixes = ("backbone.conv.", "backbone.bb_0_", "backbone.bb_1_", "backbone.bb_2_")
+    grad_segment_prefixes = (("backbone.bb_2_",), ("backbone.conv.", "backbone.bb_0_", "backbone.bb_1_"))
+
+    def __init__(self, cardinality=64, num_classes=1000):
+        super().__init__()
+        widths = [256, 512, 1024, 2048]      # num_filters * 64 // cardinality = num_filters at cardinality 64: the block output is W too (:118-131)
+        self.conv = ConvBNLayer(3, 64, 7, 2, need_dx=False, pad_cin=IMAGE_CHANNELS)
+        self.stages = []
+        cin = 64
+        for b, (n, w) in enumerate(zip(self.depth, widths)):
+            blocks = []
+            for i in range(n):
+                blk = ResNeXtBlock(cin, w, 2 if (i == 0 and b != 0) else 1, shortcut=i != 0, cardinality=cardinality)
+                self.add_module("bb_%d_%d" % (b, i), blk)
+                blocks.append(blk)
+                cin = w
+            self.stages.append(blocks)
+        self.out = hnn.Linear(2048, num_classes)     # in the reference state dict, never used (:241-249)
+        self.out.standalone = False
+
+    def forward(self, x):
+        x = Fn.conv_bn(self.conv._conv, self.conv._batch_norm, x, relu=True, defer=True)     # BatchNorm + ReLU applied by the max-pool's loads
+        x = Fn.maxpool(x, 3, 2, 1)
+        feats = []
+        for b, blocks in enumerate(self.stages):
+            if b >= 2 and ctx().tape is not None:
+                ctx().tape.splits.append(len(ctx().tape.ops))      # as ResNet.forward: before stages 3 and 4
+            for blk in blocks:
                 x = blk(x)
             feats.append(x)
         return feats
@@ -719,10 +791,10 @@ class EMRT(hnn.HipLayer):  # :184-304
             num_classes = config.DATA.NUM_CLASSES
             backbone = config.MODEL.ENCODER.TYPE.lower()
         depth = int(backbone.replace("resnet", "")) if backbone.startswith("resnet") and backbone[6:].isdigit() else None
-        if backbone == "resnet50c":
+        if backbone in ("resnet50c", "resnext50"):
             depth = 50
         if depth not in ResNet.layer_cfg:
-            raise NotImplementedError("EMRT HIP path supports resnet18/34/50/50c/101/152 backbones, got %r" % backbone)
+            raise NotImplementedError("EMRT HIP path supports resnet18/34/50/50c/101/152 and resnext50 backbones, got %r" % backbone)
         output_stride = int(config.MODEL.OUTPUT_STRIDE) if config is not None else 32
         if backbone == "resnet50c" and output_stride == 8:
             # the auxiliary head's x16 upsample (fcn_head.py:80) then lands on 2H x 2W and the reference's final resize to the
@@ -762,18 +834,23 @@ class EMRT(hnn.HipLayer):  # :184-304
                     if isinstance(m, hnn.Conv2D):
                         tnn.init.kaiming_normal_(m.weight, a=0, mode="fan_in", nonlinearity="relu")
         else:
-            self.backbone = ResNet(depth)
+            # resnext50: paddle_EMRT.py:235-236 -> resnext.ResNeXt50_64x4d (pretrained=True downloads ImageNet weights)
+            self.backbone = ResNeXt(64) if backbone == "resnext50" else ResNet(depth)
             with torch.no_grad():   # reference downloads ImageNet weights (:231-232); offline => Paddle default init
                 for m in self.backbone.modules():
                     if isinstance(m, hnn.Conv2D):
                         _paddle_conv_default_(m)
+        head = self.backbone.out if backbone == "resnext50" else self.backbone.fc
         with torch.no_grad():
-            tnn.init.xavier_uniform_(self.backbone.fc.weight)
-            tnn.init.zeros_(self.backbone.fc.bias)
+            tnn.init.xavier_uniform_(head.weight)
+            tnn.init.zeros_(head.bias)
         self.model = EncoderDecoder(backbone_num_channels=self.backbone_num_channels, hidden_dim=256, dim_feedforward=1024,
                                     dropout=0.1, num_feature_levels=3, nhead=8, num_encoder_layers=4, num_decoder_layers=2,
                                     num_encoder_points=6, num_decoder_points=6)
         self.store = None
+        # the name prefixes of the early gradient exchange's segments (engine.TrainEngine): ResNeXt's parameters are named bb_<stage>_<i>
+        self.late_grad_prefixes = getattr(self.backbone, "late_grad_prefixes", LATE_GRAD_PREFIXES)
+        self.grad_segment_prefixes = getattr(self.backbone, "grad_segment_prefixes", GRAD_SEGMENT_PREFIXES)
         self.compute_aux_in_eval = True   # the reference always evaluates the aux head (paddle_EMRT.py:300-302)
 
     # ---- device placement -----------------------------------------------------------------------
@@ -801,8 +878,6 @@ class EMRT(hnn.HipLayer):  # :184-304
                                     lr_mult_names=self.lr_mult_names(), lr_mult=0.1)
         hnn.bind_all(self, self.store)
         self.store.pack()
-        self.late_grad_prefixes = LATE_GRAD_PREFIXES
-        self.grad_segment_prefixes = GRAD_SEGMENT_PREFIXES
         return self
 
     def set_dropout(self, p):

@@ -23,9 +23,9 @@ import torch
 logger = logging.getLogger("emrt_amd.checkpoint")
 
 # last path component before ".weight" of every nn.Linear on the EMRT path (transformer_encoder_decoder.py, layers.py,
-# paddle_vision_resnet.py:fc)
+# paddle_vision_resnet.py:fc, resnext.py:out)
 _LINEAR_LEAVES = ("sampling_offsets", "attention_weights", "value_proj", "output_proj", "out_proj", "linear1", "linear2",
-                  "reference_points", "fc")
+                  "reference_points", "fc", "out")
 _SKIP_KEYS = ("StructuredToParameterName@@",)
 
 

@@ -138,6 +138,15 @@ int emrt_conv2d_wgrad_group(const EmrtWgradDesc* descs, int n, int dtype, void* 
  * an accumulate pass; stat_x: the second statistic becomes sum dx * stat_x (the BatchNorm input) instead of sum dx * mask_y,
  * which is what a relu(BatchNorm(x) + residual) join needs -- its reduction pass then disappears too */
 int emrt_conv2d_bwd(const void* x, const void* dy, const void* w_bwd_packed, void* dx, int lddx, long long dx_bs, int accumulate, float* dw, float* dbias, int N, int H, int W, int C, int ldx, long long x_bs, int OH, int OW, int OC, int lddy, long long dy_bs, int KH, int KW, int stride, int pad, double* bn_stats, const void* mask_y, int ldy, long long y_bs, float mask_scale, const void* stat_x, int ldsx, long long sx_bs, const void* addend, int ldadd, long long add_bs, int dilation, int dtype, void* stream);
+/* ---- grouped 3x3 convolution, pad 1 (csrc/gconv.hip) --------------------------------------------------------------------------------------------
+ * replaces the grouped nn.Conv2D of ResNeXt's bottleneck (backbones/resnext.py, BottleneckBlock.conv1: groups = 64).  C / groups (Cg) must be
+ * 4, 8, 16 or 32 and OC / groups a multiple of 4; stride 1 or 2.  w = [OC][3][3][Cg] (the forward operand: the compute-dtype mirror of the
+ * parameter, no transposed copy).  Forward: out = conv(in, w) * out_scale [+ bias] [relu]; bn_stats (nullable) as emrt_conv2d's; fp32 / bf16 / fp16.
+ * ldin / in_bs multiples of 8, ldout / out_bs of 4, operands 16-byte aligned.  Output written without atomics (bit-reproducible).
+ * Backward (fp32 / bf16): dx (nullable) = dgrad [+ dx if accumulate], no atomics; dw (nullable) += wgrad and dbias (nullable) += sum dy, fp32 atomics
+ * (the pixel reduction is cut into slices over blocks).  x is the forward input, dy the gradient of out. */
+int emrt_gconv2d(const void* in, const void* w, void* out, const float* bias, int N, int H, int W, int C, int ldin, long long in_bs, int OH, int OW, int OC, int ldout, long long out_bs, int stride, int groups, int relu, double* bn_stats, const float* out_scale, int dtype, void* stream);
+int emrt_gconv2d_bwd(const void* x, const void* dy, const void* w, void* dx, int lddx, long long dx_bs, int accumulate, float* dw, float* dbias, int N, int H, int W, int C, int ldx, long long x_bs, int OH, int OW, int OC, int lddy, long long dy_bs, int stride, int groups, int dtype, void* stream);
 
 /* ---- BatchNorm / SyncBatchNorm (train: fp64 sums [from the conv epilogue or emrt_bn_stats] -> [all-reduce of sums across
  * ranks] -> apply; eval: running statistics).  replaces nn.BatchNorm2D / nn.SyncBatchNorm (+ReLU, + residual add):
