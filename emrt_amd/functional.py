@@ -1894,3 +1894,27 @@ def softmax_ce(logits, labels, ignore_index, weight=1.0):
             tape.add_grad(logits, dl, owned=True)
         tape.record(bwd)
     return res
+
+
+class _AugDesc(ctypes.Structure):          # EmrtAugDesc (include/emrt_hip.h)
+    _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int), ("h", ctypes.c_int),
+                ("w", ctypes.c_int), ("off_y", ctypes.c_int), ("off_x", ctypes.c_int), ("flip", ctypes.c_int)]
+
+
+def augment_tiles(src, samples, out_size, mean, stdinv, img_pad, label_pad, label_lut=None, labels=True):
+    """Training augmentation of a packed batch of decoded tiles, one launch (csrc/augment.hip: resize, pad, crop, flip, normalise).
+    src: uint8 [n] on the device; samples: per sample (img_off, lab_off, SamplePlan) with byte offsets into src; out_size (OH, OW);
+    mean / stdinv (float64), img_pad (float32): 3 values each; label_lut: 256 values or None (identity).
+    -> (fp32 [B, 3, OH, OW], int64 [B, OH, OW] or None), allocated on src's device and written on the current stream."""
+    c = ctx()
+    OH, OW = out_size
+    B = len(samples)
+    assert src.dtype == torch.uint8 and src.dim() == 1 and B > 0
+    descs = (_AugDesc * B)(*[_AugDesc(io, lo, p.H, p.W, p.h, p.w, p.off_y, p.off_x, p.flip) for io, lo, p in samples])
+    out = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=src.device)
+    lab = torch.empty((B, OH, OW), dtype=torch.int64, device=src.device) if labels else None
+    lut = None if label_lut is None else (ctypes.c_ubyte * 256)(*[int(v) for v in label_lut])
+    _L().call("emrt_augment_tiles", P(src), src.numel(), descs, B, OH, OW, (ctypes.c_double * 3)(*[float(v) for v in mean]),
+              (ctypes.c_double * 3)(*[float(v) for v in stdinv]), (ctypes.c_float * 3)(*[float(v) for v in img_pad]), int(label_pad), lut,
+              P(out), 3 * OH * OW, P(lab), c.stream)
+    return out, lab

@@ -8,6 +8,7 @@ Directory layouts are the reference's:
   LoveDA:  <root>/Train/images_png/<n>.png + <root>/Train/masks_png/<n>.png ; <root>/Val/...
       masks are 1..7 with 0 = ignore: shifted by -1, ignore -> 255 (loveda.py:58-70)
 """
+import contextlib
 import os
 import queue
 import threading
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ..transforms import Compose
+from ..transforms import Compose, DevicePlan
 
 
 class Dataset:
@@ -135,12 +136,21 @@ class TileLoader:
                         cv.wait(timeout=0.2)
                 while not stop.is_set() and not slots.acquire(timeout=0.2):
                     pass
+                if stop.is_set():
+                    return
+                try:
+                    job = self._plan(idx)           # still this batch's turn: decisions drawn in batch order, whatever the worker count
+                except Exception as e:
+                    job = e
                 with cv:
                     turn[0] = n + 1
                     cv.notify_all()
                 if stop.is_set():
                     return
-                b = self._batch(idx)
+                try:
+                    b = job if isinstance(job, Exception) else self._batch(job)
+                except Exception as e:               # handed to the consumer, which raises it (a dead worker would leave it waiting)
+                    b = e
                 with cv:
                     done[n] = b
                     cv.notify_all()
@@ -154,10 +164,88 @@ class TileLoader:
                 with cv:
                     while n not in done:
                         cv.wait(timeout=1.0)
-                    imgs, labs = done.pop(n)
+                    b = done.pop(n)
                 slots.release()
                 n += 1
-                # consumer thread, training stream: see the class docstring
-                yield imgs.to(self.device, non_blocking=True), labs.to(self.device, non_blocking=True)
+                if isinstance(b, Exception):
+                    raise b
+                yield self._deliver(b)
         finally:
             stop.set()
+
+    def _plan(self, idx):
+        """Work a worker does while it holds batch `idx`'s turn (DeviceTileLoader draws its random decisions here); -> what _batch takes."""
+        return idx
+
+    def _deliver(self, b):
+        """Consumer thread, training stream (see the class docstring): the batch on the device."""
+        imgs, labs = b
+        return imgs.to(self.device, non_blocking=True), labs.to(self.device, non_blocking=True)
+
+
+def label_lut(shift):
+    """The label map of a dataset's `label_shift` as a 256-entry table (None = identity): LoveDA's `label - 1` in uint8 with the
+    254 -> 255 repair of Dataset.__getitem__ (class 0 = ignore -> 255, padding 255 -> 254 -> 255)."""
+    if not shift:
+        return None
+    lut = ((np.arange(256) - shift) & 255).astype(np.uint8)
+    lut[lut == 254] = 255
+    return lut
+
+
+class DeviceTileLoader(TileLoader):
+    """TileLoader with the training transforms on the GPU (train.py --device_transforms).  Same epochs() contract: endless
+    (fp32 [B,3,OH,OW], int64 [B,OH,OW]) device batches, the same values the CPU loader makes from the same seeds.
+
+    A worker, while it holds its batch's turn, reads each tile's size from the file header (no decode) and draws the sample's random
+    decisions (DevicePlan.plan), so decisions are drawn in batch and sample order whatever the number of workers; it then decodes the tiles
+    to uint8 with read_image's / read_label's PIL calls outside the turn and packs them into one pinned host buffer.  The consumer thread
+    issues one host->device copy of that buffer and one emrt_augment_tiles launch (resize, pad, crop, flip, normalise), both on the
+    training stream, into outputs from torch's caching allocator on that stream.  Never inside a graph capture: train.py calls it between
+    steps."""
+
+    def __init__(self, dataset, sampler, device, workers=4, prefetch=4):
+        super().__init__(dataset, sampler, device, workers, prefetch)
+        if dataset.mode != "train":
+            raise ValueError("DeviceTileLoader runs the training transforms; got a %r dataset" % dataset.mode)
+        self.device_plan = DevicePlan(dataset.transforms.transforms)
+        self.lut = label_lut(dataset.label_shift)
+
+    def _plan(self, idx):
+        job = []
+        for i in idx:
+            image_path, label_path = self.dataset.file_list[i]
+            with Image.open(image_path) as im:
+                W, H = im.size
+            job.append((image_path, label_path, self.device_plan.plan(H, W)))
+        sizes = {self.device_plan.out_size(p.H, p.W) for _, _, p in job}
+        if len(sizes) != 1:
+            raise ValueError("DeviceTileLoader: the samples of a batch have different output sizes %s (np.stack needs one)" % sorted(sizes))
+        return job
+
+    def _batch(self, job):
+        """Decoded uint8 sources of one batch packed into one (pinned) buffer -> (buffer, [(img_off, lab_off, SamplePlan)], (OH, OW))."""
+        total = sum(4 * p.H * p.W for _, _, p in job)
+        buf = torch.empty(total, dtype=torch.uint8, pin_memory=self.pin)
+        a = buf.numpy()
+        samples, off = [], 0
+        for image_path, label_path, p in job:
+            img = np.asarray(Image.open(image_path).convert("RGB"), dtype=np.uint8)       # read_image's calls, kept in uint8
+            lab = np.asarray(Image.open(label_path).convert("P"), dtype=np.uint8)         # read_label's
+            if img.shape != (p.H, p.W, 3) or lab.shape != (p.H, p.W):
+                raise ValueError("DeviceTileLoader: %s is %s and %s is %s; header said %dx%d" % (
+                    image_path, img.shape, label_path, lab.shape, p.H, p.W))
+            a[off:off + img.size] = img.reshape(-1)
+            a[off + img.size:off + img.size + lab.size] = lab.reshape(-1)
+            samples.append((off, off + img.size, p))
+            off += img.size + lab.size
+        return buf, samples, self.device_plan.out_size(job[0][2].H, job[0][2].W)
+
+    def _deliver(self, b):
+        from ... import functional as F
+        buf, samples, out_size = b
+        dp = self.device_plan
+        dev = torch.device(self.device)
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            src = buf.to(dev, non_blocking=True)
+            return F.augment_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut)

@@ -8,6 +8,7 @@ no antialiasing; INTER_NEAREST: floor(dst * scale)).  Random draws use the same 
 reference, so a seeded run makes the same decisions.
 """
 import random
+from collections import namedtuple
 
 import numpy as np
 from PIL import Image
@@ -79,8 +80,12 @@ class RandomHorizontalFlip:
     def __init__(self, prob=0.5):
         self.prob = prob
 
+    def draw(self):
+        """The flip decision: one Python `random.random()` (the CPU chain and DevicePlan.plan both draw it here)."""
+        return random.random() < self.prob
+
     def __call__(self, img, label=None):
-        if random.random() < self.prob:
+        if self.draw():
             img = img[:, ::-1, :]
             if label is not None:
                 label = label[:, ::-1]
@@ -109,18 +114,24 @@ class ResizeStepScaling:
             raise ValueError("min_scale_factor must be less than max_scale_factor, but they are {} and {}.".format(min_scale_factor, max_scale_factor))
         self.min_scale_factor, self.max_scale_factor, self.scale_step_size = min_scale_factor, max_scale_factor, scale_step_size
 
-    def __call__(self, img, label=None):
+    def draw(self):
+        """The scale factor, with the reference's draws: none when min == max, np.random.uniform when the step is 0, else a shuffle."""
         if self.min_scale_factor == self.max_scale_factor:
-            scale_factor = self.min_scale_factor
-        elif self.scale_step_size == 0:
-            scale_factor = np.random.uniform(self.min_scale_factor, self.max_scale_factor)
-        else:
-            num_steps = int((self.max_scale_factor - self.min_scale_factor) / self.scale_step_size + 1)
-            scale_factors = np.linspace(self.min_scale_factor, self.max_scale_factor, num_steps).tolist()
-            np.random.shuffle(scale_factors)
-            scale_factor = scale_factors[0]
-        w = int(round(scale_factor * img.shape[1]))
-        h = int(round(scale_factor * img.shape[0]))
+            return self.min_scale_factor
+        if self.scale_step_size == 0:
+            return np.random.uniform(self.min_scale_factor, self.max_scale_factor)
+        num_steps = int((self.max_scale_factor - self.min_scale_factor) / self.scale_step_size + 1)
+        scale_factors = np.linspace(self.min_scale_factor, self.max_scale_factor, num_steps).tolist()
+        np.random.shuffle(scale_factors)
+        return scale_factors[0]
+
+    @staticmethod
+    def resized(scale_factor, h, w):
+        """-> (h, w) of an h x w image scaled by scale_factor (Python round, as the reference)."""
+        return int(round(scale_factor * h)), int(round(scale_factor * w))
+
+    def __call__(self, img, label=None):
+        h, w = self.resized(self.draw(), img.shape[0], img.shape[1])
         img = resize_bilinear(img, w, h)
         if label is not None:
             label = resize_nearest(label, w, h)
@@ -151,9 +162,30 @@ class RandomPaddingCrop:
             raise TypeError("The type of `crop_size` is invalid. It should be list or tuple, but it is {}".format(type(crop_size)))
         self.crop_size, self.img_padding_value, self.label_padding_value = crop_size, img_padding_value, label_padding_value
 
+    def size(self):
+        """-> (crop height, crop width); crop_size is (w, h) or an int."""
+        if isinstance(self.crop_size, int):
+            return self.crop_size, self.crop_size
+        return self.crop_size[1], self.crop_size[0]
+
+    def draw(self, ih, iw):
+        """Crop offsets (h_off, w_off) into an ih x iw image once padded bottom / right to the crop size, with the reference's two
+        np.random.randint calls; None (no draw) when the image already has the crop size.  The draws happen whenever the size differs,
+        even when padding then makes it equal to the crop."""
+        chh, cw = self.size()
+        if ih == chh and iw == cw:
+            return None
+        ih, iw = max(ih, chh), max(iw, cw)
+        if chh > 0 and cw > 0:
+            h_off = np.random.randint(ih - chh + 1)
+            w_off = np.random.randint(iw - cw + 1)
+            return h_off, w_off
+        return None
+
     def __call__(self, img, label=None):
-        cw, chh = (self.crop_size, self.crop_size) if isinstance(self.crop_size, int) else (self.crop_size[0], self.crop_size[1])
+        chh, cw = self.size()
         ih, iw = img.shape[0], img.shape[1]
+        offsets = self.draw(ih, iw)
         if not (ih == chh and iw == cw):
             ph, pw = max(chh - ih, 0), max(cw - iw, 0)
             if ph > 0 or pw > 0:            # bottom / right padding (cv2.copyMakeBorder BORDER_CONSTANT)
@@ -166,9 +198,8 @@ class RandomPaddingCrop:
                     pl[:ih, :iw] = label
                     label = pl
                 ih, iw = img.shape[0], img.shape[1]
-            if chh > 0 and cw > 0:
-                h_off = np.random.randint(ih - chh + 1)
-                w_off = np.random.randint(iw - cw + 1)
+            if offsets is not None:
+                h_off, w_off = offsets
                 img = img[h_off:chh + h_off, w_off:w_off + cw, :]
                 if label is not None:
                     label = label[h_off:chh + h_off, w_off:w_off + cw]
@@ -176,6 +207,66 @@ class RandomPaddingCrop:
 
 
 _MEAN, _STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+
+
+# One sample's decisions for the device kernel (emrt_augment_tiles): source H x W, resized h x w, crop offsets into the resized image padded
+# bottom / right to the crop size, horizontal flip after the crop.
+SamplePlan = namedtuple("SamplePlan", "H W h w off_y off_x flip")
+
+
+class DevicePlan:
+    """A training transform list compiled for the fused device kernel (emrt_amd.functional.augment_tiles).  Two chains are supported, the
+    ones get_transforms ships: [ResizeStepScaling, RandomPaddingCrop, RandomHorizontalFlip, Normalize] (Potsdam, Vaihingen) and
+    [Normalize] (LoveDA: output size = source size).  Any other op or order raises, naming the op: nothing is skipped or left to the CPU.
+
+    plan(H, W) draws one sample's random decisions with the draw helpers the CPU transforms themselves call (ResizeStepScaling.draw,
+    RandomPaddingCrop.draw, RandomHorizontalFlip.draw), in the chain's order and under its conditions, so a seeded run makes the same
+    decisions on either path and leaves np.random / random in the same state."""
+
+    CHAINS = ((ResizeStepScaling, RandomPaddingCrop, RandomHorizontalFlip, Normalize), (Normalize,))
+
+    def __init__(self, transforms):
+        transforms = list(transforms)
+        kinds = tuple(type(t) for t in transforms)
+        if kinds not in self.CHAINS:
+            best = max(self.CHAINS, key=lambda c: sum(1 for a, b in zip(c, kinds) if a is b))
+            i = next((i for i, (a, b) in enumerate(zip(best, kinds)) if a is not b), min(len(best), len(kinds)))
+            what = ("%s at position %d" % (type(transforms[i]).__name__, i)) if i < len(transforms) else "the chain ends early"
+            raise ValueError("device transforms: %s is not supported; the device path runs [%s] or [%s] exactly, got [%s]" % (
+                what, ", ".join(c.__name__ for c in self.CHAINS[0]), ", ".join(c.__name__ for c in self.CHAINS[1]),
+                ", ".join(type(t).__name__ for t in transforms)))
+        norm = transforms[-1]
+        if len(norm.mean) != 3 or len(norm.std) != 3:
+            raise ValueError("device transforms: Normalize needs 3 channels, got mean %r std %r" % (norm.mean, norm.std))
+        self.mean = np.asarray(norm.mean, dtype=np.float64)
+        self.stdinv = 1.0 / np.asarray(norm.std, dtype=np.float64)          # as Normalize computes it
+        self.scaling = self.crop = self.flip = None
+        self.img_pad, self.label_pad = np.zeros(3, np.float32), 255
+        if len(transforms) == 4:
+            self.scaling, self.crop, self.flip = transforms[:3]
+            chh, cw = self.crop.size()
+            if chh <= 0 or cw <= 0:
+                raise ValueError("device transforms: RandomPaddingCrop size must be positive, got %r" % (self.crop.crop_size,))
+            pad = np.asarray(self.crop.img_padding_value, dtype=np.float32).reshape(-1)
+            if pad.size != 3:
+                raise ValueError("device transforms: img_padding_value needs 3 channels, got %r" % (self.crop.img_padding_value,))
+            self.img_pad = pad
+            self.label_pad = int(self.crop.label_padding_value)
+            if not 0 <= self.label_pad <= 255:
+                raise ValueError("device transforms: label_padding_value must be 0..255, got %r" % (self.crop.label_padding_value,))
+
+    def out_size(self, H, W):
+        """-> (OH, OW) of a sample whose source is H x W."""
+        return (H, W) if self.crop is None else self.crop.size()
+
+    def plan(self, H, W):
+        """Draw one H x W sample's decisions -> SamplePlan."""
+        if self.scaling is None:
+            return SamplePlan(H, W, H, W, 0, 0, 0)
+        h, w = ResizeStepScaling.resized(self.scaling.draw(), H, W)
+        off = self.crop.draw(h, w) or (0, 0)
+        flip = self.flip.draw()
+        return SamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip))
 
 
 def get_transforms(config):

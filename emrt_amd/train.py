@@ -10,7 +10,8 @@ iterations rank 0 prints the reference's log line (:177-181); every SAVE_FREQ_CH
 (model + optimizer state + iteration, so training can actually be resumed -- the reference never wired that, :103).
 The dataset pipeline (cv2 / Potsdam readers) is outside this path: tiles come from --data synthetic (default: seeded
 random tiles of DATA.CROP_SIZE, resident on the device) or from an .npz of pre-cut tiles (--data file.npz with arrays
-`images` [N,3,H,W] float32 normalised and `labels` [N,H,W] int64).
+`images` [N,3,H,W] float32 normalised and `labels` [N,H,W] int64).  --data dataset reads the reference's directory layout;
+--device_transforms then runs its training transforms on the GPU (DeviceTileLoader) instead of in the reader threads.
 """
 import argparse
 import os
@@ -46,6 +47,8 @@ def parse_args(argv=None):
     p.add_argument("--no-eval", action="store_true", help="skip the periodic evaluation (train.py:187-195) and best_model.pdparams")
     p.add_argument("--gpus", type=int, default=0, help="without a launcher (no RANK / WORLD_SIZE in the environment): start this many rank "
                    "processes, one per GPU (the reference gets its ranks from paddle.distributed.launch, train.py:116-123)")
+    p.add_argument("--device_transforms", action="store_true", help="--data dataset only: reader threads just decode tiles; the "
+                   "training transforms run as one HIP kernel per batch on the GPU (DeviceTileLoader)")
     p.add_argument("--val_tiles", type=int, default=16, help="--data synthetic / .npz without val arrays: how many held-out tiles to evaluate on")
     return p.parse_args(argv)
 
@@ -87,6 +90,8 @@ def synthetic_tiles(n, crop, ncls, seed, device):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.device_transforms and args.data != "dataset":
+        raise SystemExit("[train] --device_transforms needs --data dataset (it augments decoded tiles; --data %s has none)" % args.data)
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     if args.gpus > 1 and not launched:          # pure parent: no GPU call in this process, N fresh rank processes
         import sys
@@ -133,7 +138,7 @@ def main(argv=None):
         images, labels = synthetic_tiles(max(4 * bs * nranks, 64), config.DATA.CROP_SIZE, config.DATA.NUM_CLASSES, args.seed, dev)
         n_tiles = images.shape[0]
     elif args.data == "dataset":        # the reference's pipeline: DATA.DATASET under DATA.DATA_PATH (train.py:79-86)
-        from .src.datasets import get_dataset, TileLoader
+        from .src.datasets import get_dataset, DeviceTileLoader, TileLoader
         from .src.transforms import get_transforms
         dataset_train = get_dataset(config, data_transform=get_transforms(config), mode="train")
         n_tiles = len(dataset_train)
@@ -144,7 +149,13 @@ def main(argv=None):
     sampler = DistributedTileSampler(n_tiles, bs, rank, nranks, shuffle=True, drop_last=True, seed=args.seed)
     if args.data == "dataset":
         import copy
-        loader = TileLoader(dataset_train, copy.copy(sampler), dev, workers=max(1, config.DATA.NUM_WORKERS), prefetch=4).epochs()
+        workers = max(1, config.DATA.NUM_WORKERS)
+        if args.device_transforms:
+            loader = DeviceTileLoader(dataset_train, copy.copy(sampler), dev, workers=workers, prefetch=4).epochs()
+            if rank == 0:
+                print("[train] data: DeviceTileLoader, %d reader threads, transforms on the GPU" % workers, flush=True)
+        else:
+            loader = TileLoader(dataset_train, copy.copy(sampler), dev, workers=workers, prefetch=4).epochs()
     start_iter = 0
     if args.resume:
         ck = torch.load(args.resume, map_location="cpu")

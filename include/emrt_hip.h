@@ -148,6 +148,24 @@ int emrt_conv2d_bwd(const void* x, const void* dy, const void* w_bwd_packed, voi
 int emrt_gconv2d(const void* in, const void* w, void* out, const float* bias, int N, int H, int W, int C, int ldin, long long in_bs, int OH, int OW, int OC, int ldout, long long out_bs, int stride, int groups, int relu, double* bn_stats, const float* out_scale, int dtype, void* stream);
 int emrt_gconv2d_bwd(const void* x, const void* dy, const void* w, void* dx, int lddx, long long dx_bs, int accumulate, float* dw, float* dbias, int N, int H, int W, int C, int ldx, long long x_bs, int OH, int OW, int OC, int lddy, long long dy_bs, int stride, int groups, int dtype, void* stream);
 
+/* ---- training augmentation of decoded tiles (csrc/augment.hip) ---------------------------------------------------------------------------------
+ * replaces the numpy transform chain of the training reader (transforms/transforms.py: ResizeStepScaling -> RandomPaddingCrop -> RandomHorizontalFlip
+ * -> Normalize, or Normalize alone) for a batch whose random decisions the host has already drawn.  src: ONE device buffer of src_bytes packed uint8
+ * sources; per sample an HWC RGB image at img_off and (when labels != NULL) an HW label map at lab_off.  descs: HOST array of B descriptors.  Each
+ * sample is resized bilinearly (image) / nearest (label) from H x W to h x w, padded bottom / right with img_pad (HOST, 3 floats) / label_pad up to
+ * at least OH x OW, cropped at (off_y, off_x) to OH x OW, mirrored if flip, normalised as (v - mean) * stdinv in float64 (HOST, 3 doubles each) and
+ * rounded once to fp32; labels pass through label_lut (HOST, 256 bytes; NULL = identity).  out: fp32 [B][3][OH][OW] with batch stride out_bs;
+ * labels: int64 [B][OH][OW] (nullable).  Bit-identical to the numpy chain.  Every descriptor is checked on the host before any launch (positive
+ * sizes, crop inside the padded image, every read inside src_bytes): a bad one returns non-zero. */
+typedef struct EmrtAugDesc {
+  long long img_off, lab_off;            /* byte offsets into src */
+  int H, W;                              /* source size */
+  int h, w;                              /* resized size */
+  int off_y, off_x;                      /* crop offsets into the padded, resized sample */
+  int flip;                              /* 1 = horizontal flip after the crop */
+} EmrtAugDesc;
+int emrt_augment_tiles(const void* src, size_t src_bytes, const EmrtAugDesc* descs, int B, int OH, int OW, const double* mean, const double* stdinv, const float* img_pad, int label_pad, const unsigned char* label_lut, float* out, long long out_bs, long long* labels, void* stream);
+
 /* ---- BatchNorm / SyncBatchNorm (train: fp64 sums [from the conv epilogue or emrt_bn_stats] -> [all-reduce of sums across
  * ranks] -> apply; eval: running statistics).  replaces nn.BatchNorm2D / nn.SyncBatchNorm (+ReLU, + residual add):
  * paddle_vision_resnet.py:132-147; paddle_EMRT.py:18,22,64,86-91,131,139-141,203,206; fcn_head.py:53.

@@ -1,0 +1,305 @@
+"""CPU: the device-transform data path (train.py --device_transforms) without a GPU.  The planner draws the CPU chain's random decisions
+with the same calls, the chains it cannot run are refused, the entry point refuses bad descriptors before any launch, and the loader
+hands the entry point the header's argument list with decisions that do not depend on the worker count."""
+import argparse
+import ctypes
+import os
+import random
+import threading
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+from emrt_amd.config import get_config, update_config
+from emrt_amd.distributed import DistributedTileSampler
+from emrt_amd.src import transforms as T
+from emrt_amd.src.datasets import DeviceTileLoader, get_dataset, label_lut
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG = os.path.join(ROOT, "emrt_amd/configs/EMRT/EMRT_256x256_160k_potsdam.yaml")
+
+
+def potsdam_chain(crop):
+    """get_transforms' Potsdam chain with crop_size = (w, h)."""
+    return [T.ResizeStepScaling(0.5, 2.0, 0.25), T.RandomPaddingCrop(crop_size=crop, img_padding_value=(0, 0, 0), label_padding_value=255),
+            T.RandomHorizontalFlip(prob=0.5), T.Normalize(mean=T._MEAN, std=T._STD)]
+
+
+def forced(chain, plan):
+    """The same chain with its draws replaced by the plan's decisions (no RNG call)."""
+    if len(chain) == 4:
+        chain[0].draw = lambda: _scale_for(chain[0], plan)
+        chain[1].draw = lambda ih, iw: None if (ih, iw) == chain[1].size() else (plan.off_y, plan.off_x)
+        chain[2].draw = lambda: bool(plan.flip)
+    return T.Compose(chain)
+
+
+def _scale_for(rs, plan):
+    """A scale factor of rs's step list that gives the plan's resized size."""
+    n = int((rs.max_scale_factor - rs.min_scale_factor) / rs.scale_step_size + 1)
+    for s in np.linspace(rs.min_scale_factor, rs.max_scale_factor, n).tolist():
+        if T.ResizeStepScaling.resized(s, plan.H, plan.W) == (plan.h, plan.w):
+            return s
+    raise AssertionError("no scale factor gives %r" % (plan,))
+
+
+@pytest.fixture(autouse=True)
+def _no_loader_threads_left():
+    """np.random / random are process-global: a reader thread of an earlier test's loader that is still finishing a prefetched batch would
+    draw in the middle of these comparisons.  Wait for such threads (they end once their loader is closed)."""
+    for t in threading.enumerate():
+        if t.daemon and t.name.endswith(("(work)", "(feed)")):
+            t.join(timeout=30)
+    yield
+
+
+def _states():
+    return np.random.get_state(), random.getstate()
+
+
+def _same_state(a, b):
+    (na, ra), (nb, rb) = a, b
+    return ra == rb and na[0] == nb[0] and np.array_equal(na[1], nb[1]) and na[2:] == nb[2:]
+
+
+CASES = [((80, 96), (64, 64), 120), ((255, 257), (64, 64), 60), ((37, 41), (64, 48), 60), ((64, 64), (64, 64), 40),
+         ((48, 48), (96, 64), 30), ((512, 512), (256, 256), 6), ((256, 256), (256, 256), 10), ((129, 130), (96, 160), 20)]
+
+
+@pytest.mark.parametrize("src,crop,nseeds", CASES)
+def test_planner_draws_the_cpu_chains_decisions(src, crop, nseeds):
+    """Per seed: the CPU chain on an H x W tile, then (same seed) DevicePlan.plan(H, W).  Both leave np.random and random in the same
+    state, and the chain re-run with its draws forced to the plan's decisions gives the same arrays, so the decisions were the same.
+    Covers padding (sources below the crop), the crop size itself (scale 1.0: no crop draws), odd sizes and non-square crops."""
+    H, W = src
+    g = np.random.RandomState(H * 1000 + W)
+    img = g.randint(0, 256, (H, W, 3)).astype(np.float32)
+    lab = g.randint(0, 6, (H, W)).astype(np.uint8)
+    plan_of = T.DevicePlan(potsdam_chain(crop))
+    for seed in range(nseeds):
+        np.random.seed(seed)
+        random.seed(seed)
+        want_img, want_lab = T.Compose(potsdam_chain(crop))(img, lab)
+        after_cpu = _states()
+        np.random.seed(seed)
+        random.seed(seed)
+        p = plan_of.plan(H, W)
+        assert _same_state(after_cpu, _states()), (seed, p)
+        assert plan_of.out_size(H, W) == (crop[1], crop[0])
+        got_img, got_lab = forced(potsdam_chain(crop), p)(img, lab)
+        assert np.array_equal(want_img, got_img) and np.array_equal(want_lab, got_lab), (seed, p)
+
+
+def test_planner_draw_conditions_match_the_reference():
+    """The draws under each condition: nothing when min == max, np.random.uniform when the step is 0, two randint calls whenever the
+    resized size differs from the crop (also when padding makes it equal), none when it equals the crop."""
+    chain = [T.ResizeStepScaling(1.0, 1.0, 0.25), T.RandomPaddingCrop((64, 64)), T.RandomHorizontalFlip(0.5), T.Normalize(T._MEAN, T._STD)]
+    dp = T.DevicePlan(chain)
+    np.random.seed(1)
+    random.seed(1)
+    before = _states()
+    p = dp.plan(64, 64)
+    assert _same_state(before, (np.random.get_state(), before[1])) and p == T.SamplePlan(64, 64, 64, 64, 0, 0, p.flip)
+    np.random.seed(1)
+    p = dp.plan(40, 64)                         # padded to 64 x 64: still two randint(1) draws
+    after = np.random.get_state()
+    np.random.seed(1)
+    np.random.randint(1), np.random.randint(1)
+    assert _same_state((after, 0), (np.random.get_state(), 0))
+    assert (p.off_y, p.off_x) == (0, 0)
+    chain[0] = T.ResizeStepScaling(0.5, 2.0, 0)
+    np.random.seed(2)
+    p = T.DevicePlan(chain).plan(100, 100)
+    np.random.seed(2)
+    s = np.random.uniform(0.5, 2.0)
+    assert (p.h, p.w) == (int(round(s * 100)),) * 2
+    lo = T.DevicePlan([T.Normalize(T._MEAN, T._STD)])
+    np.random.seed(3)
+    random.seed(3)
+    before = _states()
+    assert lo.plan(70, 90) == T.SamplePlan(70, 90, 70, 90, 0, 0, 0) and lo.out_size(70, 90) == (70, 90)
+    assert _same_state(before, _states())
+    assert np.array_equal(lo.stdinv, 1.0 / np.asarray(T._STD, dtype=np.float64))
+
+
+@pytest.mark.parametrize("chain,name", [
+    (lambda: [T.Resize(64), T.Normalize()], "Resize at position 0"),
+    (lambda: [T.RandomPaddingCrop((64, 64)), T.ResizeStepScaling(), T.RandomHorizontalFlip(), T.Normalize()], "RandomPaddingCrop at position 0"),
+    (lambda: [T.ResizeStepScaling(), T.RandomPaddingCrop((64, 64)), T.Normalize()], "Normalize at position 2"),
+    (lambda: [T.ResizeStepScaling(), T.RandomPaddingCrop((64, 64)), T.RandomHorizontalFlip()], "chain ends early"),
+    (lambda: [T.Normalize(), T.RandomHorizontalFlip()], "RandomHorizontalFlip at position 1"),
+    (lambda: [], "chain ends early"),
+])
+def test_unsupported_chains_are_refused_by_name(chain, name):
+    with pytest.raises(ValueError, match=name):
+        T.DevicePlan(chain())
+
+
+def test_unsupported_parameters_are_refused():
+    with pytest.raises(ValueError, match="3 channels"):
+        T.DevicePlan([T.Normalize(mean=(0.5,), std=(0.5,))])
+    with pytest.raises(ValueError, match="label_padding_value"):
+        T.DevicePlan([T.ResizeStepScaling(), T.RandomPaddingCrop((64, 64), label_padding_value=300), T.RandomHorizontalFlip(), T.Normalize()])
+
+
+def test_device_transforms_needs_dataset_data():
+    from emrt_amd import train
+    for data in ("synthetic", "tiles.npz"):
+        with pytest.raises(SystemExit, match="--device_transforms needs --data dataset"):
+            train.main(["--device_transforms", "--data", data])
+
+
+def test_label_lut_is_lovedas_shift():
+    assert label_lut(0) is None
+    lut = label_lut(1)
+    lab = np.arange(256, dtype=np.uint8)
+    want = lab - np.uint8(1)
+    want[want == 254] = 255
+    assert np.array_equal(lut, want) and lut[0] == 255 and lut[255] == 255 and lut[1] == 0
+
+
+class _Desc(ctypes.Structure):
+    _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int), ("h", ctypes.c_int),
+                ("w", ctypes.c_int), ("off_y", ctypes.c_int), ("off_x", ctypes.c_int), ("flip", ctypes.c_int)]
+
+
+def test_entry_point_refuses_bad_descriptors_before_any_launch():
+    """Against the real library, no GPU: every bad call returns non-zero with a message before anything touches a device (the pointers
+    are never dereferenced)."""
+    from emrt_amd import _lib, build_ext
+    build_ext.build(verbose=False)
+    _lib._LIB = None
+    L = _lib.lib()
+    p = ctypes.c_void_p(0x10000)
+    mean, sinv, pad = (ctypes.c_double * 3)(1, 2, 3), (ctypes.c_double * 3)(1, 1, 1), (ctypes.c_float * 3)(0, 0, 0)
+    H, W = 40, 50
+    nbytes = 4 * H * W
+
+    def refused(descs, match, src_bytes=nbytes, OH=32, OW=32, out=p, labels=p, label_pad=255, B=None, src=p):
+        arr = (_Desc * len(descs))(*descs)
+        with pytest.raises(_lib.EmrtHipError, match=match):
+            L.call("emrt_augment_tiles", src, src_bytes, arr, len(descs) if B is None else B, OH, OW, mean, sinv, pad, label_pad, None, out,
+                   3 * OH * OW, labels, None)
+
+    ok = _Desc(0, 3 * H * W, H, W, H, W, 0, 0, 0)
+    # (every case below must fail a check: one that passed would launch on the fake pointers)
+    refused([_Desc(H * W + 1, 0, H, W, H, W, 0, 0, 0)], "descriptor 0: image outside the staged buffer")
+    refused([ok, _Desc(0, 3 * H * W + 1, H, W, H, W, 0, 0, 0)], "descriptor 1: label map outside the staged buffer")
+    refused([_Desc(-8, 3 * H * W, H, W, H, W, 0, 0, 0)], "image outside")
+    refused([ok], "label map outside", src_bytes=nbytes - 1)
+    refused([ok], "image outside", src_bytes=3 * H * W - 1)
+    refused([ok, _Desc(0, 3 * H * W, 0, W, H, W, 0, 0, 0)], "descriptor 1: sizes must be positive")
+    refused([_Desc(0, 3 * H * W, H, W, H, -3, 0, 0, 0)], "sizes must be positive")
+    refused([_Desc(0, 3 * H * W, H, W, H, W, 9, 0, 0)], "crop outside the padded image")       # 9 + 32 > 40
+    refused([_Desc(0, 3 * H * W, H, W, H, W, 0, 19, 0)], "crop outside the padded image")      # 19 + 32 > 50
+    refused([_Desc(0, 3 * H * W, H, W, 20, 20, 1, 0, 0)], "crop outside the padded image")     # padded to 32: offset must be 0
+    refused([_Desc(0, 3 * H * W, H, W, H, W, -1, 0, 0)], "crop outside")
+    refused([_Desc(0, 3 * H * W, H, W, H, W, 0, 0, 2)], "flip must be 0 or 1")
+    refused([ok], "null pointer", out=None)
+    refused([ok], "null pointer", src=None)
+    refused([ok], "positive", OH=0)
+    refused([ok], "positive", B=0)
+    refused([ok], "label_pad", label_pad=256)
+    # without labels the label offset is not read, so it is not checked; the image still is
+    refused([_Desc(3 * H * W, -1, H, W, H, W, 0, 0, 0)], "image outside", labels=None)
+
+
+def _tree(root, sizes):
+    """Potsdam layout with tiles of the given (H, W) sizes."""
+    rng = np.random.RandomState(0)
+    for sub in ("train", "test"):
+        os.makedirs(os.path.join(root, sub))
+        os.makedirs(os.path.join(root, sub + "_convert_labels"))
+        for i, (h, w) in enumerate(sizes):
+            Image.fromarray(rng.randint(0, 256, (h, w, 3), dtype=np.uint8)).save(os.path.join(root, sub, "%d.tif" % i))
+            Image.fromarray(rng.randint(0, 6, (h, w), dtype=np.uint8)).save(os.path.join(root, sub + "_convert_labels", "%d.png" % i))
+    cfg = update_config(get_config(), argparse.Namespace(cfg=CFG))
+    cfg.DATA.DATA_PATH = root
+    cfg.DATA.CROP_SIZE = [48, 32]
+    return cfg
+
+
+@pytest.fixture
+def fake():
+    from tests import fake_abi
+    f = fake_abi.install()
+    yield f
+    fake_abi.uninstall()
+
+
+def _calls(fake, ds, workers, nbatches, seed=7):
+    np.random.seed(seed)
+    random.seed(seed)
+    fake.calls.clear()
+    gen = DeviceTileLoader(ds, DistributedTileSampler(len(ds), 3, 0, 1, shuffle=True, seed=1), "cpu", workers=workers, prefetch=2).epochs()
+    outs = [next(gen) for _ in range(nbatches)]
+    calls = list(fake.calls[:nbatches])
+    _close(gen)
+    return outs, calls
+
+
+def _close(gen):
+    """Stop a loader and wait for its threads: a worker that was prefetching finishes its draws first, and the next seed must not race them."""
+    before = set(threading.enumerate())
+    gen.close()
+    for t in before:
+        if t is not threading.main_thread() and t.daemon:
+            t.join(timeout=10)
+
+
+def test_loader_calls_entry_point_with_header_arguments_in_draw_order(fake, tmp_path):
+    """Through the recording stand-in (tests/fake_abi.py, which checks every call against the header's argument list): one
+    emrt_augment_tiles call per batch, descriptors that address the packed buffer sample by sample, and the same decisions with 1 and
+    4 reader threads, which are the planner's decisions drawn in batch and sample order."""
+    sizes = [(40, 50), (20, 30), (32, 48), (57, 33), (32, 48), (70, 64)]
+    cfg = _tree(str(tmp_path / "p"), sizes)
+    ds = get_dataset(cfg, T.get_transforms(cfg), "train")
+    outs, calls = _calls(fake, ds, 1, 5)                   # 2 batches per epoch: crosses two epoch boundaries
+    assert [c[0] for c in calls] == ["emrt_augment_tiles"] * 5
+    for (img, lab), (_, args) in zip(outs, calls):
+        assert img.shape == (3, 3, 32, 48) and img.dtype == torch.float32 and lab.shape == (3, 32, 48) and lab.dtype == torch.int64
+        src, nbytes, descs, B, OH, OW, mean, sinv, pad, lpad, lut, out, out_bs, labels, stream = args
+        assert (B, OH, OW, out_bs, lpad, lut) == (3, 32, 48, 3 * 32 * 48, 255, None)
+        assert list(mean) == T._MEAN and list(sinv) == list(1.0 / np.asarray(T._STD)) and list(pad) == [0, 0, 0]
+        off = 0
+        for d in descs:
+            assert (d.img_off, d.lab_off) == (off, off + 3 * d.H * d.W) and (d.H, d.W) in sizes
+            off += 4 * d.H * d.W
+        assert nbytes == off
+    sampler = DistributedTileSampler(len(ds), 3, 0, 1, shuffle=True, seed=1)
+    np.random.seed(7)
+    random.seed(7)
+    dp = T.DevicePlan(T.get_transforms(cfg))
+    want, ep = [], 0
+    while len(want) < 5:
+        sampler.set_epoch(ep)
+        ep += 1
+        for idx in sampler:
+            want.append([tuple(dp.plan(*sizes[i])) for i in idx])
+    got = [[(d.H, d.W, d.h, d.w, d.off_y, d.off_x, d.flip) for d in args[2]] for _, args in calls]
+    assert got == want[:5]
+    _, calls4 = _calls(fake, ds, 4, 5)
+    assert [[(d.H, d.W, d.h, d.w, d.off_y, d.off_x, d.flip) for d in a[2]] for _, a in calls4] == got
+
+
+def test_loader_refuses_mixed_output_sizes_without_a_crop(fake, tmp_path):
+    """LoveDA's chain has no crop: a batch must share one source size (np.stack needs it there too); the error reaches the consumer."""
+    root = str(tmp_path / "l")
+    for sub in ("images_png", "masks_png"):
+        os.makedirs(os.path.join(root, "Train", sub))
+    for i, (h, w) in enumerate([(20, 30), (20, 30), (24, 30)]):
+        Image.fromarray(np.zeros((h, w, 3), np.uint8)).save(os.path.join(root, "Train", "images_png", "%d.png" % i))
+        Image.fromarray(np.ones((h, w), np.uint8)).save(os.path.join(root, "Train", "masks_png", "%d.png" % i))
+    cfg = update_config(get_config(), argparse.Namespace(cfg=CFG))
+    cfg.DATA.DATASET, cfg.DATA.DATA_PATH = "LoveDA", root
+    ds = get_dataset(cfg, T.get_transforms(cfg), "train")
+    gen = DeviceTileLoader(ds, DistributedTileSampler(3, 3, 0, 1, shuffle=False), "cpu", workers=2).epochs()
+    with pytest.raises(ValueError, match="different output sizes"):
+        next(gen)
+    _close(gen)
+    gen = DeviceTileLoader(ds, DistributedTileSampler(2, 2, 0, 1, shuffle=False), "cpu", workers=2).epochs()
+    next(gen)
+    assert fake.calls[-1][1][10] is not None          # LoveDA's label shift goes down as the lookup table
+    _close(gen)
