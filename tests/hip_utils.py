@@ -1,6 +1,7 @@
 """Helpers for the -m gpu parity tests: host<->device layout conversion and a tiny parameter store for single layers."""
 import contextlib
 import fcntl
+import math
 import os
 import tempfile
 
@@ -108,6 +109,113 @@ def close_gemm(name, got, ref, dtype, out_bits=None):
         idx = torch.nonzero(bad)[0].tolist()
         raise AssertionError("%s: %d/%d elements beyond the contraction-derived bound; max |diff| %.4g at rms(ref) %.4g; first at %s got %.6g ref %.6g" % (
             name, int(bad.sum()), bad.numel(), err.max().item(), rms, idx, got[tuple(idx)].item(), ref[tuple(idx)].item()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# float16 kernel parity (tests/test_gpu_fp16_kernels.py).  References are float64 torch on the CPU, computed from operands that were
+# already rounded through float16, so kernel and reference see identical inputs; what may differ is (a) the ONE rounding of the stored
+# result, at most half a float16 ulp of the exact value, and (b) the kernel's fp32 arithmetic in front of it, bounded by `slack`.
+# ---------------------------------------------------------------------------------------------------------------------------------
+EPS32 = 2.0 ** -24          # unit round-off of fp32
+F16_MAX = 65504.0
+F16_INF_FROM = 65520.0      # |x| >= this rounds to inf in float16 (round to nearest even: half way between 65504 and 2^16)
+SLACK_USE = []              # (name, worst (err - ulp/2) / slack) of every close_f16 call of this process, in call order
+
+
+def ulp16(x):
+    """Spacing of float16 at |x| (float64 tensor): 2^(e - 10) in the binade [2^e, 2^(e + 1)), 2^-24 below 2^-14 (subnormals), 32 from 2^15 up."""
+    a = x.abs().double().clamp(2.0 ** -14, 2.0 ** 15)
+    _, ex = torch.frexp(a)                                   # a = m * 2^ex with m in [0.5, 1)
+    return torch.ldexp(torch.ones_like(a), ex - 11)
+
+
+def ulp32(x):
+    a = x.abs().double().clamp_min(2.0 ** -126)
+    _, ex = torch.frexp(a)
+    return torch.ldexp(torch.ones_like(a), ex - 24)
+
+
+def round16(x):
+    """float64 -> nearest float16 value (ties to even, overflow to inf from 65520), as float64.  Done on the float16 grid directly:
+    a float64 -> float32 -> float16 cast chain would round twice."""
+    x = x.double()
+    u = ulp16(x)
+    r = torch.round(x / u) * u                               # torch.round: half to even
+    return torch.where(r.abs() >= 65536.0, torch.sign(x) * float("inf"), r)
+
+
+def gemm_slack(K, sq):
+    """fp32 accumulation error of a contraction of length K.  sq = the same operator applied to the SQUARED operands (float64), i.e. the sum
+    of the squared terms of each output.  K roundings of relative size <= 2^-24 on partial sums of random-sign terms walk sqrt(K) * 2^-24 *
+    sqrt(sum of squared terms); 8 is the margin.  (The worst-case bound K * 2^-24 * sum |terms| is 1 to 126 float16 ulps at K = 64..13 824 and
+    would hide a wrong rounding of the result: not used.)"""
+    return 8.0 * math.sqrt(K) * EPS32 * sq.double().clamp_min(0).sqrt()
+
+
+def terms_slack(*terms):
+    """The same bound for a kernel whose output is a short fp32 expression of K = len(terms) terms (interpolation, pooling, elementwise,
+    an epilogue): 8 sqrt(K) 2^-24 sqrt(sum of the squared terms).  Terms are float64 tensors broadcastable to the output."""
+    sq = None
+    for t in terms:
+        sq = t.double() ** 2 if sq is None else sq + t.double() ** 2
+    return 8.0 * math.sqrt(len(terms)) * EPS32 * sq.sqrt()
+
+
+def close_f16(name, got, ref64, slack, out_f32=False):
+    """Elementwise |got - ref64| <= ulp16(ref64) / 2 + slack (ulp32 for an fp32 output of a float16 kernel).  `slack` bounds the kernel's fp32
+    arithmetic only and comes from the reference (gemm_slack / terms_slack / a derived term the caller documents), never from a measured error.
+    Overflow: got is inf (of ref64's sign) exactly where ref64 rounds to inf in float16, finite elsewhere; only within `slack` of the
+    threshold 65520 either is accepted.  Prints and records the worst (err - ulp / 2) / slack; returns it."""
+    got = got.detach().double().cpu()
+    ref64 = ref64.detach().double().cpu()
+    slack = torch.as_tensor(slack, dtype=torch.float64).expand_as(ref64) if not torch.is_tensor(slack) else slack.double().expand_as(ref64)
+    assert got.shape == ref64.shape, "%s: shape %s vs %s" % (name, tuple(got.shape), tuple(ref64.shape))
+    assert not torch.isnan(got).any(), "%s: NaN in the output" % name
+    half = 0.5 * (ulp32(ref64) if out_f32 else ulp16(ref64))
+    if out_f32:
+        finite = torch.ones_like(ref64, dtype=torch.bool)
+        assert torch.isfinite(got).all(), "%s: non-finite fp32 output" % name
+    else:
+        over = ref64.abs() >= F16_INF_FROM
+        band = (ref64.abs() - F16_INF_FROM).abs() <= slack
+        ginf = torch.isinf(got)
+        wrong = (ginf != over) & ~band
+        if wrong.any():
+            idx = tuple(torch.nonzero(wrong)[0].tolist())
+            raise AssertionError("%s: %d outputs overflow on one side only; first at %s got %r ref %r" % (
+                name, int(wrong.sum()), idx, got[idx].item(), ref64[idx].item()))
+        both = ginf & over
+        assert (torch.sign(got[both]) == torch.sign(ref64[both])).all(), "%s: inf of the wrong sign" % name
+        finite = ~ginf & ~over
+    err = (got - ref64).abs()
+    excess = torch.where(finite, err - half, torch.zeros_like(err))
+    use = torch.where(slack > 0, excess / slack.clamp_min(1e-300), torch.where(excess > 0, torch.full_like(excess, float("inf")), torch.zeros_like(excess)))
+    worst = use.max().item() if use.numel() else 0.0
+    SLACK_USE.append((name, worst))
+    print("[close_f16] %-44s n=%-9d worst (err - ulp/2) / slack = %+.3f" % (name, ref64.numel(), worst))
+    bad = finite & (excess > slack)
+    if bad.any():
+        idx = tuple(torch.nonzero(bad)[0].tolist())
+        raise AssertionError("%s: %d/%d outputs beyond ulp16/2 + slack; worst excess / slack %.3g; first at %s got %.9g ref %.9g (ulp/2 %.3g, slack %.3g)" % (
+            name, int(bad.sum()), bad.numel(), worst, idx, got[idx].item(), ref64[idx].item(), half[idx].item(), slack[idx].item()))
+    return worst
+
+
+def rounding_is_nearest(name, got, ref64):
+    """A result rounded to nearest errs uniformly in +-ulp/2: over the outputs with |ref64| >= rms(ref64) / 4 the mean of (|got| - |ref64|) /
+    ulp16 is within 6 standard errors (0.289 / sqrt(n)) of zero.  Truncation (round toward zero) sits at -0.5.  Needs n >= 1e5 outputs after
+    the filter (enlarge the case, not the bound).  Returns the mean."""
+    got = got.detach().double().cpu().reshape(-1)
+    ref64 = ref64.detach().double().cpu().reshape(-1)
+    rms = ref64.pow(2).mean().sqrt()
+    sel = (ref64.abs() >= rms / 4) & (ref64.abs() < F16_MAX) & torch.isfinite(got)
+    n = int(sel.sum())
+    assert n >= 100000, "%s: %d outputs after the filter, need 1e5" % (name, n)
+    bias = ((got[sel].abs() - ref64[sel].abs()) / ulp16(ref64[sel])).mean().item()
+    bound = 6 * 0.289 / math.sqrt(n)
+    print("[rounding_is_nearest] %-34s n=%d mean signed error %+.5f ulp16 (bound %.5f)" % (name, n, bias, bound))
+    assert abs(bias) <= bound, "%s: mean of (|got| - |ref|) / ulp16 = %+.5f over %d outputs, bound %.5f (truncation gives -0.5)" % (name, bias, n, bound)
+    return bias
 
 
 # Processes that may hold the GPU at one time while the suite runs: the test workers (each one opens the device) and the rank processes of a
