@@ -13,7 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libemrt_hip.so")
 SOURCES = ["conv.hip", "norm.hip", "msda.hip", "attn.hip", "spatial.hip", "loss_optim.hip", "elementwise.hip", "gconv.hip", "augment.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
+HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip.h")      # the public C-ABI: csrc/common.hpp includes it, so it is an input of every object
+# (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
 
 def _hipcc():
@@ -52,8 +54,8 @@ def _fresh(target, digest):
 
 
 def source_digest():
-    """Content hash of everything libemrt_hip.so is built from: csrc/*.hip, csrc/*.hpp, the compiler path and the flags."""
-    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]
+    """Content hash of everything libemrt_hip.so is built from: csrc/*.hip, csrc/*.hpp, include/emrt_hip.h, the compiler path and the flags."""
+    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [HEADER]
     return _digest([os.path.join(CSRC, s) for s in SOURCES] + hdrs, [_hipcc()] + FLAGS)
 
 
@@ -62,7 +64,7 @@ LAST_BUILD = {"mode": None, "digest": None, "compiled": []}      # what the last
 
 def build(force=False, verbose=True):
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")]      # common.hpp, igemm8p.hpp (included by conv.hip)
+    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [HEADER]      # common.hpp (includes the public header), igemm8p.hpp (included by conv.hip)
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
@@ -73,7 +75,7 @@ def build(force=False, verbose=True):
             jobs.append(([hipcc] + FLAGS + ["-c", s, "-o", o], o, d))
 
     def run(cmd):
-        r = subprocess.run(cmd, capture_output=True, text=True)
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed: %s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
 

@@ -13,12 +13,6 @@
 #pragma clang fp contract(off)
 #include "common.hpp"
 
-// Plain-C descriptor of one sample (include/emrt_hip.h, restated here as conv.hip restates EmrtConvDesc)
-struct EmrtAugDesc {
-  long long img_off, lab_off;
-  int H, W, h, w, off_y, off_x, flip;
-};
-
 namespace emrt {
 namespace {
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include "../../include/emrt_hip.h"      // the public C-ABI: every definition under csrc/ is compiled against its prototype and its descriptor structs
 
 #define EMRT_F32 0
 #define EMRT_BF16 1

@@ -27,48 +27,48 @@ typedef __attribute__((ext_vector_type(4))) short short4_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 struct ConvArgs {
-  const void* in;
-  const void* w;
-  void* out;
-  const float* bias;
-  const float* scale;   // optional per-output-channel factor applied to the accumulator before the bias: an eval-mode BatchNorm folded
-                        // into the convolution (y = conv * gamma / sqrt(var + eps) + (beta - mean * gamma / sqrt(var + eps)))
-  const void* res;
-  int N, H, W, C, ldin;
-  long long in_bs;
-  int OH, OW, OC, ldout;
-  long long out_bs;
-  int ldres;
-  long long res_bs;
-  int KH, KW, stride, pad;
-  int dil;         // dilation of the kernel taps (resnet50c's dilated stages, backbones/resnet.py:65-66); 1 everywhere else
-  int relu, out_f32;
-  int cmajor;      // igemm8p only: channel-block-major k order (developer A/B knob igemm8p_cmajor), 0 everywhere else
-  double* stats;   // optional [8][2*OC]: per-channel sum / sum of squares of the STORED outputs (BatchNorm statistics);
-                   // fp64 atomics spread over 8 replicas (by M-tile index) so that blocks do not pile onto one address
+  const void* in = nullptr;
+  const void* w = nullptr;
+  void* out = nullptr;
+  const float* bias = nullptr;
+  const float* scale = nullptr;      // optional per-output-channel factor applied to the accumulator before the bias: an eval-mode BatchNorm folded
+                                     // into the convolution (y = conv * gamma / sqrt(var + eps) + (beta - mean * gamma / sqrt(var + eps)))
+  const void* res = nullptr;
+  int N = 0, H = 0, W = 0, C = 0, ldin = 0;
+  long long in_bs = 0;
+  int OH = 0, OW = 0, OC = 0, ldout = 0;
+  long long out_bs = 0;
+  int ldres = 0;
+  long long res_bs = 0;
+  int KH = 0, KW = 0, stride = 0, pad = 0;
+  int dil = 1;             // dilation of the kernel taps (resnet50c's dilated stages, backbones/resnet.py:65-66); 1 everywhere else
+  int relu = 0, out_f32 = 0;
+  int cmajor = 0;          // igemm8p only: channel-block-major k order (developer A/B knob igemm8p_cmajor), 0 everywhere else
+  double* stats = nullptr; // optional [8][2*OC]: per-channel sum / sum of squares of the STORED outputs (BatchNorm statistics);
+                           // fp64 atomics spread over 8 replicas (by M-tile index) so that blocks do not pile onto one address
   // optional ReLU mask: outputs are zeroed where mask_y <= 0 (same geometry as the output, own strides), and with it the
   // statistics become (sum v, sum v * mask_y).  dgrad of a conv whose input is y = relu(BatchNorm(x)) uses it to produce
   // the masked dy AND that BatchNorm's backward sums in one pass: where y > 0, xhat = (y - beta) / gamma.
-  const void* mask_y;
-  float mask_scale;   // kept outputs are multiplied by this (1 for a ReLU; 1/(1-p) for dropout(relu(.)))
+  const void* mask_y = nullptr;
+  float mask_scale = 1.f;      // kept outputs are multiplied by this (1 for a ReLU; 1/(1-p) for dropout(relu(.)))
   // optional: the second statistic multiplies with this tensor instead of mask_y (same geometry, own strides): the
   // BatchNorm INPUT when mask_y is the output of relu(BatchNorm(x) + residual), whose xhat cannot be recovered from y
-  const void* stat_x;
-  int ldsx;
-  long long sx_bs;
-  int ldy;
-  long long y_bs;
+  const void* stat_x = nullptr;
+  int ldsx = 0;
+  long long sx_bs = 0;
+  int ldy = 0;
+  long long y_bs = 0;
   // cross-block K split (igemm_body<..., XK>): the grid is xk_S copies of the tile grid, copy s walks the k-tiles [s * per, (s + 1) * per);
   // partial fp32 tiles go to xk_part [tile][s][BM][BN], arrivals are counted in xk_tick[tile], and the LAST block to arrive sums the
   // partials (in s order: bit-reproducible) and runs the epilogue.  0 / nullptr everywhere else.
-  int xk_S;
-  float* xk_part;
-  unsigned* xk_tick;
+  int xk_S = 0;
+  float* xk_part = nullptr;
+  unsigned* xk_tick = nullptr;
   // optional inverted dropout of the stored outputs, after the ReLU (emrt_conv2d_drop: linear1 -> ReLU -> Dropout of the FFN, t_e_d.py:157-161):
   // kept values are multiplied by 1 / (1 - p); the mask comes from drop_words8(seed, salt, (row * OC + col) / 8)
-  const unsigned long long* drop_seed;
-  unsigned drop_salt;
-  float drop_p;
+  const unsigned long long* drop_seed = nullptr;
+  unsigned drop_salt = 0;
+  float drop_p = 0.f;
   // A-operand BatchNorm (igemm_body<..., BNA>; emrt_conv2d_bna): `in` is the RAW output of the producing conv whose training-mode BatchNorm (+ ReLU) has
   // not been applied.  Every block derives the per-channel scale / shift from the complete fp64 batch sums in its preamble (bn_operand.hpp, as the
   // other consumers that apply a BatchNorm on load) and turns every 16-byte chunk it loads into [relu](x * scale + shift) between the global load and
@@ -825,19 +825,19 @@ __global__ __launch_bounds__(256, 4) void igemm_xk_bna_kernel(ConvArgs p) {
 // ds_read_b64_tr_b16 (bf16) or plain ds_read_b32 (f32, one k-slot per lane).
 // ------------------------------------------------------------------------------------------------
 struct WgradArgs {
-  const void* x;
-  const void* dy;
-  float* dw;
-  int N, H, W, C, ldx;
-  long long x_bs;
-  int OH, OW, OC, lddy;
-  long long dy_bs;
-  int KH, KW, stride, pad;
-  int dil;              // dilation of the kernel taps
-  int tiles_per_split;  // number of BKm pixel tiles each z-slice processes
-  float* dbias;         // optional [OC]: += sum_m dy[m][oc] (bias gradient), accumulated by the k-tile-0 blocks from the dy tiles they stream
-  int overwrite;        // 1: the caller vouches that dw is all zero AND this launch has ONE pixel slice: the tile is stored, not added with atomics
-                        // (fp32 atomics run at 1.3 TB/s against ~6 TB/s for stores: layer3 / layer4's large dW with few pixels is all epilogue)
+  const void* x = nullptr;
+  const void* dy = nullptr;
+  float* dw = nullptr;
+  int N = 0, H = 0, W = 0, C = 0, ldx = 0;
+  long long x_bs = 0;
+  int OH = 0, OW = 0, OC = 0, lddy = 0;
+  long long dy_bs = 0;
+  int KH = 0, KW = 0, stride = 0, pad = 0;
+  int dil = 1;              // dilation of the kernel taps
+  int tiles_per_split = 0;  // number of BKm pixel tiles each z-slice processes
+  float* dbias = nullptr;   // optional [OC]: += sum_m dy[m][oc] (bias gradient), accumulated by the k-tile-0 blocks from the dy tiles they stream
+  int overwrite = 0;        // 1: the caller vouches that dw is all zero AND this launch has ONE pixel slice: the tile is stored, not added with atomics
+                            // (fp32 atomics run at 1.3 TB/s against ~6 TB/s for stores: layer3 / layer4's large dW with few pixels is all epilogue)
 };
 
 template <class T>
@@ -1199,6 +1199,24 @@ static int launch_igemm(const ConvArgs& a, hipStream_t st) {
   return launch_igemm_nst<T, TM, TN, WR, WC, MODE, VEC, G, NST>(a, st);
 }
 
+// the vector path: C in whole 16-byte chunks, rows and images of `in` and the weight 16-byte aligned
+template <class T>
+static bool conv_is_vec(const ConvArgs& a) {
+  constexpr int EPC = 16 / (int)sizeof(T);
+  return (a.C % EPC == 0) && (a.ldin % EPC == 0) && (a.in_bs % EPC == 0) && (((uintptr_t)a.in) % 16 == 0) && (((uintptr_t)a.w) % 16 == 0);
+}
+
+static long long conv_blocks(const ConvArgs& a, int bm, int bn) {      // grid of bm x bn output tiles
+  const long long M = (long long)a.N * a.OH * a.OW;
+  return ((M + bm - 1) / bm) * ((a.OC + bn - 1) / bn);
+}
+
+template <class T>
+static int conv_k_tiles(const ConvArgs& a) {      // k-tiles of the 64x64 / 128x128 kernels' loop
+  constexpr int BK = 8 * (16 / (int)sizeof(T));
+  return (a.KH * a.KW * a.C + BK - 1) / BK;
+}
+
 // stride-2 data gradient through the parity-class kernel: whole classes per 64-row tile, 64-channel k-tiles, the row-vectorised epilogue
 template <class T>
 static bool igemm_s2_ok(const ConvArgs& a) {
@@ -1221,16 +1239,14 @@ static bool igemm_s2_ok(const ConvArgs& a) {
 template <class T>
 static int igemm_xk_copies(const ConvArgs& a, hipStream_t st, int want) {
   constexpr int EPC = 16 / (int)sizeof(T);
-  constexpr int BK = 8 * EPC;
   if (sizeof(T) != 2 || g_tune.xk < 0 || !g_scratch.xk_part || !g_scratch.tick || g_scratch.stream != (void*)st) return 0;
   if (a.OC <= 32 || a.OC % 8 || a.out_f32) return 0;
   auto al = [](const void* q) { return ((uintptr_t)q) % 16 == 0; };
   if (!al(a.out) || (a.res && !al(a.res)) || (a.mask_y && !al(a.mask_y)) || (a.stat_x && !al(a.stat_x))) return 0;
   if (a.ldout % EPC || a.out_bs % EPC || (a.res && (a.ldres % EPC || a.res_bs % EPC)) || (a.mask_y && (a.ldy % EPC || a.y_bs % EPC)) ||
       (a.stat_x && (a.ldsx % EPC || a.sx_bs % EPC))) return 0;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long nb = ((M + 63) / 64) * ((a.OC + 63) / 64);
-  const int nkt = (a.KH * a.KW * a.C + BK - 1) / BK;
+  const long long nb = conv_blocks(a, 64, 64);
+  const int nkt = conv_k_tiles<T>(a);
   int S = want;
   if (S <= 0) {
     // Measured on MI355X (tools/bench_conv.py xk, profiles/r5_xk_sweep.txt; us, old choice -> S = 2 / 4 / 8): the seam -- write-through drain, ticket,
@@ -1256,95 +1272,225 @@ static int igemm_xk_copies(const ConvArgs& a, hipStream_t st, int want) {
 template <class T, int MODE>
 static int launch_igemm_xk(const ConvArgs& a0, hipStream_t st, int S) {
   ConvArgs a = a0;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long nb = ((M + 63) / 64) * ((a.OC + 63) / 64);
+  const long long nb = conv_blocks(a, 64, 64);
   a.xk_S = S; a.xk_part = g_scratch.xk_part; a.xk_tick = g_scratch.tick;
   hipLaunchKernelGGL((igemm_xk_kernel<T, MODE>), dim3((unsigned)(nb * S)), dim3(256), (size_t)2 * 128 * 144, st, a);
   return check_launch("emrt_conv2d");
 }
 
+// ---- the plan of one launch: which kernel runs a convolution is decided ONCE, by conv_plan (no launch, no state), and carried out by conv_launch.
+// emrt_conv2d_bna_supported asks the same plan; the pair decision of conv_bwd_dispatch asks conv_takes_128, the ladder's own 128x128 rung.
+// (tests/test_gpu_bench_shapes.py: _expected_paths is the tests' own statement of the ladder; tests/test_conv_plan_cpu.py pins it through a recorded table)
+
+// measured on MI355X (tools/bench_conv.py): 128x128 tiles win only when the k loop is long enough to amortise their
+// prologue / epilogue (>= 16 k-tiles) and there is at least one block per CU; everything else is fastest on 64x64
+template <class T>
+static bool conv_takes_128(const ConvArgs& a) {
+  return a.OC > 64 && conv_k_tiles<T>(a) >= 16 && conv_blocks(a, 128, 128) >= 256;
+}
+
+enum ConvKind {
+  CONV_NONE,        // nothing takes it: the dropout epilogue off the vector path (conv_launch fails), a layer without operand transform (bna_plan)
+  CONV_DROP,        // 64x64 tile whose epilogue draws the dropout mask (emrt_conv2d_drop)
+  CONV_S2,          // parity-class kernel: data gradient of a stride-2 convolution
+  CONV_128x64,      // a forced tile only (knob conv_tile = 2): no rung of the ladder ends here
+  CONV_256x32,
+  CONV_XK,          // 64x64 tile, K cut over n copies of the tile grid (cross-block split)
+  CONV_8P,          // the 256x256 LDS-DMA kernel (igemm8p.hpp)
+  CONV_128,         // 128x128 tile, n = 1 or 2 wave groups (2: K split inside the block)
+  CONV_64           // 64x64 tile, n = 1, 2 or 4 wave groups (K split inside the block)
+};
+struct ConvPlan {
+  ConvKind kind;
+  int n;            // wave groups (CONV_64, CONV_128) or copies (CONV_XK)
+  bool forced;      // the knob conv_tile named this tile, not the ladder
+};
+
 template <class T, int MODE, bool VEC>
-static int conv_pick_tile(const ConvArgs& a, hipStream_t st) {
-  const long long M = (long long)a.N * a.OH * a.OW;
-  auto blocks = [&](int bmv, int bnv) { return ((M + bmv - 1) / bmv) * ((a.OC + bnv - 1) / bnv); };
+static ConvPlan conv_plan(const ConvArgs& a, hipStream_t st) {
+  constexpr bool VEC2 = VEC && sizeof(T) == 2;
   if (a.drop_seed) {      // emrt_conv2d_drop: the 64x64 tile with the dropout epilogue (the FFN's first linear: short K, thousands of tiles)
-    if constexpr (MODE == 0 && VEC && sizeof(T) != 0) {
-      constexpr int EPC = 16 / (int)sizeof(T);
-      const bool vec_out = ((uintptr_t)a.out) % 16 == 0 && a.ldout % EPC == 0 && a.out_bs % EPC == 0 && a.OC % 8 == 0 && !a.out_f32 && !a.res && !a.mask_y;
-      if (vec_out) {
-        hipLaunchKernelGGL((igemm_drop_kernel<T>), dim3((unsigned)blocks(64, 64)), dim3(256), (size_t)2 * 128 * 144, st, a);
-        return check_launch("emrt_conv2d_drop");
-      }
-    }
-    return fail("emrt_conv2d_drop", "needs 16-byte aligned rows of C, OC multiples of 8 elements (the vector path)");
+    constexpr int EPC = 16 / (int)sizeof(T);
+    const bool vec_out = ((uintptr_t)a.out) % 16 == 0 && a.ldout % EPC == 0 && a.out_bs % EPC == 0 && a.OC % 8 == 0 && !a.out_f32 && !a.res && !a.mask_y;
+    return {MODE == 0 && VEC && vec_out ? CONV_DROP : CONV_NONE, 1, false};
   }
-  if constexpr (MODE == 1 && VEC) {
-    if (!g_tune.conv_tile && igemm_s2_ok<T>(a)) {
-      // measured (tools/bench_conv.py s2): the three 3x3 stride-2 data gradients of the ResNet-50 step 25.3 / 24.3 / 27.3 -> 13.8 / 13.0 / 14.5 us
-      hipLaunchKernelGGL((igemm_s2_kernel<T>), dim3((unsigned)blocks(64, 64)), dim3(256), (size_t)2 * 128 * 144, st, a);
-      return check_launch("emrt_conv2d");
-    }
+  // measured (tools/bench_conv.py s2): the three 3x3 stride-2 data gradients of the ResNet-50 step 25.3 / 24.3 / 27.3 -> 13.8 / 13.0 / 14.5 us
+  if (MODE == 1 && VEC && !g_tune.conv_tile && igemm_s2_ok<T>(a)) return {CONV_S2, 1, false};
+  switch (g_tune.conv_tile) {      // developer knob for tools/bench_conv.py; 0 in production.  A tile this layer cannot take goes down the ladder (minus the cross-block split)
+    case 1: return {CONV_64, 1, true};
+    case 2: return {CONV_128x64, 1, true};
+    case 3: return {CONV_128, 1, true};
+    case 4: return {CONV_256x32, 1, true};
+    case 5: if (VEC) return {CONV_64, 2, true}; break;
+    case 6: if (VEC) return {CONV_64, 4, true}; break;
+    case 7: if (VEC2 && igemm8p_ok<T>(a)) return {CONV_8P, 1, true}; break;
+    case 8: if (VEC2) return {CONV_128, 2, true}; break;      // 128x128, K split over two wave groups
+    default: break;
   }
-  if (g_tune.conv_tile) {                               // developer knob for tools/bench_conv.py; 0 in production
-    switch (g_tune.conv_tile) {
-      case 1: return launch_igemm<T, 1, 1, 2, 2, MODE, VEC>(a, st);
-      case 2: return launch_igemm<T, 2, 1, 2, 2, MODE, VEC>(a, st);
-      case 3: return launch_igemm<T, 2, 2, 2, 2, MODE, VEC>(a, st);
-      case 4: return launch_igemm<T, 2, 1, 4, 1, MODE, VEC>(a, st);
-      case 5: if constexpr (VEC) return launch_igemm<T, 1, 1, 2, 2, MODE, VEC, 2>(a, st); break;
-      case 6: if constexpr (VEC) return launch_igemm<T, 1, 1, 2, 2, MODE, VEC, 4>(a, st); break;
-      case 7: if constexpr (VEC && sizeof(T) == 2) { if (igemm8p_ok<T>(a)) return launch_igemm8p<T, MODE>(a, st); } break;
-      case 8: if constexpr (VEC && sizeof(T) == 2) return launch_igemm<T, 2, 2, 2, 2, MODE, VEC, 2>(a, st); break;      // 128x128, K split over two wave groups
-      default: break;
-    }
+  if (a.OC <= 32) return {CONV_256x32, 1, false};
+  if (VEC2 && !g_tune.conv_tile) {
+    const int S = igemm_xk_copies<T>(a, st, g_tune.xk > 0 ? g_tune.xk : 0);
+    if (S >= 2) return {CONV_XK, S, false};
   }
-  if (a.OC <= 32) return launch_igemm<T, 2, 1, 4, 1, MODE, VEC>(a, st);
-  if constexpr (VEC && sizeof(T) == 2) {
-    if (!g_tune.conv_tile) {
-      const int S = igemm_xk_copies<T>(a, st, g_tune.xk > 0 ? g_tune.xk : 0);
-      if (S >= 2) return launch_igemm_xk<T, MODE>(a, st, S);
-    }
-  }
-  if constexpr (VEC && sizeof(T) == 2) {
+  if (VEC2) {
     // the 256 x 256 LDS-DMA kernel (igemm8p.hpp) wins once its grid covers most of the 256 CUs (one 128 KiB block per CU), or about half
     // of them with a long k loop; measured with tools/bench_conv.py big: UpHead conv_2 214 -> 149 us, cls_psp.0 dgrad 154 -> 110 us at
     // batch 8; 256-block grids 98 -> 72 us; 128-block grids tie at 36 k-tiles and win 276 -> 250 us at 216; 64-block grids lose
-    const long long nb256 = blocks(256, 256);
+    const long long nb256 = conv_blocks(a, 256, 256);
     const int nkt64 = a.KH * a.KW * a.C / 64;
     const int minb = g_tune.igemm8p_min_blocks;
-    if (minb > 0 && nkt64 >= 16 && (nb256 >= minb || (nb256 >= (minb * 3) / 5 && nkt64 >= 144)) && igemm8p_ok<T>(a)) return launch_igemm8p<T, MODE>(a, st);
+    if (minb > 0 && nkt64 >= 16 && (nb256 >= minb || (nb256 >= (minb * 3) / 5 && nkt64 >= 144)) && igemm8p_ok<T>(a)) return {CONV_8P, 1, false};
     // (Round 6 tried the FFN's 256 <-> 1024 linears over 10 752 rows here as well -- a SHORT k loop with a wide output: 168 tiles of 256x256 pull a quarter
     // of the 64x64 grid's 172 MB of operands.  Alone the kernels win (tools/bench_conv.py mid: forward 21.4 -> 17.5 us, data gradient 20.4 -> 16.9 us);
     // inside the captured step, with linear2's mask epilogue reading the 22 MB activation, the data gradient took 29.8 us against 27.5 us on the 64x64 tile
     // and the forward 22.4 against 24.2 (profiles/r6a_timeline_cfg2.txt): +1 us per layer in all, not kept.)
   }
-  // measured on MI355X (tools/bench_conv.py): 128x128 tiles win only when the k loop is long enough to amortise their
-  // prologue / epilogue (>= 16 k-tiles) and there is at least one block per CU; everything else is fastest on 64x64
-  constexpr int BK = 8 * (16 / (int)sizeof(T));
-  const int nkt = (a.KH * a.KW * a.C + BK - 1) / BK;
-  if constexpr (VEC && sizeof(T) == 2) {
+  const int nkt = conv_k_tiles<T>(a);
+  if (conv_takes_128<T>(a)) {
     // exactly one 128x128 block per CU and a long k loop: a second wave group walking the other half of the k-tiles (147 KB of LDS) keeps
     // the MFMA pipe fed where 4 waves per CU cannot (measured: the decoder's 32x32x1536 -> 512 3x3 forward 158 -> 138 us, 32x32x512 -> 256 data
     // gradient 35.8 -> 32.2; with two rounds of blocks -- 512 at 64x64x256 -> 256 -- the plain tile wins 51 vs 63)
-    if (a.OC > 64 && nkt >= 32 && blocks(128, 128) == 256 && !g_tune.no_ksplit128) return launch_igemm<T, 2, 2, 2, 2, MODE, VEC, 2>(a, st);
+    const bool ksplit = VEC2 && nkt >= 32 && conv_blocks(a, 128, 128) == 256 && !g_tune.no_ksplit128;
+    return {CONV_128, ksplit ? 2 : 1, false};
   }
-  if (a.OC > 64 && nkt >= 16 && blocks(128, 128) >= 256) return launch_igemm<T, 2, 2, 2, 2, MODE, VEC>(a, st);
-  if constexpr (VEC) {
+  if (VEC) {
     // at most one 64x64 block per CU and a long k loop: split K inside the block (see igemm_kernel; thresholds measured)
-    const long long nb = blocks(64, 64);
-    if (nb <= 128 && nkt >= 32) return launch_igemm<T, 1, 1, 2, 2, MODE, VEC, 4>(a, st);
-    if (nb <= 256 && nkt >= 16) return launch_igemm<T, 1, 1, 2, 2, MODE, VEC, 2>(a, st);
+    const long long nb = conv_blocks(a, 64, 64);
+    if (nb <= 128 && nkt >= 32) return {CONV_64, 4, false};
+    if (nb <= 256 && nkt >= 16) return {CONV_64, 2, false};
   }
-  return launch_igemm<T, 1, 1, 2, 2, MODE, VEC>(a, st);
+  return {CONV_64, 1, false};
+}
+
+// (the `if constexpr` guards keep the set of instantiated kernels what it was: conv_plan never names a kind outside them)
+template <class T, int MODE, bool VEC>
+static int conv_launch(const ConvArgs& a, hipStream_t st, const ConvPlan& p) {
+  constexpr bool VEC2 = VEC && sizeof(T) == 2;
+  switch (p.kind) {
+    case CONV_DROP:
+      if constexpr (MODE == 0 && VEC) {
+        hipLaunchKernelGGL((igemm_drop_kernel<T>), dim3((unsigned)conv_blocks(a, 64, 64)), dim3(256), (size_t)2 * 128 * 144, st, a);
+        return check_launch("emrt_conv2d_drop");
+      }
+      break;
+    case CONV_S2:
+      if constexpr (MODE == 1 && VEC) {
+        hipLaunchKernelGGL((igemm_s2_kernel<T>), dim3((unsigned)conv_blocks(a, 64, 64)), dim3(256), (size_t)2 * 128 * 144, st, a);
+        return check_launch("emrt_conv2d");
+      }
+      break;
+    case CONV_128x64: return launch_igemm<T, 2, 1, 2, 2, MODE, VEC>(a, st);
+    case CONV_256x32: return launch_igemm<T, 2, 1, 4, 1, MODE, VEC>(a, st);
+    case CONV_XK:
+      if constexpr (VEC2) return launch_igemm_xk<T, MODE>(a, st, p.n);
+      break;
+    case CONV_8P:
+      if constexpr (VEC2) return launch_igemm8p<T, MODE>(a, st);
+      break;
+    case CONV_128:
+      if constexpr (VEC2) {
+        if (p.n == 2) return launch_igemm<T, 2, 2, 2, 2, MODE, VEC, 2>(a, st);
+      }
+      return launch_igemm<T, 2, 2, 2, 2, MODE, VEC>(a, st);
+    case CONV_64:
+      if constexpr (VEC) {
+        if (p.n == 4) return launch_igemm<T, 1, 1, 2, 2, MODE, VEC, 4>(a, st);
+        if (p.n == 2) return launch_igemm<T, 1, 1, 2, 2, MODE, VEC, 2>(a, st);
+      }
+      return launch_igemm<T, 1, 1, 2, 2, MODE, VEC>(a, st);
+    case CONV_NONE: break;
+  }
+  return fail("emrt_conv2d_drop", "needs 16-byte aligned rows of C, OC multiples of 8 elements (the vector path)");
 }
 
 template <class T, int MODE>
 static int conv_dispatch(const ConvArgs& a, hipStream_t st) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const bool vec = (a.C % EPC == 0) && (a.ldin % EPC == 0) && (a.in_bs % EPC == 0) &&
-                   (((uintptr_t)a.in) % 16 == 0) && (((uintptr_t)a.w) % 16 == 0);
-  return vec ? conv_pick_tile<T, MODE, true>(a, st) : conv_pick_tile<T, MODE, false>(a, st);
+  if (conv_is_vec<T>(a)) return conv_launch<T, MODE, true>(a, st, conv_plan<T, MODE, true>(a, st));
+  return conv_launch<T, MODE, false>(a, st, conv_plan<T, MODE, false>(a, st));
 }
+
+// ---- the kernel-argument structs are filled HERE and nowhere else: whatever a builder does not name keeps its default (ConvArgs, WgradArgs) ----
+// Forward view: out [N][OH][OW][OC] = conv(in [N][H][W][C], w) -- emrt_conv2d's own argument list, so also its mode 1, whose caller has swapped the roles.
+static ConvArgs conv_fwd_args(const void* in, const void* w_packed, void* out, const float* bias, const void* residual, int N, int H, int W, int C, int ldin,
+                              long long in_bs, int OH, int OW, int OC, int ldout, long long out_bs, int ldres, long long res_bs, int KH, int KW, int stride,
+                              int pad, int dilation, int relu, int out_f32, double* bn_stats, int cmajor, const float* out_scale) {
+  ConvArgs a;
+  a.in = in; a.w = w_packed; a.out = out; a.bias = bias; a.scale = out_scale; a.res = residual;
+  a.N = N; a.H = H; a.W = W; a.C = C; a.ldin = ldin; a.in_bs = in_bs;
+  a.OH = OH; a.OW = OW; a.OC = OC; a.ldout = ldout; a.out_bs = out_bs;
+  a.ldres = ldres; a.res_bs = res_bs;
+  a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dilation; a.relu = relu; a.out_f32 = out_f32; a.cmajor = cmajor; a.stats = bn_stats;
+  return a;
+}
+
+// Data-gradient view of the layer x [N][H][W][C] -> y [N][OH][OW][OC]: a convolution of dy with the transposed weights whose output is dx, i.e. the
+// swapped one (in = dy, out = dx).  res: dx itself (accumulate: every element is read and written by the same thread) or the addend (dx = dgrad +
+// gradient contributions made so far).  The epilogue arguments are emrt_conv2d_bwd's; the descriptors without them leave the defaults.
+static ConvArgs conv_dgrad_args(const void* dy, const void* w_bwd_packed, void* dx, int lddx, long long dx_bs, int accumulate, const void* addend, int ldadd,
+                                long long add_bs, int N, int H, int W, int C, int OH, int OW, int OC, int lddy, long long dy_bs, int KH, int KW, int stride,
+                                int pad, int dilation, int cmajor, double* bn_stats = nullptr, const void* mask_y = nullptr, int ldy = 0, long long y_bs = 0,
+                                float mask_scale = 1.f, const void* stat_x = nullptr, int ldsx = 0, long long sx_bs = 0) {
+  ConvArgs d;
+  d.in = dy; d.w = w_bwd_packed; d.out = dx;
+  d.N = N; d.H = OH; d.W = OW; d.C = OC; d.ldin = lddy; d.in_bs = dy_bs;
+  d.OH = H; d.OW = W; d.OC = C; d.ldout = lddx; d.out_bs = dx_bs;
+  if (accumulate) { d.res = dx; d.ldres = lddx; d.res_bs = dx_bs; }
+  else if (addend) { d.res = addend; d.ldres = ldadd; d.res_bs = add_bs; }
+  d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad; d.dil = dilation; d.cmajor = cmajor; d.stats = bn_stats;
+  d.mask_y = mask_y; d.ldy = ldy; d.y_bs = y_bs; d.mask_scale = mask_scale; d.stat_x = stat_x; d.ldsx = ldsx; d.sx_bs = sx_bs;
+  return d;
+}
+
+// Weight-gradient view of the same layer (tiles_per_split is the dispatcher's: wgrad_plan)
+static WgradArgs wgrad_args(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int C, int ldx, long long x_bs, int OH, int OW, int OC,
+                            int lddy, long long dy_bs, int KH, int KW, int stride, int pad, int dilation, int overwrite) {
+  WgradArgs a;
+  a.x = x; a.dy = dy; a.dw = dw; a.dbias = dbias;
+  a.N = N; a.H = H; a.W = W; a.C = C; a.ldx = ldx; a.x_bs = x_bs;
+  a.OH = OH; a.OW = OW; a.OC = OC; a.lddy = lddy; a.dy_bs = dy_bs;
+  a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dilation; a.overwrite = overwrite;
+  return a;
+}
+
+// ---- argument validation of the convolution entry points: ONE statement of every check; each entry point names the ones it makes (and keeps its order:
+// the helper runs dimensions, kernel geometry, size formula, pixel count, extents, 24-bit arithmetic; an entry point that checks in another order, or
+// has a check of its own in between, calls it more than once).  `fn` is the entry point, so messages keep its prefix.
+struct ConvShape { int N, H, W, C, OH, OW, OC, KH, KW, stride, pad, dil; };      // the LAYER: x [N][H][W][C] -> y [N][OH][OW][OC]
+enum {
+  CK_DIMS = 1, CK_KERNEL = 2, CK_SIZE = 4, CK_PIXELS = 8,
+  CK_X = 16, CK_Y = 32, CK_W = 64,      // 2 GiB extent of x (rows ldx, images x_bs), of y (ldy, y_bs), of the weight
+  CK_X24 = 128, CK_Y24 = 256,           // 24-bit address arithmetic of the gathered operand: x, or y (the data gradients gather dy)
+  CK_GROUPED = 512                      // emrt_conv2d_group / emrt_conv2d_bwd_group: their descriptors have no dilation, say "bad dims" for the kernel geometry
+                                        // too, meet OH / OW only in the size formula, and their messages lack the parenthesis
+};
+static bool conv_size_ok(const ConvShape& s) {
+  return s.OH == (s.H + 2 * s.pad - s.dil * (s.KH - 1) - 1) / s.stride + 1 && s.OW == (s.W + 2 * s.pad - s.dil * (s.KW - 1) - 1) / s.stride + 1;
+}
+static int conv_check(const char* fn, const ConvShape& s, int ldx, long long x_bs, int ldy, long long y_bs, int dtype, int checks) {
+  const bool grouped = (checks & CK_GROUPED) != 0;
+  const long long esz = dtype == EMRT_F32 ? 4 : 2, LIM = 1ll << 31;
+  if ((checks & CK_DIMS) && !(s.N > 0 && s.H > 0 && s.W > 0 && s.C > 0 && s.OC > 0 &&
+                              (grouped ? s.KH > 0 && s.KW > 0 && s.stride > 0 && s.pad >= 0 : s.OH > 0 && s.OW > 0)))
+    return fail(fn, "bad dims");
+  if ((checks & CK_KERNEL) && !(s.KH > 0 && s.KW > 0 && s.stride > 0 && s.pad >= 0 && s.dil >= 1)) return fail(fn, "bad kernel geometry");
+  if ((checks & CK_SIZE) && !conv_size_ok(s)) return fail(fn, "output size mismatch");
+  if ((checks & CK_PIXELS) && !((long long)s.N * s.OH * s.OW + 512 < LIM && (long long)s.N * s.H * s.W + 512 < LIM))
+    return fail(fn, grouped ? "more than 2^31 pixels" : "more than 2^31 pixels (32-bit pixel arithmetic)");
+  bool ok = true;
+  if (checks & CK_X) ok = ok && x_bs >= 0 && ((long long)(s.N - 1) * x_bs + ((long long)s.H * s.W - 1) * ldx + s.C) * esz < LIM;
+  if (checks & CK_Y) ok = ok && y_bs >= 0 && ((long long)(s.N - 1) * y_bs + ((long long)s.OH * s.OW - 1) * ldy + s.OC) * esz < LIM;
+  if (checks & CK_W) ok = ok && (long long)s.OC * s.KH * s.KW * s.C * esz < LIM;
+  if (!ok) return fail(fn, grouped ? "operand spans 2 GiB or more" : "operand spans 2 GiB or more (32-bit buffer offsets)");
+  if ((checks & CK_X24) && !((long long)s.H * s.W < (1 << 24) && (long long)ldx * esz < (1 << 24) && s.stride < (1 << 12)))
+    return fail(fn, "map too large for the 24-bit address arithmetic");
+  if ((checks & CK_Y24) && !((long long)s.OH * s.OW < (1 << 24) && (long long)ldy * esz < (1 << 24) && s.stride < (1 << 12)))
+    return fail(fn, "map too large for the 24-bit address arithmetic");
+  return 0;
+}
+#define EMRT_CONV_CHECK(s, ldx, x_bs, ldy, y_bs, dtype, checks)                                  \
+  do {                                                                                           \
+    if (const int rc_ = conv_check(__func__, s, ldx, x_bs, ldy, y_bs, dtype, checks)) return rc_; \
+  } while (0)
 
 static int conv2d_impl(const void* in, const void* w_packed, void* out, const float* bias, const void* residual,
                        int N, int H, int W, int C, int ldin, long long in_bs,
@@ -1354,31 +1500,18 @@ static int conv2d_impl(const void* in, const void* w_packed, void* out, const fl
                        int mode, int relu, int out_f32, double* bn_stats, const void* mask_y, int ldy, long long y_bs,
                        int dilation, const float* out_scale, float drop_p, const unsigned long long* drop_seed, unsigned drop_salt, int dtype, void* stream) {
   EMRT_REQUIRE(in && w_packed && out, "null pointer");
-  EMRT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && OW > 0 && OC > 0, "bad dims");
-  EMRT_REQUIRE(KH > 0 && KW > 0 && stride > 0 && pad >= 0 && dilation >= 1, "bad kernel geometry");
+  // the checked shape is the layer's: in mode 1 `in` is its output side (dy).  Pixels are counted before the size formula here, with the mode and dtype checks between.
+  const ConvShape s = mode == 1 ? ConvShape{N, OH, OW, OC, H, W, C, KH, KW, stride, pad, dilation} : ConvShape{N, H, W, C, OH, OW, OC, KH, KW, stride, pad, dilation};
+  EMRT_CONV_CHECK(s, 0, 0, 0, 0, dtype, CK_DIMS | CK_KERNEL);
   EMRT_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (fwd) or 1 (dgrad)");
-  EMRT_REQUIRE((long long)N * OH * OW + 512 < (1ll << 31) && (long long)N * H * W + 512 < (1ll << 31), "more than 2^31 pixels (32-bit pixel arithmetic)");
+  EMRT_CONV_CHECK(s, 0, 0, 0, 0, dtype, CK_PIXELS);
   EMRT_REQUIRE_FWD_DTYPE(dtype);
   EMRT_REQUIRE(dtype != EMRT_F16 || mode == 0, "fp16 (dtype 2) is inference-only: forward convolution (mode 0)");
-  if (mode == 0) {
-    EMRT_REQUIRE(OH == (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 && OW == (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1, "fwd: output size mismatch");
-  } else {
-    EMRT_REQUIRE(H == (OH + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 && W == (OW + 2 * pad - dilation * (KW - 1) - 1) / stride + 1, "dgrad: size mismatch");
-  }
-  {
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long in_ext = ((long long)(N - 1) * in_bs + ((long long)H * W - 1) * ldin + C) * esz;
-    const long long w_ext = (long long)OC * KH * KW * C * esz;
-    EMRT_REQUIRE(in_bs >= 0 && in_ext < (1ll << 31) && w_ext < (1ll << 31), "operand spans 2 GiB or more (32-bit buffer offsets)");
-  }
-  ConvArgs a;
-  a.in = in; a.w = w_packed; a.out = out; a.bias = bias; a.scale = out_scale; a.res = residual;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.ldin = ldin; a.in_bs = in_bs;
-  a.OH = OH; a.OW = OW; a.OC = OC; a.ldout = ldout; a.out_bs = out_bs;
-  a.ldres = ldres; a.res_bs = res_bs;
-  a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dilation; a.relu = relu; a.out_f32 = out_f32; a.cmajor = g_tune.igemm8p_cmajor; a.stats = bn_stats;
-  a.mask_y = mask_y; a.ldy = ldy; a.y_bs = y_bs; a.mask_scale = 1.f; a.stat_x = nullptr; a.ldsx = 0; a.sx_bs = 0;
-  a.xk_S = 0; a.xk_part = nullptr; a.xk_tick = nullptr; a.drop_seed = nullptr; a.drop_salt = 0; a.drop_p = 0.f;
+  EMRT_REQUIRE(conv_size_ok(s), mode == 0 ? "fwd: output size mismatch" : "dgrad: size mismatch");
+  EMRT_CONV_CHECK(s, ldin, in_bs, ldin, in_bs, dtype, (mode == 0 ? CK_X : CK_Y) | CK_W);
+  ConvArgs a = conv_fwd_args(in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, dilation,
+                             relu, out_f32, bn_stats, g_tune.igemm8p_cmajor, out_scale);
+  a.mask_y = mask_y; a.ldy = ldy; a.y_bs = y_bs;
   if (drop_p > 0.f) { a.drop_seed = drop_seed; a.drop_salt = drop_salt; a.drop_p = drop_p; }
   EMRT_REQUIRE(!mask_y || !out_f32, "the ReLU mask needs an output in the compute dtype");
   hipStream_t st = (hipStream_t)stream;
@@ -1413,55 +1546,39 @@ extern "C" int emrt_conv2d_drop(const void* in, const void* w_packed, void* out,
 }
 
 // ---- forward convolution whose input BatchNorm (+ ReLU) is applied by the operand loads (ABI 8) -------------------------------------------------
-// Which kernel would run this layer with the BatchNorm on its A operand: 0 = none (the dispatcher would take a tile the transform is not built
-// into -- 256x32, 128x128, the 256x256 LDS-DMA kernel -- or the geometry is outside it), 1 / 2 / 4 = the 64x64 tile with that many wave groups,
-// 100 + S = the cross-block K split with S copies.  Mirrors conv_pick_tile's order of decisions for a forward vector-path layer.
+// Which kernel would run this layer with the BatchNorm on its A operand: CONV_NONE = none (the dispatcher would take a tile the transform is not built
+// into -- 256x32, 128x128, the 256x256 LDS-DMA kernel -- or the geometry is outside it), CONV_64 = the 64x64 tile with n wave groups, CONV_XK = the
+// cross-block K split with n copies.  Its own eligibility test, then the plan of the forward vector-path layer.
 template <class T>
-static int bna_choice(const ConvArgs& a, hipStream_t st) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  constexpr int BK = 8 * EPC;
-  const bool vec = (a.C % EPC == 0) && (a.ldin % EPC == 0) && (a.in_bs % EPC == 0) && (((uintptr_t)a.in) % 16 == 0) && (((uintptr_t)a.w) % 16 == 0);
-  if (!vec || a.C % BK != 0 || a.C > 1024 || a.OC <= 32) return 0;
-  if (a.stride != 1 || a.KH != a.KW || (a.KH != 1 && a.KH != 3) || a.pad != a.dil * (a.KH >> 1) || a.OH != a.H || a.OW != a.W) return 0;
-  if (((uintptr_t)a.a_out) % 16 != 0) return 0;
+static ConvPlan bna_plan(const ConvArgs& a, hipStream_t st) {
+  constexpr int BK = 8 * (16 / (int)sizeof(T));
+  const ConvPlan none = {CONV_NONE, 0, false};
+  if (!conv_is_vec<T>(a) || a.C % BK != 0 || a.C > 1024 || a.OC <= 32) return none;
+  if (a.stride != 1 || a.KH != a.KW || (a.KH != 1 && a.KH != 3) || a.pad != a.dil * (a.KH >> 1) || a.OH != a.H || a.OW != a.W) return none;
+  if (((uintptr_t)a.a_out) % 16 != 0) return none;
   // Measured on MI355X (tools/r6/bench_bna.py, profiles/r6_bna_microbench.txt; batch 8, bf16, us: emrt_bn_apply + emrt_conv2d -> this kernel):
   //   1x1  64x64x64->256   20.0 -> 18.0    32x32x128->512   15.0 -> 12.0    16x16x256->1024  12.3 -> 11.0    8x8x512->2048    14.5 -> 13.2
   //   3x3  64x64x64->64    17.0 -> 16.5    32x32x128->128   16.2 -> 15.0    16x16x256->256   19.9 -> 21.2    8x8x512->512     25.8 -> 28.2
   //        32x32x256->256  30.2 -> 37.1    32x32x512->256   56.3 -> 72.4
   // The transform runs once per loaded chunk, i.e. once per N-tile and nine times per pixel of a 3x3 layer: it pays where the k loop is short (every
   // 1x1; 3x3 up to 128 channels = 18 k-tiles) and loses where the loop is long -- there the separate launch stays (knob no_bna = -1: tests take them all)
-  if (a.KH == 3 && a.C > 128 && g_tune.no_bna != -1) return 0;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  auto blocks = [&](int bmv, int bnv) { return ((M + bmv - 1) / bmv) * ((a.OC + bnv - 1) / bnv); };
-  if (g_tune.conv_tile) return g_tune.conv_tile == 1 ? 1 : g_tune.conv_tile == 5 ? 2 : g_tune.conv_tile == 6 ? 4 : 0;
-  if constexpr (sizeof(T) == 2) {
-    const int S = igemm_xk_copies<T>(a, st, g_tune.xk > 0 ? g_tune.xk : 0);
-    if (S >= 2) return 100 + S;
-    const long long nb256 = blocks(256, 256);
-    const int nkt64 = a.KH * a.KW * a.C / 64;
-    const int minb = g_tune.igemm8p_min_blocks;
-    if (minb > 0 && nkt64 >= 16 && (nb256 >= minb || (nb256 >= (minb * 3) / 5 && nkt64 >= 144)) && igemm8p_ok<T>(a)) return 0;
-  }
-  const int nkt = (a.KH * a.KW * a.C + BK - 1) / BK;
-  if (a.OC > 64 && nkt >= 16 && blocks(128, 128) >= 256) return 0;
-  const long long nb = blocks(64, 64);
-  if (nb <= 128 && nkt >= 32) return 4;
-  if (nb <= 256 && nkt >= 16) return 2;
-  return 1;
+  if (a.KH == 3 && a.C > 128 && g_tune.no_bna != -1) return none;
+  const ConvPlan p = conv_plan<T, 0, true>(a, st);
+  if (g_tune.conv_tile && !p.forced) return none;      // a forced tile this layer cannot take: emrt_conv2d goes down the ladder, the transform declines
+  return p.kind == CONV_64 || p.kind == CONV_XK ? p : none;
 }
 
 template <class T>
-static int launch_bna(const ConvArgs& a0, hipStream_t st, int choice) {
+static int launch_bna(const ConvArgs& a0, hipStream_t st, const ConvPlan& p) {
   ConvArgs a = a0;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long nb = ((M + 63) / 64) * ((a.OC + 63) / 64);
+  const long long nb = conv_blocks(a, 64, 64);
   const size_t tab = (size_t)2 * a.C * sizeof(float);
-  if (choice >= 100) {
-    a.xk_S = choice - 100; a.xk_part = g_scratch.xk_part; a.xk_tick = g_scratch.tick;
+  if (p.kind == CONV_XK) {
+    a.xk_S = p.n; a.xk_part = g_scratch.xk_part; a.xk_tick = g_scratch.tick;
     hipLaunchKernelGGL((igemm_xk_bna_kernel<T>), dim3((unsigned)(nb * a.xk_S)), dim3(256), (size_t)2 * 128 * 144 + tab, st, a);
     return check_launch("emrt_conv2d_bna");
   }
-  const int G = choice;
+  const int G = p.n;
   size_t lds = (size_t)G * 2 * 128 * 144 + tab;
   if (G > 1 && lds < (size_t)(G - 1) * 16 * 256 * 4) lds = (size_t)(G - 1) * 16 * 256 * 4;
   static bool attr_done = false;      // one flag per element type
@@ -1477,24 +1594,22 @@ static int launch_bna(const ConvArgs& a0, hipStream_t st, int choice) {
   return check_launch("emrt_conv2d_bna");
 }
 
-static int bna_fill(ConvArgs& a, const void* in, const void* w_packed, void* out, const float* bias, const void* residual, int N, int H, int W, int C, int ldin,
-                    long long in_bs, int OH, int OW, int OC, int ldout, long long out_bs, int ldres, long long res_bs, int KH, int KW, int stride, int pad,
-                    int relu, int out_f32, double* bn_stats, int dilation, const double* sums, double count, float eps, float momentum, float* mean,
-                    float* invstd, float* run_mean, float* run_var, const float* gamma, const float* beta, int in_relu, void* a_out) {
-  a.in = in; a.w = w_packed; a.out = out; a.bias = bias; a.scale = nullptr; a.res = residual;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.ldin = ldin; a.in_bs = in_bs; a.OH = OH; a.OW = OW; a.OC = OC; a.ldout = ldout; a.out_bs = out_bs;
-  a.ldres = ldres; a.res_bs = res_bs; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dilation; a.relu = relu; a.out_f32 = out_f32;
-  a.cmajor = 0; a.stats = bn_stats; a.mask_y = nullptr; a.ldy = 0; a.y_bs = 0; a.mask_scale = 1.f; a.stat_x = nullptr; a.ldsx = 0; a.sx_bs = 0;
-  a.xk_S = 0; a.xk_part = nullptr; a.xk_tick = nullptr; a.drop_seed = nullptr; a.drop_salt = 0; a.drop_p = 0.f;
+// the forward view (no mask, no folded scale, cmajor 0) plus the BatchNorm operand: emrt_conv2d_bna's argument list without dtype and stream
+static ConvArgs bna_args(const void* in, const void* w_packed, void* out, const float* bias, const void* residual, int N, int H, int W, int C, int ldin,
+                         long long in_bs, int OH, int OW, int OC, int ldout, long long out_bs, int ldres, long long res_bs, int KH, int KW, int stride, int pad,
+                         int relu, int out_f32, double* bn_stats, int dilation, const double* sums, double count, float eps, float momentum, float* mean,
+                         float* invstd, float* run_mean, float* run_var, const float* gamma, const float* beta, int in_relu, void* a_out) {
+  ConvArgs a = conv_fwd_args(in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, dilation,
+                             relu, out_f32, bn_stats, 0, nullptr);
   a.bna.sums = sums; a.bna.inv_count = count > 0.0 ? 1.0 / count : 0.0; a.bna.eps = eps; a.bna.momentum = momentum; a.bna.mean = mean; a.bna.invstd = invstd;
   a.bna.run_mean = run_mean; a.bna.run_var = run_var; a.bna.gamma = gamma; a.bna.beta = beta; a.bna.relu = in_relu;
   a.a_out = a_out;
-  return 0;
+  return a;
 }
 
 // 1 when emrt_conv2d_bna would run these arguments (same argument list), 0 when the caller has to apply the BatchNorm with its own launch
 // (emrt_bn_apply) and call emrt_conv2d -- the layer's tile has no operand transform, or the geometry is outside it (not 1x1 / 3x3 "same" stride 1,
-// C not a multiple of 64 (32 in fp32) or > 1024, OC <= 32, unaligned rows).  No launch, no error state.
+// C not a multiple of 64 (32 in fp32) or > 1024, OC <= 32, unaligned rows).  No launch, no error state (so the checks are its own: nothing may call fail()).
 extern "C" int emrt_conv2d_bna_supported(const void* in, const void* w_packed, void* out, const float* bias, const void* residual, int N, int H, int W, int C,
                                          int ldin, long long in_bs, int OH, int OW, int OC, int ldout, long long out_bs, int ldres, long long res_bs, int KH,
                                          int KW, int stride, int pad, int relu, int out_f32, double* bn_stats, int dilation, const double* sums, double count,
@@ -1505,11 +1620,10 @@ extern "C" int emrt_conv2d_bna_supported(const void* in, const void* w_packed, v
   const long long esz = dtype == EMRT_F32 ? 4 : 2;
   if ((long long)N * H * W * C * esz >= (1ll << 31) || (long long)N * H * W + 512 >= (1ll << 31)) return 0;
   if (((long long)(N - 1) * in_bs + ((long long)H * W - 1) * ldin + C) * esz >= (1ll << 31) || (long long)OC * KH * KW * C * esz >= (1ll << 31)) return 0;
-  ConvArgs a;
-  bna_fill(a, in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, relu, out_f32, bn_stats,
-           dilation, sums, count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, in_relu, a_out);
+  const ConvArgs a = bna_args(in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, relu, out_f32,
+                              bn_stats, dilation, sums, count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, in_relu, a_out);
   hipStream_t st = (hipStream_t)stream;
-  return (dtype == EMRT_F32 ? bna_choice<float>(a, st) : bna_choice<bf16_t>(a, st)) != 0 ? 1 : 0;
+  return (dtype == EMRT_F32 ? bna_plan<float>(a, st) : bna_plan<bf16_t>(a, st)).kind != CONV_NONE ? 1 : 0;
 }
 
 // out = conv([relu](BatchNorm_train(in))) with the BatchNorm applied by the convolution's own operand loads and the normalised map written to a_out
@@ -1524,23 +1638,21 @@ extern "C" int emrt_conv2d_bna(const void* in, const void* w_packed, void* out, 
                                const float* beta, int in_relu, void* a_out, int dtype, void* stream) {
   EMRT_REQUIRE_TRAIN_DTYPE(dtype);
   EMRT_REQUIRE(in && w_packed && out && sums && mean && invstd && gamma && beta && a_out, "null pointer");
-  EMRT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && OW > 0 && OC > 0 && dilation >= 1 && count > 0.0, "bad dims");
+  const ConvShape s = {N, H, W, C, OH, OW, OC, KH, KW, stride, pad, dilation};
+  EMRT_CONV_CHECK(s, 0, 0, 0, 0, dtype, CK_DIMS);
+  EMRT_REQUIRE(dilation >= 1 && count > 0.0, "bad dims");
   EMRT_REQUIRE((run_mean != nullptr) == (run_var != nullptr), "running statistics come in pairs");
   EMRT_REQUIRE(a_out != out && a_out != in, "a_out is a buffer of its own");
+  // no kernel geometry, no size formula (bna_plan: a "same" stride-1 layer or no kernel), and only the output's pixels are counted
   EMRT_REQUIRE((long long)N * OH * OW + 512 < (1ll << 31), "more than 2^31 pixels (32-bit pixel arithmetic)");
-  {
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long in_ext = ((long long)(N - 1) * in_bs + ((long long)H * W - 1) * ldin + C) * esz;
-    EMRT_REQUIRE(in_bs >= 0 && in_ext < (1ll << 31) && (long long)OC * KH * KW * C * esz < (1ll << 31) && (long long)N * H * W * C * esz < (1ll << 31),
-                 "operand spans 2 GiB or more (32-bit buffer offsets)");
-  }
-  ConvArgs a;
-  bna_fill(a, in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, relu, out_f32, bn_stats,
-           dilation, sums, count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, in_relu, a_out);
+  EMRT_CONV_CHECK(s, ldin, in_bs, 0, 0, dtype, CK_X | CK_W);
+  EMRT_REQUIRE((long long)N * H * W * C * (dtype == EMRT_F32 ? 4 : 2) < (1ll << 31), "operand spans 2 GiB or more (32-bit buffer offsets)");      // a_out is dense
+  const ConvArgs a = bna_args(in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, relu, out_f32,
+                              bn_stats, dilation, sums, count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, in_relu, a_out);
   hipStream_t st = (hipStream_t)stream;
-  const int choice = dtype == EMRT_F32 ? bna_choice<float>(a, st) : bna_choice<bf16_t>(a, st);
-  EMRT_REQUIRE(choice != 0, "this layer has no operand-transform kernel (ask emrt_conv2d_bna_supported first)");
-  return dtype == EMRT_F32 ? launch_bna<float>(a, st, choice) : launch_bna<bf16_t>(a, st, choice);
+  const ConvPlan plan = dtype == EMRT_F32 ? bna_plan<float>(a, st) : bna_plan<bf16_t>(a, st);
+  EMRT_REQUIRE(plan.kind != CONV_NONE, "this layer has no operand-transform kernel (ask emrt_conv2d_bna_supported first)");
+  return dtype == EMRT_F32 ? launch_bna<float>(a, st, plan) : launch_bna<bf16_t>(a, st, plan);
 }
 
 // vector path eligibility of a weight-gradient problem
@@ -1625,22 +1737,13 @@ extern "C" int emrt_conv2d_wgrad(const void* x, const void* dy, float* dw,
                                  int OH, int OW, int OC, int lddy, long long dy_bs,
                                  int KH, int KW, int stride, int pad, float* dbias, int dilation, int dtype, void* stream) {
   EMRT_REQUIRE(x && dy && dw, "null pointer");
-  EMRT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && OW > 0 && OC > 0 && dilation >= 1, "bad dims");
-  EMRT_REQUIRE(OH == (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 && OW == (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1, "output size mismatch");
-  EMRT_REQUIRE((long long)N * OH * OW + 512 < (1ll << 31) && (long long)N * H * W + 512 < (1ll << 31), "more than 2^31 pixels (32-bit pixel arithmetic)");
+  const ConvShape s = {N, H, W, C, OH, OW, OC, KH, KW, stride, pad, dilation};
+  EMRT_CONV_CHECK(s, ldx, x_bs, lddy, dy_bs, dtype, CK_DIMS);      // (no kernel-geometry check here: the size formula meets KH, KW and stride unchecked)
+  EMRT_REQUIRE(dilation >= 1, "bad dims");
+  EMRT_CONV_CHECK(s, ldx, x_bs, lddy, dy_bs, dtype, CK_SIZE | CK_PIXELS);
   EMRT_REQUIRE_TRAIN_DTYPE(dtype);
-  {
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long x_ext = ((long long)(N - 1) * x_bs + ((long long)H * W - 1) * ldx + C) * esz;
-    const long long dy_ext = ((long long)(N - 1) * dy_bs + ((long long)OH * OW - 1) * lddy + OC) * esz;
-    EMRT_REQUIRE(x_bs >= 0 && dy_bs >= 0 && x_ext < (1ll << 31) && dy_ext < (1ll << 31), "operand spans 2 GiB or more (32-bit buffer offsets)");
-    EMRT_REQUIRE((long long)H * W < (1 << 24) && (long long)ldx * esz < (1 << 24) && stride < (1 << 12), "map too large for the 24-bit address arithmetic");
-  }
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.dw = dw;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.ldx = ldx; a.x_bs = x_bs;
-  a.OH = OH; a.OW = OW; a.OC = OC; a.lddy = lddy; a.dy_bs = dy_bs;
-  a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.dil = dilation; a.tiles_per_split = 0; a.dbias = dbias; a.overwrite = 0;
+  EMRT_CONV_CHECK(s, ldx, x_bs, lddy, dy_bs, dtype, CK_X | CK_Y | CK_X24);
+  const WgradArgs a = wgrad_args(x, dy, dw, dbias, N, H, W, C, ldx, x_bs, OH, OW, OC, lddy, dy_bs, KH, KW, stride, pad, dilation, 0);
   hipStream_t st = (hipStream_t)stream;
   return dtype == EMRT_F32 ? wgrad_dispatch<float>(a, st) : wgrad_dispatch<bf16_t>(a, st);
 }
@@ -2019,15 +2122,11 @@ __global__ __launch_bounds__(256, 2) void thin_fwd_bn_kernel(ThinFwdArgs p, BnOp
 template <class T>
 static int conv_bwd_dispatch(const ConvArgs& d, const WgradArgs& w0, hipStream_t st) {
   using Cfg = WgradCfg<T>;
-  constexpr int EPC = 16 / (int)sizeof(T);
-  constexpr int BK = 8 * EPC;
   WgradArgs w = w0;
-  const bool vec_d = (d.C % EPC == 0) && (d.ldin % EPC == 0) && (d.in_bs % EPC == 0) && (((uintptr_t)d.in) % 16 == 0) && (((uintptr_t)d.w) % 16 == 0);
+  const bool vec_d = conv_is_vec<T>(d);
   const bool vec_w = wgrad_is_vec<T>(w);
-  const long long Md = (long long)d.N * d.OH * d.OW;
-  const long long nd = ((Md + 63) / 64) * ((d.OC + 63) / 64);                 // 64x64 dgrad tiles
-  const int nkt = (d.KH * d.KW * d.C + BK - 1) / BK;
-  const bool big_tile = d.OC > 64 && nkt >= 16 && ((Md + 127) / 128) * ((d.OC + 127) / 128) >= 256;   // conv_pick_tile would take 128x128
+  const long long nd = conv_blocks(d, 64, 64);                 // 64x64 dgrad tiles
+  const bool big_tile = conv_takes_128<T>(d);      // the ladder's 128x128 rung alone, not the whole plan
   if (!w0.dw) return conv_dispatch<T, 1>(d, st);      // data gradient only: the caller batches the weight gradient (emrt_conv2d_wgrad_group)
   if (thin_bwd_ok<T>(d, w0) && !g_tune.no_thin_bwd) return thin_bwd_launch<T>(d, w0, st);
   int tx = 0, ty = 0, S = 0;
@@ -2112,16 +2211,9 @@ extern "C" int emrt_bn_pointwise_bwd(const void* x, int ldx, long long x_bs, con
   EMRT_REQUIRE_TRAIN_DTYPE(dtype);
   EMRT_REQUIRE(x && dy && w_bwd_packed && da && dw && mean && invstd && gamma && beta, "null pointer");
   EMRT_REQUIRE(N > 0 && HW > 0 && OC >= 1 && OC <= 8, "OC <= 8");
-  ConvArgs d;
-  memset(&d, 0, sizeof(d));
-  WgradArgs w;
-  memset(&w, 0, sizeof(w));
-  // the data-gradient view: "input" dy [N][HW][OC], "output" da [N][HW][C]
-  d.in = dy; d.w = w_bwd_packed; d.out = da; d.N = N; d.H = 1; d.W = HW; d.C = OC; d.ldin = lddy; d.in_bs = dy_bs;
-  d.OH = 1; d.OW = HW; d.OC = C; d.ldout = ldda; d.out_bs = da_bs; d.KH = d.KW = 1; d.stride = 1; d.pad = 0; d.dil = 1;
-  d.mask_y = x; d.ldy = ldx; d.y_bs = x_bs; d.mask_scale = 1.f; d.stats = stats;
-  w.x = x; w.dy = dy; w.dw = dw; w.dbias = dbias; w.N = N; w.H = 1; w.W = HW; w.C = C; w.ldx = ldx; w.x_bs = x_bs;
-  w.OH = 1; w.OW = HW; w.OC = OC; w.lddy = lddy; w.dy_bs = dy_bs; w.KH = w.KW = 1; w.stride = 1; w.pad = 0; w.dil = 1; w.overwrite = 0;
+  // a 1x1 layer [N][1][HW][C] -> [N][1][HW][OC]; its data gradient da is masked by the raw x (mask_y)
+  const ConvArgs d = conv_dgrad_args(dy, w_bwd_packed, da, ldda, da_bs, 0, nullptr, 0, 0, N, 1, HW, C, 1, HW, OC, lddy, dy_bs, 1, 1, 1, 0, 1, 0, stats, x, ldx, x_bs);
+  const WgradArgs w = wgrad_args(x, dy, dw, dbias, N, 1, HW, C, ldx, x_bs, 1, HW, OC, lddy, dy_bs, 1, 1, 1, 0, 1, 0);
   const float* xbn[4] = {mean, invstd, gamma, beta};
   hipStream_t st = (hipStream_t)stream;
   if (dtype == EMRT_F32) {
@@ -2141,37 +2233,16 @@ extern "C" int emrt_conv2d_bwd(const void* x, const void* dy, const void* w_bwd_
                                int dilation, int dtype, void* stream) {
   EMRT_REQUIRE(x && dy && w_bwd_packed && dx, "null pointer");
   EMRT_REQUIRE(dw || !dbias, "dw == NULL asks for the data gradient only: the bias gradient travels with the deferred weight gradient");
-  EMRT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && OW > 0 && OC > 0, "bad dims");
-  EMRT_REQUIRE(KH > 0 && KW > 0 && stride > 0 && pad >= 0 && dilation >= 1, "bad kernel geometry");
-  EMRT_REQUIRE(OH == (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 && OW == (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1, "output size mismatch");
-  EMRT_REQUIRE((long long)N * OH * OW + 512 < (1ll << 31) && (long long)N * H * W + 512 < (1ll << 31), "more than 2^31 pixels (32-bit pixel arithmetic)");
+  const ConvShape s = {N, H, W, C, OH, OW, OC, KH, KW, stride, pad, dilation};
+  EMRT_CONV_CHECK(s, ldx, x_bs, lddy, dy_bs, dtype, CK_DIMS | CK_KERNEL | CK_SIZE | CK_PIXELS);
   EMRT_REQUIRE_TRAIN_DTYPE(dtype);
-  {
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long x_ext = ((long long)(N - 1) * x_bs + ((long long)H * W - 1) * ldx + C) * esz;
-    const long long dy_ext = ((long long)(N - 1) * dy_bs + ((long long)OH * OW - 1) * lddy + OC) * esz;
-    const long long w_ext = (long long)OC * KH * KW * C * esz;
-    EMRT_REQUIRE(x_bs >= 0 && dy_bs >= 0 && x_ext < (1ll << 31) && dy_ext < (1ll << 31) && w_ext < (1ll << 31), "operand spans 2 GiB or more (32-bit buffer offsets)");
-    EMRT_REQUIRE((long long)H * W < (1 << 24) && (long long)ldx * esz < (1 << 24) && stride < (1 << 12), "map too large for the 24-bit address arithmetic");
-  }
-  ConvArgs d;       // dgrad: a convolution of dy with the transposed weights, output = dx (dense NHWC)
-  d.in = dy; d.w = w_bwd_packed; d.out = dx; d.bias = nullptr; d.scale = nullptr; d.res = nullptr;
-  d.N = N; d.H = OH; d.W = OW; d.C = OC; d.ldin = lddy; d.in_bs = dy_bs;
-  d.OH = H; d.OW = W; d.OC = C; d.ldout = lddx; d.out_bs = dx_bs;
-  d.ldres = 0; d.res_bs = 0;
-  if (accumulate) { d.res = dx; d.ldres = lddx; d.res_bs = dx_bs; }      // dx += : every element is read and written by the same thread
-  else if (addend) { d.res = addend; d.ldres = ldadd; d.res_bs = add_bs; }      // dx = dgrad + addend (gradient contributions made so far)
+  EMRT_CONV_CHECK(s, ldx, x_bs, lddy, dy_bs, dtype, CK_X | CK_Y | CK_W | CK_X24);
   EMRT_REQUIRE(lddx >= C && dx_bs >= 0, "bad dx strides");
   EMRT_REQUIRE(!(accumulate && addend), "accumulate adds into dx itself; addend is a different tensor");
   EMRT_REQUIRE(!stat_x || mask_y, "stat_x replaces the mask tensor in the second statistic: it needs mask_y");
-  d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad; d.dil = dilation; d.relu = 0; d.out_f32 = 0; d.cmajor = g_tune.igemm8p_cmajor; d.stats = bn_stats;
-  d.mask_y = mask_y; d.ldy = ldy; d.y_bs = y_bs; d.mask_scale = mask_scale; d.stat_x = stat_x; d.ldsx = ldsx; d.sx_bs = sx_bs;
-  d.xk_S = 0; d.xk_part = nullptr; d.xk_tick = nullptr; d.drop_seed = nullptr; d.drop_salt = 0; d.drop_p = 0.f;
-  WgradArgs w;
-  w.x = x; w.dy = dy; w.dw = dw;
-  w.N = N; w.H = H; w.W = W; w.C = C; w.ldx = ldx; w.x_bs = x_bs;
-  w.OH = OH; w.OW = OW; w.OC = OC; w.lddy = lddy; w.dy_bs = dy_bs;
-  w.KH = KH; w.KW = KW; w.stride = stride; w.pad = pad; w.dil = dilation; w.tiles_per_split = 0; w.dbias = dbias; w.overwrite = 0;
+  const ConvArgs d = conv_dgrad_args(dy, w_bwd_packed, dx, lddx, dx_bs, accumulate, addend, ldadd, add_bs, N, H, W, C, OH, OW, OC, lddy, dy_bs, KH, KW, stride, pad,
+                                     dilation, g_tune.igemm8p_cmajor, bn_stats, mask_y, ldy, y_bs, mask_scale, stat_x, ldsx, sx_bs);
+  const WgradArgs w = wgrad_args(x, dy, dw, dbias, N, H, W, C, ldx, x_bs, OH, OW, OC, lddy, dy_bs, KH, KW, stride, pad, dilation, 0);
   hipStream_t st = (hipStream_t)stream;
   return dtype == EMRT_F32 ? conv_bwd_dispatch<float>(d, w, st) : conv_bwd_dispatch<bf16_t>(d, w, st);
 }
@@ -2182,19 +2253,6 @@ extern "C" int emrt_conv2d_bwd(const void* x, const void* dy, const void* w_bwd_
 // share the launch and hide each other's latency.  Plain-C descriptors (include/emrt_hip.h).
 // ------------------------------------------------------------------------------------------------
 #define EMRT_MAX_GROUP 6
-struct EmrtConvDesc {
-  const void* in; const void* w_packed; void* out; const float* bias; const void* residual;
-  int N, H, W, C, ldin; long long in_bs;
-  int OH, OW, OC, ldout; long long out_bs;
-  int ldres; long long res_bs;
-  int KH, KW, stride, pad, relu;
-  double* bn_stats;
-  int out_f32;
-};
-struct EmrtConvBwdDesc {
-  const void* x; const void* dy; const void* w_bwd_packed; void* dx; int lddx; long long dx_bs; int accumulate; float* dw; float* dbias;
-  int N, H, W, C, ldx; long long x_bs; int OH, OW, OC, lddy; long long dy_bs; int KH, KW, stride, pad;
-};
 struct ConvGroupArgs { ConvArgs p[EMRT_MAX_GROUP]; int first[EMRT_MAX_GROUP + 1]; };
 struct BwdGroupArgs {
   ConvArgs d[EMRT_MAX_GROUP];
@@ -2229,46 +2287,40 @@ __global__ __launch_bounds__(256, 2) void bwd_group_kernel(BwdGroupArgs g) {
   }
 }
 
-static void conv_args_from_desc(ConvArgs& a, const EmrtConvDesc& d) {
-  a.in = d.in; a.w = d.w_packed; a.out = d.out; a.bias = d.bias; a.scale = nullptr; a.res = d.residual;
-  a.N = d.N; a.H = d.H; a.W = d.W; a.C = d.C; a.ldin = d.ldin; a.in_bs = d.in_bs;
-  a.OH = d.OH; a.OW = d.OW; a.OC = d.OC; a.ldout = d.ldout; a.out_bs = d.out_bs;
-  a.ldres = d.ldres; a.res_bs = d.res_bs;
-  a.KH = d.KH; a.KW = d.KW; a.stride = d.stride; a.pad = d.pad; a.dil = 1; a.relu = d.relu; a.out_f32 = d.out_f32 ? 1 : 0; a.cmajor = 0; a.stats = d.bn_stats;
-  a.mask_y = nullptr; a.ldy = 0; a.y_bs = 0; a.mask_scale = 1.f; a.stat_x = nullptr; a.ldsx = 0; a.sx_bs = 0;
-  a.xk_S = 0; a.xk_part = nullptr; a.xk_tick = nullptr; a.drop_seed = nullptr; a.drop_salt = 0; a.drop_p = 0.f;
-}
-
-template <class T>
-static bool conv_desc_is_vec(const ConvArgs& a) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  return (a.C % EPC == 0) && (a.ldin % EPC == 0) && (a.in_bs % EPC == 0) && (((uintptr_t)a.in) % 16 == 0) && (((uintptr_t)a.w) % 16 == 0);
-}
-
-template <class T>
-static int conv_group_dispatch(const EmrtConvDesc* descs, int n, hipStream_t st) {
-  ConvGroupArgs g;
+// One launch of 64x64 tiles for the n problems in g.p, side by side (igemm_group_kernel<T, MODE>) -- when every one is a vector-path problem with OC > 32
+// and at most tile_cap tiles, and they have at most 4096 tiles in all; one launch each otherwise.  Assembles the block ranges and pads the unused slots.
+template <class T, int MODE>
+static int conv_group_launch(ConvGroupArgs& g, int n, long long tile_cap, const char* fn, hipStream_t st) {
   bool groupable = true;
   long long total = 0;
   for (int i = 0; i < n; ++i) {
-    conv_args_from_desc(g.p[i], descs[i]);
-    const long long M = (long long)g.p[i].N * g.p[i].OH * g.p[i].OW;
+    const long long nb = conv_blocks(g.p[i], 64, 64);
     g.first[i] = (int)total;
-    total += ((M + 63) / 64) * ((g.p[i].OC + 63) / 64);
-    groupable = groupable && conv_desc_is_vec<T>(g.p[i]) && g.p[i].OC > 32;
+    total += nb;
+    groupable = groupable && conv_is_vec<T>(g.p[i]) && g.p[i].OC > 32 && nb <= tile_cap;
   }
   for (int i = n; i <= EMRT_MAX_GROUP; ++i) g.first[i] = (int)total;
   for (int i = n; i < EMRT_MAX_GROUP; ++i) g.p[i] = g.p[0];
   if (!groupable || total > 4096) {        // not the small vector problems this launch is for: one launch each
     for (int i = 0; i < n; ++i) {
-      const int rc = conv_dispatch<T, 0>(g.p[i], st);
+      const int rc = conv_dispatch<T, MODE>(g.p[i], st);
       if (rc) return rc;
     }
     return 0;
   }
-  const size_t lds = (size_t)2 * 128 * 144;
-  hipLaunchKernelGGL((igemm_group_kernel<T>), dim3((unsigned)total), dim3(256), lds, st, g);
-  return check_launch("emrt_conv2d_group");
+  hipLaunchKernelGGL((igemm_group_kernel<T, MODE>), dim3((unsigned)total), dim3(256), (size_t)2 * 128 * 144, st, g);
+  return check_launch(fn);
+}
+
+template <class T>
+static int conv_group_dispatch(const EmrtConvDesc* descs, int n, hipStream_t st) {
+  ConvGroupArgs g;
+  for (int i = 0; i < n; ++i) {
+    const EmrtConvDesc& d = descs[i];      // (no dilation, no folded scale, cmajor 0)
+    g.p[i] = conv_fwd_args(d.in, d.w_packed, d.out, d.bias, d.residual, d.N, d.H, d.W, d.C, d.ldin, d.in_bs, d.OH, d.OW, d.OC, d.ldout, d.out_bs, d.ldres, d.res_bs,
+                           d.KH, d.KW, d.stride, d.pad, 1, d.relu, d.out_f32 ? 1 : 0, d.bn_stats, 0, nullptr);
+  }
+  return conv_group_launch<T, 0>(g, n, 4096, "emrt_conv2d_group", st);
 }
 
 extern "C" int emrt_conv2d_group(const EmrtConvDesc* descs, int n, int dtype, void* stream) {
@@ -2277,16 +2329,18 @@ extern "C" int emrt_conv2d_group(const EmrtConvDesc* descs, int n, int dtype, vo
   for (int i = 0; i < n; ++i) {
     const EmrtConvDesc& d = descs[i];
     EMRT_REQUIRE(d.in && d.w_packed && d.out, "null pointer");
-    EMRT_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.C > 0 && d.OC > 0 && d.KH > 0 && d.KW > 0 && d.stride > 0 && d.pad >= 0, "bad dims");
-    EMRT_REQUIRE(d.OH == (d.H + 2 * d.pad - d.KH) / d.stride + 1 && d.OW == (d.W + 2 * d.pad - d.KW) / d.stride + 1, "output size mismatch");
-    EMRT_REQUIRE((long long)d.N * d.OH * d.OW + 512 < (1ll << 31) && (long long)d.N * d.H * d.W + 512 < (1ll << 31), "more than 2^31 pixels");
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long in_ext = ((long long)(d.N - 1) * d.in_bs + ((long long)d.H * d.W - 1) * d.ldin + d.C) * esz;
-    EMRT_REQUIRE(d.in_bs >= 0 && in_ext < (1ll << 31) && (long long)d.OC * d.KH * d.KW * d.C * esz < (1ll << 31), "operand spans 2 GiB or more");
+    const ConvShape s = {d.N, d.H, d.W, d.C, d.OH, d.OW, d.OC, d.KH, d.KW, d.stride, d.pad, 1};
+    EMRT_CONV_CHECK(s, d.ldin, d.in_bs, 0, 0, dtype, CK_GROUPED | CK_DIMS | CK_SIZE | CK_PIXELS | CK_X | CK_W);
   }
   hipStream_t st = (hipStream_t)stream;
   if (dtype == EMRT_F16) return conv_group_dispatch<f16_t>(descs, n, st);
   return dtype == EMRT_F32 ? conv_group_dispatch<float>(descs, n, st) : conv_group_dispatch<bf16_t>(descs, n, st);
+}
+
+// the data-gradient view of a grouped descriptor (no dilation, no fused epilogue, cmajor 0)
+static ConvArgs dgrad_args_from_bwd_desc(const EmrtConvBwdDesc& b) {
+  return conv_dgrad_args(b.dy, b.w_bwd_packed, b.dx, b.lddx, b.dx_bs, b.accumulate, nullptr, 0, 0, b.N, b.H, b.W, b.C, b.OH, b.OW, b.OC, b.lddy, b.dy_bs, b.KH, b.KW,
+                         b.stride, b.pad, 1, 0);
 }
 
 // dw == NULL in every descriptor: the data gradients only, as one grouped launch of 64x64 dgrad tiles (the weight gradients are
@@ -2294,34 +2348,8 @@ extern "C" int emrt_conv2d_group(const EmrtConvDesc* descs, int n, int dtype, vo
 template <class T>
 static int conv_dgrad_group_dispatch(const EmrtConvBwdDesc* descs, int n, hipStream_t st) {
   ConvGroupArgs g;
-  bool groupable = true;
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    const EmrtConvBwdDesc& b = descs[i];
-    ConvArgs& d = g.p[i];
-    d.in = b.dy; d.w = b.w_bwd_packed; d.out = b.dx; d.bias = nullptr; d.scale = nullptr; d.res = b.accumulate ? b.dx : nullptr;
-    d.N = b.N; d.H = b.OH; d.W = b.OW; d.C = b.OC; d.ldin = b.lddy; d.in_bs = b.dy_bs;
-    d.OH = b.H; d.OW = b.W; d.OC = b.C; d.ldout = b.lddx; d.out_bs = b.dx_bs;
-    d.ldres = b.accumulate ? b.lddx : 0; d.res_bs = b.accumulate ? b.dx_bs : 0;
-    d.KH = b.KH; d.KW = b.KW; d.stride = b.stride; d.pad = b.pad; d.dil = 1; d.relu = 0; d.out_f32 = 0; d.cmajor = 0; d.stats = nullptr;
-    d.mask_y = nullptr; d.ldy = 0; d.y_bs = 0; d.mask_scale = 1.f; d.stat_x = nullptr; d.ldsx = 0; d.sx_bs = 0;
-    d.xk_S = 0; d.xk_part = nullptr; d.xk_tick = nullptr; d.drop_seed = nullptr; d.drop_salt = 0; d.drop_p = 0.f;
-    const long long Md = (long long)d.N * d.OH * d.OW;
-    g.first[i] = (int)total;
-    total += ((Md + 63) / 64) * ((d.OC + 63) / 64);
-    groupable = groupable && conv_desc_is_vec<T>(d) && d.OC > 32;
-  }
-  for (int i = n; i <= EMRT_MAX_GROUP; ++i) g.first[i] = (int)total;
-  for (int i = n; i < EMRT_MAX_GROUP; ++i) g.p[i] = g.p[0];
-  if (!groupable || total > 4096) {
-    for (int i = 0; i < n; ++i) {
-      const int rc = conv_dispatch<T, 1>(g.p[i], st);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  hipLaunchKernelGGL((igemm_group_kernel<T, 1>), dim3((unsigned)total), dim3(256), (size_t)2 * 128 * 144, st, g);
-  return check_launch("emrt_conv2d_bwd_group");
+  for (int i = 0; i < n; ++i) g.p[i] = dgrad_args_from_bwd_desc(descs[i]);
+  return conv_group_launch<T, 1>(g, n, 4096, "emrt_conv2d_bwd_group", st);
 }
 
 template <class T>
@@ -2334,24 +2362,14 @@ static int conv_bwd_group_dispatch(const EmrtConvBwdDesc* descs, int n, hipStrea
   for (int i = 0; i < n; ++i) {
     const EmrtConvBwdDesc& b = descs[i];
     ConvArgs& d = g.d[i];
-    d.in = b.dy; d.w = b.w_bwd_packed; d.out = b.dx; d.bias = nullptr; d.scale = nullptr; d.res = b.accumulate ? b.dx : nullptr;
-    d.N = b.N; d.H = b.OH; d.W = b.OW; d.C = b.OC; d.ldin = b.lddy; d.in_bs = b.dy_bs;
-    d.OH = b.H; d.OW = b.W; d.OC = b.C; d.ldout = b.lddx; d.out_bs = b.dx_bs;
-    d.ldres = b.accumulate ? b.lddx : 0; d.res_bs = b.accumulate ? b.dx_bs : 0;
-    d.KH = b.KH; d.KW = b.KW; d.stride = b.stride; d.pad = b.pad; d.dil = 1; d.relu = 0; d.out_f32 = 0; d.cmajor = 0; d.stats = nullptr;
-    d.mask_y = nullptr; d.ldy = 0; d.y_bs = 0; d.mask_scale = 1.f; d.stat_x = nullptr; d.ldsx = 0; d.sx_bs = 0;
-    d.xk_S = 0; d.xk_part = nullptr; d.xk_tick = nullptr; d.drop_seed = nullptr; d.drop_salt = 0; d.drop_p = 0.f;
+    d = dgrad_args_from_bwd_desc(b);
     WgradArgs& w = g.w[i];
-    w.x = b.x; w.dy = b.dy; w.dw = b.dw;
-    w.N = b.N; w.H = b.H; w.W = b.W; w.C = b.C; w.ldx = b.ldx; w.x_bs = b.x_bs;
-    w.OH = b.OH; w.OW = b.OW; w.OC = b.OC; w.lddy = b.lddy; w.dy_bs = b.dy_bs;
-    w.KH = b.KH; w.KW = b.KW; w.stride = b.stride; w.pad = b.pad; w.dil = 1; w.tiles_per_split = 0; w.dbias = b.dbias; w.overwrite = 0;
-    const bool vec = conv_desc_is_vec<T>(d) && wgrad_is_vec<T>(w) && d.OC > 32;
+    w = wgrad_args(b.x, b.dy, b.dw, b.dbias, b.N, b.H, b.W, b.C, b.ldx, b.x_bs, b.OH, b.OW, b.OC, b.lddy, b.dy_bs, b.KH, b.KW, b.stride, b.pad, 1, 0);
+    const bool vec = conv_is_vec<T>(d) && wgrad_is_vec<T>(w) && d.OC > 32;
     groupable = groupable && vec;
     int tx = 1, ty = 1, S = 1;
     if (vec) wgrad_plan<T>(w, tx, ty, S);
-    const long long Md = (long long)d.N * d.OH * d.OW;
-    g.nd[i] = (int)(((Md + 63) / 64) * ((d.OC + 63) / 64));
+    g.nd[i] = (int)conv_blocks(d, 64, 64);
     g.wtx[i] = tx; g.wty[i] = ty;
     g.first[i] = (int)total;
     total += g.nd[i] + (long long)tx * ty * S;
@@ -2385,15 +2403,10 @@ extern "C" int emrt_conv2d_bwd_group(const EmrtConvBwdDesc* descs, int n, int dt
     const EmrtConvBwdDesc& b = descs[i];
     EMRT_REQUIRE(b.x && b.dy && b.w_bwd_packed && b.dx, "null pointer");
     EMRT_REQUIRE((b.dw == nullptr) == (descs[0].dw == nullptr) && (b.dw || !b.dbias), "dw == NULL (data gradients only) must hold for every problem of the group, without dbias");
-    EMRT_REQUIRE(b.N > 0 && b.H > 0 && b.W > 0 && b.C > 0 && b.OC > 0 && b.KH > 0 && b.KW > 0 && b.stride > 0 && b.pad >= 0, "bad dims");
-    EMRT_REQUIRE(b.OH == (b.H + 2 * b.pad - b.KH) / b.stride + 1 && b.OW == (b.W + 2 * b.pad - b.KW) / b.stride + 1, "output size mismatch");
-    EMRT_REQUIRE((long long)b.N * b.OH * b.OW + 512 < (1ll << 31) && (long long)b.N * b.H * b.W + 512 < (1ll << 31), "more than 2^31 pixels");
+    const ConvShape s = {b.N, b.H, b.W, b.C, b.OH, b.OW, b.OC, b.KH, b.KW, b.stride, b.pad, 1};
+    EMRT_CONV_CHECK(s, b.ldx, b.x_bs, b.lddy, b.dy_bs, dtype, CK_GROUPED | CK_DIMS | CK_SIZE | CK_PIXELS);
     EMRT_REQUIRE(b.lddx >= b.C && b.dx_bs >= 0, "bad dx strides");
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long x_ext = ((long long)(b.N - 1) * b.x_bs + ((long long)b.H * b.W - 1) * b.ldx + b.C) * esz;
-    const long long dy_ext = ((long long)(b.N - 1) * b.dy_bs + ((long long)b.OH * b.OW - 1) * b.lddy + b.OC) * esz;
-    EMRT_REQUIRE(b.x_bs >= 0 && b.dy_bs >= 0 && x_ext < (1ll << 31) && dy_ext < (1ll << 31), "operand spans 2 GiB or more");
-    EMRT_REQUIRE((long long)b.H * b.W < (1 << 24) && (long long)b.ldx * esz < (1 << 24) && b.stride < (1 << 12), "map too large for the 24-bit address arithmetic");
+    EMRT_CONV_CHECK(s, b.ldx, b.x_bs, b.lddy, b.dy_bs, dtype, CK_GROUPED | CK_X | CK_Y | CK_X24);
   }
   hipStream_t st = (hipStream_t)stream;
   return dtype == EMRT_F32 ? conv_bwd_group_dispatch<float>(descs, n, st) : conv_bwd_group_dispatch<bf16_t>(descs, n, st);
@@ -2404,50 +2417,17 @@ extern "C" int emrt_conv2d_bwd_group(const EmrtConvBwdDesc* descs, int n, int dt
 // BatchNorm backward sums, an addend).  This one mirrors the data-gradient half of emrt_conv2d_bwd argument by argument, so that a layer3 block's
 // conv1 data gradient (512 tiles of 4 k-tiles: a launch that is all ramp and tail) can take the spatial branch's pending 3x3 data gradient
 // into its launch (functional.py: the tape's stash).  n == 1 is emrt_conv2d_bwd with dw == NULL.
-struct EmrtConvDgradDesc {
-  const void* dy; const void* w_bwd_packed; void* dx; int lddx; long long dx_bs; int accumulate;
-  int N, H, W, C, OH, OW, OC, lddy; long long dy_bs; int KH, KW, stride, pad, dilation;
-  double* bn_stats; const void* mask_y; int ldy; long long y_bs; float mask_scale; const void* stat_x; int ldsx; long long sx_bs;
-  const void* addend; int ldadd; long long add_bs;
-};
-
-static void dgrad_args_from_desc(ConvArgs& d, const EmrtConvDgradDesc& b) {
-  d.in = b.dy; d.w = b.w_bwd_packed; d.out = b.dx; d.bias = nullptr; d.scale = nullptr; d.res = nullptr;
-  d.N = b.N; d.H = b.OH; d.W = b.OW; d.C = b.OC; d.ldin = b.lddy; d.in_bs = b.dy_bs;
-  d.OH = b.H; d.OW = b.W; d.OC = b.C; d.ldout = b.lddx; d.out_bs = b.dx_bs;
-  d.ldres = 0; d.res_bs = 0;
-  if (b.accumulate) { d.res = b.dx; d.ldres = b.lddx; d.res_bs = b.dx_bs; }
-  else if (b.addend) { d.res = b.addend; d.ldres = b.ldadd; d.res_bs = b.add_bs; }
-  d.KH = b.KH; d.KW = b.KW; d.stride = b.stride; d.pad = b.pad; d.dil = b.dilation; d.relu = 0; d.out_f32 = 0; d.cmajor = g_tune.igemm8p_cmajor; d.stats = b.bn_stats;
-  d.mask_y = b.mask_y; d.ldy = b.ldy; d.y_bs = b.y_bs; d.mask_scale = b.mask_scale; d.stat_x = b.stat_x; d.ldsx = b.ldsx; d.sx_bs = b.sx_bs;
-  d.xk_S = 0; d.xk_part = nullptr; d.xk_tick = nullptr; d.drop_seed = nullptr; d.drop_salt = 0; d.drop_p = 0.f;
-}
-
 template <class T>
 static int conv_dgrad_multi_dispatch(const EmrtConvDgradDesc* descs, int n, hipStream_t st) {
   ConvGroupArgs g;
-  bool groupable = n >= 2;
-  long long total = 0;
   for (int i = 0; i < n; ++i) {
-    ConvArgs& d = g.p[i];
-    dgrad_args_from_desc(d, descs[i]);
-    const long long Md = (long long)d.N * d.OH * d.OW;
-    const long long nb = ((Md + 63) / 64) * ((d.OC + 63) / 64);
-    g.first[i] = (int)total;
-    total += nb;
-    groupable = groupable && conv_desc_is_vec<T>(d) && d.OC > 32 && nb <= 2048;
+    const EmrtConvDgradDesc& b = descs[i];
+    g.p[i] = conv_dgrad_args(b.dy, b.w_bwd_packed, b.dx, b.lddx, b.dx_bs, b.accumulate, b.addend, b.ldadd, b.add_bs, b.N, b.H, b.W, b.C, b.OH, b.OW, b.OC, b.lddy,
+                             b.dy_bs, b.KH, b.KW, b.stride, b.pad, b.dilation, g_tune.igemm8p_cmajor, b.bn_stats, b.mask_y, b.ldy, b.y_bs, b.mask_scale, b.stat_x,
+                             b.ldsx, b.sx_bs);
   }
-  for (int i = n; i <= EMRT_MAX_GROUP; ++i) g.first[i] = (int)total;
-  for (int i = n; i < EMRT_MAX_GROUP; ++i) g.p[i] = g.p[0];
-  if (!groupable || total > 4096) {
-    for (int i = 0; i < n; ++i) {
-      const int rc = conv_dispatch<T, 1>(g.p[i], st);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  hipLaunchKernelGGL((igemm_group_kernel<T, 1>), dim3((unsigned)total), dim3(256), (size_t)2 * 128 * 144, st, g);
-  return check_launch("emrt_conv2d_dgrad_multi");
+  if (n == 1) return conv_dispatch<T, 1>(g.p[0], st);      // emrt_conv2d_bwd with dw == NULL
+  return conv_group_launch<T, 1>(g, n, 2048, "emrt_conv2d_dgrad_multi", st);
 }
 
 extern "C" int emrt_conv2d_dgrad_multi(const EmrtConvDgradDesc* descs, int n, int dtype, void* stream) {
@@ -2456,15 +2436,8 @@ extern "C" int emrt_conv2d_dgrad_multi(const EmrtConvDgradDesc* descs, int n, in
   for (int i = 0; i < n; ++i) {
     const EmrtConvDgradDesc& b = descs[i];
     EMRT_REQUIRE(b.dy && b.w_bwd_packed && b.dx, "null pointer");
-    EMRT_REQUIRE(b.N > 0 && b.H > 0 && b.W > 0 && b.C > 0 && b.OH > 0 && b.OW > 0 && b.OC > 0, "bad dims");
-    EMRT_REQUIRE(b.KH > 0 && b.KW > 0 && b.stride > 0 && b.pad >= 0 && b.dilation >= 1, "bad kernel geometry");
-    EMRT_REQUIRE(b.OH == (b.H + 2 * b.pad - b.dilation * (b.KH - 1) - 1) / b.stride + 1 && b.OW == (b.W + 2 * b.pad - b.dilation * (b.KW - 1) - 1) / b.stride + 1, "output size mismatch");
-    EMRT_REQUIRE((long long)b.N * b.OH * b.OW + 512 < (1ll << 31) && (long long)b.N * b.H * b.W + 512 < (1ll << 31), "more than 2^31 pixels (32-bit pixel arithmetic)");
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long dy_ext = ((long long)(b.N - 1) * b.dy_bs + ((long long)b.OH * b.OW - 1) * b.lddy + b.OC) * esz;
-    const long long w_ext = (long long)b.OC * b.KH * b.KW * b.C * esz;
-    EMRT_REQUIRE(b.dy_bs >= 0 && dy_ext < (1ll << 31) && w_ext < (1ll << 31), "operand spans 2 GiB or more (32-bit buffer offsets)");
-    EMRT_REQUIRE((long long)b.OH * b.OW < (1 << 24) && (long long)b.lddy * esz < (1 << 24) && b.stride < (1 << 12), "map too large for the 24-bit address arithmetic");
+    const ConvShape s = {b.N, b.H, b.W, b.C, b.OH, b.OW, b.OC, b.KH, b.KW, b.stride, b.pad, b.dilation};
+    EMRT_CONV_CHECK(s, 0, 0, b.lddy, b.dy_bs, dtype, CK_DIMS | CK_KERNEL | CK_SIZE | CK_PIXELS | CK_Y | CK_W | CK_Y24);      // (there is no x: dy is the gathered operand)
     EMRT_REQUIRE(b.lddx >= b.C && b.dx_bs >= 0, "bad dx strides");
     EMRT_REQUIRE(!(b.accumulate && b.addend), "accumulate adds into dx itself; addend is a different tensor");
     EMRT_REQUIRE(!b.stat_x || b.mask_y, "stat_x replaces the mask tensor in the second statistic: it needs mask_y");
@@ -2482,13 +2455,6 @@ extern "C" int emrt_conv2d_dgrad_multi(const EmrtConvDgradDesc* descs, int n, in
 // layer); a batch of 8-24 layers fills the machine with 1-4 slices each.
 // ------------------------------------------------------------------------------------------------
 #define EMRT_MAX_WGROUP 24
-struct EmrtWgradDesc {
-  const void* x; const void* dy; float* dw; float* dbias;
-  int N, H, W, C, ldx; long long x_bs;
-  int OH, OW, OC, lddy; long long dy_bs;
-  int KH, KW, stride, pad, dilation;
-  int dw_is_zero;
-};
 struct WgradGroupArgs {
   WgradArgs w[EMRT_MAX_WGROUP];
   int first[EMRT_MAX_WGROUP + 1];      // work items of problem i: [first[i], first[i+1]), slice-major (slice, oc tile, k tile)
@@ -2517,12 +2483,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_group_kernel(WgradGroupArgs g) {
   wgrad_body<T, true, 1>(g.w[i], __builtin_amdgcn_readfirstlane(t - by * tx), by, bz, smem_all);
 }
 
-static void wgrad_args_from_desc(WgradArgs& a, const EmrtWgradDesc& d) {
-  a.x = d.x; a.dy = d.dy; a.dw = d.dw;
-  a.N = d.N; a.H = d.H; a.W = d.W; a.C = d.C; a.ldx = d.ldx; a.x_bs = d.x_bs;
-  a.OH = d.OH; a.OW = d.OW; a.OC = d.OC; a.lddy = d.lddy; a.dy_bs = d.dy_bs;
-  a.KH = d.KH; a.KW = d.KW; a.stride = d.stride; a.pad = d.pad; a.dil = d.dilation; a.tiles_per_split = 0; a.dbias = d.dbias;
-  a.overwrite = d.dw_is_zero ? 1 : 0;      // (cleared below for every problem that ends up with more than one slice)
+static WgradArgs wgrad_args_from_desc(const EmrtWgradDesc& d) {      // (overwrite is cleared below for every problem that ends up with more than one slice)
+  return wgrad_args(d.x, d.dy, d.dw, d.dbias, d.N, d.H, d.W, d.C, d.ldx, d.x_bs, d.OH, d.OW, d.OC, d.lddy, d.dy_bs, d.KH, d.KW, d.stride, d.pad, d.dilation,
+                    d.dw_is_zero ? 1 : 0);
 }
 
 template <class T>
@@ -2609,16 +2572,14 @@ static int wgrad_group_dispatch(const EmrtWgradDesc* descs, int n, hipStream_t s
   long long work8 = 0;
   if constexpr (std::is_same<T, bf16_t>::value) {
     for (int i = 0; i < n && g_tune.wgroup8 > 0; ++i) {
-      WgradArgs a;
-      wgrad_args_from_desc(a, descs[i]);
+      const WgradArgs a = wgrad_args_from_desc(descs[i]);
       int tk, toc, S8, per, tiles8, steps8;
       if (wgrad_is_vec<T>(a) && !wgrad8p_plan<T>(a, tk, toc, S8, per) && wgrad8p_group_ok<T>(a, tiles8, steps8) && !aliased(i)) work8 += (long long)tiles8 * steps8;
     }
   }
   const bool use8 = g_tune.wgroup8 > 0 && work8 >= (g_tune.wgroup8_min_work > 0 ? g_tune.wgroup8_min_work : 1);
   for (int i = 0; i < n; ++i) {
-    WgradArgs a;
-    wgrad_args_from_desc(a, descs[i]);
+    WgradArgs a = wgrad_args_from_desc(descs[i]);
     // a weight used more than once in the step (a shared layer) appears as several problems with the same dw: a stored tile of one would
     // race with the atomic adds of the other (same launch), or land after them ('alone' problems are launched before the pended batch):
     // every problem whose dw another problem of this call also writes accumulates
@@ -2664,15 +2625,10 @@ extern "C" int emrt_conv2d_wgrad_group(const EmrtWgradDesc* descs, int n, int dt
   for (int i = 0; i < n; ++i) {
     const EmrtWgradDesc& d = descs[i];
     EMRT_REQUIRE(d.x && d.dy && d.dw, "null pointer");
-    EMRT_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.C > 0 && d.OH > 0 && d.OW > 0 && d.OC > 0 && d.dilation >= 1, "bad dims");
-    EMRT_REQUIRE(d.KH > 0 && d.KW > 0 && d.stride > 0 && d.pad >= 0, "bad kernel geometry");
-    EMRT_REQUIRE(d.OH == (d.H + 2 * d.pad - d.dilation * (d.KH - 1) - 1) / d.stride + 1 && d.OW == (d.W + 2 * d.pad - d.dilation * (d.KW - 1) - 1) / d.stride + 1, "output size mismatch");
-    EMRT_REQUIRE((long long)d.N * d.OH * d.OW + 512 < (1ll << 31) && (long long)d.N * d.H * d.W + 512 < (1ll << 31), "more than 2^31 pixels (32-bit pixel arithmetic)");
-    const long long esz = dtype == EMRT_F32 ? 4 : 2;
-    const long long x_ext = ((long long)(d.N - 1) * d.x_bs + ((long long)d.H * d.W - 1) * d.ldx + d.C) * esz;
-    const long long dy_ext = ((long long)(d.N - 1) * d.dy_bs + ((long long)d.OH * d.OW - 1) * d.lddy + d.OC) * esz;
-    EMRT_REQUIRE(d.x_bs >= 0 && d.dy_bs >= 0 && x_ext < (1ll << 31) && dy_ext < (1ll << 31), "operand spans 2 GiB or more (32-bit buffer offsets)");
-    EMRT_REQUIRE((long long)d.H * d.W < (1 << 24) && (long long)d.ldx * esz < (1 << 24) && d.stride < (1 << 12), "map too large for the 24-bit address arithmetic");
+    const ConvShape s = {d.N, d.H, d.W, d.C, d.OH, d.OW, d.OC, d.KH, d.KW, d.stride, d.pad, d.dilation};
+    EMRT_CONV_CHECK(s, d.ldx, d.x_bs, d.lddy, d.dy_bs, dtype, CK_DIMS);
+    EMRT_REQUIRE(d.dilation >= 1, "bad dims");
+    EMRT_CONV_CHECK(s, d.ldx, d.x_bs, d.lddy, d.dy_bs, dtype, CK_KERNEL | CK_SIZE | CK_PIXELS | CK_X | CK_Y | CK_X24);
   }
   hipStream_t st = (hipStream_t)stream;
   return dtype == EMRT_F32 ? wgrad_group_dispatch<float>(descs, n, st) : wgrad_group_dispatch<bf16_t>(descs, n, st);

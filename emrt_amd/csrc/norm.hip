@@ -1533,21 +1533,11 @@ extern "C" int emrt_colsum_levels_multi(const void* const* xs, int T, const int*
 // all-reduced between the passes: functional.conv_bn_group keeps its own path for that).
 // ------------------------------------------------------------------------------------------------
 #define EMRT_MAX_BNGROUP 8
-struct EmrtBnGroupDesc {
-  const void* x;          // raw map [M][C], row stride ldx
-  void* y;                // forward: out = [relu](BN(x)); backward: the forward's output (ReLU mask source; nullable when relu == 0)
-  const void* dy;         // backward: gradient of y
-  void* dx;               // backward: gradient of x
-  double* sums;           // forward: complete (sum x, sum x^2) [8][2C]; backward: ZEROED [8][2C], receives (sum dy', sum dy' * xhat)
-  float* mean; float* invstd; float* run_mean; float* run_var;
-  const float* gamma; const float* beta; float* dgamma; float* dbeta;
-  double count;
-  float eps, momentum;
-  int M, C, ldx, ldy, lddy, lddx, relu;
-  const void* res;        // forward, nullable: y = [relu](BN(x)) + res  (Conv2dBlock's "conv2(conv1(x)) + x", paddle_EMRT.py:24-29; its gradient is dy itself)
-  int ldres, res_hw;      // row r of the problem is pixel r % res_hw of image r / res_hw: res + image * res_bs + pixel * ldres (a level slab of the token tensor)
-  long long res_bs;
-};
+// EmrtBnGroupDesc (include/emrt_hip.h) travels in the kernel arguments as it is.  x: raw map [M][C], row stride ldx; y: forward out = [relu](BN(x)), backward the
+// forward's output (ReLU mask source; nullable when relu == 0); dy / dx: backward gradients of y / x; sums: forward the complete (sum x, sum x^2) [8][2C],
+// backward a ZEROED [8][2C] that receives (sum dy', sum dy' * xhat); res (forward, nullable): y = [relu](BN(x)) + res (Conv2dBlock's "conv2(conv1(x)) + x",
+// paddle_EMRT.py:24-29; its gradient is dy itself), row r of the problem being pixel r % res_hw of image r / res_hw: res + image * res_bs + pixel * ldres
+// (a level slab of the token tensor)
 struct BnGroupArgs { EmrtBnGroupDesc d[EMRT_MAX_BNGROUP]; int first[EMRT_MAX_BNGROUP + 1]; int n; };
 
 __device__ __forceinline__ int bn_group_pick(const BnGroupArgs& g, int& local, int& nblk) {
