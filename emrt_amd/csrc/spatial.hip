@@ -474,8 +474,8 @@ __global__ __launch_bounds__(POOL_THREADS) void adaptive_pool_fwd_kernel(PoolArg
   }
 }
 
-// backward: `in` = d(out) tokens, `out` = d(in) map (fully overwritten).  A pixel lies in at most two (overlapping)
-// bins per axis and scale: the bin floor(h*k/H) and its predecessor.
+// backward: `in` = d(out) tokens, `out` = d(in) map (fully overwritten).  Row h lies in the bins floor(h k / H) .. ceil((h + 1) k / H) - 1
+// of scale k: at most two while k <= H (neighbouring bins overlap by one pixel), ceil(k / H) + 1 on a map smaller than the scale.
 template <class T>
 __global__ __launch_bounds__(256) void adaptive_pool_bwd_kernel(PoolArgs a) {
   const long long total = (long long)a.N * a.H * a.W * a.C;
@@ -486,12 +486,13 @@ __global__ __launch_bounds__(256) void adaptive_pool_bwd_kernel(PoolArgs a) {
     float acc = 0.f;
     for (int s = 0; s < a.nscales; ++s) {
       const int k = a.k[s];
-      const int oi_hi = (h * k) / a.H, oj_hi = (w * k) / a.W;
-      for (int oi = oi_hi > 0 ? oi_hi - 1 : 0; oi <= oi_hi + 1 && oi < k; ++oi) {
+      const int oi_lo = (h * k) / a.H, oi_hi = ((h + 1) * k + a.H - 1) / a.H - 1;      // every bin that holds row h (oi_hi <= k - 1)
+      const int oj_lo = (w * k) / a.W, oj_hi = ((w + 1) * k + a.W - 1) / a.W - 1;
+      for (int oi = oi_lo; oi <= oi_hi; ++oi) {
         int h0, h1;
         bin_of(oi, k, a.H, h0, h1);
         if (h < h0 || h >= h1) continue;
-        for (int oj = oj_hi > 0 ? oj_hi - 1 : 0; oj <= oj_hi + 1 && oj < k; ++oj) {
+        for (int oj = oj_lo; oj <= oj_hi; ++oj) {
           int w0, w1;
           bin_of(oj, k, a.W, w0, w1);
           if (w < w0 || w >= w1) continue;
@@ -577,12 +578,13 @@ __global__ __launch_bounds__(256) void adaptive_pool_bwd_vec_kernel(PoolArgs a) 
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < a.nscales; ++s) {
       const int k = a.k[s];
-      const int oi_hi = (h * k) / a.H, oj_hi = (w * k) / a.W;
-      for (int oi = oi_hi > 0 ? oi_hi - 1 : 0; oi <= oi_hi + 1 && oi < k; ++oi) {
+      const int oi_lo = (h * k) / a.H, oi_hi = ((h + 1) * k + a.H - 1) / a.H - 1;      // every bin that holds row h (oi_hi <= k - 1)
+      const int oj_lo = (w * k) / a.W, oj_hi = ((w + 1) * k + a.W - 1) / a.W - 1;
+      for (int oi = oi_lo; oi <= oi_hi; ++oi) {
         int h0, h1;
         bin_of(oi, k, a.H, h0, h1);
         if (h < h0 || h >= h1) continue;
-        for (int oj = oj_hi > 0 ? oj_hi - 1 : 0; oj <= oj_hi + 1 && oj < k; ++oj) {
+        for (int oj = oj_lo; oj <= oj_hi; ++oj) {
           int w0, w1;
           bin_of(oj, k, a.W, w0, w1);
           if (w < w0 || w >= w1) continue;

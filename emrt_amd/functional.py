@@ -27,9 +27,13 @@ def _check_map(t):
     """(N, H, W, C, ld, bs) of an NHWC map view; [B, L, C] tokens count as [B, 1, L, C], [M, C] as [1, 1, M, C]."""
     assert t.stride(-1) == 1, "inner stride must be 1: %s %s" % (tuple(t.shape), t.stride())
     if t.dim() == 4:
-        assert t.stride(1) == t.shape[2] * t.stride(2), \
+        N, H, W, C = t.shape
+        # torch leaves the stride of a dimension of size 1 at whatever the producing view had (a [N, C, 1, 1] map permuted to NHWC keeps
+        # stride 1 for H and W): such a stride addresses nothing, so the pixel and image strides come from the next dimension that does
+        ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if N > 1 else C))
+        assert H == 1 or W == 1 or t.stride(1) == W * t.stride(2), \
             "expected an NHWC view with dense rows, got shape %s strides %s" % (tuple(t.shape), t.stride())
-        return t.shape[0], t.shape[1], t.shape[2], t.shape[3], t.stride(2), t.stride(0)
+        return N, H, W, C, ld, (t.stride(0) if N > 1 else H * W * ld)
     if t.dim() == 3:
         return t.shape[0], 1, t.shape[1], t.shape[2], t.stride(1), t.stride(0)
     assert t.dim() == 2

@@ -1,0 +1,596 @@
+"""Seeded random case lists for the shape sweeps of csrc/norm.hip, csrc/spatial.hip and the inference glue
+(tests/test_gpu_norm_fuzz.py, tests/test_gpu_spatial_fuzz.py, tests/test_gpu_infer_glue.py), and the dispatchers' shape predicates
+restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
+entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
+seed or a range cannot silently empty one.
+
+A case is a tuple whose first element is its id; the generators draw with random.Random(<fixed seed>) and steer every draw towards one
+regime in turn (the `kinds` lists), then the REGIMES predicates -- written against the mirrored dispatcher predicates, not against the
+steering -- say what each case actually hits.  Every case stays below MAX_ELEMS elements per tensor: the cost of a case is its float64
+CPU reference, not the GPU.
+
+Regime -> case ids (regime_table() renders this text; the CPU test compares):
+
+  batchnorm         256 threads, rows_per_pass > 1, M < rows_per_pass  bn1101-{0,6,11,12,17}
+  batchnorm         256 threads, rows_per_pass > 1, M ragged against it bn1101-{1,7,13}
+  batchnorm         threads = C/4, whole waves                         bn1101-{2,8,14}
+  batchnorm         threads = C/4, a partial last wave                 bn1101-{3,5,9,15}
+  batchnorm         C = 1024 (256 threads, one row per pass)           bn1101-{4,10,16}
+  groupnorm         fused (one block per image and group)              gn1202-{0,3,4,5,6,9,10,11,12,15}
+  groupnorm         two-pass because HW > 4096                         gn1202-{1,7,13}
+  groupnorm         two-pass because C/G > 256                         gn1202-{2,8,14}
+  groupnorm         HW = 1                                             gn1202-{3,9,15}
+  groupnorm_levels  L = 1                                              gnl1303-{0,4}
+  groupnorm_levels  L = 4                                              gnl1303-{1,2,5}
+  groupnorm_levels  a level of one row                                 gnl1303-{2,6,7}
+  groupnorm_levels  row-major kernels (C = 8 G)                        gnl1303-{0,1,4,5}
+  groupnorm_levels  block per (level, image, group)                    gnl1303-{2,3,6,7}
+  layernorm         C < 256 (a partial pass)                           ln1404-{0,7,9,17}
+  layernorm         C = 256 (one whole pass)                           ln1404-{1,4,10,15}
+  layernorm         C > 256 with a ragged last pass                    ln1404-{2,5,8,11}
+  layernorm         C = 1024                                           ln1404-{3,6,12,16}
+  layernorm         rows % 4 != 0                                      ln1404-{1,3,4,5,6,7,8,10,11,12,13,14,16,17}
+  layernorm         rows = 1                                           ln1404-{5,8,14}
+  layernorm         backward blocks loop under the block cap           ln1404-{6,15}
+  layernorm         form ln(a)                                         ln1404-{0,3,6,9,12,15}
+  layernorm         form ln(a+b)                                       ln1404-{1,4,7,10,13,16}
+  layernorm         form ln(a+b,post)                                  ln1404-{2,5,8,11,14,17}
+  resize            up on both axes                                    rs1505-{0,4,7,8,11,13,17,20}
+  resize            down on both axes                                  rs1505-{1,5,14,18,19,21,23}
+  resize            mixed: up on one axis, down on the other           rs1505-{2,6,9,10,12,15,22,24,25}
+  resize            identity                                           rs1505-{3,16}
+  resize            down with align_corners=False                      rs1505-{1,5,6,9,19,21,22,23}
+  resize            1-pixel input                                      rs1505-{4,17}
+  resize            1-pixel output                                     rs1505-{5,18}
+  resize            NHWC, 8 channels per access (bf16)                 rs1505-{0,8,17,20,21,24}
+  resize            NHWC, 4 channels per access                        rs1505-{5,7,9,13,22}
+  resize            NHWC, scalar                                       rs1505-{1,2,3,4,10,14,15,16,18,23}
+  resize            backward: block per source pixel                   rs1505-{0,7,13,17,20}
+  resize            fp32 NCHW output and its two-kernel backward       rs1505-{6,11,12,19,25}
+  resize            fused addend                                       rs1505-{2,3,5,8,13,15,16,17,21,22,23}
+  maxpool           stride < k (windows overlap)                       mp1606-{0,6,11,12,17}
+  maxpool           stride = k                                         mp1606-{1,4,7,9,13}
+  maxpool           stride > k (pixels in no window)                   mp1606-{2,3,5,8,10,14,15,16}
+  maxpool           k = 1                                              mp1606-{2,3,4,9,13,15,16}
+  maxpool           k = 7                                              mp1606-{17}
+  maxpool           forward 8 channels per thread, backward 4          mp1606-{3,4,8,9,13,14}
+  maxpool           forward scalar, backward 4 channels per thread     mp1606-{1,2,6,7,11,12,16,17}
+  maxpool           scalar both ways                                   mp1606-{0,5,10,15}
+  adaptive_pool     H or W < k                                         ap1707-{0,5,10}
+  adaptive_pool     non-square map                                     ap1707-{0,1,2,3,4,5,6,7,8,9,10,11,12,13}
+  adaptive_pool     forward: several blocks per bin                    ap1707-{2,7,9,12}
+  adaptive_pool     forward: one block per bin                         ap1707-{0,1,3,4,5,6,8,10,11,13}
+  adaptive_pool     scalar path (C % 4 != 0)                           ap1707-{3,5,8,13}
+  adaptive_pool     backward: two-bin table                            ap1707-{1,2,4,6,7,9,11,12}
+  adaptive_pool     backward: general gather                           ap1707-{0,10}
+  adaptive_pool     input is a slice of a wider buffer                 ap1707-{0,1,2,3,4,6,7,9,10,11,12}
+  pyramid           one launch per direction, fp32 and bf16            py1808-{0,4,6,8}
+  pyramid           one launch in fp32, per scale in bf16 (8-byte slices) py1808-{2,10}
+  pyramid           per-scale fallback by the knob                     py1808-{1,3,5,7,9,11}
+
+Not reachable through the wrappers, on purpose:
+  * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
+    draws no align_corners=False case; the per-scale resize kernels see both conventions in the resize sweep.
+  * the 64-bit index branch of unravel3 / unravel4 (csrc/common.hpp) needs more than 2^32 elements and stays unexercised.
+"""
+import random
+
+MAX_ELEMS = 400000
+
+
+def _ceil_div(a, b):
+    return -(-a // b)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# BatchNorm (training): emrt_bn_stats / emrt_bn_apply / emrt_bn_bwd_reduce / emrt_bn_bwd_dx
+# ---------------------------------------------------------------------------------------------------------------------------------
+def bn_rowgeom(C):
+    """(threads, rows_per_pass) or None.  Mirrors bn_rowgeom (csrc/norm.hip), without the grid size."""
+    quads = C // 4
+    if quads <= 256:
+        if quads == 0 or 256 % quads:
+            return None
+        return 256, 256 // quads
+    if quads <= 512:
+        return quads, 1
+    return None
+
+
+def bn_in_domain(case):
+    _, N, H, W, C, relu, with_res, _ = case
+    return C % 4 == 0 and bn_rowgeom(C) is not None and N * H * W >= 2 and (relu or not with_res)
+
+
+BN_NARROW = (4, 8, 16, 32, 128, 1024)
+BN_WIDE = (1028, 1536, 2044, 2048)
+
+
+def bn_cases(seed=1101, n=18):
+    """(id, N, H, W, C, relu, with_res, seed)"""
+    rng = random.Random(seed)
+    kinds = ["short", "ragged", "whole-waves", "part-wave", "C=1024", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        if kind in ("short", "ragged"):
+            C = rng.choice((4, 8, 16, 32, 128))
+        elif kind == "whole-waves":
+            C = rng.choice((1536, 2048))
+        elif kind == "part-wave":
+            C = rng.choice((1028, 2044))
+        elif kind == "C=1024":
+            C = 1024
+        else:
+            C = rng.choice(BN_NARROW + BN_WIDE)
+        N, H, W = rng.randint(1, 3), rng.randint(1, 16), rng.randint(1, 16)
+        M = N * H * W
+        if M < 8 or M > min(600, MAX_ELEMS // C):
+            continue
+        _, rpp = bn_rowgeom(C)
+        if kind == "short" and not (rpp > 1 and M < rpp):
+            continue
+        if kind == "ragged" and not (rpp > 1 and M > rpp and M % rpp):
+            continue
+        relu, with_res = rng.choice(((True, True), (True, False), (False, False)))      # as test_batch_norm_train
+        out.append(("bn%d-%d" % (seed, len(out)), N, H, W, C, relu, with_res, seed + len(out)))
+    return out
+
+
+def _bn_geo(c):
+    """(threads, rows_per_pass, M) of a BatchNorm case"""
+    return bn_rowgeom(c[4]) + (c[1] * c[2] * c[3],)
+
+
+BN_REGIMES = [
+    ("256 threads, rows_per_pass > 1, M < rows_per_pass", lambda c: _bn_geo(c)[0] == 256 and 1 < _bn_geo(c)[1] and _bn_geo(c)[2] < _bn_geo(c)[1]),
+    ("256 threads, rows_per_pass > 1, M ragged against it", lambda c: _bn_geo(c)[0] == 256 and 1 < _bn_geo(c)[1] < _bn_geo(c)[2] and _bn_geo(c)[2] % _bn_geo(c)[1] != 0),
+    ("threads = C/4, whole waves", lambda c: c[4] > 1024 and _bn_geo(c)[0] == c[4] // 4 and _bn_geo(c)[0] % 64 == 0),
+    ("threads = C/4, a partial last wave", lambda c: c[4] > 1024 and _bn_geo(c)[0] == c[4] // 4 and _bn_geo(c)[0] % 64 != 0),
+    ("C = 1024 (256 threads, one row per pass)", lambda c: c[4] == 1024),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GroupNorm: emrt_groupnorm_fwd / emrt_groupnorm_bwd
+# ---------------------------------------------------------------------------------------------------------------------------------
+def gn_use_fused(HW, C, G):
+    """Mirrors gn_use_fused (csrc/norm.hip): one block per (image, group), else the two-pass statistics + apply kernels."""
+    cpg = C // G
+    return HW <= 4096 and cpg % 4 == 0 and cpg // 4 <= 64 and 256 % (cpg // 4) == 0 and (cpg // 4) * 64 >= 64
+
+
+def gn_in_domain(case):
+    """the EMRT_REQUIRE of emrt_groupnorm_fwd / _bwd"""
+    _, N, H, W, C, G, _, _, _ = case
+    return (C % 4 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0 and 0 < G <= 256 and C % G == 0 and (C // G) % 4 == 0
+            and N >= 1 and H * W >= 1 and (C // G) * H * W >= 16)
+
+
+def gn_cases(seed=1202, n=16):
+    """(id, N, H, W, C, G, gelu, with_res, seed)"""
+    rng = random.Random(seed)
+    kinds = ["fused", "hw>4096", "wide-group", "hw=1", "fused", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        C = 2 ** rng.randint(4, 10)
+        N = rng.randint(1, 3)
+        H, W = rng.randint(1, 40), rng.randint(1, 40)
+        if kind == "hw>4096":
+            C, N = rng.choice((16, 32, 64)), 1
+            H, W = rng.randint(58, 80), rng.randint(58, 80)
+            if not 4096 < H * W <= 5200:
+                continue
+        elif kind == "wide-group":
+            C = rng.choice((512, 1024))
+        elif kind == "hw=1":
+            H = W = 1
+        cpgs = [cpg for cpg in (2 ** e for e in range(2, 11)) if cpg <= C and C // cpg <= 256]
+        if kind == "wide-group":
+            cpgs = [cpg for cpg in cpgs if cpg > 256]
+        elif kind == "fused":
+            cpgs = [cpg for cpg in cpgs if cpg <= 256]
+        G = C // rng.choice(cpgs)
+        if N * H * W * C > MAX_ELEMS or (C // G) * H * W < 16:
+            continue
+        gelu, with_res = rng.random() < 0.5, rng.random() < 0.5
+        out.append(("gn%d-%d" % (seed, len(out)), N, H, W, C, G, gelu, with_res, seed + len(out)))
+    return out
+
+
+GN_REGIMES = [
+    ("fused (one block per image and group)", lambda c: gn_use_fused(c[2] * c[3], c[4], c[5])),
+    ("two-pass because HW > 4096", lambda c: not gn_use_fused(c[2] * c[3], c[4], c[5]) and c[2] * c[3] > 4096),
+    ("two-pass because C/G > 256", lambda c: not gn_use_fused(c[2] * c[3], c[4], c[5]) and c[4] // c[5] > 256),
+    ("HW = 1", lambda c: c[2] * c[3] == 1),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GroupNorm over token levels: emrt_groupnorm_levels_fwd / _bwd
+# ---------------------------------------------------------------------------------------------------------------------------------
+def gn_rows_ok(C, G):
+    """Mirrors gn_rows_ok (csrc/norm.hip) for dense token tensors (ld = C, bs = Lv * C): the row-major statistics + apply pair, else one
+    block per (level, image, group)."""
+    return C == 8 * G and 256 % G == 0 and C <= 256
+
+
+def gnl_in_domain(case):
+    _, B, hws, C, G, _, _, _ = case
+    return G > 0 and C % G == 0 and gn_use_fused(1, C, G) and 1 <= len(hws) <= 4 and all(1 <= n <= 4096 for n in hws) and B >= 1
+
+
+GNL_PAIRS = ((256, 32), (64, 4))          # the model's, and one other pair gn_use_fused(1, C, G) accepts (16 channels per group)
+
+
+def gnl_cases(seed=1303, n=8):
+    """(id, B, level sizes, C, G, gelu, with_res, seed)"""
+    rng = random.Random(seed)
+    kinds = ["L=1", "L=4", "one-row", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        C, G = GNL_PAIRS[(len(out) // 2) % 2]
+        L = {"L=1": 1, "L=4": 4}.get(kind, rng.randint(1, 4))
+        hws = [rng.choice((1, rng.randint(2, 30), rng.randint(31, 400), rng.randint(401, 4096))) for _ in range(L)]      # not sorted
+        if kind == "one-row":
+            hws[rng.randrange(L)] = 1
+        B = rng.randint(1, 2)
+        if B * sum(hws) * C > MAX_ELEMS or (C // G) * min(hws) < 16:
+            continue
+        out.append(("gnl%d-%d" % (seed, len(out)), B, tuple(hws), C, G, rng.random() < 0.5, rng.random() < 0.5, seed + len(out)))
+    return out
+
+
+GNL_REGIMES = [
+    ("L = 1", lambda c: len(c[2]) == 1),
+    ("L = 4", lambda c: len(c[2]) == 4),
+    ("a level of one row", lambda c: 1 in c[2]),
+    ("row-major kernels (C = 8 G)", lambda c: gn_rows_ok(c[3], c[4])),
+    ("block per (level, image, group)", lambda c: not gn_rows_ok(c[3], c[4])),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LayerNorm: emrt_layernorm_fwd / emrt_layernorm_bwd
+# ---------------------------------------------------------------------------------------------------------------------------------
+def ln_bwd_blocks(rows, C, rows_knob=0, max_blocks_knob=0, threads_knob=512):
+    """(blocks, capped).  Mirrors ln_bwd_blocks (csrc/norm.hip) with the tuning knobs ln_bwd_rows / ln_bwd_max_blocks / ln_bwd_threads;
+    capped: the block cap, not the row count, decides the grid, so every block loops over more rows than `per`."""
+    wide = C <= 256 and threads_knob >= 512
+    per = rows_knob if rows_knob > 0 else (64 if wide else 32)
+    cap = max_blocks_knob if max_blocks_knob > 0 else (256 if wide else 512)
+    blocks = _ceil_div(rows, per)
+    capped = blocks > cap
+    return max(1, min(blocks, cap)), capped
+
+
+def ln_in_domain(case):
+    _, B, L, C, form, max_blocks, rows_knob, _ = case
+    return C % 4 == 0 and 12 <= C <= 1024 and B * L >= 1 and form in LN_FORMS and max_blocks >= 0 and rows_knob >= 0
+
+
+LN_CS = (12, 64, 100, 252, 256, 260, 512, 1000, 1024)
+LN_FORMS = ("a", "a+b", "a+b,post")
+
+
+def ln_cases(seed=1404, n=18):
+    """(id, B, L, C, form, ln_bwd_max_blocks, ln_bwd_rows, seed); the knobs are 0 (library default) except in the block-cap cases"""
+    rng = random.Random(seed)
+    kinds = ["C<256", "C=256", "C>256 ragged", "C=1024", "rows%4", "rows=1", "cap", "any", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        C = {"C<256": rng.choice((12, 64, 100, 252)), "C=256": 256, "C>256 ragged": rng.choice((260, 1000)), "C=1024": 1024}.get(kind, rng.choice(LN_CS))
+        B, L = rng.randint(1, 3), rng.randint(1, 233)
+        if kind == "rows=1":
+            B = L = 1
+        rows = B * L
+        if rows * C > MAX_ELEMS or (kind == "rows%4" and rows % 4 == 0):
+            continue
+        knobs = (0, 0)
+        if kind == "cap":
+            knobs = rng.choice(((2, 0), (3, 8)))
+            if not ln_bwd_blocks(rows, C, knobs[1], knobs[0])[1]:
+                continue
+        out.append(("ln%d-%d" % (seed, len(out)), B, L, C, LN_FORMS[len(out) % 3], knobs[0], knobs[1], seed + len(out)))
+    return out
+
+
+LN_REGIMES = [
+    ("C < 256 (a partial pass)", lambda c: c[3] < 256),
+    ("C = 256 (one whole pass)", lambda c: c[3] == 256),
+    ("C > 256 with a ragged last pass", lambda c: c[3] > 256 and c[3] % 256 != 0),
+    ("C = 1024", lambda c: c[3] == 1024),
+    ("rows % 4 != 0", lambda c: (c[1] * c[2]) % 4 != 0),
+    ("rows = 1", lambda c: c[1] * c[2] == 1),
+    ("backward blocks loop under the block cap", lambda c: ln_bwd_blocks(c[1] * c[2], c[3], c[6], c[5])[1]),
+] + [("form ln(%s)" % f, (lambda f_: lambda c: c[4] == f_)(f)) for f in LN_FORMS]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# bilinear resize: emrt_resize_bilinear_fwd / _bwd
+# ---------------------------------------------------------------------------------------------------------------------------------
+def vec_width(C, fp32, widths=(8, 4, 1)):
+    """Channels per access for a dense, aligned map.  Mirrors the v8 / v4 / scalar choice of emrt_resize_bilinear_fwd / _bwd (8 only for the
+    16-bit types), emrt_maxpool_fwd (widths = (8, 1), every type) and emrt_maxpool_bwd / emrt_adaptive_avgpool_bwd (widths = (4, 1))."""
+    for v in widths:
+        if C % v == 0 and not (v == 8 and fp32 and 4 in widths):
+            return v
+    return 1
+
+
+def resize_bwd_wide(C, IH, IW, OH, OW):
+    """Mirrors the block-per-source-pixel condition of emrt_resize_bilinear_bwd (RBW_THREADS = 1024)."""
+    return C % 4 == 0 and C // 4 <= 1024 and OH * OW >= 16 * IH * IW
+
+
+def resize_in_domain(case):
+    _, N, IH, IW, C, OH, OW, _, add, nchw, _ = case
+    return min(N, IH, IW, C, OH, OW) >= 1 and not (add and nchw)
+
+
+RESIZE_CS = (3, 6, 7, 8, 20, 64)
+
+
+def resize_cases(seed=1505, n=26):
+    """(id, N, IH, IW, C, OH, OW, align_corners, add_t, out_nchw_f32, seed)"""
+    rng = random.Random(seed)
+    kinds = ["up", "down", "mixed", "identity", "in 1x1", "out 1x1", "nchw", "wide", "C%8", "C%4", "scalar", "any", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        IH, IW, OH, OW = (rng.randint(1, 40) for _ in range(4))
+        C = {"C%8": rng.choice((8, 64)), "C%4": 20, "scalar": rng.choice((3, 6, 7)), "wide": rng.choice((8, 20, 64))}.get(kind, rng.choice(RESIZE_CS))
+        if kind == "identity":
+            OH, OW = IH, IW
+        elif kind == "in 1x1":
+            IH = IW = 1
+        elif kind == "out 1x1":
+            OH = OW = 1
+        elif kind == "wide":
+            IH, IW = rng.randint(1, 9), rng.randint(1, 9)
+            OH, OW = rng.randint(4 * IH, 40), rng.randint(4 * IW, 40)
+        elif kind == "up" and not (OH >= IH and OW >= IW and (OH, OW) != (IH, IW)):
+            continue
+        elif kind == "down" and not (OH <= IH and OW <= IW and (OH, OW) != (IH, IW)):
+            continue
+        elif kind == "mixed" and not ((OH > IH and OW < IW) or (OH < IH and OW > IW)):
+            continue
+        nchw = kind == "nchw" or (kind == "any" and rng.random() < 0.3)
+        add = (not nchw) and rng.random() < 0.5
+        out.append(("rs%d-%d" % (seed, len(out)), rng.randint(1, 3), IH, IW, C, OH, OW, rng.random() < 0.5, add, nchw, seed + len(out)))
+    return out
+
+
+RESIZE_REGIMES = [
+    ("up on both axes", lambda c: c[5] >= c[2] and c[6] >= c[3] and (c[5], c[6]) != (c[2], c[3])),
+    ("down on both axes", lambda c: c[5] <= c[2] and c[6] <= c[3] and (c[5], c[6]) != (c[2], c[3])),
+    ("mixed: up on one axis, down on the other", lambda c: (c[5] > c[2] and c[6] < c[3]) or (c[5] < c[2] and c[6] > c[3])),
+    ("identity", lambda c: (c[5], c[6]) == (c[2], c[3])),
+    ("down with align_corners=False", lambda c: not c[7] and (c[5] < c[2] or c[6] < c[3])),
+    ("1-pixel input", lambda c: c[2] == c[3] == 1),
+    ("1-pixel output", lambda c: c[5] == c[6] == 1),
+    ("NHWC, 8 channels per access (bf16)", lambda c: not c[9] and vec_width(c[4], False) == 8),
+    ("NHWC, 4 channels per access", lambda c: not c[9] and vec_width(c[4], True) == 4 and vec_width(c[4], False) == 4),
+    ("NHWC, scalar", lambda c: not c[9] and vec_width(c[4], True) == 1),
+    ("backward: block per source pixel", lambda c: not c[9] and resize_bwd_wide(c[4], c[2], c[3], c[5], c[6])),
+    ("fp32 NCHW output and its two-kernel backward", lambda c: c[9]),
+    ("fused addend", lambda c: c[8]),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# max pooling: emrt_maxpool_fwd / emrt_maxpool_bwd
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pool_out(S, k, stride, pad):
+    return (S + 2 * pad - k) // stride + 1
+
+
+def maxpool_in_domain(case):
+    _, N, H, W, C, k, stride, pad, _ = case
+    return (0 < k <= 15 and stride > 0 and 0 <= pad < k and pad <= k // 2          # (pad <= k // 2: torch's limit, which the reference needs)
+            and pool_out(H, k, stride, pad) >= 1 and pool_out(W, k, stride, pad) >= 1 and H + 2 * pad >= k and W + 2 * pad >= k)
+
+
+MAXPOOL_CS = (3, 4, 12, 8, 64)
+
+
+def maxpool_cases(seed=1606, n=18):
+    """(id, N, H, W, C, k, stride, pad, seed)"""
+    rng = random.Random(seed)
+    kinds = ["stride<k", "stride=k", "stride>k", "k=1", "any", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        k = 7 if len(out) == n - 1 else (1 if kind == "k=1" else rng.randint(1, 5))          # one k = 7
+        stride = rng.randint(1, k + 1)
+        pad = rng.randint(0, k // 2)
+        H, W = rng.randint(3, 30), rng.randint(3, 30)
+        if (kind == "stride<k" and not stride < k) or (kind == "stride=k" and stride != k) or (kind == "stride>k" and not stride > k):
+            continue
+        if H + 2 * pad < k or W + 2 * pad < k:
+            continue
+        out.append(("mp%d-%d" % (seed, len(out)), rng.randint(1, 3), H, W, MAXPOOL_CS[len(out) % len(MAXPOOL_CS)], k, stride, pad, seed + len(out)))
+    return out
+
+
+MAXPOOL_REGIMES = [
+    ("stride < k (windows overlap)", lambda c: c[6] < c[5]),
+    ("stride = k", lambda c: c[6] == c[5]),
+    ("stride > k (pixels in no window)", lambda c: c[6] > c[5]),
+    ("k = 1", lambda c: c[5] == 1),
+    ("k = 7", lambda c: c[5] == 7),
+    ("forward 8 channels per thread, backward 4", lambda c: vec_width(c[4], True, (8, 1)) == 8),
+    ("forward scalar, backward 4 channels per thread", lambda c: vec_width(c[4], True, (8, 1)) == 1 and vec_width(c[4], True, (4, 1)) == 4),
+    ("scalar both ways", lambda c: vec_width(c[4], True, (4, 1)) == 1),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# adaptive average pooling to tokens: emrt_adaptive_avgpool_fwd / _bwd
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pool_split(H, W, C, Ctot, scales):
+    """Mirrors the split-bin choice of emrt_adaptive_avgpool_fwd (pool_split_plan and the vector condition in front of it, csrc/spatial.hip)
+    for a channel slice [.., :C] of a dense [N, H, W, Ctot] map: several blocks per bin."""
+    kmin = min(scales)
+    big = ((H + kmin - 1) // kmin + 1) * ((W + kmin - 1) // kmin + 1)
+    cq = C // 4
+    return Ctot % 4 == 0 and C % 4 == 0 and cq <= 256 and (cq & (cq - 1)) == 0 and big >= 512
+
+
+def pool_bwd_kernel(H, W, C, scales):
+    """'table' | 'gather' | 'scalar'.  Mirrors the kernel choice of emrt_adaptive_avgpool_bwd (dense gradients)."""
+    if C % 4:
+        return "scalar"
+    return "table" if H + W <= 512 and all(k <= min(H, W) for k in scales) else "gather"
+
+
+def adaptive_in_domain(case):
+    _, N, H, W, C, Ctot, scales, _ = case
+    return min(N, H, W, C) >= 1 and Ctot >= C and 1 <= len(scales) <= 4 and len(set(scales)) == len(scales) and all(1 <= k <= 8 for k in scales)
+
+
+ADAPTIVE_CS = (4, 8, 64, 100, 6)          # functional.adaptive_avgpool_tokens lets C % 4 != 0 through: C = 6 takes the scalar kernels
+
+
+def adaptive_cases(seed=1707, n=14):
+    """(id, N, H, W, C, Ctot, scales, seed): the input is the channel slice [.., :C] of a [N, H, W, Ctot] buffer"""
+    rng = random.Random(seed)
+    kinds = ["H or W < k", "non-square", "split", "scalar", "any"]
+    out = []
+    while len(out) < n:
+        kind = kinds[len(out) % len(kinds)]
+        scales = tuple(rng.sample(range(1, 9), rng.randint(1, 4)))
+        H, W = rng.randint(1, 50), rng.randint(1, 50)
+        C = {"split": rng.choice((4, 8, 64)), "scalar": 6}.get(kind, rng.choice(ADAPTIVE_CS))
+        if kind == "H or W < k":
+            if rng.random() < 0.5:
+                H = rng.randint(1, max(1, max(scales) - 1))
+            else:
+                W = rng.randint(1, max(1, max(scales) - 1))
+        Ctot = C + (rng.choice((0, 4, 8, 60)) if C % 4 == 0 else rng.choice((0, 2, 5)))
+        N = rng.randint(1, 3)
+        if N * H * W * Ctot > MAX_ELEMS:
+            continue
+        if (kind == "H or W < k" and not min(H, W) < max(scales)) or (kind == "non-square" and H == W) or (kind == "split" and not pool_split(H, W, C, Ctot, scales)):
+            continue
+        out.append(("ap%d-%d" % (seed, len(out)), N, H, W, C, Ctot, scales, seed + len(out)))
+    return out
+
+
+ADAPTIVE_REGIMES = [
+    ("H or W < k", lambda c: min(c[2], c[3]) < max(c[6])),
+    ("non-square map", lambda c: c[2] != c[3]),
+    ("forward: several blocks per bin", lambda c: pool_split(c[2], c[3], c[4], c[5], c[6])),
+    ("forward: one block per bin", lambda c: not pool_split(c[2], c[3], c[4], c[5], c[6])),
+    ("scalar path (C % 4 != 0)", lambda c: c[4] % 4 != 0),
+    ("backward: two-bin table", lambda c: pool_bwd_kernel(c[2], c[3], c[4], c[6]) == "table"),
+    ("backward: general gather", lambda c: pool_bwd_kernel(c[2], c[3], c[4], c[6]) == "gather"),
+    ("input is a slice of a wider buffer", lambda c: c[5] > c[4]),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# pyramid token maps: emrt_pyramid_resize_fwd / _bwd (functional.pyramid_tokens_to_maps)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pyramid_in_domain(case):
+    _, B, C, scales, OH, OW, grouped, _ = case
+    return (B >= 1 and C % 4 == 0 and 4 <= C <= 256 and 1 <= len(scales) <= 4 and len(set(scales)) == len(scales)
+            and all(1 <= k <= 8 for k in scales) and OH >= 4 * max(scales) and OW >= 4 * max(scales))
+
+
+def pyramid_grouped(C, scales, OH, OW, esz, knob):
+    """Mirrors the `grouped` choice of functional.pyramid_tokens_to_maps and of its backward, for maps that are the channel slices
+    C .. C * (len(scales) + 1) of one 16-byte aligned NHWC concat buffer (and gradients that are the same slices of another): the knob
+    (Context.pyramid_group), at most four scales, C % 4 == 0, and every slice on a 16-byte boundary, which is C * esz % 16 == 0; the
+    row and image strides are multiples of C.  The backward also wants OH * OW >= 16 k^2, which the entry point's OH, OW >= 4 max(k)
+    implies.  esz = bytes per element: at C = 4 or 12 the bf16 slices start on an 8-byte boundary and each scale gets its own launch."""
+    return (knob and len(scales) <= 4 and C % 4 == 0 and (C * esz) % 16 == 0
+            and all(OH * OW >= 16 * k * k for k in scales))
+
+
+def pyramid_cases(seed=1808, n=12):
+    """(id, B, C, scales, OH, OW, knob, seed); knob = Context.pyramid_group: one launch per direction where pyramid_grouped allows
+    it, or always one per scale"""
+    rng = random.Random(seed)
+    out = []
+    while len(out) < n:
+        scales = tuple(rng.sample(range(1, 9), rng.randint(1, 4)))
+        kmax = max(scales)
+        OH, OW = rng.randint(4 * kmax, 4 * kmax + 12), rng.randint(4 * kmax, 4 * kmax + 12)
+        B, C = rng.randint(1, 3), rng.choice((4, 8, 12, 16, 32, 64, 128, 256))
+        if B * OH * OW * C * (len(scales) + 1) > MAX_ELEMS:
+            continue
+        out.append(("py%d-%d" % (seed, len(out)), B, C, scales, OH, OW, len(out) % 2 == 0, seed + len(out)))
+    return out
+
+
+PYRAMID_REGIMES = [
+    ("one launch per direction, fp32 and bf16", lambda c: pyramid_grouped(c[2], c[3], c[4], c[5], 4, c[6]) and pyramid_grouped(c[2], c[3], c[4], c[5], 2, c[6])),
+    ("one launch in fp32, per scale in bf16 (8-byte slices)", lambda c: pyramid_grouped(c[2], c[3], c[4], c[5], 4, c[6]) and not pyramid_grouped(c[2], c[3], c[4], c[5], 2, c[6])),
+    ("per-scale fallback by the knob", lambda c: not c[6]),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# sliding-window glue: emrt_window_accumulate
+# ---------------------------------------------------------------------------------------------------------------------------------
+def window_vec4(W, cw, origins_yx):
+    """Mirrors the vec4 condition of emrt_window_accumulate (csrc/spatial.hip) for 16-byte aligned buffers: four x per thread."""
+    return W % 4 == 0 and cw % 4 == 0 and all(x % 4 == 0 for _, x in origins_yx)
+
+
+# One image: classes, H, W, window height and width; irregular overlaps (pixels covered 1, 2, 3 and 4 times) and the columns from x = 20 on
+# covered by no window.  "grid": every origin's x, cw and W are multiples of 4; "odd": the same windows with one origin of each of the two
+# calls moved by one pixel, so that both calls leave the vec4 kernel.
+WINDOW_IMAGE = dict(C=5, H=20, W=24, ch=8, cw=8)
+WINDOW_ORIGINS = {
+    "grid": ((0, 0), (0, 4), (4, 0), (4, 4), (2, 8), (11, 0), (12, 12), (9, 8)),
+    "odd": ((0, 0), (0, 4), (4, 1), (4, 4), (2, 8), (11, 1), (12, 12), (9, 8)),
+}
+WINDOW_SPLIT = 5          # the windows go in two calls ([:5], [5:]) into the same final / count, as slide_inference's max_batch chunks do
+
+
+def window_cover(origins_yx, H, W, ch, cw):
+    """times each pixel is covered: [H][W] list of ints"""
+    cov = [[0] * W for _ in range(H)]
+    for y0, x0 in origins_yx:
+        for y in range(y0, y0 + ch):
+            for x in range(x0, x0 + cw):
+                cov[y][x] += 1
+    return cov
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+CASES = {
+    "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
+    "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
+}
+REGIMES = {
+    "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
+    "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
+}
+IN_DOMAIN = {
+    "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
+    "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
+}
+
+
+REGIME_MIN = {("maxpool", "k = 7"): 1}          # cases a regime must keep: two, except where the sweep asks for exactly one
+
+
+def regime_hits(op):
+    """[(regime, [ids of the cases that hit it])]"""
+    return [(name, [c[0] for c in CASES[op] if pred(c)]) for name, pred in REGIMES[op]]
+
+
+def regime_table():
+    """the table of the module docstring, one line per regime"""
+    lines = []
+    for op in CASES:
+        for name, ids in regime_hits(op):
+            short = sorted(int(i.rsplit("-", 1)[1]) for i in ids)
+            lines.append("  %-17s %-50s %s-{%s}" % (op, name, ids[0].rsplit("-", 1)[0] if ids else "", ",".join(str(s) for s in short)))
+    return "\n".join(lines)

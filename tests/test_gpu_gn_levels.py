@@ -18,13 +18,22 @@ from tests.hip_utils import init, dev
 pytestmark = pytest.mark.gpu
 
 
-def _run(dtype, B, hws, gelu, with_res, group_blocks, seed=0):
+def _run(dtype, B, hws, gelu, with_res, group_blocks, seed=0, C=256, G=32, per_group=False):
+    """per_group (the shape sweep of tests/test_gpu_norm_fuzz.py): per-channel and, on top, per-group scales in [0.5, 2] and shifts in [-2, 2]
+    instead of one scale and shift for the whole tensor; the smallest population standard deviation of the rounded input is returned as
+    "min_std"."""
     c = init(dtype)
-    L, C, G = len(hws), 256, 32
+    L = len(hws)
     Lv = sum(hws)
     g = torch.Generator().manual_seed(seed)
     tdt = c.tdtype
-    x = (torch.randn(B, Lv, C, generator=g) * 1.5 + 0.3).to(tdt)
+    if per_group:
+        s_c, m_c = torch.rand(C, generator=g) * 1.5 + 0.5, torch.rand(C, generator=g) * 4 - 2
+        s_g = (torch.rand(G, generator=g) * 1.5 + 0.5).repeat_interleave(C // G)
+        m_g = (torch.rand(G, generator=g) * 4 - 2).repeat_interleave(C // G)
+        x = ((torch.randn(B, Lv, C, generator=g) * s_c + m_c) * s_g + m_g).to(tdt)
+    else:
+        x = (torch.randn(B, Lv, C, generator=g) * 1.5 + 0.3).to(tdt)
     res = torch.randn(B, Lv, C, generator=g).to(tdt) if with_res else None
     dy = torch.randn(B, Lv, C, generator=g).to(tdt)
     gam = [torch.rand(C, generator=g) + 0.5 for _ in range(L)]
@@ -33,9 +42,10 @@ def _run(dtype, B, hws, gelu, with_res, group_blocks, seed=0):
     xr = x.double().requires_grad_(True)
     gr = [t.double().requires_grad_(True) for t in gam]
     br = [t.double().requires_grad_(True) for t in bet]
-    outs, s0 = [], 0
+    outs, s0, min_std = [], 0, float("inf")
     for l, n in enumerate(hws):
         xl = xr[:, s0:s0 + n].transpose(1, 2)                         # [B, C, n]
+        min_std = min(min_std, xl.detach().reshape(B, G, -1).var(dim=2, unbiased=False).sqrt().min().item())
         o = F.group_norm(xl, G, gr[l], br[l], 1e-5)
         if gelu:
             o = F.gelu(o)
@@ -72,7 +82,7 @@ def _run(dtype, B, hws, gelu, with_res, group_blocks, seed=0):
         torch.cuda.synchronize()
     finally:
         Lb.set_tuning("gn_group_blocks", old)
-    return dict(out=out.float().cpu(), dx=dx.float().cpu(), dgam=[t.cpu() for t in dgd], dbet=[t.cpu() for t in dbd], mean=mean.cpu(),
+    return dict(min_std=min_std, out=out.float().cpu(), dx=dx.float().cpu(), dgam=[t.cpu() for t in dgd], dbet=[t.cpu() for t in dbd], mean=mean.cpu(),
                 rstd=rstd.cpu(), want=want.detach().float(), wdx=xr.grad.float(), wdg=[t.grad.float() for t in gr], wdb=[t.grad.float() for t in br])
 
 
@@ -81,12 +91,15 @@ def _run(dtype, B, hws, gelu, with_res, group_blocks, seed=0):
 @pytest.mark.parametrize("gelu,with_res", [(True, True), (False, False)])
 @pytest.mark.parametrize("group_blocks", [False, True])
 def test_groupnorm_levels_match_torch(dtype, B, hws, gelu, with_res, group_blocks):
-    r = _run(dtype, B, hws, gelu, with_res, group_blocks)
+    _check(_run(dtype, B, hws, gelu, with_res, group_blocks), dtype, len(hws))
+
+
+def _check(r, dtype, L):
     tol = 2e-4 if dtype == F32 else 3e-2           # bf16: one rounding of an O(4) output (2^-8 relative)
     assert (r["out"] - r["want"]).abs().max().item() < tol * max(1.0, r["want"].abs().max().item())
     scale = max(1.0, r["wdx"].abs().max().item())
     assert (r["dx"] - r["wdx"]).abs().max().item() < tol * scale
-    for l in range(len(hws)):
+    for l in range(L):
         for got, want in ((r["dgam"][l], r["wdg"][l]), (r["dbet"][l], r["wdb"][l])):
             assert (got - want).abs().max().item() < 2e-3 * max(1.0, want.abs().max().item()), l
 

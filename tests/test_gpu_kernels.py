@@ -18,6 +18,11 @@ from tests.hip_utils import close_gemm, init, dev_map, host_map, dev, host, rnd,
 DTYPES = [F32, BF16]
 
 
+def leaf(t, ref):
+    """a fresh autograd leaf holding t in the reference precision"""
+    return t.detach().to(ref).clone().requires_grad_(True)
+
+
 def run_bwd(tape, outs_and_grads, watched):
     for o, g in outs_and_grads:
         tape.add_grad(o, g)
@@ -182,9 +187,37 @@ def test_conv_on_the_padded_image(dtype, k, stride, pad):
 @pytest.mark.parametrize("relu,with_res", [(True, True), (True, False), (False, False)])
 def test_batch_norm_train(dtype, shape, relu, with_res):
     N, H, W, C = shape
+    bn_train_case(dtype, N, H, W, C, relu, with_res)
+
+
+def population_floor(name, x, dims, skip=None):
+    """Precondition of the norm sweeps, on the ROUNDED input: the smallest population standard deviation among the normalised populations
+    (x reduced over `dims`; `skip`: a boolean mask of populations made constant on purpose) is above 0.1, so that 1 / sigma does not
+    amplify fp32 noise past the bounds of the fixed-shape tests.  An assert, not a skip: the seeds are fixed."""
+    sd = x.double().var(dim=dims, unbiased=False).sqrt()
+    if skip is not None:
+        sd = sd[~skip]
+    assert sd.min().item() > 0.1, "%s: a population of the drawn input has standard deviation %.4g" % (name, sd.min().item())
+
+
+def bn_train_case(dtype, N, H, W, C, relu, with_res, seed=4, per_channel=False, dead_channel=None, ref=torch.float32):
+    """BatchNorm2D in training mode against F.batch_norm + autograd in `ref` precision on the rounded operands: forward, dx, dres, dgamma, dbeta,
+    running statistics.  per_channel: x = randn * s_c + m_c with s_c in [0.5, 2], m_c in [-2, 2] drawn per channel, so that a kernel which
+    normalised channel c with another channel's statistics is far outside every bound (one s, m for the whole tensor hides it);
+    dead_channel: that channel is all zeros (a dead post-ReLU channel: variance exactly 0)."""
     c = init(dtype)
-    g = torch.Generator().manual_seed(4)
-    x = rnd(torch.randn(N, C, H, W, generator=g) * 2 + 0.5)
+    g = torch.Generator().manual_seed(seed)
+    if per_channel:
+        s_c, m_c = torch.rand(C, generator=g) * 1.5 + 0.5, torch.rand(C, generator=g) * 4 - 2
+        x = torch.randn(N, C, H, W, generator=g) * s_c.view(1, C, 1, 1) + m_c.view(1, C, 1, 1)
+        dead = torch.zeros(C, dtype=torch.bool)
+        if dead_channel is not None:
+            x[:, dead_channel] = 0.0
+            dead[dead_channel] = True
+        x = rnd(x)
+        population_floor("bn", x, (0, 2, 3), dead)
+    else:
+        x = rnd(torch.randn(N, C, H, W, generator=g) * 2 + 0.5)
     res = rnd(torch.randn(N, C, H, W, generator=g)) if with_res else None
     bn = hnn.BatchNorm2D(C)
     with torch.no_grad():
@@ -192,16 +225,16 @@ def test_batch_norm_train(dtype, shape, relu, with_res):
         bn.bias.copy_(torch.randn(C, generator=g) * 0.2)
     gam, bet = bn.weight.detach().clone(), bn.bias.detach().clone()
     Holder(bn=bn).place()
-    xr = x.clone().requires_grad_(True)
-    rr = res.clone().requires_grad_(True) if with_res else None
-    gr, br_ = gam.clone().requires_grad_(True), bet.clone().requires_grad_(True)
+    xr = leaf(x, ref)
+    rr = leaf(res, ref) if with_res else None
+    gr, br_ = leaf(gam, ref), leaf(bet, ref)
     o = F.batch_norm(xr, None, None, gr, br_, True, 0.1, 1e-5)
     if with_res:
         o = o + rr
     if relu:
         o = F.relu(o)
     dy = rnd(torch.randn(o.shape, generator=g))
-    o.backward(dy)
+    o.backward(dy.to(ref))
     xd = dev_map(x)
     rd = dev_map(res) if with_res else None
     tape = Tape()
@@ -220,10 +253,15 @@ def test_batch_norm_train(dtype, shape, relu, with_res):
     close("bn dgamma", host(bn.weight.grad), gr.grad, dtype, sc)
     close("bn dbeta", host(bn.bias.grad), br_.grad, dtype, sc)
     # running statistics: Paddle convention (momentum 0.9, biased variance)
-    mean = x.mean(dim=(0, 2, 3))
-    var = x.var(dim=(0, 2, 3), unbiased=False)
+    mean = x.to(ref).mean(dim=(0, 2, 3))
+    var = x.to(ref).var(dim=(0, 2, 3), unbiased=False)
     close("bn run_mean", host(bn._buffers["_mean"]), 0.1 * mean, F32, atol=1e-4)
     close("bn run_var", host(bn._buffers["_variance"]), 0.9 + 0.1 * var, F32, atol=1e-3)
+    if dead_channel is not None:
+        assert not relu and not with_res
+        yh = host_map(y)[:, dead_channel]
+        assert torch.isfinite(yh).all() and torch.isfinite(host_map(outs[0])).all()
+        close("bn dead channel = beta", yh, bet[dead_channel].expand_as(yh), dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -382,28 +420,46 @@ def test_batch_norm_eval_and_slice_output(dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("gelu,with_res", [(True, True), (False, False)])
 def test_group_norm(dtype, gelu, with_res):
+    group_norm_case(dtype, 3, 16, 16, 256, 32, gelu, with_res)
+
+
+def group_norm_case(dtype, N, H, W, C, G, gelu, with_res, seed=6, per_group=False, dead_group=None, ref=torch.float32):
+    """hnn.GroupNorm (+GELU, +residual) against F.group_norm + autograd in `ref` precision on the rounded operands.  per_group: per-channel
+    scale / shift (s_c in [0.5, 2], m_c in [-2, 2]) and on top per-group ones of the same ranges, so that neighbouring channels and groups
+    differ in their statistics by far more than any tolerance; dead_group: that group of image 0 is all zeros (variance exactly 0)."""
     c = init(dtype)
-    g = torch.Generator().manual_seed(6)
-    N, H, W, C = 3, 16, 16, 256
-    x = rnd(torch.randn(N, C, H, W, generator=g) * 1.5 + 0.3)
+    g = torch.Generator().manual_seed(seed)
+    if per_group:
+        s_c, m_c = torch.rand(C, generator=g) * 1.5 + 0.5, torch.rand(C, generator=g) * 4 - 2
+        s_g = (torch.rand(G, generator=g) * 1.5 + 0.5).repeat_interleave(C // G)
+        m_g = (torch.rand(G, generator=g) * 4 - 2).repeat_interleave(C // G)
+        x = (torch.randn(N, C, H, W, generator=g) * s_c.view(1, C, 1, 1) + m_c.view(1, C, 1, 1)) * s_g.view(1, C, 1, 1) + m_g.view(1, C, 1, 1)
+        dead = torch.zeros(N, G, dtype=torch.bool)
+        if dead_group is not None:
+            x[0, dead_group * (C // G):(dead_group + 1) * (C // G)] = 0.0
+            dead[0, dead_group] = True
+        x = rnd(x)
+        population_floor("gn", x.reshape(N, G, -1), (2,), dead)
+    else:
+        x = rnd(torch.randn(N, C, H, W, generator=g) * 1.5 + 0.3)
     res = rnd(torch.randn(N, C, H, W, generator=g)) if with_res else None
-    gn = hnn.GroupNorm(32, C)
+    gn = hnn.GroupNorm(G, C)
     with torch.no_grad():
         gn.weight.copy_(torch.rand(C, generator=g) + 0.5)
         gn.bias.copy_(torch.randn(C, generator=g) * 0.3)
     gam, bet = gn.weight.detach().clone(), gn.bias.detach().clone()
     Holder(gn=gn).place()
-    xr = x.clone().requires_grad_(True)
-    gr, br_ = gam.clone().requires_grad_(True), bet.clone().requires_grad_(True)
-    o = F.group_norm(xr, 32, gr, br_, 1e-5)
+    xr = leaf(x, ref)
+    gr, br_ = leaf(gam, ref), leaf(bet, ref)
+    o = F.group_norm(xr, G, gr, br_, 1e-5)
     if gelu:
         o = F.gelu(o)
     rr = None
     if with_res:
-        rr = res.clone().requires_grad_(True)
+        rr = leaf(res, ref)
         o = o + rr
     dy = rnd(torch.randn(o.shape, generator=g))
-    o.backward(dy)
+    o.backward(dy.to(ref))
     xd = dev_map(x)
     rd = dev_map(res) if with_res else None
     tape = Tape()
@@ -421,41 +477,76 @@ def test_group_norm(dtype, gelu, with_res):
     sc = math.sqrt(N * H * W)
     close("gn dgamma", host(gn.weight.grad), gr.grad, dtype, sc)
     close("gn dbeta", host(gn.bias.grad), br_.grad, dtype, sc)
+    if dead_group is not None:
+        assert not gelu and not with_res
+        ch = slice(dead_group * (C // G), (dead_group + 1) * (C // G))
+        yh = host_map(y)[0, ch]
+        assert torch.isfinite(yh).all() and torch.isfinite(host_map(outs[0])).all()
+        close("gn dead group = beta", yh, bet[ch].view(-1, 1, 1).expand_as(yh), dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_layer_norm_residual_post(dtype):
+    layer_norm_case(dtype, 3, 113, 256, "a+b,post")
+
+
+def layer_norm_case(dtype, B, L, C, form, seed=7, spread=False, dead_row=None, ref=torch.float32):
+    """hnn.LayerNorm as ln(a) / ln(a, b) / ln(a, b, post=) (form "a" / "a+b" / "a+b,post") against F.layer_norm + autograd in `ref` precision on
+    the rounded operands.  spread: a = (randn * s_c + m_c) * s_r + m_r with per-channel and per-row scales in [0.5, 2] and shifts in [-2, 2]
+    (rows differ in their statistics by far more than any tolerance); dead_row: that row of the LayerNorm input is all zeros."""
     c = init(dtype)
-    g = torch.Generator().manual_seed(7)
-    B, L, C = 3, 113, 256
-    a, b, post = (rnd(torch.randn(B, L, C, generator=g)) for _ in range(3))
+    g = torch.Generator().manual_seed(seed)
+    with_b, with_post = form != "a", form == "a+b,post"
+    if spread:
+        s_c, m_c = torch.rand(C, generator=g) * 1.5 + 0.5, torch.rand(C, generator=g) * 4 - 2
+        s_r, m_r = torch.rand(B, L, 1, generator=g) * 1.5 + 0.5, torch.rand(B, L, 1, generator=g) * 4 - 2
+        a = (torch.randn(B, L, C, generator=g) * s_c + m_c) * s_r + m_r
+        b, post = torch.randn(B, L, C, generator=g), torch.randn(B, L, C, generator=g)
+        dead = torch.zeros(B * L, dtype=torch.bool)
+        if dead_row is not None:
+            a.view(B * L, C)[dead_row] = 0.0
+            b.view(B * L, C)[dead_row] = 0.0
+            dead[dead_row] = True
+        a, b, post = rnd(a), rnd(b), rnd(post)
+        population_floor("ln", (a + b if with_b else a).reshape(B * L, C), (1,), dead)
+    else:
+        a, b, post = (rnd(torch.randn(B, L, C, generator=g)) for _ in range(3))
     ln = hnn.LayerNorm(C)
     with torch.no_grad():
         ln.weight.copy_(torch.rand(C, generator=g) + 0.5)
         ln.bias.copy_(torch.randn(C, generator=g) * 0.3)
     gam, bet = ln.weight.detach().clone(), ln.bias.detach().clone()
     Holder(ln=ln).place()
-    ar, br_, pr = (t.clone().requires_grad_(True) for t in (a, b, post))
-    gr, ber = gam.clone().requires_grad_(True), bet.clone().requires_grad_(True)
-    zr = rnd((ar + br_).detach()) if dtype == BF16 else None
-    o = F.layer_norm(ar + br_, (C,), gr, ber, 1e-5) + pr
+    ar, br_, pr = (leaf(t, ref) for t in (a, b, post))
+    gr, ber = leaf(gam, ref), leaf(bet, ref)
+    o = F.layer_norm(ar + br_ if with_b else ar, (C,), gr, ber, 1e-5)
+    if with_post:
+        o = o + pr
     dy = rnd(torch.randn(o.shape, generator=g))
-    o.backward(dy)
-    ad, bd, pd = dev(a), dev(b), dev(post)
+    o.backward(dy.to(ref))
+    ad, bd, pd = dev(a), dev(b) if with_b else None, dev(post) if with_post else None
     tape = Tape()
     c.tape = tape
     y = ln(ad, bd, post=pd)
     c.tape = None
-    for t in (ad, bd, pd):
+    watched = [t for t in (ad, bd, pd) if t is not None]
+    for t in watched:
         tape.watch(t)
     close("ln fwd", host(y), o.detach(), dtype)
-    da, db, dp = run_bwd(tape, [(y, dev(dy))], [ad, bd, pd])
-    close("ln da", host(da), ar.grad, dtype, 2.0)
-    close("ln db", host(db), br_.grad, dtype, 2.0)
-    close("ln dpost", host(dp), pr.grad, dtype)
+    grads = run_bwd(tape, [(y, dev(dy))], watched)
+    close("ln da", host(grads[0]), ar.grad, dtype, 2.0)
+    if with_b:
+        close("ln db", host(grads[1]), br_.grad, dtype, 2.0)
+    if with_post:
+        close("ln dpost", host(grads[2]), pr.grad, dtype)
     sc = math.sqrt(B * L)
     close("ln dgamma", host(ln.weight.grad), gr.grad, dtype, sc)
     close("ln dbeta", host(ln.bias.grad), ber.grad, dtype, sc)
+    if dead_row is not None:
+        assert not with_post
+        yh = host(y).view(B * L, C)[dead_row]
+        assert torch.isfinite(yh).all() and torch.isfinite(host(grads[0])).all()
+        close("ln dead row = beta", yh, bet, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -1193,47 +1284,52 @@ def test_mha_mfma_kernels_dropout_and_agreement_with_the_valu_kernels():
                                   (2, 10, 10, 32, 10, 10, True), (2, 2, 2, 64, 16, 16, False), (1, 8, 8, 512, 32, 32, False)])
 def test_resize_bilinear(dtype, case):
     N, IH, IW, C, OH, OW, ac = case
+    resize_case(dtype, N, IH, IW, C, OH, OW, ac)
+
+
+def resize_case(dtype, N, IH, IW, C, OH, OW, ac, add=True, nchw=False, seed=10, ref=torch.float32):
+    """Fn.resize_bilinear (+ fused addend | fp32 NCHW output) against F.interpolate + autograd in `ref` precision on the rounded operands.
+    dx sums (OH / IH) * (OW / IW) output gradients per input pixel: its bound grows with the square root of that count (1 when downscaling)."""
+    assert not (add and nchw)
     c = init(dtype)
-    g = torch.Generator().manual_seed(10)
+    g = torch.Generator().manual_seed(seed)
     x = rnd(torch.randn(N, C, IH, IW, generator=g))
-    add_t = rnd(torch.randn(N, C, OH, OW, generator=g))
-    xr, ar = x.clone().requires_grad_(True), add_t.clone().requires_grad_(True)
-    o = F.interpolate(xr, size=(OH, OW), mode="bilinear", align_corners=ac) + ar
-    dy = rnd(torch.randn(o.shape, generator=g))
-    o.backward(dy)
-    xd, ad = dev_map(x), dev_map(add_t)
+    add_t = rnd(torch.randn(N, C, OH, OW, generator=g)) if add else None
+    xr = leaf(x, ref)
+    ar = leaf(add_t, ref) if add else None
+    o = F.interpolate(xr, size=(OH, OW), mode="bilinear", align_corners=ac)
+    if add:
+        o = o + ar
+    dy = torch.randn(o.shape, generator=g)
+    if not nchw:
+        dy = rnd(dy)
+    o.backward(dy.to(ref))
+    xd = dev_map(x)
+    ad = dev_map(add_t) if add else None
     tape = Tape()
     c.tape = tape
-    y = Fn.resize_bilinear(xd, OH, OW, ac, add_t=ad)
+    y = Fn.resize_bilinear(xd, OH, OW, ac, add_t=ad, out_nchw_f32=nchw)
     c.tape = None
     tape.watch(xd)
-    tape.watch(ad)
+    if add:
+        tape.watch(ad)
+    dx_scale = float(max(1, (OH // IH) * (OW // IW))) ** 0.5
+    if nchw:
+        assert y.dtype == torch.float32 and tuple(y.shape) == (N, C, OH, OW)
+        close("resize nchw fwd", y.cpu(), o.detach(), dtype, atol=1e-5 if dtype == F32 else None)
+        dx, = run_bwd(tape, [(y, dev(dy, torch.float32))], [xd])
+        close("resize nchw dx", host_map(dx), xr.grad, dtype, dx_scale)
+        return
     close("resize fwd", host_map(y), o.detach(), dtype)
-    dx, da = run_bwd(tape, [(y, dev_map(dy))], [xd, ad])
-    close("resize dx", host_map(dx), xr.grad, dtype, float(max(1, (OH // IH) * (OW // IW))) ** 0.5)
-    close("resize dadd", host_map(da), ar.grad, dtype)
+    grads = run_bwd(tape, [(y, dev_map(dy))], [xd] + ([ad] if add else []))
+    close("resize dx", host_map(grads[0]), xr.grad, dtype, dx_scale)
+    if add:
+        close("resize dadd", host_map(grads[1]), ar.grad, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_resize_to_nchw_logits(dtype):
-    c = init(dtype)
-    g = torch.Generator().manual_seed(11)
-    N, IH, IW, C = 2, 16, 16, 6
-    x = rnd(torch.randn(N, C, IH, IW, generator=g))
-    xr = x.clone().requires_grad_(True)
-    o = F.interpolate(xr, size=(32, 32), mode="bilinear", align_corners=False)
-    dy = torch.randn(o.shape, generator=g)
-    o.backward(dy)
-    xd = dev_map(x)
-    tape = Tape()
-    c.tape = tape
-    y = Fn.resize_bilinear(xd, 32, 32, False, out_nchw_f32=True)
-    c.tape = None
-    tape.watch(xd)
-    assert y.dtype == torch.float32 and tuple(y.shape) == (N, C, 32, 32)
-    close("resize nchw fwd", y.cpu(), o.detach(), dtype, atol=1e-5 if dtype == F32 else None)
-    dx, = run_bwd(tape, [(y, dev(dy, torch.float32))], [xd])
-    close("resize nchw dx", host_map(dx), xr.grad, dtype, 2.0)
+    resize_case(dtype, 2, 16, 16, 6, 32, 32, False, add=False, nchw=True, seed=11)          # (dx bound: sqrt(2 * 2) = 2.0)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -1258,20 +1354,27 @@ def test_adaptive_pool_and_maxpool(dtype):
     close("pool dx", host_map(dx), xr.grad, dtype)
     # max pool, with ties (post-ReLU style input); C = 64 takes the 8-channel kernel, C = 3 (the image itself, spatial_branch) the scalar one
     for Cm in (64, 3):
-        x2 = rnd(F.relu(torch.randn(N, Cm, 17, 19, generator=g)))
-        x2r = x2.clone().requires_grad_(True)
-        m = F.max_pool2d(x2r, 3, 2, 1)
-        dm = rnd(torch.randn(m.shape, generator=g))
-        m.backward(dm)
-        x2d = dev_map(x2)
-        tape = Tape()
-        c.tape = tape
-        y2 = Fn.maxpool(x2d, 3, 2, 1)
-        c.tape = None
-        tape.watch(x2d)
-        close("maxpool fwd C=%d" % Cm, host_map(y2), m.detach(), dtype, atol=0, rtol=0)
-        dx2, = run_bwd(tape, [(y2, dev_map(dm))], [x2d])
-        close("maxpool dx C=%d" % Cm, host_map(dx2), x2r.grad, dtype)
+        maxpool_case(dtype, rnd(F.relu(torch.randn(N, Cm, 17, 19, generator=g))), 3, 2, 1, g)
+
+
+def maxpool_case(dtype, x, k, stride, pad, g, ref=torch.float32):
+    """Fn.maxpool on the rounded [N, C, H, W] input x against F.max_pool2d + autograd: the forward bit for bit, dx routed to the first maximum
+    in scan order (csrc/spatial.hip and torch agree on that rule).  g: the generator the output gradient is drawn from."""
+    c = ctx()
+    Cm = x.shape[1]
+    x2r = leaf(x, ref)
+    m = F.max_pool2d(x2r, k, stride, pad)
+    dm = rnd(torch.randn(m.shape, generator=g))
+    m.backward(dm.to(ref))
+    x2d = dev_map(x)
+    tape = Tape()
+    c.tape = tape
+    y2 = Fn.maxpool(x2d, k, stride, pad)
+    c.tape = None
+    tape.watch(x2d)
+    close("maxpool fwd C=%d" % Cm, host_map(y2), m.detach(), dtype, atol=0, rtol=0)
+    dx2, = run_bwd(tape, [(y2, dev_map(dm))], [x2d])
+    close("maxpool dx C=%d" % Cm, host_map(dx2), x2r.grad, dtype)
 
 
 def test_nchw_ingest_and_elementwise():
@@ -1745,15 +1848,19 @@ def test_msda_golden_vectors(dtype):
 def test_adaptive_pool_split_bins(dtype, H, W, C, Ctot):
     """AdaptiveAvgPool2D pyramid (paddle_EMRT.py:62,70-78) on maps below and above the size at which a bin is pooled by several blocks
     (csrc/spatial.hip: adaptive_pool_part_kernel), on a channel slice of a wider buffer as in the model, non-square and odd sizes."""
+    adaptive_pool_case(dtype, 3, H, W, C, Ctot, [1, 3, 6, 8])
+
+
+def adaptive_pool_case(dtype, N, H, W, C, Ctot, scales, seed=5, ref=torch.float32):
+    """Fn.adaptive_avgpool_tokens on the channel slice [.., :C] of a [N, H, W, Ctot] map against F.adaptive_avg_pool2d + autograd."""
     c = init(dtype)
-    g = torch.Generator().manual_seed(5)
-    N = 3
-    scales = [1, 3, 6, 8]
+    g = torch.Generator().manual_seed(seed)
+    scales = list(scales)
     x = rnd(torch.randn(N, Ctot, H, W, generator=g))
-    xr = x[:, :C].clone().requires_grad_(True)
+    xr = leaf(x[:, :C], ref)
     toks = torch.cat([F.adaptive_avg_pool2d(xr, k).reshape(N, C, -1) for k in scales], -1).transpose(1, 2)
     dy = rnd(torch.randn(toks.shape, generator=g))
-    toks.backward(dy)
+    toks.backward(dy.to(ref))
     xd = dev_map(x)[..., :C]
     tape = Tape()
     c.tape = tape
@@ -2277,31 +2384,11 @@ def test_pyramid_maps_resized_in_one_launch(dtype, OH, OW, C):
     scales, B = [1, 3, 6, 8], 3
     ntok = sum(k * k for k in scales)
     g = torch.Generator().manual_seed(3)
+    init(dtype)
     tok = rnd(torch.randn(B, ntok, C, generator=g))
     dcat = rnd(torch.randn(B, OH, OW, C * 5, generator=g))
-
-    def run(grouped):
-        c = init(dtype)
-        c.pyramid_group = grouped
-        td = dev(tok)
-        cat = c.zeros((B, OH, OW, C * 5))
-        outs = [Fn.narrow(cat, 3, C * (1 + i), C) for i in range(4)]
-        tape = Tape()
-        c.tape = tape
-        L = _lib.lib()
-        L.start_record()
-        Fn.pyramid_tokens_to_maps(td, scales, OH, OW, outs)
-        c.tape = None
-        tape.watch(td)
-        dd = dev(dcat)
-        dtok, = run_bwd(tape, [(o, Fn.narrow(dd, 3, C * (1 + i), C)) for i, o in enumerate(outs)], [td])
-        names = [n for n, _ in L.stop_record()]
-        torch.cuda.synchronize()
-        c.pyramid_group = True
-        return names, host(cat), host(dtok)
-
-    names, cat, dtok = run(True)
-    names0, cat0, dtok0 = run(False)
+    names, cat, dtok = pyramid_run(dtype, tok, dcat, scales, OH, OW, True)
+    names0, cat0, dtok0 = pyramid_run(dtype, tok, dcat, scales, OH, OW, False)
     wide = OH * OW >= 16 * 64          # (the grouped backward is the block-per-source-pixel form: every map >= x4 smaller per axis)
     assert names.count("emrt_pyramid_resize_fwd") == 1 and "emrt_resize_bilinear_fwd" not in names
     assert names.count("emrt_pyramid_resize_bwd") == (1 if wide else 0) and names.count("emrt_resize_bilinear_bwd") == (0 if wide else 4)
@@ -2312,14 +2399,49 @@ def test_pyramid_maps_resized_in_one_launch(dtype, OH, OW, C):
     for name_, u, v in (("maps", cat, cat0), ("dtokens", dtok, dtok0)):
         assert (u - v).abs().max().item() <= ulp * v.abs().max().item(), (name_, (u - v).abs().max().item())
         assert dtype == F32 or (u != v).float().mean().item() < 2e-3, name_
-    tr = tok.clone().requires_grad_(True)
-    s0, ref = 0, []
+    pyramid_vs_torch(dtype, tok, dcat, scales, OH, OW, cat, dtok)
+
+
+def pyramid_run(dtype, tok, dcat, scales, OH, OW, grouped):
+    """Fn.pyramid_tokens_to_maps into the channel slices 1.. of a [B, OH, OW, C * (len(scales) + 1)] concat buffer and its backward from the
+    same slices of dcat, as one launch per direction (grouped) or one per scale -> (launch names, concat buffer, token gradient) on the host."""
+    from emrt_amd import _lib
+    B, _, C = tok.shape
+    n = len(scales)
+    c = init(dtype)
+    c.pyramid_group = grouped
+    try:
+        td = dev(tok)
+        cat = c.zeros((B, OH, OW, C * (n + 1)))
+        outs = [Fn.narrow(cat, 3, C * (1 + i), C) for i in range(n)]
+        tape = Tape()
+        c.tape = tape
+        L = _lib.lib()
+        L.start_record()
+        Fn.pyramid_tokens_to_maps(td, list(scales), OH, OW, outs)
+        c.tape = None
+        tape.watch(td)
+        dd = dev(dcat)
+        dtok, = run_bwd(tape, [(o, Fn.narrow(dd, 3, C * (1 + i), C)) for i, o in enumerate(outs)], [td])
+        names = [n_ for n_, _ in L.stop_record()]
+        torch.cuda.synchronize()
+    finally:
+        c.pyramid_group = True
+    return names, host(cat), host(dtok)
+
+
+def pyramid_vs_torch(dtype, tok, dcat, scales, OH, OW, cat, dtok, ref=torch.float32):
+    """the concat buffer and the token gradient of pyramid_run against F.interpolate(align_corners=True) + autograd per scale"""
+    B, _, C = tok.shape
+    tr = leaf(tok, ref)
+    s0, maps = 0, []
     for k in scales:
         m = tr[:, s0:s0 + k * k].reshape(B, k, k, C).permute(0, 3, 1, 2)
-        ref.append(F.interpolate(m, size=(OH, OW), mode="bilinear", align_corners=True).permute(0, 2, 3, 1))
+        maps.append(F.interpolate(m, size=(OH, OW), mode="bilinear", align_corners=True).permute(0, 2, 3, 1))
         s0 += k * k
-    full = torch.cat(ref, 3)
-    full.backward(dcat[..., C:])
+    full = torch.cat(maps, 3)
+    full.backward(dcat[..., C:].to(ref))
+    assert float(cat[..., :C].abs().max()) == 0.0          # the slice in front of the maps is not touched
     close("pyramid fwd", cat[..., C:], full.detach(), dtype)
     close("pyramid dtokens", dtok, tr.grad, dtype, math.sqrt(OH * OW))
 
