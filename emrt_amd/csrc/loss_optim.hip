@@ -7,6 +7,7 @@
 //    step counter so the whole step can live in one hipGraph)
 //  * per-step weight packing: fp32 master [OC][taps][C] -> compute-dtype forward copy [OC][taps][C] and transposed
 //    dgrad copy [C][taps][OC] (LDS 32x32 tile transpose, one launch for every GEMM weight of the model).
+#include <cfloat>
 #include "common.hpp"
 
 using namespace emrt;
@@ -290,12 +291,9 @@ struct SgdArgs {
   void* mirror;                  // optional: compute-dtype copy of the parameters, same indexing as p
 };
 
+// the element arithmetic of the Momentum update, shared by the kernel with the built-in polynomial and the one that takes an EmrtLrSchedule
 template <class MT, bool NT>
-__global__ __launch_bounds__(256) void sgd_momentum_kernel(SgdArgs a) {
-  long long t = a.step ? a.step[0] : 0;
-  if (t > a.decay_steps) t = a.decay_steps;
-  const float frac = 1.f - (float)((double)t / (double)a.decay_steps);
-  const float lr = (a.base_lr - a.end_lr) * powf(frac, a.power) + a.end_lr;
+__device__ __forceinline__ void sgd_momentum_update(const SgdArgs& a, const float lr) {
   if (a.lr_out && blockIdx.x == 0 && threadIdx.x == 0) a.lr_out[0] = lr;
   const float scale = a.state ? a.state[0] : 1.f;
   MT* mirror = (MT*)a.mirror;
@@ -353,6 +351,170 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(SgdArgs a) {
       const float v = fmaf(a.momentum, a.v[i], g);
       a.v[i] = v;
       const float pn = fmaf(-(lr * mult), v, p);
+      a.p[i] = pn;
+      if (mirror) mirror[i] = from_f32<MT>(pn);
+    }
+  }
+}
+
+template <class MT, bool NT>
+__global__ __launch_bounds__(256) void sgd_momentum_kernel(SgdArgs a) {
+  long long t = a.step ? a.step[0] : 0;
+  if (t > a.decay_steps) t = a.decay_steps;
+  const float frac = 1.f - (float)((double)t / (double)a.decay_steps);
+  const float lr = (a.base_lr - a.end_lr) * powf(frac, a.power) + a.end_lr;
+  sgd_momentum_update<MT, NT>(a, lr);
+}
+
+// Learning rate of step s (the device step counter = paddle's last_epoch) under an EmrtLrSchedule (include/emrt_hip.h states the four kinds;
+// solver/lr_scheduler.py:30-267).  fp32, every step quotient formed in double as the polynomial above does; the ONE copy both
+// schedule-driven optimizer kernels use.
+__device__ __forceinline__ float lr_at(const EmrtLrSchedule& sc, long long s) {
+  const long long T = sc.total_steps, W = sc.warmup_steps;
+  if (sc.kind == 0) {
+    const long long t = s > T ? T : s;
+    const float frac = 1.f - (float)((double)t / (double)T);
+    return (sc.base_lr - sc.end_lr) * powf(frac, sc.power) + sc.end_lr;
+  }
+  if (sc.kind == 1) {
+    float lr;
+    if (s < W) {
+      lr = sc.warmup_lr_init + (sc.base_lr - sc.warmup_lr_init) * (float)((double)s / (double)W);
+    } else {
+      const float f = 1.f - (float)((double)(s - W) / (double)(T - W));
+      if (f < 0.f) return sc.end_lr;            // the reference's pow() turns complex here and it answers lr_min
+      lr = sc.warmup_lr_init + (sc.base_lr - sc.warmup_lr_init) * powf(f, sc.power);
+    }
+    return lr <= sc.end_lr ? sc.end_lr : lr;
+  }
+  if (sc.kind == 2) {
+    if (s < W) return sc.warmup_lr_init + (sc.base_lr - sc.warmup_lr_init) * (float)((double)s / (double)W);
+    const long long tc = s % T;
+    return sc.end_lr + 0.5f * (sc.base_lr - sc.end_lr) * (1.f + cosf(3.14159265358979323846f * (float)((double)tc / (double)T)));
+  }
+  if (s <= W) return sc.base_lr * (float)((double)s / (double)W);
+  int k = 0;
+  for (int i = 0; i < sc.nmilestones; ++i) k += (sc.milestones[i] <= s) ? 1 : 0;
+  return sc.base_lr * powf(sc.gamma, (float)k);
+}
+
+struct SgdSchedArgs {
+  SgdArgs s;
+  EmrtLrSchedule sched;
+};
+
+template <class MT, bool NT>
+__global__ __launch_bounds__(256) void sgd_momentum_sched_kernel(SgdSchedArgs a) {
+  sgd_momentum_update<MT, NT>(a.s, lr_at(a.sched, a.s.step ? a.s.step[0] : 0));
+}
+
+struct AdamArgs {
+  float* p; const float* g; float* m; float* v;
+  long long n;
+  const float* state;            // clip scale at [0]
+  const long long* step;         // device step counter: this is update number step[0] + 1
+  EmrtLrSchedule sched;
+  float beta1, beta2, eps, weight_decay;
+  int decoupled;
+  int nranges;
+  long long r0[32], r1[32];
+  float range_mult;
+  float* lr_out;
+  void* mirror;
+};
+
+// Adam / AdamW, one streaming pass in the shape of the Momentum update above (four elements per thread, 16-byte non-temporal accesses on
+// the four fp32 streams, the mirror written from the new master value, the scalar tail in block 0).
+// What depends on the step alone is formed ONCE PER BLOCK, in double, and handed round through LDS: t = step + 1, the bias terms
+// 1 - beta^t (fp32 powf of 0.999^t has lost them at t ~ 1e5), and from them, for lr and for lr * range_mult, the step size
+// lr_e * sqrt(1 - beta2^t) / (1 - beta1^t) and the decoupled decay factor 1 - lr_e * wd, plus eps * sqrt(1 - beta2^t): one rounding each.
+// The moments go through double as well -- g = grad * scale is exact there and m, v are rounded once --, the rest is fp32 with explicit
+// fused multiply-adds and the correctly rounded square root and division: sqrtf and / are that under hipcc's defaults, which the build's flags
+// leave alone (no -ffast-math, no -fno-hip-fp32-correctly-rounded-divide-sqrt); HIP's __fsqrt_rn is NOT (it compiles to the bare v_sqrt_f32).
+struct AdamConsts {
+  float step_size, step_size_r, decay, decay_r, eps_t;      // _r: inside an lr-mult range
+};
+
+template <bool DECOUPLED>
+__device__ __forceinline__ float adam_element(const AdamConsts& c, const double b1, const double b2, const double scale, const double wd, const int sel,
+                                              const float p, const float g, float& m, float& v) {
+  double gd = (double)g * scale;
+  if (!DECOUPLED) gd = fma(wd, (double)p, gd);
+  m = (float)fma(b1, (double)m, (1.0 - b1) * gd);
+  v = (float)fma(b2, (double)v, (1.0 - b2) * (gd * gd));
+  const float pd = DECOUPLED ? p * (sel ? c.decay_r : c.decay) : p;
+  const float q = m / (sqrtf(v) + c.eps_t);       // 0 / (0 + eps_t) = 0: padded stem channels stay exactly zero
+  return fmaf(-(sel ? c.step_size_r : c.step_size), q, pd);
+}
+
+template <class MT, bool NT, bool DECOUPLED>
+__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
+  __shared__ AdamConsts cs;
+  if (threadIdx.x == 0) {
+    const long long s = a.step ? a.step[0] : 0;
+    const float lr = lr_at(a.sched, s);
+    if (a.lr_out && blockIdx.x == 0) a.lr_out[0] = lr;
+    const double t = (double)(s + 1);
+    const double bc1 = 1.0 - pow((double)a.beta1, t), bc2s = sqrt(1.0 - pow((double)a.beta2, t));
+    const double lre = (double)lr, lre_r = (double)lr * (double)a.range_mult;
+    cs.step_size = (float)(lre * bc2s / bc1);
+    cs.step_size_r = (float)(lre_r * bc2s / bc1);
+    cs.decay = (float)(1.0 - lre * (double)a.weight_decay);
+    cs.decay_r = (float)(1.0 - lre_r * (double)a.weight_decay);
+    cs.eps_t = (float)((double)a.eps * bc2s);
+  }
+  __syncthreads();
+  const AdamConsts c = cs;
+  const double b1 = (double)a.beta1, b2 = (double)a.beta2, wd = (double)a.weight_decay, scale = a.state ? (double)a.state[0] : 1.0;
+  MT* mirror = (MT*)a.mirror;
+  const long long n4 = a.n / 4;
+  for (long long i4 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i4 < n4; i4 += (long long)gridDim.x * blockDim.x) {
+    const long long i = i4 * 4;
+    typedef __attribute__((ext_vector_type(4))) float adam_f32x4;
+    adam_f32x4 pq, gq, mq, vq;
+    if (NT) {
+      pq = __builtin_nontemporal_load(reinterpret_cast<const adam_f32x4*>(a.p) + i4);
+      gq = __builtin_nontemporal_load(reinterpret_cast<const adam_f32x4*>(a.g) + i4);
+      mq = __builtin_nontemporal_load(reinterpret_cast<const adam_f32x4*>(a.m) + i4);
+      vq = __builtin_nontemporal_load(reinterpret_cast<const adam_f32x4*>(a.v) + i4);
+    } else {
+      pq = reinterpret_cast<const adam_f32x4*>(a.p)[i4];
+      gq = reinterpret_cast<const adam_f32x4*>(a.g)[i4];
+      mq = reinterpret_cast<const adam_f32x4*>(a.m)[i4];
+      vq = reinterpret_cast<const adam_f32x4*>(a.v)[i4];
+    }
+    float p[4] = {pq[0], pq[1], pq[2], pq[3]}, m[4] = {mq[0], mq[1], mq[2], mq[3]}, v[4] = {vq[0], vq[1], vq[2], vq[3]};
+    const float g[4] = {gq[0], gq[1], gq[2], gq[3]};
+    bool any = false;
+    for (int r = 0; r < a.nranges; ++r) any |= (i + 3 >= a.r0[r] && i < a.r1[r]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      int sel = 0;
+      if (any)
+        for (int r = 0; r < a.nranges; ++r)
+          if (i + e >= a.r0[r] && i + e < a.r1[r]) sel = 1;
+      p[e] = adam_element<DECOUPLED>(c, b1, b2, scale, wd, sel, p[e], g[e], m[e], v[e]);
+    }
+    if (NT) {
+      __builtin_nontemporal_store((adam_f32x4){m[0], m[1], m[2], m[3]}, reinterpret_cast<adam_f32x4*>(a.m) + i4);
+      __builtin_nontemporal_store((adam_f32x4){v[0], v[1], v[2], v[3]}, reinterpret_cast<adam_f32x4*>(a.v) + i4);
+      __builtin_nontemporal_store((adam_f32x4){p[0], p[1], p[2], p[3]}, reinterpret_cast<adam_f32x4*>(a.p) + i4);
+    } else {
+      reinterpret_cast<float4*>(a.m)[i4] = make_float4(m[0], m[1], m[2], m[3]);
+      reinterpret_cast<float4*>(a.v)[i4] = make_float4(v[0], v[1], v[2], v[3]);
+      reinterpret_cast<float4*>(a.p)[i4] = make_float4(p[0], p[1], p[2], p[3]);
+    }
+    if (mirror) Vec4<MT>::store(mirror + i, p);
+  }
+  if (blockIdx.x == 0) {
+    for (long long i = n4 * 4 + threadIdx.x; i < a.n; i += blockDim.x) {
+      int sel = 0;
+      for (int r = 0; r < a.nranges; ++r)
+        if (i >= a.r0[r] && i < a.r1[r]) sel = 1;
+      float m = a.m[i], v = a.v[i];
+      const float pn = adam_element<DECOUPLED>(c, b1, b2, scale, wd, sel, a.p[i], a.g[i], m, v);
+      a.m[i] = m;
+      a.v[i] = v;
       a.p[i] = pn;
       if (mirror) mirror[i] = from_f32<MT>(pn);
     }
@@ -440,6 +602,94 @@ extern "C" int emrt_sgd_momentum_step(float* params, const float* grads, float* 
     else hipLaunchKernelGGL((sgd_momentum_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   }
   return check_launch("emrt_sgd_momentum_step");
+}
+
+// host-side refusals of a schedule descriptor (nothing is launched for a bad one); NULL when it is fine
+static const char* lr_schedule_problem(const EmrtLrSchedule* sc) {
+  if (!sc) return "null schedule";
+  if (sc->kind < 0 || sc->kind > 3) return "unknown schedule kind (0 PolynomialDecay, 1 WarmupPolyLR, 2 WarmupCosineLR, 3 WarmupMultiStepLR)";
+  if (sc->total_steps < 1) return "total_steps must be positive";
+  if (sc->warmup_steps < 0) return "warmup_steps must not be negative";
+  if (sc->kind == 1 && sc->total_steps <= sc->warmup_steps) return "WarmupPolyLR needs total_steps > warmup_steps";
+  if (sc->kind == 3 && sc->warmup_steps < 1) return "WarmupMultiStepLR needs warmup_steps >= 1";
+  if (sc->nmilestones < 0 || sc->nmilestones > 16) return "0..16 milestones";
+  for (int i = 1; i < sc->nmilestones; ++i)
+    if (sc->milestones[i] <= sc->milestones[i - 1]) return "milestones must be increasing";
+  return nullptr;
+}
+
+extern "C" int emrt_sgd_momentum_step_sched(float* params, const float* grads, float* velocity, long long n, const float* clip_state,
+                                            const long long* step, const EmrtLrSchedule* sched, float momentum, float weight_decay,
+                                            const long long* ranges /*host [nranges][2]*/, int nranges, float range_mult, float* lr_out,
+                                            void* mirror, int mirror_dtype, void* stream) {
+  EMRT_REQUIRE(params && grads && velocity, "null pointer");
+  EMRT_REQUIRE(!mirror || mirror_dtype == EMRT_BF16 || mirror_dtype == EMRT_F16, "the parameter mirror is bf16 or fp16");
+  EMRT_REQUIRE(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)velocity) % 16 == 0 && (!mirror || (uintptr_t)mirror % 8 == 0), "buffers must be 16-byte aligned");
+  EMRT_REQUIRE(nranges >= 0 && nranges <= 32 && (nranges == 0 || ranges), "0..32 lr-mult ranges");
+  if (const char* why = lr_schedule_problem(sched)) return emrt::fail(__func__, why);
+  SgdSchedArgs b;
+  memset(&b, 0, sizeof(b));
+  SgdArgs& a = b.s;
+  a.p = params; a.g = grads; a.v = velocity; a.n = n; a.state = clip_state; a.step = step;
+  a.momentum = momentum; a.weight_decay = weight_decay; a.nranges = nranges; a.range_mult = range_mult; a.lr_out = lr_out;
+  a.mirror = mirror;
+  for (int r = 0; r < nranges; ++r) { a.r0[r] = ranges[2 * r]; a.r1[r] = ranges[2 * r + 1]; }
+  b.sched = *sched;
+  int grid = (int)((n / 4 + 255) / 256);
+  if (grid > 8192) grid = 8192;
+  if (grid < 1) grid = 1;
+  const bool nt = g_tune.sgd_nt != 0;
+  if (mirror && mirror_dtype == EMRT_F16) {
+    if (nt) hipLaunchKernelGGL((sgd_momentum_sched_kernel<f16_t, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, b);
+    else hipLaunchKernelGGL((sgd_momentum_sched_kernel<f16_t, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, b);
+  } else {
+    if (nt) hipLaunchKernelGGL((sgd_momentum_sched_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, b);
+    else hipLaunchKernelGGL((sgd_momentum_sched_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, b);
+  }
+  return check_launch("emrt_sgd_momentum_step_sched");
+}
+
+template <class MT>
+static void launch_adamw(const AdamArgs& a, int grid, bool nt, bool decoupled, hipStream_t st) {
+  if (nt) {
+    if (decoupled) hipLaunchKernelGGL((adamw_kernel<MT, true, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((adamw_kernel<MT, true, false>), dim3(grid), dim3(256), 0, st, a);
+  } else {
+    if (decoupled) hipLaunchKernelGGL((adamw_kernel<MT, false, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((adamw_kernel<MT, false, false>), dim3(grid), dim3(256), 0, st, a);
+  }
+}
+
+extern "C" int emrt_adamw_step(float* params, const float* grads, float* moment1, float* moment2, long long n, const float* clip_state,
+                               const long long* step, const EmrtLrSchedule* sched, float beta1, float beta2, float eps, float weight_decay,
+                               int decoupled, const long long* ranges /*host [nranges][2]*/, int nranges, float range_mult, float* lr_out,
+                               void* mirror, int mirror_dtype, void* stream) {
+  EMRT_REQUIRE(params && grads && moment1 && moment2, "null pointer");
+  EMRT_REQUIRE(!mirror || mirror_dtype == EMRT_BF16 || mirror_dtype == EMRT_F16, "the parameter mirror is bf16 or fp16");
+  EMRT_REQUIRE(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)moment1 | (uintptr_t)moment2) % 16 == 0 && (!mirror || (uintptr_t)mirror % 8 == 0),
+               "buffers must be 16-byte aligned");
+  EMRT_REQUIRE(nranges >= 0 && nranges <= 32 && (nranges == 0 || ranges), "0..32 lr-mult ranges");
+  EMRT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "0 <= beta < 1");
+  EMRT_REQUIRE(eps > 0.f, "eps must be positive");
+  // the kernel adds eps * sqrt(1 - beta2^t) in fp32, smallest at t = 1: were that to underflow, an all-zero element (a padded stem channel) would
+  // compute 0 / 0 instead of staying zero
+  EMRT_REQUIRE((float)((double)eps * sqrt(1.0 - (double)beta2)) >= FLT_MIN, "eps is too small: eps * sqrt(1 - beta2) must be a normal fp32 number");
+  EMRT_REQUIRE(decoupled == 0 || decoupled == 1, "decoupled is 0 (Adam) or 1 (AdamW)");
+  if (const char* why = lr_schedule_problem(sched)) return emrt::fail(__func__, why);
+  AdamArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = params; a.g = grads; a.m = moment1; a.v = moment2; a.n = n; a.state = clip_state; a.step = step;
+  a.sched = *sched;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.decoupled = decoupled;
+  a.nranges = nranges; a.range_mult = range_mult; a.lr_out = lr_out; a.mirror = mirror;
+  for (int r = 0; r < nranges; ++r) { a.r0[r] = ranges[2 * r]; a.r1[r] = ranges[2 * r + 1]; }
+  int grid = (int)((n / 4 + 255) / 256);
+  if (grid > 8192) grid = 8192;
+  if (grid < 1) grid = 1;
+  const bool nt = g_tune.sgd_nt != 0;
+  if (mirror && mirror_dtype == EMRT_F16) launch_adamw<f16_t>(a, grid, nt, decoupled != 0, (hipStream_t)stream);
+  else launch_adamw<bf16_t>(a, grid, nt, decoupled != 0, (hipStream_t)stream);
+  return check_launch("emrt_adamw_step");
 }
 
 extern "C" int emrt_counter_add(long long* counter, long long delta, void* stream) {

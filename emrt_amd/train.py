@@ -32,14 +32,16 @@ from .src.models.solver import get_optimizer, get_scheduler
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="EMRT (MI355X HIP path) training")
-    p.add_argument("--config", dest="cfg", type=str,
+    p.add_argument("--config", "--cfg", dest="cfg", type=str,
                    default=os.path.join(os.path.dirname(__file__), "configs/EMRT/EMRT_256x256_160k_potsdam.yaml"), help="The config file.")
     p.add_argument("--seed", dest="seed", default=1234, type=int, help="Set the random seed during training.")
     p.add_argument("--data", default="synthetic", help="'synthetic', 'dataset' (DATA.DATASET under DATA.DATA_PATH, the reference's "
                    "directory layout) or a .npz of pre-cut tiles")
     p.add_argument("--data_path", default=None, help="override DATA.DATA_PATH of the yaml")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--iters", type=int, default=None, help="override TRAIN.ITERS")
+    p.add_argument("--iters", type=int, default=None, help="override TRAIN.ITERS.  Under WarmupPolyLR a value at or below LR_SCHEDULER.WARM_UP_STEPS also shortens the "
+                   "warmup to a quarter of it (none at all for 1 to 3), with a log line; the schedule follows the --iters of the run at hand, so resume with "
+                   "the --iters the checkpoint was trained with to continue the same schedule")
     p.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying a captured hipGraph")
     p.add_argument("--resume", default=None, help="checkpoint written by this script")
     p.add_argument("--save_dir", default=None, help="override SAVE_DIR of the yaml (the reference's yamls point at the authors' disks)")
@@ -51,6 +53,21 @@ def parse_args(argv=None):
                    "training transforms run as one HIP kernel per batch on the GPU (DeviceTileLoader)")
     p.add_argument("--val_tiles", type=int, default=16, help="--data synthetic / .npz without val arrays: how many held-out tiles to evaluate on")
     return p.parse_args(argv)
+
+
+def shorten_warmup(config, iters, verbose=True):
+    """--iters N at or below the yaml's WARM_UP_STEPS leaves WarmupPolyLR without a decay phase, and it refuses that (max_iters must exceed
+    warmup_steps): the warmup then shrinks with the run, to a quarter of it, with a log line.  The other schedules accept any --iters and are left alone.
+    For --iters 1 to 3 the quarter is 0: no warmup.  The shortened value is not stored in a checkpoint: a --resume rebuilds the schedule from the yaml and ITS
+    --iters, so a different --iters gives a different warmup under the restored step counter."""
+    sch = config.TRAIN.LR_SCHEDULER
+    if sch.NAME != "WarmupPolyLR" or sch.WARM_UP_STEPS < iters:
+        return False
+    new = iters // 4
+    if verbose:
+        print("[train] --iters %d is not more than LR_SCHEDULER.WARM_UP_STEPS %d: warming up over %d steps instead" % (iters, sch.WARM_UP_STEPS, new), flush=True)
+    sch.WARM_UP_STEPS = new
+    return True
 
 
 class TimeAverager:  # utils/timer.py:17-40
@@ -128,6 +145,7 @@ def main(argv=None):
     iters = args.iters or config.TRAIN.ITERS
     if args.iters:
         config.TRAIN.ITERS = iters
+        shorten_warmup(config, iters, verbose=rank == 0)
     lr_scheduler = get_scheduler(config)
     optimizer = get_optimizer(model, lr_scheduler, config)
     loss_func = get_loss_function(config)

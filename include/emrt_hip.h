@@ -342,6 +342,32 @@ int emrt_scalar_axpby(float* out, const float* a, float wa, const float* b, floa
 size_t emrt_gradnorm_workspace_bytes(void);
 int emrt_grad_clip_scale(const float* grads, long long n, float clip, float* state, void* workspace, void* stream);
 int emrt_sgd_momentum_step(float* params, const float* grads, float* velocity, long long n, const float* clip_state, const long long* step, float base_lr, float end_lr, float power, long long decay_steps, float momentum, float weight_decay, const long long* ranges, int nranges, float range_mult, float* lr_out, void* mirror, int mirror_dtype, void* stream);
+/* ---- Adam / AdamW and the warmup schedules (solver/optimizer.py:43-55, solver/lr_scheduler.py:30-267); additive to ABI 9.
+ * EmrtLrSchedule: HOST descriptor of a learning-rate schedule, copied into the kernel arguments and evaluated on the device from the step
+ * counter s (= paddle's last_epoch), so nothing is baked into a captured graph.  W = warmup_steps, T = total_steps:
+ *   kind 0 PolynomialDecay   (base - end) * (1 - min(s, T) / T)^power + end                    (lr_scheduler.py:244-248)
+ *   kind 1 WarmupPolyLR      s < W: init + (base - init) * s / W; else f = 1 - (s - W) / (T - W): f < 0 -> end, else init + (base - init) * f^power;
+ *                            a value <= end becomes end in both branches                         (lr_scheduler.py:120-184)
+ *   kind 2 WarmupCosineLR    s < W: init + s * (base - init) / W; else end + (base - end) / 2 * (1 + cos(pi * (s mod T) / T))   (lr_scheduler.py:30-117,
+ *                            as get_scheduler builds it: t_mul = decay_rate = 1, no prefix, no cycle limit)
+ *   kind 3 WarmupMultiStepLR s <= W: base * s / W; else base * gamma^(number of milestones <= s)  (lr_scheduler.py:187-240)
+ * Refused before any launch: an unknown kind, total_steps < 1, warmup_steps < 0, total_steps <= warmup_steps (kind 1), warmup_steps < 1 (kind 3),
+ * nmilestones outside 0..16, milestones that do not increase. */
+typedef struct EmrtLrSchedule {
+  int kind;
+  float base_lr, end_lr, power, warmup_lr_init, gamma;
+  long long total_steps, warmup_steps;
+  int nmilestones;
+  long long milestones[16];
+} EmrtLrSchedule;
+/* emrt_sgd_momentum_step with lr = the schedule's value in place of the built-in polynomial: same element arithmetic (kind 0 gives the same bits). */
+int emrt_sgd_momentum_step_sched(float* params, const float* grads, float* velocity, long long n, const float* clip_state, const long long* step, const EmrtLrSchedule* sched, float momentum, float weight_decay, const long long* ranges, int nranges, float range_mult, float* lr_out, void* mirror, int mirror_dtype, void* stream);
+/* One streaming pass of Adam (decoupled = 0: g += weight_decay * p, paddle.optimizer.Adam) or AdamW (decoupled = 1: p *= 1 - lr_e * weight_decay) with
+ * t = step[0] + 1, lr_e = lr * range_mult inside `ranges` (else lr), g = grad * clip_state[0] (clip_state NULL == 1):
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  p -= lr_e * sqrt(1 - beta2^t) / (1 - beta1^t) * m / (sqrt(v) + eps * sqrt(1 - beta2^t))
+ * (paddle's placement of epsilon; algebraically m_hat / (sqrt(v_hat) + eps)).  The bias terms are formed in double from the device step counter;
+ * square root and division are correctly rounded.  moment1 / moment2: fp32, same indexing as params.  mirror as in emrt_sgd_momentum_step. */
+int emrt_adamw_step(float* params, const float* grads, float* moment1, float* moment2, long long n, const float* clip_state, const long long* step, const EmrtLrSchedule* sched, float beta1, float beta2, float eps, float weight_decay, int decoupled, const long long* ranges, int nranges, float range_mult, float* lr_out, void* mirror, int mirror_dtype, void* stream);
 /* ---- evaluation metric counts (src/utils/metrics.py:20-59 calculate_area; val.py:197-209): out[3][num_classes] (int64, ACCUMULATED into: the caller zeroes it
  * once per evaluation) += per-class pixel counts of (pred == label), pred, label over the pixels whose label != ignore_index; predictions / labels outside
  * [0, num_classes) are counted nowhere.  pred int32 (the argmax map of emrt_argmax / the sliding-window engine), label int64 (label_is_int64) or int32. */
