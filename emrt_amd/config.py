@@ -125,6 +125,9 @@ _DEFAULTS = {
         "LOSS": "MixSoftmaxCrossEntropyLoss", "WEIGHTS": [1, 0.4, 0.4, 0.4, 0.4], "USE_GPU": True, "LAST_EPOCH": 0,
         "BASE_LR": 0.001, "END_LR": 1e-4, "DECODER_LR_COEF": 1.0, "ITERS": 80000, "POWER": 0.9, "DECAY_STEPS": 80000,
         "APEX": False, "IGNORE_INDEX": 255,
+        # not in the reference's tree: OhemCrossEntropyLoss's constructor arguments (losses/ohem_cross_entropy_loss.py:18) and the class-weight
+        # option of its cross entropy (losses/cross_entropy_loss.py:30-35; empty = off), which the reference leaves to code
+        "OHEM": {"THRESH": 0.7, "MIN_KEPT": 10000}, "CLASS_WEIGHTS": [],
         "LR_SCHEDULER": {"NAME": "PolynomialDecay", "WARM_UP_STEPS": 0, "WARM_UP_LR_INIT": 0.0, "MILESTONES": [30, 60, 90],
                          "POWER": 0.9, "GAMMA": 0.1},
         "OPTIMIZER": {"NAME": "SGD", "EPS": 1e-8, "BETAS": (0.9, 0.999), "MOMENTUM": 0.9, "NESTEROV": False, "WEIGHT_DECAY": 0.0,

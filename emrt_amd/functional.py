@@ -1856,15 +1856,35 @@ def sigmoid_f32(x):
 # ---------------------------------------------------------------------------------------------------
 # loss
 # ---------------------------------------------------------------------------------------------------
-def softmax_ce_pair(logits_a, logits_b, labels, ignore_index, wa, wb):
+def _class_weight_ok(class_weight, C):
+    assert class_weight.dtype == torch.float32 and class_weight.is_contiguous() and class_weight.numel() == C
+
+
+def softmax_ce_pair(logits_a, logits_b, labels, ignore_index, wa, wb, class_weight=None):
     """CE of two heads on the same labels (MixSoftmaxCrossEntropyLoss: main + aux) in one forward pass and one backward launch.
-    Returns (res_a, res_b, total): device float[2] = {loss, count} per head and float[1] = wa * loss_a + wb * loss_b."""
+    Returns (res_a, res_b, total): device float[2] = {loss, count} per head and float[1] = wa * loss_a + wb * loss_b.
+    class_weight (device fp32 [C] or None): nn.CrossEntropyLoss(weight=...) -- sum w[y] CE / sum w[y]; the count becomes sum w[y]."""
     c = ctx()
     N, C, H, W = logits_a.shape
     assert tuple(logits_b.shape) == (N, C, H, W) and logits_a.dtype == logits_b.dtype == torch.float32 and logits_a.is_contiguous() and logits_b.is_contiguous()
     assert labels.dtype == torch.int64 and labels.is_contiguous()
     res_a, res_b, total = c.empty((2,), torch.float32), c.empty((2,), torch.float32), c.empty((1,), torch.float32)
     ws = c.workspace(_L().query("emrt_ce_workspace_bytes"))
+    if class_weight is not None:
+        _class_weight_ok(class_weight, C)
+        _L().call("emrt_wce_pair_fwd", P(logits_a), P(logits_b), P(labels), P(class_weight), N, C, H, W, ignore_index, float(wa), float(wb), P(res_a),
+                  P(res_b), P(total), P(ws), c.stream)
+        tape = c.tape
+        if tape is not None:
+            def bwd_w():
+                up_a, up_b = tape.pop_grad(res_a), tape.pop_grad(res_b)
+                da, db = c.empty((N, C, H, W), torch.float32), c.empty((N, C, H, W), torch.float32)
+                _L().call("emrt_wce_pair_bwd", P(logits_a), P(logits_b), P(labels), P(class_weight), P(res_a), P(up_a), P(up_b), float(wa), float(wb),
+                          N, C, H, W, ignore_index, P(da), P(db), c.stream)
+                tape.add_grad(logits_a, da, owned=True)
+                tape.add_grad(logits_b, db, owned=True)
+            tape.record(bwd_w)
+        return res_a, res_b, total
     _L().call("emrt_softmax_ce_pair_fwd", P(logits_a), P(logits_b), P(labels), N, C, H, W, ignore_index, float(wa), float(wb), P(res_a), P(res_b), P(total),
               P(ws), c.stream)
     tape = c.tape
@@ -1880,14 +1900,27 @@ def softmax_ce_pair(logits_a, logits_b, labels, ignore_index, wa, wb):
     return res_a, res_b, total
 
 
-def softmax_ce(logits, labels, ignore_index, weight=1.0):
+def softmax_ce(logits, labels, ignore_index, weight=1.0, class_weight=None):
     """Mean CE over non-ignored pixels of fp32 NCHW logits; returns a device float[2] = {loss, count}.
-    Backward writes weight * upstream * (softmax - onehot)/count as the gradient of `logits`."""
+    Backward writes weight * upstream * (softmax - onehot)/count as the gradient of `logits`.
+    class_weight (device fp32 [C] or None): nn.CrossEntropyLoss(weight=...) -- sum w[y] CE / sum w[y]; the count becomes sum w[y]."""
     c = ctx()
     N, C, H, W = logits.shape
     assert logits.dtype == torch.float32 and logits.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous()
     res = c.empty((2,), torch.float32)
     ws = c.workspace(_L().query("emrt_ce_workspace_bytes"))
+    if class_weight is not None:
+        _class_weight_ok(class_weight, C)
+        _L().call("emrt_wce_fwd", P(logits), P(labels), P(class_weight), N, C, H, W, ignore_index, P(res), P(ws), c.stream)
+        tape = c.tape
+        if tape is not None:
+            def bwd_w():
+                up = tape.pop_grad(res)
+                dl = c.empty((N, C, H, W), torch.float32)
+                _L().call("emrt_wce_bwd", P(logits), P(labels), P(class_weight), P(res), P(up), float(weight), N, C, H, W, ignore_index, P(dl), c.stream)
+                tape.add_grad(logits, dl, owned=True)
+            tape.record(bwd_w)
+        return res
     _L().call("emrt_softmax_ce_fwd", P(logits), P(labels), N, C, H, W, ignore_index, P(res), P(ws), c.stream)
     tape = c.tape
     if tape is not None:
@@ -1900,7 +1933,58 @@ def softmax_ce(logits, labels, ignore_index, weight=1.0):
     return res
 
 
-class _AugDesc(ctypes.Structure):          # EmrtAugDesc (include/emrt_hip.h)
+def ohem_ce(logits, labels, ignore_index, thresh=0.7, min_kept=10000, weight=1.0):
+    """OhemCrossEntropyLoss of one head (fp32 NCHW logits) with the threshold selected on the device: no host read, capturable.
+    Returns (res, prob): res = device float[8] {loss, kept count, threshold, non-ignored count, 1 / (kept + 1e-5 N H W), ...} and prob = the
+    stored probability of every pixel's own class (fp32 [N, H, W]) that forward and backward both decide membership from.
+    Backward writes weight * upstream * (softmax - onehot) / (kept + 1e-5 N H W) on the kept pixels, zeros elsewhere."""
+    c = ctx()
+    N, C, H, W = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous()
+    if int(min_kept) < 0:
+        raise ValueError("min_kept must be >= 0, got %r" % (min_kept,))
+    res, prob = c.empty((8,), torch.float32), c.empty((N, H, W), torch.float32)
+    ws = c.workspace(_L().query("emrt_ohem_workspace_bytes", N * H * W, 1))
+    _L().call("emrt_ohem_ce_fwd", P(logits), P(labels), N, C, H, W, ignore_index, float(thresh), int(min_kept), P(prob), P(res), P(ws), c.stream)
+    tape = c.tape
+    if tape is not None:
+        def bwd():
+            up = tape.pop_grad(res)   # device scalar or None (== 1)
+            dl = c.empty((N, C, H, W), torch.float32)
+            _L().call("emrt_ohem_ce_bwd", P(logits), P(labels), P(prob), P(res), P(up), float(weight), N, C, H, W, ignore_index, P(dl), c.stream)
+            tape.add_grad(logits, dl, owned=True)
+        tape.record(bwd)
+    return res, prob
+
+
+def ohem_ce_pair(logits_a, logits_b, labels, ignore_index, thresh, min_kept, wa, wb):
+    """ohem_ce of two heads on the same labels (main + aux) through the launches of one: the head is a grid dimension of every kernel, each
+    head's threshold, loss and gradient are the single form's bits.  Returns (res_a, res_b, total, prob_a, prob_b); total = wa * loss_a + wb * loss_b."""
+    c = ctx()
+    N, C, H, W = logits_a.shape
+    assert tuple(logits_b.shape) == (N, C, H, W) and logits_a.dtype == logits_b.dtype == torch.float32 and logits_a.is_contiguous() and logits_b.is_contiguous()
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    if int(min_kept) < 0:
+        raise ValueError("min_kept must be >= 0, got %r" % (min_kept,))
+    res_a, res_b, total = c.empty((8,), torch.float32), c.empty((8,), torch.float32), c.empty((1,), torch.float32)
+    prob_a, prob_b = c.empty((N, H, W), torch.float32), c.empty((N, H, W), torch.float32)
+    ws = c.workspace(_L().query("emrt_ohem_workspace_bytes", N * H * W, 2))
+    _L().call("emrt_ohem_ce_pair_fwd", P(logits_a), P(logits_b), P(labels), N, C, H, W, ignore_index, float(thresh), int(min_kept), float(wa), float(wb),
+              P(prob_a), P(prob_b), P(res_a), P(res_b), P(total), P(ws), c.stream)
+    tape = c.tape
+    if tape is not None:
+        def bwd():
+            up_a, up_b = tape.pop_grad(res_a), tape.pop_grad(res_b)      # device scalars or None (== 1)
+            da, db = c.empty((N, C, H, W), torch.float32), c.empty((N, C, H, W), torch.float32)
+            _L().call("emrt_ohem_ce_pair_bwd", P(logits_a), P(logits_b), P(labels), P(prob_a), P(prob_b), P(res_a), P(res_b), P(up_a), P(up_b), float(wa),
+                      float(wb), N, C, H, W, ignore_index, P(da), P(db), c.stream)
+            tape.add_grad(logits_a, da, owned=True)
+            tape.add_grad(logits_b, db, owned=True)
+        tape.record(bwd)
+    return res_a, res_b, total, prob_a, prob_b
+
+
+class _AugDesc(ctypes.Structure):         # EmrtAugDesc (include/emrt_hip.h)
     _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int), ("h", ctypes.c_int),
                 ("w", ctypes.c_int), ("off_y", ctypes.c_int), ("off_x", ctypes.c_int), ("flip", ctypes.c_int)]
 

@@ -331,6 +331,31 @@ int emrt_softmax_ce_bwd(const float* logits, const long long* labels, const floa
 int emrt_softmax_ce_pair_fwd(const float* logits_a, const float* logits_b, const long long* labels, int N, int C, int H, int W, int ignore_index, float wa, float wb, float* res_a, float* res_b, float* total, void* workspace, void* stream);
 int emrt_softmax_ce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* res_a, const float* up_a, const float* up_b, float wa, float wb, int N, int C, int H, int W, int ignore_index, float* dlogits_a, float* dlogits_b, void* stream);
 int emrt_scalar_axpby(float* out, const float* a, float wa, const float* b, float wb, void* stream);
+/* ---- OhemCrossEntropyLoss (losses/ohem_cross_entropy_loss.py:41-79) with the selection on the device; additive to ABI 9.  npix = N * H * W counts
+ * the ignored pixels too; p = softmax probability of a pixel's own class, stored in `prob` (fp32 [npix], the caller's: the backward reads it; an
+ * ignored pixel holds the pattern 0xffffffff).  threshold = +inf (every non-ignored pixel kept) when min_kept >= num_valid or num_valid == 0;
+ * else thresh, raised to the min_kept-th smallest p over the non-ignored pixels (rank from 1; an exact 11 + 11 + 10 bit radix select on the bit
+ * patterns, integer atomics only) when min_kept > 0 and that p > thresh.  kept = non-ignored and STORED p < threshold, strictly: the k-th pixel
+ * and its ties are dropped, as in the reference.  result (device float[8], five used) = {sum of kept CE / (kept + 1e-5 npix), kept count,
+ * threshold, num_valid, 1 / (kept + 1e-5 npix) or 0 when nothing is kept}.  No host read, synchronisation or allocation: capturable.
+ * Backward: dlogits = weight * upstream * (softmax - onehot) * result[4] on the kept pixels (decided from the stored p again), zeros elsewhere;
+ * upstream NULL == 1.  Refused before any launch: null pointers, N / C / H / W < 1, npix >= 2^31, min_kept < 0, a NaN thresh.
+ * The pair form runs the main and the auxiliary head on the same labels through the SAME launches (the head is a grid dimension: 9 forward
+ * launches and 1 backward launch for both, each head's results the bits of the single form) and forms total[0] = wa * loss_a + wb * loss_b.
+ * workspace: emrt_ohem_workspace_bytes(npix, heads), heads = 1 (single form) or 2 (pair form). */
+size_t emrt_ohem_workspace_bytes(long long npix, int heads);
+int emrt_ohem_ce_fwd(const float* logits, const long long* labels, int N, int C, int H, int W, int ignore_index, float thresh, long long min_kept, float* prob, float* result, void* workspace, void* stream);
+int emrt_ohem_ce_bwd(const float* logits, const long long* labels, const float* prob, const float* result, const float* upstream, float weight, int N, int C, int H, int W, int ignore_index, float* dlogits, void* stream);
+int emrt_ohem_ce_pair_fwd(const float* logits_a, const float* logits_b, const long long* labels, int N, int C, int H, int W, int ignore_index, float thresh, long long min_kept, float wa, float wb, float* prob_a, float* prob_b, float* res_a, float* res_b, float* total, void* workspace, void* stream);
+int emrt_ohem_ce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* prob_a, const float* prob_b, const float* res_a, const float* res_b, const float* up_a, const float* up_b, float wa, float wb, int N, int C, int H, int W, int ignore_index, float* dlogits_a, float* dlogits_b, void* stream);
+/* ---- nn.CrossEntropyLoss(weight = class_weight, ignore_index) (losses/cross_entropy_loss.py:30-35, the class-weight option): loss = sum w[y] CE /
+ * sum w[y] over the non-ignored pixels, dlogits = weight * upstream * w[y] * (softmax - onehot) / sum w[y].  class_weight: DEVICE float[C], or NULL
+ * == all ones (then the results of emrt_softmax_ce_* to the last bits).  result / res_a / res_b (device float[2]) = {loss, sum w[y]}; the pair form is
+ * emrt_softmax_ce_pair_* with the weights: one forward and one backward launch for both heads.  workspace: emrt_ce_workspace_bytes(). */
+int emrt_wce_fwd(const float* logits, const long long* labels, const float* class_weight, int N, int C, int H, int W, int ignore_index, float* result, void* workspace, void* stream);
+int emrt_wce_bwd(const float* logits, const long long* labels, const float* class_weight, const float* result, const float* upstream, float weight, int N, int C, int H, int W, int ignore_index, float* dlogits, void* stream);
+int emrt_wce_pair_fwd(const float* logits_a, const float* logits_b, const long long* labels, const float* class_weight, int N, int C, int H, int W, int ignore_index, float wa, float wb, float* res_a, float* res_b, float* total, void* workspace, void* stream);
+int emrt_wce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* class_weight, const float* res_a, const float* up_a, const float* up_b, float wa, float wb, int N, int C, int H, int W, int ignore_index, float* dlogits_a, float* dlogits_b, void* stream);
 
 /* ---- optimizer: ClipGradByGlobalNorm + L2 decay + Momentum over one flat fp32 buffer, PolynomialDecay evaluated
  * on the device from a step counter: solver/optimizer.py:29-40, solver/lr_scheduler.py:244-248.
