@@ -573,16 +573,14 @@ extern "C" int emrt_mha_fwd(const void* q, int ldq, const void* k, int ldk, cons
   const bool mfma = dtype != EMRT_F32 && !g_tune.mha_valu && L >= 2 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 &&
                     (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0) && ((uintptr_t)o % 8 == 0);
   if (path_out) *path_out = mfma ? 1 : 0;      // what `probs` holds now: the backward must be told (emrt_mha_bwd: path)
-  if (mfma) {
-    const int threads = 64 * ((L + 15) / 16);
-    if (dtype == EMRT_BF16) hipLaunchKernelGGL((mha_fwd_mfma_kernel<bf16_t>), dim3(B * M), dim3(threads), 0, st, a);
-    else hipLaunchKernelGGL((mha_fwd_mfma_kernel<f16_t>), dim3(B * M), dim3(threads), 0, st, a);
+  return with_fwd_dtype("emrt_mha_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (mfma) {
+      const int threads = 64 * ((L + 15) / 16);
+      if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((mha_fwd_mfma_kernel<T>), dim3(B * M), dim3(threads), 0, st, a);      // (mfma is never set for f32)
+    } else hipLaunchKernelGGL((mha_fwd_kernel<T>), dim3(B * M * nchunk), dim3(4 * MHA_FWD_ROWS), lds, st, a, nchunk);
     return check_launch("emrt_mha_fwd");
-  }
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((mha_fwd_kernel<float>), dim3(B * M * nchunk), dim3(4 * MHA_FWD_ROWS), lds, st, a, nchunk);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((mha_fwd_kernel<bf16_t>), dim3(B * M * nchunk), dim3(4 * MHA_FWD_ROWS), lds, st, a, nchunk);
-  else hipLaunchKernelGGL((mha_fwd_kernel<f16_t>), dim3(B * M * nchunk), dim3(4 * MHA_FWD_ROWS), lds, st, a, nchunk);
-  return check_launch("emrt_mha_fwd");
+  });
 }
 
 extern "C" int emrt_mha_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* probs,
@@ -624,7 +622,9 @@ extern "C" int emrt_mha_bwd(const void* q, int ldq, const void* k, int ldk, cons
     hipLaunchKernelGGL((mha_bwd_mfma_kernel<bf16_t>), dim3(B * M, g_tune.mha_bwd_split ? 2 : 1), dim3(64 * ((L + 15) / 16)), 0, st, a);
     return check_launch("emrt_mha_bwd");
   }
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((mha_bwd_kernel<float>), dim3(B * M), dim3(MHA_THREADS), lds, st, a);
-  else hipLaunchKernelGGL((mha_bwd_kernel<bf16_t>), dim3(B * M), dim3(MHA_THREADS), lds, st, a);
-  return check_launch("emrt_mha_bwd");
+  return with_train_dtype("emrt_mha_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((mha_bwd_kernel<T>), dim3(B * M), dim3(MHA_THREADS), lds, st, a);
+    return check_launch("emrt_mha_bwd");
+  });
 }

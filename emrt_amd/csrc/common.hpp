@@ -352,8 +352,28 @@ __device__ __forceinline__ void unravel4(long long idx, int D0, int D1, int D2, 
 }
 
 // entry points with a backward / training-only meaning accept f32 and bf16; fp16 (dtype 2) is inference-only
-#define EMRT_REQUIRE_TRAIN_DTYPE(dtype) EMRT_REQUIRE((dtype) == EMRT_F32 || (dtype) == EMRT_BF16, "dtype must be 0 (f32) or 1 (bf16): fp16 (2) is inference-only")
-#define EMRT_REQUIRE_FWD_DTYPE(dtype) EMRT_REQUIRE((dtype) == EMRT_F32 || (dtype) == EMRT_BF16 || (dtype) == EMRT_F16, "dtype must be 0 (f32), 1 (bf16) or 2 (f16)")
+#define EMRT_TRAIN_DTYPE_MSG "dtype must be 0 (f32) or 1 (bf16): fp16 (2) is inference-only"
+#define EMRT_FWD_DTYPE_MSG "dtype must be 0 (f32), 1 (bf16) or 2 (f16)"
+#define EMRT_REQUIRE_TRAIN_DTYPE(dtype) EMRT_REQUIRE((dtype) == EMRT_F32 || (dtype) == EMRT_BF16, EMRT_TRAIN_DTYPE_MSG)
+#define EMRT_REQUIRE_FWD_DTYPE(dtype) EMRT_REQUIRE((dtype) == EMRT_F32 || (dtype) == EMRT_BF16 || (dtype) == EMRT_F16, EMRT_FWD_DTYPE_MSG)
+
+// The ONE place where the ABI's dtype code becomes an element type: f is a generic lambda, called with a value of the element type
+// ([&](auto t) { using T = decltype(t); ... }), that returns the entry point's int.  with_train_dtype instantiates f for float and bf16_t only
+// (kernels with a training-only meaning have no f16_t instantiation), with_fwd_dtype for f16_t too.  Any other code is refused under the
+// entry point's name fn: the backstop behind the EMRT_REQUIRE_*_DTYPE line every entry point carries, never a silent "everything else is bf16".
+template <class F>
+inline int with_train_dtype(const char* fn, int dtype, F&& f) {
+  if (dtype == EMRT_F32) return f(float{});
+  if (dtype == EMRT_BF16) return f(bf16_t{});
+  return fail(fn, EMRT_TRAIN_DTYPE_MSG);
+}
+template <class F>
+inline int with_fwd_dtype(const char* fn, int dtype, F&& f) {
+  if (dtype == EMRT_F32) return f(float{});
+  if (dtype == EMRT_BF16) return f(bf16_t{});
+  if (dtype == EMRT_F16) return f(f16_t{});
+  return fail(fn, EMRT_FWD_DTYPE_MSG);
+}
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 

@@ -1515,9 +1515,11 @@ static int conv2d_impl(const void* in, const void* w_packed, void* out, const fl
   if (drop_p > 0.f) { a.drop_seed = drop_seed; a.drop_salt = drop_salt; a.drop_p = drop_p; }
   EMRT_REQUIRE(!mask_y || !out_f32, "the ReLU mask needs an output in the compute dtype");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) return mode == 0 ? conv_dispatch<float, 0>(a, st) : conv_dispatch<float, 1>(a, st);
-  if (dtype == EMRT_F16) return conv_dispatch<f16_t, 0>(a, st);
-  return mode == 0 ? conv_dispatch<bf16_t, 0>(a, st) : conv_dispatch<bf16_t, 1>(a, st);
+  return with_fwd_dtype(__func__, dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (std::is_same<T, f16_t>::value) return conv_dispatch<T, 0>(a, st);      // (mode 1 was refused above: no fp16 data gradient is built)
+    else return mode == 0 ? conv_dispatch<T, 0>(a, st) : conv_dispatch<T, 1>(a, st);
+  });
 }
 
 extern "C" int emrt_conv2d(const void* in, const void* w_packed, void* out, const float* bias, const void* residual,
@@ -1623,7 +1625,7 @@ extern "C" int emrt_conv2d_bna_supported(const void* in, const void* w_packed, v
   const ConvArgs a = bna_args(in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, relu, out_f32,
                               bn_stats, dilation, sums, count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, in_relu, a_out);
   hipStream_t st = (hipStream_t)stream;
-  return (dtype == EMRT_F32 ? bna_plan<float>(a, st) : bna_plan<bf16_t>(a, st)).kind != CONV_NONE ? 1 : 0;
+  return with_train_dtype("emrt_conv2d_bna_supported", dtype, [&](auto t) { return bna_plan<decltype(t)>(a, st).kind != CONV_NONE ? 1 : 0; });      // (dtype was checked above)
 }
 
 // out = conv([relu](BatchNorm_train(in))) with the BatchNorm applied by the convolution's own operand loads and the normalised map written to a_out
@@ -1650,9 +1652,12 @@ extern "C" int emrt_conv2d_bna(const void* in, const void* w_packed, void* out, 
   const ConvArgs a = bna_args(in, w_packed, out, bias, residual, N, H, W, C, ldin, in_bs, OH, OW, OC, ldout, out_bs, ldres, res_bs, KH, KW, stride, pad, relu, out_f32,
                               bn_stats, dilation, sums, count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, in_relu, a_out);
   hipStream_t st = (hipStream_t)stream;
-  const ConvPlan plan = dtype == EMRT_F32 ? bna_plan<float>(a, st) : bna_plan<bf16_t>(a, st);
-  EMRT_REQUIRE(plan.kind != CONV_NONE, "this layer has no operand-transform kernel (ask emrt_conv2d_bna_supported first)");
-  return dtype == EMRT_F32 ? launch_bna<float>(a, st, plan) : launch_bna<bf16_t>(a, st, plan);
+  return with_train_dtype("emrt_conv2d_bna", dtype, [&](auto t) {
+    using T = decltype(t);
+    const ConvPlan plan = bna_plan<T>(a, st);
+    if (plan.kind == CONV_NONE) return fail("emrt_conv2d_bna", "this layer has no operand-transform kernel (ask emrt_conv2d_bna_supported first)");
+    return launch_bna<T>(a, st, plan);
+  });
 }
 
 // vector path eligibility of a weight-gradient problem
@@ -1745,7 +1750,7 @@ extern "C" int emrt_conv2d_wgrad(const void* x, const void* dy, float* dw,
   EMRT_CONV_CHECK(s, ldx, x_bs, lddy, dy_bs, dtype, CK_X | CK_Y | CK_X24);
   const WgradArgs a = wgrad_args(x, dy, dw, dbias, N, H, W, C, ldx, x_bs, OH, OW, OC, lddy, dy_bs, KH, KW, stride, pad, dilation, 0);
   hipStream_t st = (hipStream_t)stream;
-  return dtype == EMRT_F32 ? wgrad_dispatch<float>(a, st) : wgrad_dispatch<bf16_t>(a, st);
+  return with_train_dtype("emrt_conv2d_wgrad", dtype, [&](auto t) { return wgrad_dispatch<decltype(t)>(a, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2190,16 +2195,13 @@ extern "C" int emrt_bn_pointwise_fwd(const void* x, int ldx, long long x_bs, con
   if (blocks > cap) blocks = cap;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)2 * C * sizeof(float);
-#define EMRT_THIN_FWD(TT)                                                                                                     \
-  do {                                                                                                                        \
-    if (cgs == 5) hipLaunchKernelGGL((thin_fwd_bn_kernel<TT, 5>), dim3((unsigned)blocks), dim3(256), lds, st, a, b);           \
-    else if (cgs == 4) hipLaunchKernelGGL((thin_fwd_bn_kernel<TT, 4>), dim3((unsigned)blocks), dim3(256), lds, st, a, b);      \
-    else hipLaunchKernelGGL((thin_fwd_bn_kernel<TT, 3>), dim3((unsigned)blocks), dim3(256), lds, st, a, b);                    \
-  } while (0)
-  if (dtype == EMRT_F32) EMRT_THIN_FWD(float);
-  else EMRT_THIN_FWD(bf16_t);
-#undef EMRT_THIN_FWD
-  return check_launch("emrt_bn_pointwise_fwd");
+  return with_train_dtype("emrt_bn_pointwise_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (cgs == 5) hipLaunchKernelGGL((thin_fwd_bn_kernel<T, 5>), dim3((unsigned)blocks), dim3(256), lds, st, a, b);
+    else if (cgs == 4) hipLaunchKernelGGL((thin_fwd_bn_kernel<T, 4>), dim3((unsigned)blocks), dim3(256), lds, st, a, b);
+    else hipLaunchKernelGGL((thin_fwd_bn_kernel<T, 3>), dim3((unsigned)blocks), dim3(256), lds, st, a, b);
+    return check_launch("emrt_bn_pointwise_fwd");
+  });
 }
 
 // backward of the same layer in one pass: da = dy . w masked by a = relu(BN(x)) > 0 (a re-derived from the raw x per element),
@@ -2216,12 +2218,11 @@ extern "C" int emrt_bn_pointwise_bwd(const void* x, int ldx, long long x_bs, con
   const WgradArgs w = wgrad_args(x, dy, dw, dbias, N, 1, HW, C, ldx, x_bs, 1, HW, OC, lddy, dy_bs, 1, 1, 1, 0, 1, 0);
   const float* xbn[4] = {mean, invstd, gamma, beta};
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) {
-    EMRT_REQUIRE(thin_bwd_ok<float>(d, w), "shape outside the thin kernel (C a power of two in 32..1024, 16-byte aligned rows)");
-    return thin_bwd_launch<float>(d, w, st, xbn);
-  }
-  EMRT_REQUIRE(thin_bwd_ok<bf16_t>(d, w), "shape outside the thin kernel (C a power of two in 32..1024, 16-byte aligned rows)");
-  return thin_bwd_launch<bf16_t>(d, w, st, xbn);
+  return with_train_dtype("emrt_bn_pointwise_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (!thin_bwd_ok<T>(d, w)) return fail("emrt_bn_pointwise_bwd", "shape outside the thin kernel (C a power of two in 32..1024, 16-byte aligned rows)");
+    return thin_bwd_launch<T>(d, w, st, xbn);
+  });
 }
 
 
@@ -2244,7 +2245,7 @@ extern "C" int emrt_conv2d_bwd(const void* x, const void* dy, const void* w_bwd_
                                      dilation, g_tune.igemm8p_cmajor, bn_stats, mask_y, ldy, y_bs, mask_scale, stat_x, ldsx, sx_bs);
   const WgradArgs w = wgrad_args(x, dy, dw, dbias, N, H, W, C, ldx, x_bs, OH, OW, OC, lddy, dy_bs, KH, KW, stride, pad, dilation, 0);
   hipStream_t st = (hipStream_t)stream;
-  return dtype == EMRT_F32 ? conv_bwd_dispatch<float>(d, w, st) : conv_bwd_dispatch<bf16_t>(d, w, st);
+  return with_train_dtype("emrt_conv2d_bwd", dtype, [&](auto t) { return conv_bwd_dispatch<decltype(t)>(d, w, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2333,8 +2334,7 @@ extern "C" int emrt_conv2d_group(const EmrtConvDesc* descs, int n, int dtype, vo
     EMRT_CONV_CHECK(s, d.ldin, d.in_bs, 0, 0, dtype, CK_GROUPED | CK_DIMS | CK_SIZE | CK_PIXELS | CK_X | CK_W);
   }
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F16) return conv_group_dispatch<f16_t>(descs, n, st);
-  return dtype == EMRT_F32 ? conv_group_dispatch<float>(descs, n, st) : conv_group_dispatch<bf16_t>(descs, n, st);
+  return with_fwd_dtype("emrt_conv2d_group", dtype, [&](auto t) { return conv_group_dispatch<decltype(t)>(descs, n, st); });
 }
 
 // the data-gradient view of a grouped descriptor (no dilation, no fused epilogue, cmajor 0)
@@ -2409,7 +2409,7 @@ extern "C" int emrt_conv2d_bwd_group(const EmrtConvBwdDesc* descs, int n, int dt
     EMRT_CONV_CHECK(s, b.ldx, b.x_bs, b.lddy, b.dy_bs, dtype, CK_GROUPED | CK_X | CK_Y | CK_X24);
   }
   hipStream_t st = (hipStream_t)stream;
-  return dtype == EMRT_F32 ? conv_bwd_group_dispatch<float>(descs, n, st) : conv_bwd_group_dispatch<bf16_t>(descs, n, st);
+  return with_train_dtype("emrt_conv2d_bwd_group", dtype, [&](auto t) { return conv_bwd_group_dispatch<decltype(t)>(descs, n, st); });
 }
 
 // ---- data gradients of INDEPENDENT layers with their fused epilogues, side by side (ABI 9) ----------------------------------------------------
@@ -2444,7 +2444,7 @@ extern "C" int emrt_conv2d_dgrad_multi(const EmrtConvDgradDesc* descs, int n, in
     for (int j = 0; j < i; ++j) EMRT_REQUIRE(descs[j].dx != b.dx, "two problems of one launch must not write the same dx");
   }
   hipStream_t st = (hipStream_t)stream;
-  return dtype == EMRT_F32 ? conv_dgrad_multi_dispatch<float>(descs, n, st) : conv_dgrad_multi_dispatch<bf16_t>(descs, n, st);
+  return with_train_dtype("emrt_conv2d_dgrad_multi", dtype, [&](auto t) { return conv_dgrad_multi_dispatch<decltype(t)>(descs, n, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2631,5 +2631,5 @@ extern "C" int emrt_conv2d_wgrad_group(const EmrtWgradDesc* descs, int n, int dt
     EMRT_CONV_CHECK(s, d.ldx, d.x_bs, d.lddy, d.dy_bs, dtype, CK_KERNEL | CK_SIZE | CK_PIXELS | CK_X | CK_Y | CK_X24);
   }
   hipStream_t st = (hipStream_t)stream;
-  return dtype == EMRT_F32 ? wgrad_group_dispatch<float>(descs, n, st) : wgrad_group_dispatch<bf16_t>(descs, n, st);
+  return with_train_dtype("emrt_conv2d_wgrad_group", dtype, [&](auto t) { return wgrad_group_dispatch<decltype(t)>(descs, n, st); });
 }

@@ -264,22 +264,16 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI* __restrict__ in, TO
     out[i] = from_f32<TO>(to_f32(in[i]));
 }
 
-// out[r][c] = in[r][c] for a strided 2-D copy with dtype conversion f32 -> T (rows x cols, lds in elements)
-#define LAUNCH_T(dtype, KERNEL, GRID, ...)                                                            \
-  do {                                                                                                \
-    if ((dtype) == EMRT_F32) hipLaunchKernelGGL((KERNEL<float>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<bf16_t>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__);              \
-  } while (0)
-
 extern "C" int emrt_add(const void* a, const void* b, void* out, long long n, long long period, int dtype, void* stream) {
   EMRT_REQUIRE_FWD_DTYPE(dtype);
   EMRT_REQUIRE(a && b && out, "null pointer");
   EMRT_REQUIRE(n % 4 == 0 && period % 4 == 0 && period > 0, "n and period must be multiples of 4");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((add_kernel<float>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n / 4, period / 4);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((add_kernel<bf16_t>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n / 4, period / 4);
-  else hipLaunchKernelGGL((add_kernel<f16_t>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const f16_t*)a, (const f16_t*)b, (f16_t*)out, n / 4, period / 4);
-  return check_launch("emrt_add");
+  return with_fwd_dtype("emrt_add", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((add_kernel<T>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)out, n / 4, period / 4);
+    return check_launch("emrt_add");
+  });
 }
 
 extern "C" int emrt_add3d(const void* a, long long a_bs, long long a_rs, const void* b, long long b_bs, long long b_rs, void* out,
@@ -291,10 +285,11 @@ extern "C" int emrt_add3d(const void* a, long long a_bs, long long a_rs, const v
   EMRT_REQUIRE(B > 0 && rows > 0 && cols > 0 && rows < (1ll << 31) && cols < (1ll << 31), "rows / cols must be in [1, 2^31)");
   hipStream_t st = (hipStream_t)stream;
   const int grid = ew_grid(B * rows * (cols / 4));
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((add3d_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)a, a_bs, a_rs, (const float*)b, b_bs, b_rs, (float*)out, out_bs, out_rs, B, rows, cols / 4);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((add3d_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)a, a_bs, a_rs, (const bf16_t*)b, b_bs, b_rs, (bf16_t*)out, out_bs, out_rs, B, rows, cols / 4);
-  else hipLaunchKernelGGL((add3d_kernel<f16_t>), dim3(grid), dim3(256), 0, st, (const f16_t*)a, a_bs, a_rs, (const f16_t*)b, b_bs, b_rs, (f16_t*)out, out_bs, out_rs, B, rows, cols / 4);
-  return check_launch("emrt_add3d");
+  return with_fwd_dtype("emrt_add3d", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((add3d_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)a, a_bs, a_rs, (const T*)b, b_bs, b_rs, (T*)out, out_bs, out_rs, B, rows, cols / 4);
+    return check_launch("emrt_add3d");
+  });
 }
 
 // ---- token concat / split: [B][n_i][C] dense parts <-> dense [B][sum n_i][C] in ONE launch (the pyramid-pooling tokens of
@@ -338,11 +333,12 @@ extern "C" int emrt_concat_tokens(void* const* parts, const int* n, int nparts, 
   a.nparts = nparts; a.B = B; a.C4 = C / 4; a.total = total;
   hipStream_t st = (hipStream_t)stream;
   const int grid = ew_grid((long long)B * total * (C / 4));
-#define CONCAT_LAUNCH(T) do { if (split) hipLaunchKernelGGL((concat_tokens_kernel<T, 1>), dim3(grid), dim3(256), 0, st, a, (T*)whole); \
-                              else hipLaunchKernelGGL((concat_tokens_kernel<T, 0>), dim3(grid), dim3(256), 0, st, a, (T*)whole); } while (0)
-  if (dtype == EMRT_F32) CONCAT_LAUNCH(float); else if (dtype == EMRT_BF16) CONCAT_LAUNCH(bf16_t); else CONCAT_LAUNCH(f16_t);
-#undef CONCAT_LAUNCH
-  return check_launch("emrt_concat_tokens");
+  return with_fwd_dtype("emrt_concat_tokens", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (split) hipLaunchKernelGGL((concat_tokens_kernel<T, 1>), dim3(grid), dim3(256), 0, st, a, (T*)whole);
+    else hipLaunchKernelGGL((concat_tokens_kernel<T, 0>), dim3(grid), dim3(256), 0, st, a, (T*)whole);
+    return check_launch("emrt_concat_tokens");
+  });
 }
 
 extern "C" int emrt_acc3d(void* dst, long long dst_bs, long long dst_rs, const void* src, long long src_bs, long long src_rs, long long B,
@@ -353,10 +349,11 @@ extern "C" int emrt_acc3d(void* dst, long long dst_bs, long long dst_rs, const v
   EMRT_REQUIRE(B > 0 && rows > 0 && cols > 0 && rows < (1ll << 31) && cols < (1ll << 31), "rows / cols must be in [1, 2^31)");
   hipStream_t st = (hipStream_t)stream;
   const int grid = ew_grid(B * rows * (cols / 4));
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((acc3d_kernel<float>), dim3(grid), dim3(256), 0, st, (float*)dst, dst_bs, dst_rs, (const float*)src, src_bs, src_rs, B, rows, cols / 4);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((acc3d_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (bf16_t*)dst, dst_bs, dst_rs, (const bf16_t*)src, src_bs, src_rs, B, rows, cols / 4);
-  else hipLaunchKernelGGL((acc3d_kernel<f16_t>), dim3(grid), dim3(256), 0, st, (f16_t*)dst, dst_bs, dst_rs, (const f16_t*)src, src_bs, src_rs, B, rows, cols / 4);
-  return check_launch("emrt_acc3d");
+  return with_fwd_dtype("emrt_acc3d", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((acc3d_kernel<T>), dim3(grid), dim3(256), 0, st, (T*)dst, dst_bs, dst_rs, (const T*)src, src_bs, src_rs, B, rows, cols / 4);
+    return check_launch("emrt_acc3d");
+  });
 }
 
 extern "C" int emrt_add_f32row(const void* a, const float* row, void* out, long long n, long long period, int dtype, void* stream) {
@@ -364,10 +361,11 @@ extern "C" int emrt_add_f32row(const void* a, const float* row, void* out, long 
   EMRT_REQUIRE(a && row && out, "null pointer");
   EMRT_REQUIRE(n % 4 == 0 && period % 4 == 0 && period > 0, "n and period must be multiples of 4");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((add_f32row_kernel<float>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)a, row, (float*)out, n / 4, period / 4);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((add_f32row_kernel<bf16_t>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const bf16_t*)a, row, (bf16_t*)out, n / 4, period / 4);
-  else hipLaunchKernelGGL((add_f32row_kernel<f16_t>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const f16_t*)a, row, (f16_t*)out, n / 4, period / 4);
-  return check_launch("emrt_add_f32row");
+  return with_fwd_dtype("emrt_add_f32row", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((add_f32row_kernel<T>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const T*)a, row, (T*)out, n / 4, period / 4);
+    return check_launch("emrt_add_f32row");
+  });
 }
 
 extern "C" int emrt_add_f32row_levels(const void* a, const float* rows, void* out, const int* level_start, int L, int Lv, int C, int dtype, void* stream) {
@@ -383,10 +381,11 @@ extern "C" int emrt_add_f32row_levels(const void* a, const float* rows, void* ou
   }
   const long long n4 = (long long)Lv * C / 4;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((add_f32row_levels_kernel<float>), dim3(ew_grid(n4)), dim3(256), 0, st, (const float*)a, rows, (float*)out, n4, C / 4, ls);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((add_f32row_levels_kernel<bf16_t>), dim3(ew_grid(n4)), dim3(256), 0, st, (const bf16_t*)a, rows, (bf16_t*)out, n4, C / 4, ls);
-  else hipLaunchKernelGGL((add_f32row_levels_kernel<f16_t>), dim3(ew_grid(n4)), dim3(256), 0, st, (const f16_t*)a, rows, (f16_t*)out, n4, C / 4, ls);
-  return check_launch("emrt_add_f32row_levels");
+  return with_fwd_dtype("emrt_add_f32row_levels", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((add_f32row_levels_kernel<T>), dim3(ew_grid(n4)), dim3(256), 0, st, (const T*)a, rows, (T*)out, n4, C / 4, ls);
+    return check_launch("emrt_add_f32row_levels");
+  });
 }
 
 extern "C" int emrt_dropout_fwd(const void* x, void* y, long long n, float p, const unsigned long long* seed, unsigned salt, int mode,
@@ -396,9 +395,11 @@ extern "C" int emrt_dropout_fwd(const void* x, void* y, long long n, float p, co
   EMRT_REQUIRE(n % 4 == 0 && p >= 0.f && p < 1.f, "n must be a multiple of 4, 0 <= p < 1");
   EMRT_REQUIRE(mode == 0 || (hw > 0 && C > 0), "channel mode needs hw and C");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((dropout_fwd_kernel<float>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)x, (float*)y, n / 4, p, seed, salt, mode, hw, C);
-  else hipLaunchKernelGGL((dropout_fwd_kernel<bf16_t>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, n / 4, p, seed, salt, mode, hw, C);
-  return check_launch("emrt_dropout_fwd");
+  return with_train_dtype("emrt_dropout_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((dropout_fwd_kernel<T>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const T*)x, (T*)y, n / 4, p, seed, salt, mode, hw, C);
+    return check_launch("emrt_dropout_fwd");
+  });
 }
 
 extern "C" int emrt_mask_bwd(const void* dy, const void* relu_out, void* dx, long long n, float p, const unsigned long long* seed,
@@ -408,9 +409,11 @@ extern "C" int emrt_mask_bwd(const void* dy, const void* relu_out, void* dx, lon
   EMRT_REQUIRE(n % 4 == 0 && p >= 0.f && p < 1.f, "n must be a multiple of 4, 0 <= p < 1");
   EMRT_REQUIRE(p == 0.f || seed || relu_out, "dropout needs a device seed (or, seed == NULL, the stored output of emrt_conv2d_drop as relu_out)");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((mask_bwd_kernel<float>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const float*)dy, (const float*)relu_out, (float*)dx, n / 4, p, seed, salt, mode, hw, C);
-  else hipLaunchKernelGGL((mask_bwd_kernel<bf16_t>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)relu_out, (bf16_t*)dx, n / 4, p, seed, salt, mode, hw, C);
-  return check_launch("emrt_mask_bwd");
+  return with_train_dtype("emrt_mask_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((mask_bwd_kernel<T>), dim3(ew_grid(n / 4)), dim3(256), 0, st, (const T*)dy, (const T*)relu_out, (T*)dx, n / 4, p, seed, salt, mode, hw, C);
+    return check_launch("emrt_mask_bwd");
+  });
 }
 
 extern "C" int emrt_sigmoid_fwd(const float* x, float* y, long long n, void* stream) {
@@ -430,12 +433,12 @@ extern "C" int emrt_cast(const void* in, void* out, long long n, int direction, 
   EMRT_REQUIRE(in && out, "null pointer");
   hipStream_t st = (hipStream_t)stream;
   const int grid = ew_grid(n);
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(grid), dim3(256), 0, st, (const float*)in, (float*)out, n);
-  else if (dtype == EMRT_BF16 && direction == 0) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, st, (const float*)in, (bf16_t*)out, n);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), dim3(grid), dim3(256), 0, st, (const bf16_t*)in, (float*)out, n);
-  else if (direction == 0) hipLaunchKernelGGL((cast_kernel<float, f16_t>), dim3(grid), dim3(256), 0, st, (const float*)in, (f16_t*)out, n);
-  else hipLaunchKernelGGL((cast_kernel<f16_t, float>), dim3(grid), dim3(256), 0, st, (const f16_t*)in, (float*)out, n);
-  return check_launch("emrt_cast");
+  return with_fwd_dtype("emrt_cast", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (direction == 0) hipLaunchKernelGGL((cast_kernel<float, T>), dim3(grid), dim3(256), 0, st, (const float*)in, (T*)out, n);
+    else hipLaunchKernelGGL((cast_kernel<T, float>), dim3(grid), dim3(256), 0, st, (const T*)in, (float*)out, n);
+    return check_launch("emrt_cast");
+  });
 }
 
 extern "C" int emrt_memset(void* ptr, int value, size_t bytes, void* stream) {

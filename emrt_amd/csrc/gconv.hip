@@ -378,9 +378,7 @@ extern "C" int emrt_gconv2d(const void* in, const void* w, void* out, const floa
   a.OH = OH; a.OW = OW; a.OC = OC; a.ldout = ldout; a.out_bs = out_bs;
   a.stride = stride; a.relu = relu; a.accumulate = 0; a.Cg = C / groups; a.Og = OC / groups; a.ldres = 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == EMRT_F32) return launch_fwd<float>(a, st);
-  if (dtype == EMRT_F16) return launch_fwd<f16_t>(a, st);
-  return launch_fwd<bf16_t>(a, st);
+  return with_fwd_dtype("emrt_gconv2d", dtype, [&](auto t) { return launch_fwd<decltype(t)>(a, st); });
 }
 
 extern "C" int emrt_gconv2d_bwd(const void* x, const void* dy, const void* w, void* dx, int lddx, long long dx_bs, int accumulate, float* dw, float* dbias,
@@ -400,7 +398,7 @@ extern "C" int emrt_gconv2d_bwd(const void* x, const void* dy, const void* w, vo
     a.N = N; a.H = OH; a.W = OW; a.C = OC; a.ldin = lddy; a.in_bs = dy_bs;
     a.OH = H; a.OW = W; a.OC = C; a.ldout = lddx; a.out_bs = dx_bs;
     a.stride = stride; a.relu = 0; a.accumulate = accumulate; a.Cg = C / groups; a.Og = OC / groups; a.ldres = 0;
-    const int r = dtype == EMRT_F32 ? launch_dgrad<float>(a, st) : launch_dgrad<bf16_t>(a, st);
+    const int r = with_train_dtype("emrt_gconv2d_bwd", dtype, [&](auto t) { return launch_dgrad<decltype(t)>(a, st); });
     if (r) return r;
   }
   if (dw || dbias) {
@@ -410,7 +408,7 @@ extern "C" int emrt_gconv2d_bwd(const void* x, const void* dy, const void* w, vo
     b.N = N; b.H = H; b.W = W; b.C = C; b.ldx = ldx; b.x_bs = x_bs;
     b.OH = OH; b.OW = OW; b.OC = OC; b.lddy = lddy; b.dy_bs = dy_bs;
     b.stride = stride; b.Cg = C / groups; b.Og = OC / groups; b.rows_per_slice = 0;
-    return dtype == EMRT_F32 ? launch_wgrad<float>(b, st) : launch_wgrad<bf16_t>(b, st);
+    return with_train_dtype("emrt_gconv2d_bwd", dtype, [&](auto t) { return launch_wgrad<decltype(t)>(b, st); });
   }
   return 0;
 }

@@ -812,14 +812,13 @@ extern "C" int emrt_pack_weights(const float* master, void* packed, const long l
   EMRT_REQUIRE(master && packed && desc_dev, "null pointer");
   EMRT_REQUIRE(ndesc > 0 && total_tiles > 0 && total_tiles < 2147483647LL && total_tiles64 >= 0 && total_tiles64 < 2147483647LL, "bad descriptor table");
   hipStream_t st = (hipStream_t)stream;
-  if (bwd_only && total_tiles64 > 0) {
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((pack_bwd64_kernel<float>), dim3((unsigned)total_tiles64), dim3(256), 0, st, master, (float*)packed, desc_dev, ndesc);
-    else if (dtype == EMRT_BF16) hipLaunchKernelGGL((pack_bwd64_kernel<bf16_t>), dim3((unsigned)total_tiles64), dim3(256), 0, st, master, (bf16_t*)packed, desc_dev, ndesc);
-    else hipLaunchKernelGGL((pack_bwd64_kernel<f16_t>), dim3((unsigned)total_tiles64), dim3(256), 0, st, master, (f16_t*)packed, desc_dev, ndesc);
+  return with_fwd_dtype("emrt_pack_weights", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (bwd_only && total_tiles64 > 0) {
+      hipLaunchKernelGGL((pack_bwd64_kernel<T>), dim3((unsigned)total_tiles64), dim3(256), 0, st, master, (T*)packed, desc_dev, ndesc);
+      return check_launch("emrt_pack_weights");
+    }
+    hipLaunchKernelGGL((pack_weights_kernel<T>), dim3((unsigned)total_tiles), dim3(256), 0, st, master, (T*)packed, desc_dev, ndesc, bwd_only);
     return check_launch("emrt_pack_weights");
-  }
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((pack_weights_kernel<float>), dim3((unsigned)total_tiles), dim3(256), 0, st, master, (float*)packed, desc_dev, ndesc, bwd_only);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((pack_weights_kernel<bf16_t>), dim3((unsigned)total_tiles), dim3(256), 0, st, master, (bf16_t*)packed, desc_dev, ndesc, bwd_only);
-  else hipLaunchKernelGGL((pack_weights_kernel<f16_t>), dim3((unsigned)total_tiles), dim3(256), 0, st, master, (f16_t*)packed, desc_dev, ndesc, bwd_only);
-  return check_launch("emrt_pack_weights");
+  });
 }

@@ -1569,23 +1569,31 @@ static bool msda_mf_plan(const MsdaArgs& a, int L, MsdaMfPlan& pl, int& nbands) 
   return nbands <= 65535;
 }
 
+// The (levels, points) pairs the MSDA kernels are built for, named ONCE: f(integral_constant<int, L>, integral_constant<int, P>) launches the
+// instantiation and returns the entry point's int; any other pair is the caller's error `unsupported` under the name fn.  ONE_LEVEL = false
+// leaves (1, 4) out (the band kernels are not built for it).  A `static` local of the generic lambda f exists once per (L, P) -- and once per
+// element type when the caller is itself a template: one "LDS limit raised" flag per kernel instantiation.
+template <bool ONE_LEVEL = true, class F>
+static int with_levels_points(int L, int P, const char* fn, const char* unsupported, F&& f) {
+  if (L == 3 && P == 6) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 6>{});
+  if (L == 4 && P == 4) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
+  if (L == 3 && P == 4) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{});
+  if constexpr (ONE_LEVEL)
+    if (L == 1 && P == 4) return f(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
+  return fail(fn, unsupported);
+}
+
 static int msda_launch_mf(const MsdaArgs& a, int L, int P, const MsdaMfPlan& pl, int nbands, hipStream_t st) {
   size_t lds = (size_t)2 * pl.npix_cap * MSDA_MF_PITCH * 4 + 2 * 32 * MSDA_MF_GP * 2 + 64 * 4;
   const size_t epi = (size_t)pl.npix_cap * 33 * 4;          // the epilogue's fp32 image starts at the first weight tile
   if (lds < epi) lds = epi;
-#define MSDA_MF_CASE(LL, PP)                                                                                  \
-  if (L == LL && P == PP) {                                                                                   \
-    static bool attr = false;                                                                                 \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_value_mfma_kernel<LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; } \
-    hipLaunchKernelGGL((msda_bwd_value_mfma_kernel<LL, PP>), dim3(a.B * a.M, nbands), dim3(512), lds, st, a, pl); \
-    return check_launch("emrt_msda_bwd(matrix-product scatter)");                                             \
-  }
-  MSDA_MF_CASE(3, 6)
-  MSDA_MF_CASE(4, 4)
-  MSDA_MF_CASE(3, 4)
-  MSDA_MF_CASE(1, 4)
-#undef MSDA_MF_CASE
-  return fail("emrt_msda_bwd", "unsupported (levels, points) for the matrix-product scatter");
+  return with_levels_points(L, P, "emrt_msda_bwd", "unsupported (levels, points) for the matrix-product scatter", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_value_mfma_kernel<LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
+    hipLaunchKernelGGL((msda_bwd_value_mfma_kernel<LL, PP>), dim3(a.B * a.M, nbands), dim3(512), lds, st, a, pl);
+    return check_launch("emrt_msda_bwd(matrix-product scatter)");
+  });
 }
 
 // pixels of a scatter range: (npix + 2 guard) * 33 * 4 B of slab + 20 480 B of sample records must fit the 160 KiB LDS
@@ -1732,19 +1740,13 @@ template <class T>
 static int msda_launch(const MsdaArgs& a, int L, int P, int mode /*0 fwd, 1 bwd atomic, 2 bwd grads only*/, hipStream_t st) {
   const long long pairs = (long long)a.B * a.Lq * a.M;
   const unsigned grid = (unsigned)((pairs + 63) / 64);
-#define MSDA_CASE(LL, PP)                                                                                     \
-  if (L == LL && P == PP) {                                                                                   \
-    if (mode == 0) hipLaunchKernelGGL((msda_fwd_kernel<T, LL, PP>), dim3(grid), dim3(256), 0, st, a);          \
-    else if (mode == 1) hipLaunchKernelGGL((msda_bwd_kernel<T, LL, PP, true>), dim3(grid), dim3(256), 0, st, a); \
-    else hipLaunchKernelGGL((msda_bwd_kernel<T, LL, PP, false>), dim3(grid), dim3(256), 0, st, a);             \
-    return check_launch(mode ? "emrt_msda_bwd" : "emrt_msda_fwd");                                            \
-  }
-  MSDA_CASE(3, 6)
-  MSDA_CASE(4, 4)
-  MSDA_CASE(3, 4)
-  MSDA_CASE(1, 4)
-#undef MSDA_CASE
-  return fail("emrt_msda", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)");
+  return with_levels_points(L, P, "emrt_msda", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    if (mode == 0) hipLaunchKernelGGL((msda_fwd_kernel<T, LL, PP>), dim3(grid), dim3(256), 0, st, a);
+    else if (mode == 1) hipLaunchKernelGGL((msda_bwd_kernel<T, LL, PP, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((msda_bwd_kernel<T, LL, PP, false>), dim3(grid), dim3(256), 0, st, a);
+    return check_launch(mode ? "emrt_msda_bwd" : "emrt_msda_fwd");
+  });
 }
 
 // forward only (the one MSDA kernel fp16 inference needs)
@@ -1752,52 +1754,35 @@ template <class T>
 static int msda_launch_fwd(const MsdaArgs& a, int L, int P, hipStream_t st) {
   const long long pairs = (long long)a.B * a.Lq * a.M;
   const unsigned grid = (unsigned)((pairs + 63) / 64);
-#define MSDA_FWD_CASE(LL, PP)                                                                                 \
-  if (L == LL && P == PP) {                                                                                   \
-    hipLaunchKernelGGL((msda_fwd_kernel<T, LL, PP>), dim3(grid), dim3(256), 0, st, a);                        \
-    return check_launch("emrt_msda_fwd");                                                                     \
-  }
-  MSDA_FWD_CASE(3, 6)
-  MSDA_FWD_CASE(4, 4)
-  MSDA_FWD_CASE(3, 4)
-  MSDA_FWD_CASE(1, 4)
-#undef MSDA_FWD_CASE
-  return fail("emrt_msda_fwd", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)");
+  return with_levels_points(L, P, "emrt_msda_fwd", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    hipLaunchKernelGGL((msda_fwd_kernel<T, LL, PP>), dim3(grid), dim3(256), 0, st, a);
+    return check_launch("emrt_msda_fwd");
+  });
 }
 
 template <class T>
 static int msda_launch_fwd_lds(const MsdaArgs& a, int L, int P, int chunks, int qpb, int guard, size_t slab, hipStream_t st) {
   int threads = g_tune.msda_fwd_threads;
   if (threads < 64 || threads > 1024 || (threads & 63)) threads = 1024;
-#define MSDA_FWD_LDS_CASE(LL, PP)                                                                                         \
-  if (L == LL && P == PP) {                                                                                             \
-    static bool attr = false;                                                                                           \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_fwd_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; } \
-    hipLaunchKernelGGL((msda_fwd_lds_kernel<T, LL, PP>), dim3(a.B * a.M * chunks), dim3(threads), slab, st, a, qpb, chunks, guard, g_tune.msda_fwd_probe); \
-    return check_launch("emrt_msda_fwd(lds)");                                                                          \
-  }
-  MSDA_FWD_LDS_CASE(3, 6)
-  MSDA_FWD_LDS_CASE(4, 4)
-  MSDA_FWD_LDS_CASE(3, 4)
-  MSDA_FWD_LDS_CASE(1, 4)
-#undef MSDA_FWD_LDS_CASE
-  return fail("emrt_msda_fwd", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)");
+  return with_levels_points(L, P, "emrt_msda_fwd", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_fwd_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
+    hipLaunchKernelGGL((msda_fwd_lds_kernel<T, LL, PP>), dim3(a.B * a.M * chunks), dim3(threads), slab, st, a, qpb, chunks, guard, g_tune.msda_fwd_probe);
+    return check_launch("emrt_msda_fwd(lds)");
+  });
 }
 
 template <class T>
 static int msda_launch_fwd_band(const MsdaArgs& a, int L, int P, int NB, int halo, int guard, size_t slab, hipStream_t st) {
-#define MSDA_FWD_BAND_CASE(LL, PP)                                                                                        \
-  if (L == LL && P == PP) {                                                                                             \
-    static bool attr = false;                                                                                           \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_fwd_band_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; } \
-    hipLaunchKernelGGL((msda_fwd_band_kernel<T, LL, PP>), dim3(a.B * a.M * NB), dim3(1024), slab, st, a, NB, halo, guard); \
-    return check_launch("emrt_msda_fwd(band)");                                                                         \
-  }
-  MSDA_FWD_BAND_CASE(3, 6)
-  MSDA_FWD_BAND_CASE(4, 4)
-  MSDA_FWD_BAND_CASE(3, 4)
-#undef MSDA_FWD_BAND_CASE
-  return fail("emrt_msda_fwd", "unsupported (levels, points) for the band kernel");
+  return with_levels_points<false>(L, P, "emrt_msda_fwd", "unsupported (levels, points) for the band kernel", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_fwd_band_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
+    hipLaunchKernelGGL((msda_fwd_band_kernel<T, LL, PP>), dim3(a.B * a.M * NB), dim3(1024), slab, st, a, NB, halo, guard);
+    return check_launch("emrt_msda_fwd(band)");
+  });
 }
 
 // Band plan for a pyramid whose whole slab does not fit: the number of bands NB (every level's height divisible by it) and the halo
@@ -1828,52 +1813,35 @@ static bool msda_band_plan(const MsdaArgs& a, int L, int bm, int guard, int& NB_
 
 template <class T>
 static int msda_launch_bwd_grad_lds(const MsdaArgs& a, int L, int P, int chunks, int qpb, int guard, size_t slab, hipStream_t st) {
-#define MSDA_BWD_GLDS_CASE(LL, PP)                                                                                        \
-  if (L == LL && P == PP) {                                                                                             \
-    static bool attr = false;                                                                                           \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; } \
-    hipLaunchKernelGGL((msda_bwd_lds_kernel<T, LL, PP>), dim3(a.B * a.M * chunks), dim3(1024), slab, st, a, qpb, chunks, guard); \
-    return check_launch("emrt_msda_bwd(lds gradients)");                                                                \
-  }
-  MSDA_BWD_GLDS_CASE(3, 6)
-  MSDA_BWD_GLDS_CASE(4, 4)
-  MSDA_BWD_GLDS_CASE(3, 4)
-  MSDA_BWD_GLDS_CASE(1, 4)
-#undef MSDA_BWD_GLDS_CASE
-  return fail("emrt_msda_bwd", "unsupported (levels, points)");
+  return with_levels_points(L, P, "emrt_msda_bwd", "unsupported (levels, points)", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
+    hipLaunchKernelGGL((msda_bwd_lds_kernel<T, LL, PP>), dim3(a.B * a.M * chunks), dim3(1024), slab, st, a, qpb, chunks, guard);
+    return check_launch("emrt_msda_bwd(lds gradients)");
+  });
 }
 
 template <class T>
 static int msda_launch_bwd_grad_band(const MsdaArgs& a, int L, int P, int NB, int halo, int guard, size_t slab, hipStream_t st) {
-#define MSDA_BWD_BAND_CASE(LL, PP)                                                                                        \
-  if (L == LL && P == PP) {                                                                                             \
-    static bool attr = false;                                                                                           \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_lds_kernel<T, LL, PP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; } \
-    hipLaunchKernelGGL((msda_bwd_lds_kernel<T, LL, PP, true>), dim3(a.B * a.M * NB), dim3(1024), slab, st, a, NB, halo, guard); \
-    return check_launch("emrt_msda_bwd(band gradients)");                                                               \
-  }
-  MSDA_BWD_BAND_CASE(3, 6)
-  MSDA_BWD_BAND_CASE(4, 4)
-  MSDA_BWD_BAND_CASE(3, 4)
-#undef MSDA_BWD_BAND_CASE
-  return fail("emrt_msda_bwd", "unsupported (levels, points) for the band kernel");
+  return with_levels_points<false>(L, P, "emrt_msda_bwd", "unsupported (levels, points) for the band kernel", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_lds_kernel<T, LL, PP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
+    hipLaunchKernelGGL((msda_bwd_lds_kernel<T, LL, PP, true>), dim3(a.B * a.M * NB), dim3(1024), slab, st, a, NB, halo, guard);
+    return check_launch("emrt_msda_bwd(band gradients)");
+  });
 }
 
 template <class T>
 static int msda_launch_lds(const MsdaArgs& a, int L, int P, int ngroups, size_t lds, hipStream_t st) {
-#define MSDA_LDS_CASE(LL, PP)                                                                                 \
-  if (L == LL && P == PP) {                                                                                   \
-    static bool attr = false;                                                                                 \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_value_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; } \
-    hipLaunchKernelGGL((msda_bwd_value_lds_kernel<T, LL, PP>), dim3(a.B * a.M, ngroups), dim3(1024), lds, st, a, ((g_tune.msda_fwd_probe >> 4) & 127) | (g_tune.msda_scatter_merge ? 128 : 0)); \
-    return check_launch("emrt_msda_bwd(lds scatter)");                                                        \
-  }
-  MSDA_LDS_CASE(3, 6)
-  MSDA_LDS_CASE(4, 4)
-  MSDA_LDS_CASE(3, 4)
-  MSDA_LDS_CASE(1, 4)
-#undef MSDA_LDS_CASE
-  return fail("emrt_msda_bwd", "unsupported (levels, points) for the LDS scatter");
+  return with_levels_points(L, P, "emrt_msda_bwd", "unsupported (levels, points) for the LDS scatter", [&](auto ll, auto pp) {
+    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_value_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
+    hipLaunchKernelGGL((msda_bwd_value_lds_kernel<T, LL, PP>), dim3(a.B * a.M, ngroups), dim3(1024), lds, st, a, ((g_tune.msda_fwd_probe >> 4) & 127) | (g_tune.msda_scatter_merge ? 128 : 0));
+    return check_launch("emrt_msda_bwd(lds scatter)");
+  });
 }
 
 static int msda_fill(MsdaArgs& a, const int* shapes_hw, int L, int Lv) {
@@ -1912,26 +1880,30 @@ extern "C" int emrt_msda_fwd(const void* value, int ldv, long long v_bs, const f
   for (int l = 0; l < L; ++l) wmax = a.w[l] > wmax ? a.w[l] : wmax;
   const int guard = wmax + 2;                                  // zero rows on both sides of the staged slab (msda_fwd_lds_kernel)
   const size_t slab = (size_t)(Lv + 2 * guard) * MSDA_FWD_PITCH;
-  if (dtype != EMRT_F32 && slab <= 159 * 1024 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs && !g_tune.msda_fwd_global) {
-    // one block per CU (the slab takes most of its LDS): as close to 256 blocks as whole chunks of >= 128 queries allow
-    int chunks = (256 + B * M / 2) / (B * M);
-    if (g_tune.msda_fwd_chunks > 0) chunks = g_tune.msda_fwd_chunks;
-    if (chunks > (Lq + 127) / 128) chunks = (Lq + 127) / 128;
-    if (chunks < 1) chunks = 1;
-    const int qpb = (Lq + chunks - 1) / chunks;
-    chunks = (Lq + qpb - 1) / qpb;
-    return dtype == EMRT_BF16 ? msda_launch_fwd_lds<bf16_t>(a, L, P, chunks, qpb, guard, slab, st) : msda_launch_fwd_lds<f16_t>(a, L, P, chunks, qpb, guard, slab, st);
-  }
-  if (dtype != EMRT_F32 && slab > 159 * 1024 && Lq == Lv && L >= 2 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs &&
-      !g_tune.msda_fwd_global) {
-    // self-attention over a pyramid too large for one slab: row bands (msda_fwd_band_kernel)
-    int NB = 0, halo = 0;
-    size_t bslab = 0;
-    if (msda_band_plan(a, L, B * M, guard, NB, halo, bslab))
-      return dtype == EMRT_BF16 ? msda_launch_fwd_band<bf16_t>(a, L, P, NB, halo, guard, bslab, st) : msda_launch_fwd_band<f16_t>(a, L, P, NB, halo, guard, bslab, st);
-  }
-  if (dtype == EMRT_F16) return msda_launch_fwd<f16_t>(a, L, P, st);
-  return dtype == EMRT_F32 ? msda_launch_fwd<float>(a, L, P, st) : msda_launch_fwd<bf16_t>(a, L, P, st);
+  return with_fwd_dtype("emrt_msda_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (sizeof(T) == 2) {      // the LDS-staged kernels are built for the 16-bit types only
+      if (slab <= 159 * 1024 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs && !g_tune.msda_fwd_global) {
+        // one block per CU (the slab takes most of its LDS): as close to 256 blocks as whole chunks of >= 128 queries allow
+        int chunks = (256 + B * M / 2) / (B * M);
+        if (g_tune.msda_fwd_chunks > 0) chunks = g_tune.msda_fwd_chunks;
+        if (chunks > (Lq + 127) / 128) chunks = (Lq + 127) / 128;
+        if (chunks < 1) chunks = 1;
+        const int qpb = (Lq + chunks - 1) / chunks;
+        chunks = (Lq + qpb - 1) / qpb;
+        return msda_launch_fwd_lds<T>(a, L, P, chunks, qpb, guard, slab, st);
+      }
+      if (slab > 159 * 1024 && Lq == Lv && L >= 2 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs &&
+          !g_tune.msda_fwd_global) {
+        // self-attention over a pyramid too large for one slab: row bands (msda_fwd_band_kernel)
+        int NB = 0, halo = 0;
+        size_t bslab = 0;
+        if (msda_band_plan(a, L, B * M, guard, NB, halo, bslab))
+          return msda_launch_fwd_band<T>(a, L, P, NB, halo, guard, bslab, st);
+      }
+    }
+    return msda_launch_fwd<T>(a, L, P, st);
+  });
 }
 
 // dvalue: when emrt_msda_bwd_uses_lds(shapes) it is [B][Lv][M*D] in the COMPUTE dtype and fully overwritten (workspace
@@ -1988,12 +1960,15 @@ extern "C" int emrt_msda_bwd(const void* value, int ldv, long long v_bs, const f
       a.gmax_n = NB;
       rc = msda_launch_bwd_grad_band<bf16_t>(a, L, P, NB, halo, guard, bslab, st);
     } else {
-      rc = dtype == EMRT_F32 ? msda_launch<float>(a, L, P, 2, st) : msda_launch<bf16_t>(a, L, P, 2, st);
+      rc = with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) { return msda_launch<decltype(t)>(a, L, P, 2, st); });
       if (!rc && Lq >= 1024 && M <= 8 && 256 % (M * 4) == 0) {      // long scans only: the extra launch costs ~3 us
         a.gmax = (float*)workspace + (size_t)B * Lq * M * L * P;
         a.gmax_n = (Lq + 63) / 64;
-        if (dtype == EMRT_F32) hipLaunchKernelGGL((msda_absmax_kernel<float>), dim3(B * a.gmax_n), dim3(256), 0, st, (const float*)dout, Lq, M, a.gmax_n, a.gmax);
-        else hipLaunchKernelGGL((msda_absmax_kernel<bf16_t>), dim3(B * a.gmax_n), dim3(256), 0, st, (const bf16_t*)dout, Lq, M, a.gmax_n, a.gmax);
+        rc = with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) {
+          using T = decltype(t);
+          hipLaunchKernelGGL((msda_absmax_kernel<T>), dim3(B * a.gmax_n), dim3(256), 0, st, (const T*)dout, Lq, M, a.gmax_n, a.gmax);
+          return 0;
+        });
       }
     }
     if (rc) return rc;
@@ -2007,11 +1982,11 @@ extern "C" int emrt_msda_bwd(const void* value, int ldv, long long v_bs, const f
     a.g_npix_max = (npix_max + 2 * guard + 3) & ~3;          // slab + both guard bands; keeps the records 16-byte aligned
     const size_t lds = (size_t)a.g_npix_max * MSDA_SLAB_PITCH * sizeof(int) + 32 * 32 * (sizeof(float4) + sizeof(int));
     EMRT_REQUIRE(a.f_n == 0 || a.gmax_n > 0, "internal: query-split scatter planned without the max |dout| partials");
-    rc = dtype == EMRT_F32 ? msda_launch_lds<float>(a, L, P, ng, lds, st) : msda_launch_lds<bf16_t>(a, L, P, ng, lds, st);
+    rc = with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) { return msda_launch_lds<decltype(t)>(a, L, P, ng, lds, st); });
     if (rc || a.f_n == 0) return rc;
     hipLaunchKernelGGL((msda_bwd_value_finalize_kernel<bf16_t>), dim3(B * M, a.f_n, 8), dim3(256), 0, st, a);
     return check_launch("emrt_msda_bwd(scatter finalize)");
   }
   a.dvalue = (float*)dvalue;
-  return dtype == EMRT_F32 ? msda_launch<float>(a, L, P, 1, st) : msda_launch<bf16_t>(a, L, P, 1, st);
+  return with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) { return msda_launch<decltype(t)>(a, L, P, 1, st); });
 }

@@ -1227,16 +1227,6 @@ __global__ __launch_bounds__(TPB) void ln_bwd_kernel(const T* __restrict__ z, co
 // ------------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------------
-#define DT_SWITCH(dtype, EXPR_F32, EXPR_BF16) \
-  do {                                        \
-    if ((dtype) == EMRT_F32) { EXPR_F32; } else { EXPR_BF16; } \
-  } while (0)
-// forward (inference-capable) entry points also take fp16
-#define DT_SWITCH3(dtype, EXPR_F32, EXPR_BF16, EXPR_F16) \
-  do {                                                   \
-    if ((dtype) == EMRT_F32) { EXPR_F32; } else if ((dtype) == EMRT_BF16) { EXPR_BF16; } else { EXPR_F16; } \
-  } while (0)
-
 extern "C" size_t emrt_colreduce_workspace_bytes(long long M, int C) {
   int tx, gx, gy;
   col_reduce_geometry(M, C, tx, gx, gy);
@@ -1270,10 +1260,11 @@ extern "C" int emrt_bn_stats(const void* x, int ldx, long long M, int C, double*
   int tx, gx, gy;
   col_reduce_geometry(M, C, tx, gx, gy);
   hipStream_t st = (hipStream_t)stream;
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((col_reduce_kernel<float, 0>), dim3(gx, gy), dim3(256), 0, st, (const float*)x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr, M, C, tx, nullptr, M, 0LL, sums, nullptr),
-            hipLaunchKernelGGL((col_reduce_kernel<bf16_t, 0>), dim3(gx, gy), dim3(256), 0, st, (const bf16_t*)x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr, M, C, tx, nullptr, M, 0LL, sums, nullptr));
-  return check_launch("emrt_bn_stats");
+  return with_train_dtype("emrt_bn_stats", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((col_reduce_kernel<T, 0>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr, M, C, tx, nullptr, M, 0LL, sums, nullptr);
+    return check_launch("emrt_bn_stats");
+  });
 }
 
 // y = [relu](BN(x) [+ res]).  sums != null: training -- statistics = sums / count (count may be the global row count after a
@@ -1291,11 +1282,11 @@ extern "C" int emrt_bn_apply(const void* x, int ldx, const void* res, int ldres,
   const double inv_count = sums ? 1.0 / count : 0.0;
   BnOperand none;
   memset(&none, 0, sizeof(none));
-  DT_SWITCH3(dtype,
-            hipLaunchKernelGGL((bn_apply_kernel<float>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const float*)x, ldx, (const float*)res, ldres, (float*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, none),
-            hipLaunchKernelGGL((bn_apply_kernel<bf16_t>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const bf16_t*)x, ldx, (const bf16_t*)res, ldres, (bf16_t*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, none),
-            hipLaunchKernelGGL((bn_apply_kernel<f16_t>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const f16_t*)x, ldx, (const f16_t*)res, ldres, (f16_t*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, none));
-  return check_launch("emrt_bn_apply");
+  return with_fwd_dtype("emrt_bn_apply", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const T*)x, ldx, (const T*)res, ldres, (T*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, none);
+    return check_launch("emrt_bn_apply");
+  });
 }
 
 // out = [relu](BN_train(x) + BN_train(res_raw)): the join at the end of the FIRST block of a ResNet stage, where the shortcut is
@@ -1320,10 +1311,11 @@ extern "C" int emrt_bn_apply_join(const void* x, int ldx, const void* res_raw, i
   hipStream_t st = (hipStream_t)stream;
   const double inv_count = 1.0 / count;
   const size_t lds = (size_t)4 * C * sizeof(float);
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((bn_apply_kernel<float, true>), dim3(grid), dim3(threads), lds, st, (const float*)x, ldx, (const float*)res_raw, ldres, (float*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, r),
-            hipLaunchKernelGGL((bn_apply_kernel<bf16_t, true>), dim3(grid), dim3(threads), lds, st, (const bf16_t*)x, ldx, (const bf16_t*)res_raw, ldres, (bf16_t*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, r));
-  return check_launch("emrt_bn_apply_join");
+  return with_train_dtype("emrt_bn_apply_join", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_apply_kernel<T, true>), dim3(grid), dim3(threads), lds, st, (const T*)x, ldx, (const T*)res_raw, ldres, (T*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, r);
+    return check_launch("emrt_bn_apply_join");
+  });
 }
 
 // Eval-mode BatchNorm as a per-channel affine map, for every BatchNorm of a model in one launch: block i handles row i of
@@ -1366,16 +1358,15 @@ extern "C" int emrt_bn_bwd_reduce(const void* x, int ldx, const void* dy, int ld
   int tx, gx, gy;
   col_reduce_geometry(M, C, tx, gx, gy);
   hipStream_t st = (hipStream_t)stream;
-  if (mask_beta) {
-    DT_SWITCH(dtype,
-              hipLaunchKernelGGL((col_reduce_kernel<float, 3>), dim3(gx, gy), dim3(256), 0, st, (const float*)x, ldx, (const float*)dy, lddy, (const float*)nullptr, 0, mean, invstd, M, C, tx, nullptr, M, 0LL, sums, nullptr, mask_gamma, mask_beta),
-              hipLaunchKernelGGL((col_reduce_kernel<bf16_t, 3>), dim3(gx, gy), dim3(256), 0, st, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, (const bf16_t*)nullptr, 0, mean, invstd, M, C, tx, nullptr, M, 0LL, sums, nullptr, mask_gamma, mask_beta));
+  return with_train_dtype("emrt_bn_bwd_reduce", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (mask_beta) {
+      hipLaunchKernelGGL((col_reduce_kernel<T, 3>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)nullptr, 0, mean, invstd, M, C, tx, nullptr, M, 0LL, sums, nullptr, mask_gamma, mask_beta);
+      return check_launch("emrt_bn_bwd_reduce");
+    }
+    hipLaunchKernelGGL((col_reduce_kernel<T, 1>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)y, ldy, mean, invstd, M, C, tx, nullptr, M, 0LL, sums, nullptr);
     return check_launch("emrt_bn_bwd_reduce");
-  }
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((col_reduce_kernel<float, 1>), dim3(gx, gy), dim3(256), 0, st, (const float*)x, ldx, (const float*)dy, lddy, (const float*)y, ldy, mean, invstd, M, C, tx, nullptr, M, 0LL, sums, nullptr),
-            hipLaunchKernelGGL((col_reduce_kernel<bf16_t, 1>), dim3(gx, gy), dim3(256), 0, st, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, (const bf16_t*)y, ldy, mean, invstd, M, C, tx, nullptr, M, 0LL, sums, nullptr));
-  return check_launch("emrt_bn_bwd_reduce");
+  });
 }
 
 // BN backward step 2: dx (and optional dres = masked dy); dgamma += , dbeta += from `local_sums` when given (SyncBN: the
@@ -1394,16 +1385,15 @@ extern "C" int emrt_bn_bwd_dx(const void* x, int ldx, const void* dy, int lddy, 
   int threads, rpp, grid;
   EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
   hipStream_t st = (hipStream_t)stream;
-  if (mask_beta) {
-    DT_SWITCH(dtype,
-              hipLaunchKernelGGL((bn_bwd_dx_kernel<float, true>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const float*)x, ldx, (const float*)dy, lddy, (const float*)nullptr, 0, (float*)dx, lddx, (float*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, nullptr, 0, mask_beta),
-              hipLaunchKernelGGL((bn_bwd_dx_kernel<bf16_t, true>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, (const bf16_t*)nullptr, 0, (bf16_t*)dx, lddx, (bf16_t*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, nullptr, 0, mask_beta));
+  return with_train_dtype("emrt_bn_bwd_dx", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (mask_beta) {
+      hipLaunchKernelGGL((bn_bwd_dx_kernel<T, true>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)nullptr, 0, (T*)dx, lddx, (T*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, nullptr, 0, mask_beta);
+      return check_launch("emrt_bn_bwd_dx");
+    }
+    hipLaunchKernelGGL((bn_bwd_dx_kernel<T>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)y, ldy, (T*)dx, lddx, (T*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, beta_y_moments, sums_vs_x, mask_beta);
     return check_launch("emrt_bn_bwd_dx");
-  }
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((bn_bwd_dx_kernel<float>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const float*)x, ldx, (const float*)dy, lddy, (const float*)y, ldy, (float*)dx, lddx, (float*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, beta_y_moments, sums_vs_x, mask_beta),
-            hipLaunchKernelGGL((bn_bwd_dx_kernel<bf16_t>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, (const bf16_t*)y, ldy, (bf16_t*)dx, lddx, (bf16_t*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, beta_y_moments, sums_vs_x, mask_beta));
-  return check_launch("emrt_bn_bwd_dx");
+  });
 }
 
 // narrow matrices (C not a multiple of 4: class logits, reference-point coordinates): one block per channel
@@ -1430,22 +1420,22 @@ extern "C" int emrt_colsum_acc(const void* x, int ldx, long long rows_per_batch,
   EMRT_REQUIRE_TRAIN_DTYPE(dtype);
   EMRT_REQUIRE(rows_per_batch > 0, "bad batch geometry");
   EMRT_REQUIRE(x && dbias && workspace, "null pointer");
-  if (C % 4 != 0 || ldx % 4 != 0 || x_bs % 4 != 0) {
-    hipStream_t st0 = (hipStream_t)stream;
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((colsum_scalar_kernel<float>), dim3(C), dim3(256), 0, st0, (const float*)x, ldx, rows_per_batch, x_bs, M, dbias);
-    else hipLaunchKernelGGL((colsum_scalar_kernel<bf16_t>), dim3(C), dim3(256), 0, st0, (const bf16_t*)x, ldx, rows_per_batch, x_bs, M, dbias);
-    return check_launch("emrt_colsum_acc(scalar)");
-  }
-  int tx, gx, gy;
-  col_reduce_geometry(M, C, tx, gx, gy);
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace;
-  const bool direct = g_tune.ln_atomic != 0;       // developer knob shared with emrt_layernorm_bwd: 0 = partials + finalize launch
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((col_reduce_kernel<float, 2>), dim3(gx, gy), dim3(256), 0, st, (const float*)x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr, M, C, tx, partial, rows_per_batch, x_bs, nullptr, direct ? dbias : nullptr),
-            hipLaunchKernelGGL((col_reduce_kernel<bf16_t, 2>), dim3(gx, gy), dim3(256), 0, st, (const bf16_t*)x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr, M, C, tx, partial, rows_per_batch, x_bs, nullptr, direct ? dbias : nullptr));
-  if (!direct) hipLaunchKernelGGL(partials_acc_kernel, dim3((C + 31) / 32), dim3(256), 0, st, partial, gx, C, (float*)nullptr, dbias);   // slot 0 only
-  return check_launch("emrt_colsum_acc");
+  return with_train_dtype("emrt_colsum_acc", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C % 4 != 0 || ldx % 4 != 0 || x_bs % 4 != 0) {
+      hipStream_t st0 = (hipStream_t)stream;
+      hipLaunchKernelGGL((colsum_scalar_kernel<T>), dim3(C), dim3(256), 0, st0, (const T*)x, ldx, rows_per_batch, x_bs, M, dbias);
+      return check_launch("emrt_colsum_acc(scalar)");
+    }
+    int tx, gx, gy;
+    col_reduce_geometry(M, C, tx, gx, gy);
+    hipStream_t st = (hipStream_t)stream;
+    float* partial = (float*)workspace;
+    const bool direct = g_tune.ln_atomic != 0;       // developer knob shared with emrt_layernorm_bwd: 0 = partials + finalize launch
+    hipLaunchKernelGGL((col_reduce_kernel<T, 2>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, ldx, nullptr, 0, nullptr, 0, nullptr, nullptr, M, C, tx, partial, rows_per_batch, x_bs, nullptr, direct ? dbias : nullptr);
+    if (!direct) hipLaunchKernelGGL(partials_acc_kernel, dim3((C + 31) / 32), dim3(256), 0, st, partial, gx, C, (float*)nullptr, dbias);   // slot 0 only
+    return check_launch("emrt_colsum_acc");
+  });
 }
 
 // dst[l][c] += sum over the T tensors, the B batch elements and the tokens of level l of x_t[b][tok][c]: the gradient of the level embedding
@@ -1519,9 +1509,11 @@ extern "C" int emrt_colsum_levels_multi(const void* const* xs, int T, const int*
   if (gx > 64) gx = 64;
   const int gz = T * B >= 8 ? 4 : 1;            // the (tensor, batch) pairs over 4 blocks: <= 64 x L x 4 blocks, each ending in C fp32 atomics
   hipStream_t st = (hipStream_t)stream;
-  DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_levels_kernel<float>), dim3(gx, L, gz), dim3(256), 0, st, a),
-            hipLaunchKernelGGL((colsum_levels_kernel<bf16_t>), dim3(gx, L, gz), dim3(256), 0, st, a));
-  return check_launch("emrt_colsum_levels_multi");
+  return with_train_dtype("emrt_colsum_levels_multi", dtype, [&](auto t) {
+    using E = decltype(t);
+    hipLaunchKernelGGL((colsum_levels_kernel<E>), dim3(gx, L, gz), dim3(256), 0, st, a);
+    return check_launch("emrt_colsum_levels_multi");
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1713,9 +1705,11 @@ extern "C" int emrt_bn_group_apply(const EmrtBnGroupDesc* descs, int n, int dtyp
   int cmax = 0;
   for (int i = 0; i < n; ++i) cmax = descs[i].C > cmax ? descs[i].C : cmax;
   hipStream_t st = (hipStream_t)stream;
-  DT_SWITCH(dtype, hipLaunchKernelGGL((bn_group_apply_kernel<float>), dim3(g.first[n]), dim3(256), 2 * cmax * sizeof(float), st, g),
-            hipLaunchKernelGGL((bn_group_apply_kernel<bf16_t>), dim3(g.first[n]), dim3(256), 2 * cmax * sizeof(float), st, g));
-  return check_launch("emrt_bn_group_apply");
+  return with_train_dtype("emrt_bn_group_apply", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_group_apply_kernel<T>), dim3(g.first[n]), dim3(256), 2 * cmax * sizeof(float), st, g);
+    return check_launch("emrt_bn_group_apply");
+  });
 }
 
 // both backward passes (reduce, then dx: two launches); `sums` of every problem must be ZERO on entry
@@ -1727,11 +1721,12 @@ extern "C" int emrt_bn_group_bwd(const EmrtBnGroupDesc* descs, int n, int dtype,
   int cmax = 0;
   for (int i = 0; i < n; ++i) cmax = descs[i].C > cmax ? descs[i].C : cmax;
   hipStream_t st = (hipStream_t)stream;
-  DT_SWITCH(dtype, hipLaunchKernelGGL((bn_group_bwd_reduce_kernel<float>), dim3(g.first[n]), dim3(256), 0, st, g),
-            hipLaunchKernelGGL((bn_group_bwd_reduce_kernel<bf16_t>), dim3(g.first[n]), dim3(256), 0, st, g));
-  DT_SWITCH(dtype, hipLaunchKernelGGL((bn_group_bwd_dx_kernel<float>), dim3(g.first[n]), dim3(256), 4 * cmax * sizeof(float), st, g),
-            hipLaunchKernelGGL((bn_group_bwd_dx_kernel<bf16_t>), dim3(g.first[n]), dim3(256), 4 * cmax * sizeof(float), st, g));
-  return check_launch("emrt_bn_group_bwd");
+  return with_train_dtype("emrt_bn_group_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_group_bwd_reduce_kernel<T>), dim3(g.first[n]), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((bn_group_bwd_dx_kernel<T>), dim3(g.first[n]), dim3(256), 4 * cmax * sizeof(float), st, g);
+    return check_launch("emrt_bn_group_bwd");
+  });
 }
 
 // one block per (image, group) when the slice is small enough for two cheap passes and the group is 4..256 channels wide
@@ -1758,24 +1753,18 @@ extern "C" int emrt_groupnorm_fwd(const void* x, int ldx, long long x_bs, const 
   EMRT_REQUIRE(C % 4 == 0 && (C / 4) <= 256 && 256 % (C / 4) == 0 && G > 0 && G <= 256 && C % G == 0 && (C / G) % 4 == 0, "unsupported C/G");
   EMRT_REQUIRE(ldx % 4 == 0 && ldout % 4 == 0 && x_bs % 4 == 0 && out_bs % 4 == 0, "strides must be multiples of 4");
   hipStream_t st = (hipStream_t)stream;
-  if (gn_use_fused(HW, C, G)) {
-    DT_SWITCH3(dtype,
-              hipLaunchKernelGGL((gn_fused_fwd_kernel<float>), dim3(N * G), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)res, ldres, res_bs, (float*)out, ldout, out_bs, gamma, beta, mean, rstd, HW, C, G, eps, gelu),
-              hipLaunchKernelGGL((gn_fused_fwd_kernel<bf16_t>), dim3(N * G), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)res, ldres, res_bs, (bf16_t*)out, ldout, out_bs, gamma, beta, mean, rstd, HW, C, G, eps, gelu),
-              hipLaunchKernelGGL((gn_fused_fwd_kernel<f16_t>), dim3(N * G), dim3(256), 0, st, (const f16_t*)x, ldx, x_bs, (const f16_t*)res, ldres, res_bs, (f16_t*)out, ldout, out_bs, gamma, beta, mean, rstd, HW, C, G, eps, gelu));
+  return with_fwd_dtype("emrt_groupnorm_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (gn_use_fused(HW, C, G)) {
+      hipLaunchKernelGGL((gn_fused_fwd_kernel<T>), dim3(N * G), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)res, ldres, res_bs, (T*)out, ldout, out_bs, gamma, beta, mean, rstd, HW, C, G, eps, gelu);
+      return check_launch("emrt_groupnorm_fwd");
+    }
+    int ppb;
+    const int blocks = gn_geom(HW, C, &ppb);
+    hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(blocks, N), dim3(256), 0, st, (const T*)x, ldx, x_bs, workspace, HW, C, G, ppb);
+    hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(blocks, N), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)res, ldres, res_bs, (T*)out, ldout, out_bs, gamma, beta, workspace, mean, rstd, HW, C, G, eps, gelu, ppb);
     return check_launch("emrt_groupnorm_fwd");
-  }
-  int ppb;
-  const int blocks = gn_geom(HW, C, &ppb);
-  DT_SWITCH3(dtype,
-            hipLaunchKernelGGL((gn_stats_kernel<float>), dim3(blocks, N), dim3(256), 0, st, (const float*)x, ldx, x_bs, workspace, HW, C, G, ppb),
-            hipLaunchKernelGGL((gn_stats_kernel<bf16_t>), dim3(blocks, N), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, workspace, HW, C, G, ppb),
-            hipLaunchKernelGGL((gn_stats_kernel<f16_t>), dim3(blocks, N), dim3(256), 0, st, (const f16_t*)x, ldx, x_bs, workspace, HW, C, G, ppb));
-  DT_SWITCH3(dtype,
-            hipLaunchKernelGGL((gn_apply_kernel<float>), dim3(blocks, N), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)res, ldres, res_bs, (float*)out, ldout, out_bs, gamma, beta, workspace, mean, rstd, HW, C, G, eps, gelu, ppb),
-            hipLaunchKernelGGL((gn_apply_kernel<bf16_t>), dim3(blocks, N), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)res, ldres, res_bs, (bf16_t*)out, ldout, out_bs, gamma, beta, workspace, mean, rstd, HW, C, G, eps, gelu, ppb),
-            hipLaunchKernelGGL((gn_apply_kernel<f16_t>), dim3(blocks, N), dim3(256), 0, st, (const f16_t*)x, ldx, x_bs, (const f16_t*)res, ldres, res_bs, (f16_t*)out, ldout, out_bs, gamma, beta, workspace, mean, rstd, HW, C, G, eps, gelu, ppb));
-  return check_launch("emrt_groupnorm_fwd");
+  });
 }
 
 // workspace: fp64 [N*C*2], PRE-ZEROED by the caller (per-image per-channel sums)
@@ -1787,22 +1776,19 @@ extern "C" int emrt_groupnorm_bwd(const void* x, int ldx, long long x_bs, const 
   EMRT_REQUIRE(x && dy && dx && gamma && beta && mean && rstd && workspace, "null pointer");
   EMRT_REQUIRE(C % 4 == 0 && (C / 4) <= 256 && 256 % (C / 4) == 0 && G > 0 && G <= 256 && C % G == 0 && (C / G) % 4 == 0, "unsupported C/G");
   hipStream_t st = (hipStream_t)stream;
-  if (gn_use_fused(HW, C, G)) {
-    DT_SWITCH(dtype,
-              hipLaunchKernelGGL((gn_fused_bwd_kernel<float>), dim3(N * G), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)dy, lddy, dy_bs, (float*)dx, lddx, dx_bs, gamma, beta, mean, rstd, dgamma, dbeta, HW, C, G, gelu),
-              hipLaunchKernelGGL((gn_fused_bwd_kernel<bf16_t>), dim3(N * G), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)dy, lddy, dy_bs, (bf16_t*)dx, lddx, dx_bs, gamma, beta, mean, rstd, dgamma, dbeta, HW, C, G, gelu));
+  return with_train_dtype("emrt_groupnorm_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (gn_use_fused(HW, C, G)) {
+      hipLaunchKernelGGL((gn_fused_bwd_kernel<T>), dim3(N * G), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)dy, lddy, dy_bs, (T*)dx, lddx, dx_bs, gamma, beta, mean, rstd, dgamma, dbeta, HW, C, G, gelu);
+      return check_launch("emrt_groupnorm_bwd");
+    }
+    int ppb;
+    const int blocks = gn_geom(HW, C, &ppb);
+    hipLaunchKernelGGL((gn_bwd_reduce_kernel<T>), dim3(blocks, N), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)dy, lddy, dy_bs, gamma, beta, mean, rstd, workspace, HW, C, G, gelu, ppb);
+    const size_t lds = (size_t)2 * G * sizeof(float);
+    hipLaunchKernelGGL((gn_bwd_dx_kernel<T>), dim3(blocks, N), dim3(256), lds, st, (const T*)x, ldx, x_bs, (const T*)dy, lddy, dy_bs, (T*)dx, lddx, dx_bs, gamma, beta, mean, rstd, workspace, dgamma, dbeta, HW, C, G, gelu, ppb);
     return check_launch("emrt_groupnorm_bwd");
-  }
-  int ppb;
-  const int blocks = gn_geom(HW, C, &ppb);
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((gn_bwd_reduce_kernel<float>), dim3(blocks, N), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)dy, lddy, dy_bs, gamma, beta, mean, rstd, workspace, HW, C, G, gelu, ppb),
-            hipLaunchKernelGGL((gn_bwd_reduce_kernel<bf16_t>), dim3(blocks, N), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)dy, lddy, dy_bs, gamma, beta, mean, rstd, workspace, HW, C, G, gelu, ppb));
-  const size_t lds = (size_t)2 * G * sizeof(float);
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((gn_bwd_dx_kernel<float>), dim3(blocks, N), dim3(256), lds, st, (const float*)x, ldx, x_bs, (const float*)dy, lddy, dy_bs, (float*)dx, lddx, dx_bs, gamma, beta, mean, rstd, workspace, dgamma, dbeta, HW, C, G, gelu, ppb),
-            hipLaunchKernelGGL((gn_bwd_dx_kernel<bf16_t>), dim3(blocks, N), dim3(256), lds, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)dy, lddy, dy_bs, (bf16_t*)dx, lddx, dx_bs, gamma, beta, mean, rstd, workspace, dgamma, dbeta, HW, C, G, gelu, ppb));
-  return check_launch("emrt_groupnorm_bwd");
+  });
 }
 
 extern "C" int emrt_layernorm_fwd(const void* a, const void* b, const void* post, void* z, void* out, const float* gamma,
@@ -1815,11 +1801,11 @@ extern "C" int emrt_layernorm_fwd(const void* a, const void* b, const void* post
   EMRT_REQUIRE(C % 4 == 0 && C <= 1024, "C must be a multiple of 4 and <= 1024");
   hipStream_t st = (hipStream_t)stream;
   const int grid = (int)((rows + 3) / 4);
-  DT_SWITCH3(dtype,
-            hipLaunchKernelGGL((ln_fwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)a, (const float*)b, (const float*)post, (float*)z, (float*)out, gamma, beta, mean, rstd, rows, C, eps, pdrop, seed, salt, (const float*)qpos, qpos_rows, (float*)q_out),
-            hipLaunchKernelGGL((ln_fwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (const bf16_t*)post, (bf16_t*)z, (bf16_t*)out, gamma, beta, mean, rstd, rows, C, eps, pdrop, seed, salt, (const bf16_t*)qpos, qpos_rows, (bf16_t*)q_out),
-            hipLaunchKernelGGL((ln_fwd_kernel<f16_t>), dim3(grid), dim3(256), 0, st, (const f16_t*)a, (const f16_t*)b, (const f16_t*)post, (f16_t*)z, (f16_t*)out, gamma, beta, mean, rstd, rows, C, eps, pdrop, seed, salt, (const f16_t*)qpos, qpos_rows, (f16_t*)q_out));
-  return check_launch("emrt_layernorm_fwd");
+  return with_fwd_dtype("emrt_layernorm_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((ln_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)a, (const T*)b, (const T*)post, (T*)z, (T*)out, gamma, beta, mean, rstd, rows, C, eps, pdrop, seed, salt, (const T*)qpos, qpos_rows, (T*)q_out);
+    return check_launch("emrt_layernorm_fwd");
+  });
 }
 
 // blocks of the LayerNorm backward: ~32 rows (8 per wave) each, at most 512 partial-sum rows for the finalize
@@ -1860,19 +1846,17 @@ extern "C" int emrt_layernorm_bwd(const void* z, const void* dy, void* dz, const
   const bool direct = (dgamma || dbeta) && g_tune.ln_atomic != 0;       // developer knob: 0 = partials + finalize launch
   const size_t lds = (size_t)(wide ? 16 : 8) * C * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define LN_BWD_ARGS(T) (const T*)z, (const T*)dy, (T*)dz, gamma, mean, rstd, partial, rows, C, rpb, (T*)dz_branch, pdrop, seed, salt, direct ? dgamma : nullptr, direct ? dbeta : nullptr, (const T*)dz_addend, (const T*)dy2, (T*)dysum
-#define LN_BWD_LAUNCH_W(T, R, NQ) do { if (dy2) hipLaunchKernelGGL((ln_bwd_kernel<T, R, NQ, 512, true>), dim3((unsigned)blocks), dim3(512), lds, st, LN_BWD_ARGS(T)); \
-                                       else hipLaunchKernelGGL((ln_bwd_kernel<T, R, NQ, 512, false>), dim3((unsigned)blocks), dim3(512), lds, st, LN_BWD_ARGS(T)); } while (0)
-#define LN_BWD_LAUNCH(T, R, NQ) do { if (dy2) hipLaunchKernelGGL((ln_bwd_kernel<T, R, NQ, 256, true>), dim3((unsigned)blocks), dim3(256), lds, st, LN_BWD_ARGS(T)); \
-                                     else hipLaunchKernelGGL((ln_bwd_kernel<T, R, NQ, 256, false>), dim3((unsigned)blocks), dim3(256), lds, st, LN_BWD_ARGS(T)); } while (0)
-  if (wide) DT_SWITCH(dtype, LN_BWD_LAUNCH_W(float, 4, 1), LN_BWD_LAUNCH_W(bf16_t, 4, 1));
-  else if (small) DT_SWITCH(dtype, LN_BWD_LAUNCH(float, 4, 1), LN_BWD_LAUNCH(bf16_t, 4, 1));
-  else DT_SWITCH(dtype, LN_BWD_LAUNCH(float, 2, 4), LN_BWD_LAUNCH(bf16_t, 2, 4));
-#undef LN_BWD_LAUNCH
-#undef LN_BWD_LAUNCH_W
-#undef LN_BWD_ARGS
-  if (!direct) hipLaunchKernelGGL(partials_acc_kernel, dim3((2 * C + 31) / 32), dim3(256), 0, st, partial, (int)blocks, C, dgamma, dbeta);
-  return check_launch("emrt_layernorm_bwd");
+  return with_train_dtype("emrt_layernorm_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    auto launch = [&](auto* kernel, int threads) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), lds, st, (const T*)z, (const T*)dy, (T*)dz, gamma, mean, rstd, partial, rows, C, rpb, (T*)dz_branch, pdrop, seed, salt, direct ? dgamma : nullptr, direct ? dbeta : nullptr, (const T*)dz_addend, (const T*)dy2, (T*)dysum);
+    };
+    if (wide) launch(dy2 ? ln_bwd_kernel<T, 4, 1, 512, true> : ln_bwd_kernel<T, 4, 1, 512, false>, 512);
+    else if (small) launch(dy2 ? ln_bwd_kernel<T, 4, 1, 256, true> : ln_bwd_kernel<T, 4, 1, 256, false>, 256);
+    else launch(dy2 ? ln_bwd_kernel<T, 2, 4, 256, true> : ln_bwd_kernel<T, 2, 4, 256, false>, 256);
+    if (!direct) hipLaunchKernelGGL(partials_acc_kernel, dim3((2 * C + 31) / 32), dim3(256), 0, st, partial, (int)blocks, C, dgamma, dbeta);
+    return check_launch("emrt_layernorm_bwd");
+  });
 }
 
 static int gn_fill_levels(GnLevels& lv, const int* level_start, const int* level_hw, int L, const float* const* gamma, const float* const* beta,
@@ -1915,25 +1899,19 @@ extern "C" int emrt_groupnorm_levels_fwd(const void* x, int ldx, long long x_bs,
   GnLevels lv;
   EMRT_REQUIRE(gn_fill_levels(lv, level_start, level_hw, L, gamma, beta, nullptr, nullptr) == 0, "1..4 levels of at most 4096 rows");
   hipStream_t st = (hipStream_t)stream;
-  if (stat_ws && mean && rstd && !g_tune.gn_group_blocks && gn_rows_ok(C, G, ldx, res ? ldres : 8, ldout, x_bs, res ? res_bs : 8, out_bs)) {
-    GnRows gs, ga;
-    gs.lv = lv; ga.lv = lv;
-    const unsigned bs = (unsigned)(gn_rows_plan(gs, g_tune.gn_stat_rows) * N), ba = (unsigned)(gn_rows_plan(ga, g_tune.gn_apply_rows) * N);
-    DT_SWITCH3(dtype,
-              hipLaunchKernelGGL((gn_rows_stats_kernel<float>), dim3(bs), dim3(256), 0, st, (const float*)x, ldx, x_bs, gs, stat_ws, N, G),
-              hipLaunchKernelGGL((gn_rows_stats_kernel<bf16_t>), dim3(bs), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, gs, stat_ws, N, G),
-              hipLaunchKernelGGL((gn_rows_stats_kernel<f16_t>), dim3(bs), dim3(256), 0, st, (const f16_t*)x, ldx, x_bs, gs, stat_ws, N, G));
-    DT_SWITCH3(dtype,
-              hipLaunchKernelGGL((gn_rows_apply_kernel<float>), dim3(ba), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)res, ldres, res_bs, (float*)out, ldout, out_bs, ga, stat_ws, mean, rstd, N, G, eps, gelu),
-              hipLaunchKernelGGL((gn_rows_apply_kernel<bf16_t>), dim3(ba), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)res, ldres, res_bs, (bf16_t*)out, ldout, out_bs, ga, stat_ws, mean, rstd, N, G, eps, gelu),
-              hipLaunchKernelGGL((gn_rows_apply_kernel<f16_t>), dim3(ba), dim3(256), 0, st, (const f16_t*)x, ldx, x_bs, (const f16_t*)res, ldres, res_bs, (f16_t*)out, ldout, out_bs, ga, stat_ws, mean, rstd, N, G, eps, gelu));
+  return with_fwd_dtype("emrt_groupnorm_levels_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (stat_ws && mean && rstd && !g_tune.gn_group_blocks && gn_rows_ok(C, G, ldx, res ? ldres : 8, ldout, x_bs, res ? res_bs : 8, out_bs)) {
+      GnRows gs, ga;
+      gs.lv = lv; ga.lv = lv;
+      const unsigned bs = (unsigned)(gn_rows_plan(gs, g_tune.gn_stat_rows) * N), ba = (unsigned)(gn_rows_plan(ga, g_tune.gn_apply_rows) * N);
+      hipLaunchKernelGGL((gn_rows_stats_kernel<T>), dim3(bs), dim3(256), 0, st, (const T*)x, ldx, x_bs, gs, stat_ws, N, G);
+      hipLaunchKernelGGL((gn_rows_apply_kernel<T>), dim3(ba), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)res, ldres, res_bs, (T*)out, ldout, out_bs, ga, stat_ws, mean, rstd, N, G, eps, gelu);
+      return check_launch("emrt_groupnorm_levels_fwd");
+    }
+    hipLaunchKernelGGL((gn_levels_fwd_kernel<T>), dim3(L * N * G), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)res, ldres, res_bs, (T*)out, ldout, out_bs, lv, mean, rstd, N, C, G, eps, gelu);
     return check_launch("emrt_groupnorm_levels_fwd");
-  }
-  DT_SWITCH3(dtype,
-            hipLaunchKernelGGL((gn_levels_fwd_kernel<float>), dim3(L * N * G), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)res, ldres, res_bs, (float*)out, ldout, out_bs, lv, mean, rstd, N, C, G, eps, gelu),
-            hipLaunchKernelGGL((gn_levels_fwd_kernel<bf16_t>), dim3(L * N * G), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)res, ldres, res_bs, (bf16_t*)out, ldout, out_bs, lv, mean, rstd, N, C, G, eps, gelu),
-            hipLaunchKernelGGL((gn_levels_fwd_kernel<f16_t>), dim3(L * N * G), dim3(256), 0, st, (const f16_t*)x, ldx, x_bs, (const f16_t*)res, ldres, res_bs, (f16_t*)out, ldout, out_bs, lv, mean, rstd, N, C, G, eps, gelu));
-  return check_launch("emrt_groupnorm_levels_fwd");
+  });
 }
 
 extern "C" int emrt_groupnorm_levels_bwd(const void* x, int ldx, long long x_bs, const void* dy, int lddy, long long dy_bs, void* dx,
@@ -1947,20 +1925,17 @@ extern "C" int emrt_groupnorm_levels_bwd(const void* x, int ldx, long long x_bs,
   GnLevels lv;
   EMRT_REQUIRE(gn_fill_levels(lv, level_start, level_hw, L, gamma, beta, dgamma, dbeta) == 0, "1..4 levels of at most 4096 rows");
   hipStream_t st = (hipStream_t)stream;
-  if (stat_ws && !g_tune.gn_group_blocks && gn_rows_ok(C, G, ldx, lddy, lddx, x_bs, dy_bs, dx_bs)) {
-    GnRows gs, ga;
-    gs.lv = lv; ga.lv = lv;
-    const unsigned bs = (unsigned)(gn_rows_plan(gs, g_tune.gn_bwd_stat_rows) * N), ba = (unsigned)(gn_rows_plan(ga, g_tune.gn_apply_rows) * N);
-    DT_SWITCH(dtype,
-              hipLaunchKernelGGL((gn_rows_bwd_stats_kernel<float>), dim3(bs), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)dy, lddy, dy_bs, gs, mean, rstd, stat_ws, N, G, gelu),
-              hipLaunchKernelGGL((gn_rows_bwd_stats_kernel<bf16_t>), dim3(bs), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)dy, lddy, dy_bs, gs, mean, rstd, stat_ws, N, G, gelu));
-    DT_SWITCH(dtype,
-              hipLaunchKernelGGL((gn_rows_bwd_dx_kernel<float>), dim3(ba), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)dy, lddy, dy_bs, (float*)dx, lddx, dx_bs, ga, mean, rstd, stat_ws, N, G, gelu),
-              hipLaunchKernelGGL((gn_rows_bwd_dx_kernel<bf16_t>), dim3(ba), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)dy, lddy, dy_bs, (bf16_t*)dx, lddx, dx_bs, ga, mean, rstd, stat_ws, N, G, gelu));
+  return with_train_dtype("emrt_groupnorm_levels_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (stat_ws && !g_tune.gn_group_blocks && gn_rows_ok(C, G, ldx, lddy, lddx, x_bs, dy_bs, dx_bs)) {
+      GnRows gs, ga;
+      gs.lv = lv; ga.lv = lv;
+      const unsigned bs = (unsigned)(gn_rows_plan(gs, g_tune.gn_bwd_stat_rows) * N), ba = (unsigned)(gn_rows_plan(ga, g_tune.gn_apply_rows) * N);
+      hipLaunchKernelGGL((gn_rows_bwd_stats_kernel<T>), dim3(bs), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)dy, lddy, dy_bs, gs, mean, rstd, stat_ws, N, G, gelu);
+      hipLaunchKernelGGL((gn_rows_bwd_dx_kernel<T>), dim3(ba), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)dy, lddy, dy_bs, (T*)dx, lddx, dx_bs, ga, mean, rstd, stat_ws, N, G, gelu);
+      return check_launch("emrt_groupnorm_levels_bwd");
+    }
+    hipLaunchKernelGGL((gn_levels_bwd_kernel<T>), dim3(L * N * G), dim3(256), 0, st, (const T*)x, ldx, x_bs, (const T*)dy, lddy, dy_bs, (T*)dx, lddx, dx_bs, lv, mean, rstd, N, C, G, gelu);
     return check_launch("emrt_groupnorm_levels_bwd");
-  }
-  DT_SWITCH(dtype,
-            hipLaunchKernelGGL((gn_levels_bwd_kernel<float>), dim3(L * N * G), dim3(256), 0, st, (const float*)x, ldx, x_bs, (const float*)dy, lddy, dy_bs, (float*)dx, lddx, dx_bs, lv, mean, rstd, N, C, G, gelu),
-            hipLaunchKernelGGL((gn_levels_bwd_kernel<bf16_t>), dim3(L * N * G), dim3(256), 0, st, (const bf16_t*)x, ldx, x_bs, (const bf16_t*)dy, lddy, dy_bs, (bf16_t*)dx, lddx, dx_bs, lv, mean, rstd, N, C, G, gelu));
-  return check_launch("emrt_groupnorm_levels_bwd");
+  });
 }

@@ -796,18 +796,6 @@ static inline int ew_grid(long long total) {
   return (int)g;
 }
 
-#define DT3(dtype, KERNEL, GRID, ...)                                                                 \
-  do {                                                                                                \
-    if ((dtype) == EMRT_F32) hipLaunchKernelGGL((KERNEL<float>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__); \
-    else if ((dtype) == EMRT_BF16) hipLaunchKernelGGL((KERNEL<bf16_t>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<f16_t>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__);               \
-  } while (0)
-#define DT2(dtype, KERNEL, GRID, ...)                                                                 \
-  do {                                                                                                \
-    if ((dtype) == EMRT_F32) hipLaunchKernelGGL((KERNEL<float>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<bf16_t>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__);              \
-  } while (0)
-
 extern "C" int emrt_resize_bilinear_fwd(const void* in, long long in_bs, int in_ld, int IH, int IW, void* out, long long out_bs,
                                         int out_ld, int OH, int OW, const void* add, long long add_bs, int add_ld, int N, int C,
                                         int align_corners, int out_nchw_f32, int dtype, void* stream) {
@@ -821,32 +809,28 @@ extern "C" int emrt_resize_bilinear_fwd(const void* in, long long in_bs, int in_
   a.add = add; a.add_bs = add_bs; a.add_ld = add_ld; a.N = N; a.C = C;
   a.ay = make_axis(IH, OH, align_corners); a.ax = make_axis(IW, OW, align_corners); a.out_nchw_f32 = out_nchw_f32;
   hipStream_t st = (hipStream_t)stream;
-  if (out_nchw_f32) {
-    const int grid = ew_grid((long long)N * C * OH * OW);
-    DT3(dtype, resize_fwd_nchw_kernel, grid, a);
-    return check_launch("emrt_resize_bilinear_fwd");
-  }
   const bool v4 = C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0 && in_bs % 4 == 0 && out_bs % 4 == 0 &&
                   (!add || (add_ld % 4 == 0 && add_bs % 4 == 0)) && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
                   (!add || (uintptr_t)add % 16 == 0);
   const bool v8 = v4 && dtype != EMRT_F32 && C % 8 == 0 && in_ld % 8 == 0 && out_ld % 8 == 0 && in_bs % 8 == 0 && out_bs % 8 == 0 &&
                   (!add || (add_ld % 8 == 0 && add_bs % 8 == 0));      // bf16: 16-byte accesses
-  if (v8) {
-    const int grid = ew_grid((long long)N * OH * OW * (C / 8));
-    if (dtype == EMRT_BF16) hipLaunchKernelGGL((resize_fwd_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((resize_fwd_kernel<f16_t, 8>), dim3(grid), dim3(256), 0, st, a);
-  } else if (v4) {
-    const int grid = ew_grid((long long)N * OH * OW * (C / 4));
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_fwd_kernel<float, 4>), dim3(grid), dim3(256), 0, st, a);
-    else if (dtype == EMRT_BF16) hipLaunchKernelGGL((resize_fwd_kernel<bf16_t, 4>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((resize_fwd_kernel<f16_t, 4>), dim3(grid), dim3(256), 0, st, a);
-  } else {
-    const int grid = ew_grid((long long)N * OH * OW * C);
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_fwd_kernel<float, 1>), dim3(grid), dim3(256), 0, st, a);
-    else if (dtype == EMRT_BF16) hipLaunchKernelGGL((resize_fwd_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((resize_fwd_kernel<f16_t, 1>), dim3(grid), dim3(256), 0, st, a);
-  }
-  return check_launch("emrt_resize_bilinear_fwd");
+  return with_fwd_dtype("emrt_resize_bilinear_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (out_nchw_f32) {
+      const int grid = ew_grid((long long)N * C * OH * OW);
+      hipLaunchKernelGGL((resize_fwd_nchw_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    } else if (v8) {
+      const int grid = ew_grid((long long)N * OH * OW * (C / 8));
+      if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((resize_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, st, a);      // (v8 is never set for f32)
+    } else if (v4) {
+      const int grid = ew_grid((long long)N * OH * OW * (C / 4));
+      hipLaunchKernelGGL((resize_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+      const int grid = ew_grid((long long)N * OH * OW * C);
+      hipLaunchKernelGGL((resize_fwd_kernel<T, 1>), dim3(grid), dim3(256), 0, st, a);
+    }
+    return check_launch("emrt_resize_bilinear_fwd");
+  });
 }
 
 // every block of a BatchNorm-operand kernel first derives the per-channel constants (C x 16 fp64 loads from L2 + fp64 math, ~2 us): few,
@@ -891,10 +875,13 @@ extern "C" int emrt_bn_resize_bilinear_fwd(const void* in, long long in_bs, int 
   const bool v8 = dtype != EMRT_F32 && C % 8 == 0 && 256 % (C / 8) == 0 && in_ld % 8 == 0 && out_ld % 8 == 0 && in_bs % 8 == 0 && out_bs % 8 == 0;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)2 * C * sizeof(float);
-  if (v8) hipLaunchKernelGGL((resize_fwd_bn_kernel<bf16_t, 8>), dim3(bn_operand_grid((long long)N * OH * OW * (C / 8))), dim3(256), lds, st, a, b);
-  else if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_fwd_bn_kernel<float, 4>), dim3(bn_operand_grid((long long)N * OH * OW * (C / 4))), dim3(256), lds, st, a, b);
-  else hipLaunchKernelGGL((resize_fwd_bn_kernel<bf16_t, 4>), dim3(bn_operand_grid((long long)N * OH * OW * (C / 4))), dim3(256), lds, st, a, b);
-  return check_launch("emrt_bn_resize_bilinear_fwd");
+  return with_train_dtype("emrt_bn_resize_bilinear_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (v8) {
+      if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((resize_fwd_bn_kernel<T, 8>), dim3(bn_operand_grid((long long)N * OH * OW * (C / 8))), dim3(256), lds, st, a, b);
+    } else hipLaunchKernelGGL((resize_fwd_bn_kernel<T, 4>), dim3(bn_operand_grid((long long)N * OH * OW * (C / 4))), dim3(256), lds, st, a, b);
+    return check_launch("emrt_bn_resize_bilinear_fwd");
+  });
 }
 
 extern "C" size_t emrt_resize_bwd_workspace_bytes(int N, int C, int OH, int IW, int dout_nchw_f32) {
@@ -911,39 +898,34 @@ extern "C" int emrt_resize_bilinear_bwd(const void* dout, long long do_bs, int d
   a.din = din; a.di_bs = di_bs; a.di_ld = di_ld; a.IH = IH; a.IW = IW; a.N = N; a.C = C;
   a.ay = make_axis(IH, OH, align_corners); a.ax = make_axis(IW, OW, align_corners); a.dout_nchw_f32 = dout_nchw_f32;
   hipStream_t st = (hipStream_t)stream;
-  if (dout_nchw_f32) {
-    EMRT_REQUIRE(workspace, "fp32 NCHW gradient needs the emrt_resize_bwd_workspace_bytes() workspace");
-    float* tmp = (float*)workspace;
-    hipLaunchKernelGGL(resize_bwd_nchw_w_kernel, dim3(ew_grid((long long)N * C * OH * IW)), dim3(256), 0, st, a, tmp);
-    const int grid = ew_grid((long long)N * C * IH * IW);
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_bwd_nchw_h_kernel<float>), dim3(grid), dim3(256), 0, st, a, (const float*)tmp);
-    else hipLaunchKernelGGL((resize_bwd_nchw_h_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, a, (const float*)tmp);
-    return check_launch("emrt_resize_bilinear_bwd");
-  }
+  if (dout_nchw_f32) EMRT_REQUIRE(workspace, "fp32 NCHW gradient needs the emrt_resize_bwd_workspace_bytes() workspace");
   const bool v4 = C % 4 == 0 && do_ld % 4 == 0 && di_ld % 4 == 0 && do_bs % 4 == 0 && di_bs % 4 == 0 &&
                   ((uintptr_t)dout % 16 == 0) && ((uintptr_t)din % 16 == 0);
-  if (v4 && C / 4 <= RBW_THREADS && ((long long)OH * OW >= 16ll * IH * IW)) {     // >= x4 per axis: block per source pixel
-    int chunks = 1;
-    while (chunks < 8 && (long long)N * IH * IW * chunks < 256 && (C / 4) % (chunks * 2) == 0 && (C / 4) / (chunks * 2) >= 8) chunks *= 2;
-    const dim3 grid((unsigned)(N * IH * IW), (unsigned)chunks);
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_bwd_wide_kernel<float>), grid, dim3(RBW_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((resize_bwd_wide_kernel<bf16_t>), grid, dim3(RBW_THREADS), 0, st, a);
-    return check_launch("emrt_resize_bilinear_bwd");
-  }
   const bool v8 = v4 && dtype != EMRT_F32 && C % 8 == 0 && do_ld % 8 == 0 && di_ld % 8 == 0 && do_bs % 8 == 0 && di_bs % 8 == 0;
-  if (v8) {
-    const int grid = ew_grid((long long)N * IH * IW * (C / 8));
-    hipLaunchKernelGGL((resize_bwd_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, st, a);
-  } else if (v4) {
-    const int grid = ew_grid((long long)N * IH * IW * (C / 4));
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_bwd_kernel<float, 4>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((resize_bwd_kernel<bf16_t, 4>), dim3(grid), dim3(256), 0, st, a);
-  } else {
-    const int grid = ew_grid((long long)N * IH * IW * C);
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_bwd_kernel<float, 1>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((resize_bwd_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, st, a);
-  }
-  return check_launch("emrt_resize_bilinear_bwd");
+  return with_train_dtype("emrt_resize_bilinear_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (dout_nchw_f32) {
+      float* tmp = (float*)workspace;
+      hipLaunchKernelGGL(resize_bwd_nchw_w_kernel, dim3(ew_grid((long long)N * C * OH * IW)), dim3(256), 0, st, a, tmp);
+      const int grid = ew_grid((long long)N * C * IH * IW);
+      hipLaunchKernelGGL((resize_bwd_nchw_h_kernel<T>), dim3(grid), dim3(256), 0, st, a, (const float*)tmp);
+    } else if (v4 && C / 4 <= RBW_THREADS && ((long long)OH * OW >= 16ll * IH * IW)) {     // >= x4 per axis: block per source pixel
+      int chunks = 1;
+      while (chunks < 8 && (long long)N * IH * IW * chunks < 256 && (C / 4) % (chunks * 2) == 0 && (C / 4) / (chunks * 2) >= 8) chunks *= 2;
+      const dim3 grid((unsigned)(N * IH * IW), (unsigned)chunks);
+      hipLaunchKernelGGL((resize_bwd_wide_kernel<T>), grid, dim3(RBW_THREADS), 0, st, a);
+    } else if (v8) {
+      const int grid = ew_grid((long long)N * IH * IW * (C / 8));
+      if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((resize_bwd_kernel<T, 8>), dim3(grid), dim3(256), 0, st, a);
+    } else if (v4) {
+      const int grid = ew_grid((long long)N * IH * IW * (C / 4));
+      hipLaunchKernelGGL((resize_bwd_kernel<T, 4>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+      const int grid = ew_grid((long long)N * IH * IW * C);
+      hipLaunchKernelGGL((resize_bwd_kernel<T, 1>), dim3(grid), dim3(256), 0, st, a);
+    }
+    return check_launch("emrt_resize_bilinear_bwd");
+  });
 }
 
 // ABI 6: the decoder's pyramid maps in ONE launch per direction.  tokens [N][sum k^2][C] dense (the k x k map of scale i starts at token
@@ -992,13 +974,13 @@ extern "C" int emrt_pyramid_resize_fwd(const void* tokens, const int* scales, in
   EMRT_REQUIRE(m.first[nscales] <= 0xffffffffll, "too many elements");
   hipStream_t st = (hipStream_t)stream;
   const int grid = ew_grid(m.first[nscales]);
-  if (vec == 8) {
-    if (dtype == EMRT_BF16) hipLaunchKernelGGL((resize_fwd_pyramid_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, st, m);
-    else hipLaunchKernelGGL((resize_fwd_pyramid_kernel<f16_t, 8>), dim3(grid), dim3(256), 0, st, m);
-  } else if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_fwd_pyramid_kernel<float, 4>), dim3(grid), dim3(256), 0, st, m);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((resize_fwd_pyramid_kernel<bf16_t, 4>), dim3(grid), dim3(256), 0, st, m);
-  else hipLaunchKernelGGL((resize_fwd_pyramid_kernel<f16_t, 4>), dim3(grid), dim3(256), 0, st, m);
-  return check_launch("emrt_pyramid_resize_fwd");
+  return with_fwd_dtype("emrt_pyramid_resize_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (vec == 8) {
+      if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((resize_fwd_pyramid_kernel<T, 8>), dim3(grid), dim3(256), 0, st, m);
+    } else hipLaunchKernelGGL((resize_fwd_pyramid_kernel<T, 4>), dim3(grid), dim3(256), 0, st, m);
+    return check_launch("emrt_pyramid_resize_fwd");
+  });
 }
 
 extern "C" int emrt_pyramid_resize_bwd(const void* const* douts, const int* do_ld, const long long* do_bs, int OH, int OW, void* dtokens,
@@ -1021,9 +1003,11 @@ extern "C" int emrt_pyramid_resize_bwd(const void* const* douts, const int* do_l
   }
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)m.first[nscales]);
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((resize_bwd_pyramid_kernel<float>), grid, dim3(RBW_THREADS), 0, st, m);
-  else hipLaunchKernelGGL((resize_bwd_pyramid_kernel<bf16_t>), grid, dim3(RBW_THREADS), 0, st, m);
-  return check_launch("emrt_pyramid_resize_bwd");
+  return with_train_dtype("emrt_pyramid_resize_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((resize_bwd_pyramid_kernel<T>), grid, dim3(RBW_THREADS), 0, st, m);
+    return check_launch("emrt_pyramid_resize_bwd");
+  });
 }
 
 static int fill_pool(PoolArgs& a, const int* scales, int nscales) {
@@ -1153,31 +1137,26 @@ extern "C" int emrt_adaptive_avgpool_fwd(const void* in, long long in_bs, int in
   a.in = in; a.in_bs = in_bs; a.in_ld = in_ld; a.H = H; a.W = W; a.out = out; a.out_bs = out_bs; a.out_ld = out_ld; a.N = N; a.C = C;
   EMRT_REQUIRE(fill_pool(a, scales, nscales) == 0, "1..4 scales supported");
   hipStream_t st = (hipStream_t)stream;
+  bool split = false;      // partial sums through the workspace + a final launch
   if (workspace) {
     const int esz = dtype == EMRT_F32 ? 4 : 2;
     const bool vec = (in_ld % 4 == 0) && (in_bs % 4 == 0) && (out_ld % 4 == 0) && (out_bs % 4 == 0) && (((uintptr_t)in) % (4 * esz) == 0) &&
                      (((uintptr_t)out) % (4 * esz) == 0) && (((uintptr_t)workspace) % 16 == 0);
     if (vec && pool_split_plan(a, H, W, C, scales, nscales)) {
       EMRT_REQUIRE(workspace_bytes >= (size_t)N * a.nitem * C * sizeof(float), "workspace smaller than emrt_adaptive_avgpool_workspace_bytes()");
-      const dim3 grid((unsigned)(N * a.nitem));
-      const int fg = ew_grid((long long)N * a.ntok * (C / 4));
-      if (dtype == EMRT_F32) {
-        hipLaunchKernelGGL((adaptive_pool_part_kernel<float>), grid, dim3(POOL_THREADS), 0, st, a, workspace);
-        hipLaunchKernelGGL((adaptive_pool_final_kernel<float>), dim3(fg), dim3(256), 0, st, a, (const float*)workspace);
-      } else if (dtype == EMRT_BF16) {
-        hipLaunchKernelGGL((adaptive_pool_part_kernel<bf16_t>), grid, dim3(POOL_THREADS), 0, st, a, workspace);
-        hipLaunchKernelGGL((adaptive_pool_final_kernel<bf16_t>), dim3(fg), dim3(256), 0, st, a, (const float*)workspace);
-      } else {
-        hipLaunchKernelGGL((adaptive_pool_part_kernel<f16_t>), grid, dim3(POOL_THREADS), 0, st, a, workspace);
-        hipLaunchKernelGGL((adaptive_pool_final_kernel<f16_t>), dim3(fg), dim3(256), 0, st, a, (const float*)workspace);
-      }
-      return check_launch("emrt_adaptive_avgpool_fwd");
+      split = true;
     }
   }
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((adaptive_pool_fwd_kernel<float>), dim3(N * a.ntok), dim3(POOL_THREADS), 0, st, a);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((adaptive_pool_fwd_kernel<bf16_t>), dim3(N * a.ntok), dim3(POOL_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((adaptive_pool_fwd_kernel<f16_t>), dim3(N * a.ntok), dim3(POOL_THREADS), 0, st, a);
-  return check_launch("emrt_adaptive_avgpool_fwd");
+  return with_fwd_dtype("emrt_adaptive_avgpool_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (split) {
+      const dim3 grid((unsigned)(N * a.nitem));
+      const int fg = ew_grid((long long)N * a.ntok * (C / 4));
+      hipLaunchKernelGGL((adaptive_pool_part_kernel<T>), grid, dim3(POOL_THREADS), 0, st, a, workspace);
+      hipLaunchKernelGGL((adaptive_pool_final_kernel<T>), dim3(fg), dim3(256), 0, st, a, (const float*)workspace);
+    } else hipLaunchKernelGGL((adaptive_pool_fwd_kernel<T>), dim3(N * a.ntok), dim3(POOL_THREADS), 0, st, a);
+    return check_launch("emrt_adaptive_avgpool_fwd");
+  });
 }
 
 extern "C" int emrt_adaptive_avgpool_bwd(const void* dout, long long do_bs, int do_ld, void* din, long long di_bs, int di_ld, int H,
@@ -1196,17 +1175,20 @@ extern "C" int emrt_adaptive_avgpool_bwd(const void* dout, long long do_bs, int 
   // most one pixel); a pooled map smaller than a scale (k > S: a pixel can belong to 3 or more bins) takes the general gather kernels
   bool two_bins = true;
   for (int i = 0; i < nscales; ++i) two_bins = two_bins && scales[i] <= (H < W ? H : W);
-  if (vec && H + W <= 512 && two_bins) {
-    const int grid = ew_grid((long long)N * H * W * (C / 4));
-    DT2(dtype, adaptive_pool_bwd_tab_kernel, grid, a);
-  } else if (vec) {
-    const int grid = ew_grid((long long)N * H * W * (C / 4));
-    DT2(dtype, adaptive_pool_bwd_vec_kernel, grid, a);
-  } else {
-    const int grid = ew_grid((long long)N * H * W * C);
-    DT2(dtype, adaptive_pool_bwd_kernel, grid, a);
-  }
-  return check_launch("emrt_adaptive_avgpool_bwd");
+  return with_train_dtype("emrt_adaptive_avgpool_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (vec && H + W <= 512 && two_bins) {
+      const int grid = ew_grid((long long)N * H * W * (C / 4));
+      hipLaunchKernelGGL((adaptive_pool_bwd_tab_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    } else if (vec) {
+      const int grid = ew_grid((long long)N * H * W * (C / 4));
+      hipLaunchKernelGGL((adaptive_pool_bwd_vec_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+      const int grid = ew_grid((long long)N * H * W * C);
+      hipLaunchKernelGGL((adaptive_pool_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    }
+    return check_launch("emrt_adaptive_avgpool_bwd");
+  });
 }
 
 extern "C" int emrt_maxpool_fwd(const void* in, void* out, unsigned char* argmax, int N, int H, int W, int C, int k, int stride, int pad,
@@ -1220,14 +1202,17 @@ extern "C" int emrt_maxpool_fwd(const void* in, void* out, unsigned char* argmax
   a.OH = (H + 2 * pad - k) / stride + 1; a.OW = (W + 2 * pad - k) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
   const int esz = dtype == EMRT_F32 ? 4 : 2;
-  if (C % 8 == 0 && ((uintptr_t)in % (8 * esz) == 0) && ((uintptr_t)out % (8 * esz) == 0) && (!argmax || (uintptr_t)argmax % 8 == 0)) {
-    const int grid = ew_grid((long long)N * a.OH * a.OW * (C / 8));
-    DT3(dtype, maxpool_fwd_vec8_kernel, grid, a);
+  return with_fwd_dtype("emrt_maxpool_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C % 8 == 0 && ((uintptr_t)in % (8 * esz) == 0) && ((uintptr_t)out % (8 * esz) == 0) && (!argmax || (uintptr_t)argmax % 8 == 0)) {
+      const int grid = ew_grid((long long)N * a.OH * a.OW * (C / 8));
+      hipLaunchKernelGGL((maxpool_fwd_vec8_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+      const int grid = ew_grid((long long)N * a.OH * a.OW * C);
+      hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+    }
     return check_launch("emrt_maxpool_fwd");
-  }
-  const int grid = ew_grid((long long)N * a.OH * a.OW * C);
-  DT3(dtype, maxpool_fwd_kernel, grid, a);
-  return check_launch("emrt_maxpool_fwd");
+  });
 }
 
 // out = maxpool([relu](BatchNorm_train(in))) in one pass over the raw map (see emrt_bn_resize_bilinear_fwd).  C % 8 == 0, C <= 4096.
@@ -1250,9 +1235,11 @@ extern "C" int emrt_bn_maxpool_fwd(const void* in, void* out, unsigned char* arg
   hipStream_t st = (hipStream_t)stream;
   const int grid = bn_operand_grid((long long)N * a.OH * a.OW * (C / 8));
   const size_t lds = (size_t)2 * C * sizeof(float);
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((maxpool_fwd_bn_kernel<float>), dim3(grid), dim3(256), lds, st, a, b);
-  else hipLaunchKernelGGL((maxpool_fwd_bn_kernel<bf16_t>), dim3(grid), dim3(256), lds, st, a, b);
-  return check_launch("emrt_bn_maxpool_fwd");
+  return with_train_dtype("emrt_bn_maxpool_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((maxpool_fwd_bn_kernel<T>), dim3(grid), dim3(256), lds, st, a, b);
+    return check_launch("emrt_bn_maxpool_fwd");
+  });
 }
 
 extern "C" int emrt_maxpool_bwd(const unsigned char* argmax, const void* dout, void* din, int N, int H, int W, int C, int k, int stride,
@@ -1267,16 +1254,17 @@ extern "C" int emrt_maxpool_bwd(const unsigned char* argmax, const void* dout, v
   a.OH = (H + 2 * pad - k) / stride + 1; a.OW = (W + 2 * pad - k) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
   const bool v4 = C % 4 == 0 && ((uintptr_t)dout % 16 == 0) && ((uintptr_t)din % 16 == 0) && ((uintptr_t)argmax % 4 == 0);
-  if (v4) {
-    const int grid = ew_grid((long long)N * H * W * (C / 4));
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((maxpool_bwd_kernel<float, 4>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, 4>), dim3(grid), dim3(256), 0, st, a);
-  } else {
-    const int grid = ew_grid((long long)N * H * W * C);
-    if (dtype == EMRT_F32) hipLaunchKernelGGL((maxpool_bwd_kernel<float, 1>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, st, a);
-  }
-  return check_launch("emrt_maxpool_bwd");
+  return with_train_dtype("emrt_maxpool_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    if (v4) {
+      const int grid = ew_grid((long long)N * H * W * (C / 4));
+      hipLaunchKernelGGL((maxpool_bwd_kernel<T, 4>), dim3(grid), dim3(256), 0, st, a);
+    } else {
+      const int grid = ew_grid((long long)N * H * W * C);
+      hipLaunchKernelGGL((maxpool_bwd_kernel<T, 1>), dim3(grid), dim3(256), 0, st, a);
+    }
+    return check_launch("emrt_maxpool_bwd");
+  });
 }
 
 extern "C" int emrt_nchw_to_nhwc(const float* in, void* out, int N, int C, int H, int W, int c_out, int dtype, void* stream) {
@@ -1284,20 +1272,19 @@ extern "C" int emrt_nchw_to_nhwc(const float* in, void* out, int N, int C, int H
   EMRT_REQUIRE(in && out, "null pointer");
   EMRT_REQUIRE(c_out >= C, "the output has at least the input's channels");
   hipStream_t st = (hipStream_t)stream;
-  if ((c_out == 8 || c_out == 4) && C <= c_out && ((uintptr_t)out % 32 == 0)) {
-    const long long HW = (long long)H * W;
-    const int g2 = ew_grid((long long)N * HW);
-#define INGEST(T, CO) hipLaunchKernelGGL((nchw_to_nhwc_pix_kernel<T, CO>), dim3(g2), dim3(256), 0, st, in, (T*)out, N, C, HW)
-    if (c_out == 8) { if (dtype == EMRT_F32) INGEST(float, 8); else if (dtype == EMRT_BF16) INGEST(bf16_t, 8); else INGEST(f16_t, 8); }
-    else { if (dtype == EMRT_F32) INGEST(float, 4); else if (dtype == EMRT_BF16) INGEST(bf16_t, 4); else INGEST(f16_t, 4); }
-#undef INGEST
+  return with_fwd_dtype("emrt_nchw_to_nhwc", dtype, [&](auto t) {
+    using T = decltype(t);
+    if ((c_out == 8 || c_out == 4) && C <= c_out && ((uintptr_t)out % 32 == 0)) {
+      const long long HW = (long long)H * W;
+      const int g2 = ew_grid((long long)N * HW);
+      if (c_out == 8) hipLaunchKernelGGL((nchw_to_nhwc_pix_kernel<T, 8>), dim3(g2), dim3(256), 0, st, in, (T*)out, N, C, HW);
+      else hipLaunchKernelGGL((nchw_to_nhwc_pix_kernel<T, 4>), dim3(g2), dim3(256), 0, st, in, (T*)out, N, C, HW);
+    } else {
+      const int grid = ew_grid((long long)N * c_out * H * W);
+      hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(grid), dim3(256), 0, st, in, (T*)out, N, C, H, W, c_out);
+    }
     return check_launch("emrt_nchw_to_nhwc");
-  }
-  const int grid = ew_grid((long long)N * c_out * H * W);
-  if (dtype == EMRT_F32) hipLaunchKernelGGL((nchw_to_nhwc_kernel<float>), dim3(grid), dim3(256), 0, st, in, (float*)out, N, C, H, W, c_out);
-  else if (dtype == EMRT_BF16) hipLaunchKernelGGL((nchw_to_nhwc_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, in, (bf16_t*)out, N, C, H, W, c_out);
-  else hipLaunchKernelGGL((nchw_to_nhwc_kernel<f16_t>), dim3(grid), dim3(256), 0, st, in, (f16_t*)out, N, C, H, W, c_out);
-  return check_launch("emrt_nchw_to_nhwc");
+  });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -115,6 +115,70 @@ def test_abi6_entry_points_refuse_bad_arguments_before_any_launch(built):
     refused("emrt_adaptive_avgpool_fwd", p, 32 * 32 * 256, 256, 32, 32, p, 50 * 256, 256, 8, 256, scp, 4, p, need - 4, 1, None, match="workspace smaller")
 
 
+# the entry points whose FIRST check is the dtype check, by the macro they carry (csrc/common.hpp)
+DTYPE_FIRST_FWD = [          # EMRT_REQUIRE_FWD_DTYPE: f32, bf16 and f16
+    "emrt_acc3d", "emrt_adaptive_avgpool_fwd", "emrt_add", "emrt_add3d", "emrt_add_f32row", "emrt_add_f32row_levels", "emrt_bn_apply", "emrt_cast",
+    "emrt_concat_tokens", "emrt_groupnorm_fwd", "emrt_groupnorm_levels_fwd", "emrt_layernorm_fwd", "emrt_maxpool_fwd", "emrt_mha_fwd", "emrt_msda_fwd",
+    "emrt_nchw_to_nhwc", "emrt_pack_weights", "emrt_pyramid_resize_fwd", "emrt_resize_bilinear_fwd",
+]
+DTYPE_FIRST_TRAIN = [        # EMRT_REQUIRE_TRAIN_DTYPE: f32 and bf16, f16 is refused as inference-only
+    "emrt_adaptive_avgpool_bwd", "emrt_bn_apply_join", "emrt_bn_bwd_dx", "emrt_bn_bwd_reduce", "emrt_bn_group_apply", "emrt_bn_group_bwd",
+    "emrt_bn_maxpool_fwd", "emrt_bn_pointwise_bwd", "emrt_bn_pointwise_fwd", "emrt_bn_resize_bilinear_fwd", "emrt_bn_stats", "emrt_colsum_acc",
+    "emrt_colsum_levels_multi", "emrt_conv2d_bna", "emrt_conv2d_drop", "emrt_dropout_fwd", "emrt_gconv2d_bwd", "emrt_groupnorm_bwd",
+    "emrt_groupnorm_levels_bwd", "emrt_layernorm_bwd", "emrt_mask_bwd", "emrt_maxpool_bwd", "emrt_mha_bwd", "emrt_msda_bwd", "emrt_pyramid_resize_bwd",
+    "emrt_resize_bilinear_bwd",
+]
+
+
+def _dtype_first_in_sources():
+    """{name: "FWD" | "TRAIN"} of the extern "C" functions of csrc/*.hip whose first statement is an EMRT_REQUIRE_*_DTYPE line"""
+    found = {}
+    for f in glob.glob(os.path.join(ROOT, "emrt_amd/csrc/*.hip")):
+        for m in re.finditer(r'extern "C" int (emrt_\w+)\([^{]*\)\s*\{\s*EMRT_REQUIRE_(FWD|TRAIN)_DTYPE\(dtype\);', open(f).read()):
+            found[m.group(1)] = m.group(2)
+    return found
+
+
+def test_dtype_first_lists_match_the_sources():
+    found = _dtype_first_in_sources()
+    assert sorted(n for n, k in found.items() if k == "FWD") == sorted(DTYPE_FIRST_FWD)
+    assert sorted(n for n, k in found.items() if k == "TRAIN") == sorted(DTYPE_FIRST_TRAIN)
+    assert len(DTYPE_FIRST_FWD) + len(DTYPE_FIRST_TRAIN) == 45
+
+
+@pytest.mark.parametrize("name", DTYPE_FIRST_FWD + DTYPE_FIRST_TRAIN)
+def test_dtype_refusals_name_the_entry_point(built, name):
+    """The dtype check is the first check of these entry points and returns before anything else is looked at: every pointer is null and every
+    number 0 here (nothing is launched, nothing dereferenced; no GPU needed).  An unknown code (3) is refused under the entry point's own name;
+    float16 (2) is refused as inference-only by the training entry points and passes the dtype check of the entry points of the float16 ledger
+    (COVERED and EXEMPT of tests/test_gpu_fp16_kernels.py), which then stop at a later argument check.  emrt_conv2d_drop is in both groups: it
+    is EXEMPT from a float16 kernel test BECAUSE its EMRT_REQUIRE_TRAIN_DTYPE line refuses float16, so the inference-only answer is the one
+    asserted for it."""
+    from emrt_amd import _lib
+    from tests.test_fp16_ledger_cpu import _ledger
+    L = _lib.lib()
+    ret, args = _lib.parse_header()[name]
+    assert ret == "int" and [a for _, a in args].count("dtype") == 1
+
+    def refusal(dtype):
+        vals = [dtype if a == "dtype" else (None if t.endswith("*") else (0.0 if t in ("float", "double") else 0)) for t, a in args]
+        with pytest.raises(_lib.EmrtHipError) as e:
+            L.call(name, *vals)
+        text = str(e.value)
+        assert text.startswith(name + " failed") and "launch failed" not in text, text
+        return text
+
+    text = refusal(3)
+    assert ": %s: dtype must be" % name in text, text
+    text = refusal(2)
+    covered, exempt, _, _ = _ledger()
+    if name in DTYPE_FIRST_TRAIN:
+        assert ": %s: dtype must be" % name in text and "inference-only" in text, text
+    else:
+        assert name in covered or name in exempt, name
+        assert "dtype must be" not in text and "inference-only" not in text, text
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from emrt_amd import _lib
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
