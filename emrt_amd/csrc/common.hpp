@@ -377,4 +377,22 @@ inline int with_fwd_dtype(const char* fn, int dtype, F&& f) {
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- windows of the sliding-window inference glue (spatial.hip, scene.hip): up to EMRT_MAX_WINDOWS origins ride in the kernel arguments
+#define EMRT_MAX_WINDOWS 64
+struct WindowArgs {
+  int n, C, H, W, ch, cw;
+  int y0[EMRT_MAX_WINDOWS], x0[EMRT_MAX_WINDOWS];
+};
+// origins_yx: HOST int[n][2]; -1 unless 1 <= n <= EMRT_MAX_WINDOWS and every ch x cw window lies inside the H x W image
+inline int fill_windows(WindowArgs& a, const int* origins_yx, int n, int C, int H, int W, int ch, int cw) {
+  if (n < 1 || n > EMRT_MAX_WINDOWS) return -1;
+  a.n = n; a.C = C; a.H = H; a.W = W; a.ch = ch; a.cw = cw;
+  for (int j = 0; j < n; ++j) {
+    a.y0[j] = origins_yx[2 * j];
+    a.x0[j] = origins_yx[2 * j + 1];
+    if (a.y0[j] < 0 || a.x0[j] < 0 || a.y0[j] + ch > H || a.x0[j] + cw > W) return -1;
+  }
+  return 0;
+}
+
 }  // namespace emrt

@@ -1291,12 +1291,6 @@ extern "C" int emrt_nchw_to_nhwc(const float* in, void* out, int N, int C, int H
 // Sliding-window inference glue (reference: src/api/infer.py:22-80, 145-155): crop the windows of one image into a
 // batch, accumulate the windows' logits with a hit count, normalise, argmax.  fp32 NCHW throughout, as the reference.
 // ------------------------------------------------------------------------------------------------
-#define EMRT_MAX_WINDOWS 64
-struct WindowArgs {
-  int n, C, H, W, ch, cw;
-  int y0[EMRT_MAX_WINDOWS], x0[EMRT_MAX_WINDOWS];
-};
-
 __global__ __launch_bounds__(256) void crop_windows_kernel(const float* __restrict__ img, float* __restrict__ batch, WindowArgs a) {
   const long long total = (long long)a.n * a.C * a.ch * a.cw;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -1384,17 +1378,6 @@ __global__ __launch_bounds__(256) void argmax_nchw_kernel(const float* __restric
     }
     pred[idx] = bi;
   }
-}
-
-static int fill_windows(WindowArgs& a, const int* origins_yx, int n, int C, int H, int W, int ch, int cw) {
-  if (n < 1 || n > EMRT_MAX_WINDOWS) return -1;
-  a.n = n; a.C = C; a.H = H; a.W = W; a.ch = ch; a.cw = cw;
-  for (int j = 0; j < n; ++j) {
-    a.y0[j] = origins_yx[2 * j];
-    a.x0[j] = origins_yx[2 * j + 1];
-    if (a.y0[j] < 0 || a.x0[j] < 0 || a.y0[j] + ch > H || a.x0[j] + cw > W) return -1;
-  }
-  return 0;
 }
 
 extern "C" int emrt_crop_windows(const float* img, float* batch, const int* origins_yx /*host, [n][2]*/, int n, int C, int H, int W,

@@ -111,13 +111,10 @@ def _flip_w(x):
     return out
 
 
-def ms_inference(model, img, ori_shape, is_slide, base_size, stride_size, crop_size, num_classes, scales=(1.0,),
-                 flip_horizontal=True, flip_vertical=False, rescale_from_ori=False):
-    """Multi-scale + horizontal-flip inference (infer.py:160-260): per scale, sliding-window logits -> resize to
-    `ori_shape` -> softmax, summed over scales and flips, then argmax.  img: one fp32 [3,h,w] device tensor (or a list of
-    one); returns int32 [1,1,H,W].  The reference's quirk is kept: each scale resizes the image produced for the previous
-    scale (its `img` variable is reassigned, :240) to a size derived from the ORIGINAL input size.  Every array operation
-    is a HIP kernel (resize, flip, softmax-accumulate, argmax)."""
+def ms_accumulate(model, img, ori_shape, is_slide, base_size, stride_size, crop_size, num_classes, scales=(1.0,),
+                  flip_horizontal=True, flip_vertical=False, rescale_from_ori=False):
+    """The accumulation of ms_inference without its argmax: fp32 [1, ncls, H, W], the softmax of every scale and flip summed (what
+    ms_inference takes the argmax of, and what api.scene.ScenePredictor finishes into a colour map).  Arguments as ms_inference."""
     if not isinstance(scales, (tuple, list)):
         raise TypeError("`scales` expects tuple/list, but received {}".format(type(scales)))
     if rescale_from_ori or not is_slide:
@@ -145,6 +142,20 @@ def ms_inference(model, img, ori_shape, is_slide, base_size, stride_size, crop_s
                 logit = _flip_w(logit)
             logit = _resize_nchw_f32(logit, H, W)
             L.call("emrt_softmax_nchw_acc", Fn.P(logit), Fn.P(final), 1, num_classes, H, W, c.stream)
+    return final
+
+
+def ms_inference(model, img, ori_shape, is_slide, base_size, stride_size, crop_size, num_classes, scales=(1.0,),
+                 flip_horizontal=True, flip_vertical=False, rescale_from_ori=False):
+    """Multi-scale + horizontal-flip inference (infer.py:160-260): per scale, sliding-window logits -> resize to
+    `ori_shape` -> softmax, summed over scales and flips, then argmax.  img: one fp32 [3,h,w] device tensor (or a list of
+    one); returns int32 [1,1,H,W].  The reference's quirk is kept: each scale resizes the image produced for the previous
+    scale (its `img` variable is reassigned, :240) to a size derived from the ORIGINAL input size.  Every array operation
+    is a HIP kernel (resize, flip, softmax-accumulate, argmax)."""
+    final = ms_accumulate(model, img, ori_shape, is_slide, base_size, stride_size, crop_size, num_classes, scales, flip_horizontal,
+                          flip_vertical, rescale_from_ori)
+    L, c = Fn._L(), ctx()
+    H, W = final.shape[-2:]
     pred = c.empty((1, 1, H, W), torch.int32)
     L.call("emrt_argmax_nchw", Fn.P(final), Fn.P(pred), 1, num_classes, H, W, c.stream)
     return pred

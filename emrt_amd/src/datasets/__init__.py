@@ -79,6 +79,20 @@ def get_dataset(config, data_transform, mode="train"):
     raise NotImplementedError("{} dataset is not supported".format(name))
 
 
+def test_images(config):
+    """Image paths of the configured dataset's test split, in the order a `val` Dataset lists them (Potsdam / Vaihingen: <root>/test,
+    LoveDA: <root>/Val/images_png) -- what `python -m emrt_amd.predict` predicts without --input.  No labels are needed or looked for."""
+    name, root = config.DATA.DATASET, config.DATA.DATA_PATH
+    if name in ("Potsdam", "Vaihingen"):
+        img_dir = os.path.join(root, "test")
+    elif name == "LoveDA":
+        img_dir = os.path.join(root, "Val", "images_png")
+    else:
+        raise NotImplementedError("{} dataset is not supported".format(name))
+    files = sorted(os.listdir(img_dir), key=lambda x: int(os.path.splitext(x)[0]))
+    return [os.path.join(img_dir, f) for f in files]
+
+
 class TileLoader:
     """Iteration-based training loader (utils/dataloader.py:22-49): `sampler` yields index lists (DistributedTileSampler);
     `workers` threads decode + augment tiles (PIL and numpy release the GIL for the heavy parts) into PINNED host batches;

@@ -319,6 +319,18 @@ int emrt_argmax_nchw(const float* logits, int* pred, int N, int C, int H, int W,
 int emrt_flip_w(const float* in, float* out, long long rows, int W, void* stream);
 int emrt_softmax_nchw_acc(const float* logits, float* acc, int N, int C, int H, int W, void* stream);
 
+/* ---- whole-scene prediction (python -m emrt_amd.predict); additive to ABI 9, fp32 / uint8 only (no dtype argument).
+ * emrt_scene_crop_windows_u8: windows of a uint8 [H][W][3] RGB scene -> batch fp32 [n][3][ch][cw], normalised as transforms.Normalize does it:
+ * (float)(((double)u8 - mean[c]) * stdinv[c]), bit for bit the CPU transform.  origins_yx and the window checks as emrt_crop_windows.
+ * emrt_scene_finish: values fp32 [N][C][H][W] (the sliding window's sums, softmax sums or plain logits), count fp32 [N][H][W] or NULL ->
+ * index uint8 [N][H][W] = argmax over c of values / count (emrt_window_normalise's division, emrt_argmax_nchw's rule: first maximum wins, a NaN
+ * counts as the maximum, a pixel nobody covered -- 0 / 0 -- is class 0), color uint8 [N][H][W][3] = palette[index] (NULL: not wanted), overlay =
+ * (uint8)floor(alpha * color + (1 - alpha) * scene + 0.5) in fp32 (NULL: not wanted; needs scene uint8 [N][H][W][3]), areas[index] += 1 (device
+ * long long [C], ADDED to: the caller zeroes it; integer atomics, the same sums on every run; NULL: not wanted).  palette: HOST bytes [C][3].
+ * Refused before any launch: C outside 1..256, null values / index / palette, overlay without scene, alpha outside [0, 1], N * H * W >= 2^31. */
+int emrt_scene_crop_windows_u8(const unsigned char* scene, float* batch, const int* origins_yx, int n, int H, int W, int ch, int cw, double mean0, double mean1, double mean2, double stdinv0, double stdinv1, double stdinv2, void* stream);
+int emrt_scene_finish(const float* values, const float* count, const unsigned char* palette, const unsigned char* scene, float alpha, unsigned char* index, unsigned char* color, unsigned char* overlay, long long* areas, int N, int C, int H, int W, void* stream);
+
 /* ---- loss: nn.CrossEntropyLoss(ignore_index, axis=1) on fp32 NCHW logits, int64 labels:
  * losses/mix_softmax_cross_entropy_loss.py:27-35.  result (device float[2]) = {mean loss, non-ignored count}. */
 size_t emrt_ce_workspace_bytes(void);
