@@ -90,8 +90,11 @@ class GraphSequence:
 
 class TrainEngine:
     def __init__(self, model, optimizer, loss_fn, world_size=1, use_graph=True, warmup_eager=2, bucket_elems=32 * 1024 * 1024,
-                 overlap=False, two_phase=None, early_exchange=True, exchange_dtype=None):
+                 overlap=False, two_phase=None, early_exchange=True, exchange_dtype=None, batch_source=None):
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
+        # batch_source (datasets.SceneSampler): the engine owns the batch buffers and the source's fill(images, labels) runs at the head of every
+        # step -- its launches are part of the captured step, so step() takes no tensors and nothing is staged between replays
+        self.batch_source = batch_source
         self.world = world_size
         self.use_graph = use_graph
         self.warmup_eager = warmup_eager
@@ -100,6 +103,10 @@ class TrainEngine:
         self.images = self.labels = None
         self.loss_t = None
         c = ctx()
+        if batch_source is not None:
+            B, OH, OW = batch_source.batch_shape
+            self.images = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=c.device)
+            self.labels = torch.empty((B, OH, OW), dtype=torch.int64, device=c.device)
         c.world_size = world_size
         c.sync_bn = True
         c.overlap = overlap            # False | "pair" | "deferred": wgrad on a second stream (runtime.Context.fork)
@@ -136,6 +143,8 @@ class TrainEngine:
         """split=False: the whole forward + backward, returns the loss tensor.  split=True: runs backward's first segment
         only and returns (loss tensor, [callable per remaining segment])."""
         c = ctx()
+        if self.batch_source is not None:      # this step's batch, drawn on the device from the step counter (before anything reads images / labels)
+            self.batch_source.fill(images, labels)
         _lib.lib().call("emrt_counter_add", Fn.P(c._seed), _SEED_STRIDE & 0x7FFFFFFFFFFFFFFF, c.stream)   # fresh dropout masks
         side = c.prologue_side and not c.overlap and not c.wgrad_side and getattr(self.model.store, "desc", None) is not None
         if side and self.model.store.dirty:      # master weights edited since the last step: the full refresh (forward mirror first) on this stream, now
@@ -201,8 +210,9 @@ class TrainEngine:
 
     def _capture(self, images, labels):
         c = ctx()
-        self.images = images.clone()
-        self.labels = labels.clone()
+        if self.batch_source is None:
+            self.images = images.clone()
+            self.labels = labels.clone()
         c.workspace(64 << 20)
         # the weight-gradient scratch is registered by the first bf16 training step, but never from inside a capture: when the captured
         # step IS the first one (warmup_eager=0, a re-capture after init_device) it has to exist before the capture begins, or the graph
@@ -241,8 +251,15 @@ class TrainEngine:
         _lib.lib().call("emrt_memcpy", ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), dst.numel() * dst.element_size(), ctx().stream)
 
     # -- public ------------------------------------------------------------------------------------
-    def step(self, images, labels):
-        """images fp32 [B,3,H,W], labels int64 [B,H,W] on the device.  Returns the device loss tensor (float[1])."""
+    def step(self, images=None, labels=None):
+        """images fp32 [B,3,H,W], labels int64 [B,H,W] on the device; with a batch_source, no arguments: the source fills the engine's own
+        buffers inside the step.  Returns the device loss tensor (float[1])."""
+        if self.batch_source is not None:
+            if images is not None or labels is not None:
+                raise ValueError("TrainEngine.step: this engine draws its batches from its batch_source; step() takes no tensors")
+            images, labels = self.images, self.labels
+        elif images is None or labels is None:
+            raise ValueError("TrainEngine.step: images and labels are required (the engine has no batch_source)")
         self.model.train()
         self.calls += 1
         if not self.use_graph or self.calls <= self.warmup_eager:

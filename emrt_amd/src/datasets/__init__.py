@@ -7,8 +7,11 @@ Directory layouts are the reference's:
       labels are class indices 0..5, 255 = ignore
   LoveDA:  <root>/Train/images_png/<n>.png + <root>/Train/masks_png/<n>.png ; <root>/Val/...
       masks are 1..7 with 0 = ignore: shifted by -1, ignore -> 255 (loveda.py:58-70)
+Whole scenes (train.py --data scenes; no counterpart in the reference): <root>/images/<name>.* + <root>/labels/<name>.* (uint8 class indices),
+optionally <root>/val_images + <root>/val_labels: SceneBank keeps them in device memory, SceneSampler cuts the training tiles there.
 """
 import contextlib
+import ctypes
 import os
 import queue
 import threading
@@ -263,3 +266,209 @@ class DeviceTileLoader(TileLoader):
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
             src = buf.to(dev, non_blocking=True)
             return F.augment_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut)
+
+
+# ---- whole scenes resident in device memory (train.py --data scenes) -----------------------------------------------------------
+
+class _SceneEntry(ctypes.Structure):       # EmrtSceneEntry (include/emrt_hip.h)
+    _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+MAX_SCALES = 16           # csrc/augment.hip SCENE_MAX_SCALES: scale entries of one emrt_scene_draw launch
+DRAW_COLS = 10            # a row of the draw table: scene, y0, x0, scale_index, h, w, off_y, off_x, flip, 0
+
+
+def _free_device_bytes(device):
+    """Free memory of a GPU in bytes; None for a host `device` (the CPU tests: no limit is checked there)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return None
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+@contextlib.contextmanager
+def _no_pixel_limit():
+    """PIL refuses images above ~179 Mpixel as decompression bombs; an ISPRS scene mosaic may be larger and is the user's own file."""
+    old, Image.MAX_IMAGE_PIXELS = Image.MAX_IMAGE_PIXELS, None
+    try:
+        yield
+    finally:
+        Image.MAX_IMAGE_PIXELS = old
+
+
+def scene_files(img_dir, label_dir):
+    """-> [(name, image path, label path)] in name order: every file of img_dir with the file of label_dir that has the same name, or the same
+    stem when the extensions differ (a .tif scene with its .png class map).  A scene without a label map is an error, by name."""
+    if not os.path.isdir(img_dir):
+        raise FileNotFoundError("scenes: no directory %s" % img_dir)
+    labels = {}
+    for f in sorted(os.listdir(label_dir)) if os.path.isdir(label_dir) else []:
+        labels.setdefault(os.path.splitext(f)[0], f)
+    out = []
+    for f in sorted(os.listdir(img_dir)):
+        lab = f if os.path.exists(os.path.join(label_dir, f)) else labels.get(os.path.splitext(f)[0])
+        if lab is None:
+            raise FileNotFoundError("scenes: %s has no label map named %s.* under %s" % (os.path.join(img_dir, f), os.path.splitext(f)[0], label_dir))
+        out.append((os.path.splitext(f)[0], os.path.join(img_dir, f), os.path.join(label_dir, lab)))
+    if not out:
+        raise ValueError("scenes: %s holds no images" % img_dir)
+    return out
+
+
+class SceneBank:
+    """Whole training scenes in ONE uint8 device buffer: <root>/images/* (RGB) with the same-named uint8 class-index maps of <root>/labels/* (the
+    format of the *_convert_labels trees).  Scene i is its HWC image at img_off[i] followed by its HW label map at lab_off[i].
+
+    bank.buffer     uint8 [nbytes] on `device`
+    bank.sizes      [(H, W)] per scene, bank.names their file stems, bank.offsets [(img_off, lab_off)]
+    bank.tables(th, tw) -> the scene table and the cumulative table of tile origins, on the device and as the host mirrors the entry points
+                    check (emrt_scene_draw / emrt_scene_sample)
+    label_shift     the dataset's label shift (LoveDA: 1), applied by the sampler through label_lut"""
+
+    def __init__(self, root, device, label_shift=0):
+        self.root, self.device, self.label_shift = root, torch.device(device), int(label_shift)
+        files = scene_files(os.path.join(root, "images"), os.path.join(root, "labels"))
+        self.names, self.sizes, self.offsets = [], [], []
+        total = 0
+        with _no_pixel_limit():
+            for name, ip, lp in files:          # headers only: sizes and modes are known before a byte is decoded or uploaded
+                with Image.open(ip) as im, Image.open(lp) as lab:
+                    if im.mode != "RGB":
+                        raise ValueError("scenes: %s is a %s image; the bank holds 8-bit RGB scenes" % (ip, im.mode))
+                    if lab.mode not in ("L", "P"):
+                        raise ValueError("scenes: %s is a %s image; label maps are uint8 class indices (modes L or P)" % (lp, lab.mode))
+                    if im.size != lab.size:
+                        raise ValueError("scenes: %s is %dx%d but its label map %s is %dx%d" % (ip, im.size[1], im.size[0], lp, lab.size[1], lab.size[0]))
+                    W, H = im.size
+                self.names.append(name)
+                self.sizes.append((H, W))
+                self.offsets.append((total, total + 3 * H * W))
+                total += 4 * H * W
+            self.nbytes = total
+            free = _free_device_bytes(self.device)
+            if free is not None and total > free:
+                raise MemoryError("scenes: the bank of %d scenes needs %d bytes, the device has %d bytes free" % (len(files), total, free))
+            self.buffer = torch.empty(total, dtype=torch.uint8, device=self.device)
+            for (name, ip, lp), (io, lo), (H, W) in zip(files, self.offsets, self.sizes):
+                img = np.array(Image.open(ip).convert("RGB"), dtype=np.uint8)         # read_image's / read_label's calls, kept in uint8
+                lab = np.array(Image.open(lp).convert("P"), dtype=np.uint8)
+                self.buffer[io:lo].copy_(torch.from_numpy(img.reshape(-1)))
+                self.buffer[lo:lo + H * W].copy_(torch.from_numpy(lab.reshape(-1)))
+        self._tables = {}
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def origins(self, th, tw):
+        """Tile origins per scene, (H - th + 1) * (W - tw + 1); a tile larger than a scene is an error naming both."""
+        for i, (H, W) in enumerate(self.sizes):
+            if th > H or tw > W:
+                raise ValueError("scenes: the %dx%d tile is larger than scene %d (%s, %dx%d)" % (th, tw, i, self.names[i], H, W))
+        return [(H - th + 1) * (W - tw + 1) for H, W in self.sizes]
+
+    def tables(self, th, tw):
+        """-> (scenes_dev uint8 tensor, cum_dev int64 tensor, scenes_host ctypes array, cum_host ctypes array) for a th x tw tile."""
+        if (th, tw) not in self._tables:
+            n = len(self)
+            host = (_SceneEntry * n)(*[_SceneEntry(io, lo, H, W) for (io, lo), (H, W) in zip(self.offsets, self.sizes)])
+            cum = np.concatenate([[0], np.cumsum(self.origins(th, tw), dtype=np.int64)]).astype(np.int64)
+            cum_host = (ctypes.c_longlong * (n + 1))(*cum.tolist())
+            scenes_dev = torch.from_numpy(np.frombuffer(bytes(host), dtype=np.uint8).copy()).to(self.device)
+            cum_dev = torch.from_numpy(cum).to(self.device)
+            self._tables[(th, tw)] = (scenes_dev, cum_dev, host, cum_host)
+        return self._tables[(th, tw)]
+
+
+class SceneSampler:
+    """The training batches of `--data scenes`: SceneSampler(bank, transforms, batch_size, seed, rank).fill(images, labels) enqueues two launches on
+    the current stream -- emrt_scene_draw (every random decision of the batch, from the device step counter) and emrt_scene_sample (the transform
+    chain on the drawn windows) -- and touches nothing else, so it can run inside a captured training step.
+
+    `transforms` is one of the two chains DevicePlan accepts.  Potsdam / Vaihingen: the source tile is the crop size, the scale table is
+    ResizeStepScaling.resized(factor, th, tw) over its np.linspace factors (Python's round stays on the host).  [Normalize] alone (LoveDA): pass
+    `tile` = (h, w); one scale entry of the tile's own size, no flip.  The bank's label_shift goes down as label_lut.
+    The draws are a pure function of (seed, step counter, rank, sample): restoring the step counter continues the same data stream."""
+
+    def __init__(self, bank, transforms, batch_size, seed, rank=0, tile=None):
+        self.bank, self.plan = bank, DevicePlan(list(transforms))
+        dp = self.plan
+        if dp.crop is not None:
+            crop = dp.crop.size()
+            if tile is not None and tuple(tile) != tuple(crop):
+                raise ValueError("scenes: the source tile of this chain is its crop size %r, got tile %r" % (crop, tuple(tile)))
+            self.tile = self.crop = (int(crop[0]), int(crop[1]))
+            sc = dp.scaling
+            if sc.min_scale_factor == sc.max_scale_factor:
+                factors = [sc.min_scale_factor]
+            elif sc.scale_step_size == 0:
+                raise ValueError("scenes: ResizeStepScaling with scale_step_size 0 draws a continuous factor; the device sampler draws from a table of steps")
+            else:
+                factors = np.linspace(sc.min_scale_factor, sc.max_scale_factor, int((sc.max_scale_factor - sc.min_scale_factor) / sc.scale_step_size + 1)).tolist()
+            self.scales = [type(sc).resized(f, *self.tile) for f in factors]
+            self.flip_prob = float(dp.flip.prob)
+        else:
+            if tile is None:
+                raise ValueError("scenes: a chain without RandomPaddingCrop needs the tile size, tile=(h, w)")
+            self.tile = self.crop = (int(tile[0]), int(tile[1]))
+            self.scales = [self.tile]
+            self.flip_prob = 0.0
+        if not 1 <= len(self.scales) <= MAX_SCALES:
+            raise ValueError("scenes: %d scale steps; the device sampler takes 1 to %d" % (len(self.scales), MAX_SCALES))
+        if min(min(s) for s in self.scales) < 1:
+            raise ValueError("scenes: a scale step resizes the %r tile to nothing: %r" % (self.tile, self.scales))
+        if not 0.0 <= self.flip_prob <= 1.0:
+            raise ValueError("scenes: flip probability %r is outside [0, 1]" % self.flip_prob)
+        self.batch_size, self.rank = int(batch_size), int(rank)
+        if self.batch_size < 1 or self.rank < 0:
+            raise ValueError("scenes: batch_size must be positive and rank non-negative, got %r and %r" % (batch_size, rank))
+        self.key = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.total_origins = sum(bank.origins(*self.tile))
+        self.lut = label_lut(bank.label_shift)
+        self.draws = torch.zeros((self.batch_size, DRAW_COLS), dtype=torch.int32, device=bank.device)
+        self._tables = bank.tables(*self.tile)       # uploaded here: fill() may run under stream capture, where no host -> device copy can
+        # the HOST arguments of the two launches, built once: constants of the run, safe to bake into a captured graph
+        self._scale_hw = (ctypes.c_int * (2 * len(self.scales)))(*[int(v) for hw in self.scales for v in hw])
+        self._mean = (ctypes.c_double * 3)(*[float(v) for v in dp.mean])
+        self._stdinv = (ctypes.c_double * 3)(*[float(v) for v in dp.stdinv])
+        self._pad = (ctypes.c_float * 3)(*[float(v) for v in dp.img_pad])
+        self._lut = None if self.lut is None else (ctypes.c_ubyte * 256)(*[int(v) for v in self.lut])
+
+    @property
+    def batch_shape(self):
+        """(B, OH, OW) of the batches fill() writes."""
+        return (self.batch_size,) + self.crop
+
+    def fill(self, images, labels):
+        """images fp32 [B, 3, OH, OW], labels int64 [B, OH, OW], contiguous, on the bank's device: the next batch, on the current stream."""
+        from ... import functional as Fn
+        from ...runtime import ctx
+        B, (OH, OW), (th, tw) = self.batch_size, self.crop, self.tile
+        if images.dtype != torch.float32 or tuple(images.shape) != (B, 3, OH, OW) or not images.is_contiguous():
+            raise ValueError("scenes: images must be contiguous fp32 %r, got %s %r" % ((B, 3, OH, OW), images.dtype, tuple(images.shape)))
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B, OH, OW) or not labels.is_contiguous():
+            raise ValueError("scenes: labels must be contiguous int64 %r, got %s %r" % ((B, OH, OW), labels.dtype, tuple(labels.shape)))
+        c = ctx()
+        scenes_dev, cum_dev, scenes_host, cum_host = self._tables
+        n = len(self.bank)
+        key = self.key - (1 << 64) if self.key >= (1 << 63) else self.key         # the same 64 bits as a C long long
+        L = Fn._L()
+        L.call("emrt_scene_draw", Fn.P(c.step_counter), Fn.P(scenes_dev), Fn.P(cum_dev), ctypes.cast(scenes_host, ctypes.c_void_p),
+               ctypes.cast(cum_host, ctypes.c_void_p), n, self.bank.nbytes, key, self.rank, B, th, tw, OH, OW, self.flip_prob,
+               ctypes.cast(self._scale_hw, ctypes.c_void_p), len(self.scales), Fn.P(self.draws), c.stream)
+        L.call("emrt_scene_sample", Fn.P(self.bank.buffer), self.bank.nbytes, Fn.P(scenes_dev), ctypes.cast(scenes_host, ctypes.c_void_p), n,
+               Fn.P(self.draws), B, th, tw, OH, OW, ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._stdinv, ctypes.c_void_p),
+               ctypes.cast(self._pad, ctypes.c_void_p), int(self.plan.label_pad),
+               None if self._lut is None else ctypes.cast(self._lut, ctypes.c_void_p), Fn.P(images), 3 * OH * OW, Fn.P(labels), c.stream)
+
+
+class SceneVal(Dataset):
+    """The validation scenes of a scene tree, <root>/val_images/* with <root>/val_labels/*, as a `val` Dataset (what ValTiles / evaluate() take)."""
+
+    def __init__(self, transforms, dataset_root, num_classes, label_shift=0):
+        self.transforms, self.mode, self.num_classes, self.ignore_index = Compose(transforms), "val", num_classes, 255
+        self.dataset_root, self.label_shift = dataset_root, label_shift
+        self.file_list = [[ip, lp] for _, ip, lp in scene_files(os.path.join(dataset_root, "val_images"), os.path.join(dataset_root, "val_labels"))]
+
+    def __getitem__(self, idx):
+        with _no_pixel_limit():
+            return super().__getitem__(idx)

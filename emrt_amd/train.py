@@ -12,6 +12,8 @@ The dataset pipeline (cv2 / Potsdam readers) is outside this path: tiles come fr
 random tiles of DATA.CROP_SIZE, resident on the device) or from an .npz of pre-cut tiles (--data file.npz with arrays
 `images` [N,3,H,W] float32 normalised and `labels` [N,H,W] int64).  --data dataset reads the reference's directory layout;
 --device_transforms then runs its training transforms on the GPU (DeviceTileLoader) instead of in the reader threads.
+--data scenes uploads the whole scenes of <DATA.DATA_PATH>/images + /labels once (SceneBank) and cuts every training tile out of device memory
+inside the captured step (SceneSampler): no reader threads, no per-step copy; periodic evaluation reads <root>/val_images + /val_labels.
 """
 import argparse
 import os
@@ -36,7 +38,8 @@ def parse_args(argv=None):
                    default=os.path.join(os.path.dirname(__file__), "configs/EMRT/EMRT_256x256_160k_potsdam.yaml"), help="The config file.")
     p.add_argument("--seed", dest="seed", default=1234, type=int, help="Set the random seed during training.")
     p.add_argument("--data", default="synthetic", help="'synthetic', 'dataset' (DATA.DATASET under DATA.DATA_PATH, the reference's "
-                   "directory layout) or a .npz of pre-cut tiles")
+                   "directory layout), 'scenes' (whole scenes under DATA.DATA_PATH/images + /labels, resident on the GPU; tiles are cut "
+                   "there at random positions) or a .npz of pre-cut tiles")
     p.add_argument("--data_path", default=None, help="override DATA.DATA_PATH of the yaml")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--iters", type=int, default=None, help="override TRAIN.ITERS.  Under WarmupPolyLR a value at or below LR_SCHEDULER.WARM_UP_STEPS also shortens the "
@@ -68,6 +71,22 @@ def shorten_warmup(config, iters, verbose=True):
         print("[train] --iters %d is not more than LR_SCHEDULER.WARM_UP_STEPS %d: warming up over %d steps instead" % (iters, sch.WARM_UP_STEPS, new), flush=True)
     sch.WARM_UP_STEPS = new
     return True
+
+
+class _Steps:
+    """Stands where the tile sampler stands in the training loop when the batches are drawn on the device (--data scenes): `n` steps per epoch."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def set_epoch(self, epoch):
+        pass
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        return iter([None] * self.n)
 
 
 class TimeAverager:  # utils/timer.py:17-40
@@ -107,6 +126,9 @@ def synthetic_tiles(n, crop, ncls, seed, device):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.device_transforms and args.data == "scenes":
+        raise SystemExit("[train] --device_transforms cannot be combined with --data scenes: it augments the decoded tiles of --data dataset; "
+                         "--data scenes already runs the transforms on the GPU, on tiles cut from the resident scenes")
     if args.device_transforms and args.data != "dataset":
         raise SystemExit("[train] --device_transforms needs --data dataset (it augments decoded tiles; --data %s has none)" % args.data)
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
@@ -127,6 +149,10 @@ def main(argv=None):
         config.SAVE_DIR = args.save_dir
     if args.data_path:
         config.DATA.DATA_PATH = args.data_path
+    if args.data == "scenes" and not args.no_eval:      # said at start-up, not at the first checkpoint
+        root = config.DATA.DATA_PATH
+        if not (os.path.isdir(os.path.join(root, "val_images")) and os.path.isdir(os.path.join(root, "val_labels"))):
+            raise SystemExit("[train] --data scenes: %s has no val_images/ and val_labels/ for the periodic evaluation; add them or pass --no-eval" % root)
     model = get_model(config)
     if config.MODEL.PRETRAINED:
         # MODEL.PRETRAINED / --pretrained_backbone (config.py:245-246): a whole-model file (.pdparams or torch) or an ImageNet
@@ -151,8 +177,19 @@ def main(argv=None):
     loss_func = get_loss_function(config)
     bs = config.DATA.BATCH_SIZE
     dev = torch.device("cuda", local_rank)
-    loader = None
-    if args.data == "synthetic":
+    loader = source = None
+    if args.data == "scenes":           # whole scenes resident in device memory; every batch is cut and augmented inside the step
+        from .src.datasets import SceneBank, SceneSampler
+        from .src.transforms import get_transforms
+        root = config.DATA.DATA_PATH
+        tile = (config.DATA.CROP_SIZE[1], config.DATA.CROP_SIZE[0])        # CROP_SIZE is (w, h)
+        bank = SceneBank(root, dev, label_shift=1 if config.DATA.DATASET == "LoveDA" else 0)
+        source = SceneSampler(bank, get_transforms(config), bs, args.seed, rank, tile=tile)
+        n_tiles = None
+        if rank == 0:
+            print("[train] data: %d scenes resident on the GPU (%.1f MB), %d tile origins, %d scale steps; tiles are drawn and cut on the device" % (
+                len(bank), bank.nbytes / 1e6, source.total_origins, len(source.scales)), flush=True)
+    elif args.data == "synthetic":
         images, labels = synthetic_tiles(max(4 * bs * nranks, 64), config.DATA.CROP_SIZE, config.DATA.NUM_CLASSES, args.seed, dev)
         n_tiles = images.shape[0]
     elif args.data == "dataset":        # the reference's pipeline: DATA.DATASET under DATA.DATA_PATH (train.py:79-86)
@@ -164,7 +201,10 @@ def main(argv=None):
         z = np.load(args.data)
         images, labels = torch.from_numpy(z["images"]).float().to(dev), torch.from_numpy(z["labels"]).long().to(dev)
         n_tiles = images.shape[0]
-    sampler = DistributedTileSampler(n_tiles, bs, rank, nranks, shuffle=True, drop_last=True, seed=args.seed)
+    if source is not None:              # an "epoch" of the log line: as many tiles as the scenes hold side by side
+        sampler = _Steps(max(1, -(-source.total_origins // (tile[0] * tile[1] * bs * nranks))))
+    else:
+        sampler = DistributedTileSampler(n_tiles, bs, rank, nranks, shuffle=True, drop_last=True, seed=args.seed)
     if args.data == "dataset":
         import copy
         workers = max(1, config.DATA.NUM_WORKERS)
@@ -180,7 +220,7 @@ def main(argv=None):
         model.load_state_dict(ck["model"])
         optimizer.set_state_dict(ck["optimizer"])
         start_iter = ck["iter"]
-    engine = TrainEngine(model, optimizer, loss_func, nranks, use_graph=not args.no_graph)
+    engine = TrainEngine(model, optimizer, loss_func, nranks, use_graph=not args.no_graph, batch_source=source)
     if rank == 0:
         # the shipped yamls carry the reference authors' own disks as SAVE_DIR: a run that cannot checkpoint must say so
         # at once, not after 160k iterations (train.py:197-220 writes there unconditionally)
@@ -198,9 +238,13 @@ def main(argv=None):
     # ---- validation set for the periodic evaluation (train.py:88-100, 187-195; val_in_train.py:19-125) ---------------------
     val_images = val_labels = None
     if not args.no_eval:
-        if args.data == "dataset":
+        if args.data in ("dataset", "scenes"):
             from .src.transforms import get_val_transforms
-            ds_val = get_dataset(config, data_transform=get_val_transforms(config), mode="val")
+            if args.data == "scenes":
+                from .src.datasets import SceneVal
+                ds_val = SceneVal(get_val_transforms(config), config.DATA.DATA_PATH, config.DATA.NUM_CLASSES, bank.label_shift)
+            else:
+                ds_val = get_dataset(config, data_transform=get_val_transforms(config), mode="val")
             from .val import ValTiles       # decoded lazily, this rank's shard only, kept on the host between evaluations
             cache = {}
             val_images, val_labels = ValTiles(ds_val, 0, cache), ValTiles(ds_val, 1, cache)
@@ -230,12 +274,15 @@ def main(argv=None):
             cur_iter += 1
             reader_cost.record(time.time() - batch_start)
             lr = optimizer.get_lr()
-            if loader is not None:
-                bx, by = next(loader)       # decoded / augmented by the reader threads, already on the device
+            if source is not None:
+                loss_t = engine.step()      # the batch is drawn and cut inside the step
             else:
-                ib = torch.as_tensor(idx, device=dev)
-                bx, by = images[ib], labels[ib]
-            loss_t = engine.step(bx, by)
+                if loader is not None:
+                    bx, by = next(loader)       # decoded / augmented by the reader threads, already on the device
+                else:
+                    ib = torch.as_tensor(idx, device=dev)
+                    bx, by = images[ib], labels[ib]
+                loss_t = engine.step(bx, by)
             pending.append(loss_t.clone())          # no device->host sync per step (the reference syncs here, :160)
             batch_cost.record(time.time() - batch_start, num_samples=bs)
             if cur_iter % config.LOGGING_INFO_FREQ == 0:

@@ -165,6 +165,28 @@ typedef struct EmrtAugDesc {
   int flip;                              /* 1 = horizontal flip after the crop */
 } EmrtAugDesc;
 int emrt_augment_tiles(const void* src, size_t src_bytes, const EmrtAugDesc* descs, int B, int OH, int OW, const double* mean, const double* stdinv, const float* img_pad, int label_pad, const unsigned char* label_lut, float* out, long long out_bs, long long* labels, void* stream);
+/* Training tiles cut out of whole scenes that are resident in device memory (train.py --data scenes): the same chain as above, with
+ * the random decisions drawn on the device from the step counter, so both launches can sit inside a captured training step and a replay cuts a new
+ * batch.  bank: ONE device buffer of bank_bytes uint8; scene i is an HWC RGB image at img_off and an HW label map at lab_off, H x W.  The scene
+ * table exists twice with the same content: `scenes` in DEVICE memory for the kernels, `scenes_host` for the checks (likewise cum_origins, int64
+ * [n_scenes + 1]: cum[0] = 0, cum[i + 1] - cum[i] = (H_i - th + 1) * (W_i - tw + 1), the tile origins of scene i).
+ * emrt_scene_draw: one thread per sample writes one row of draws, int32 [B][10] = scene, y0, x0, scale_index, h, w, off_y, off_x, flip, 0.
+ *   Philox4x32-10 with key = (low, high word of `key`) and counter = (low, high word of *step_counter, rank * B + b, j), j = 0, 1, 2 the sample's
+ *   128-bit blocks; a 64-bit value is (word[2k + 1] << 32) | word[2k] and a uniform integer below n is the high 64 bits of value * n.
+ *   block 0: words 0-1 the tile origin among cum[n_scenes] (scene by binary search, y0 = rem / (W - tw + 1), x0 = rem % (W - tw + 1)), words 2-3 the
+ *   scale index below n_scales; block 1: words 0-1 off_y below max(h, OH) - OH + 1, words 2-3 off_x likewise; block 2: flip = word 0 * 2^-32 <
+ *   flip_prob in double.  scale_hw: HOST, n_scales <= 16 resized sizes {h, w} of the th x tw tile.  step_counter is read on the DEVICE.
+ * emrt_scene_sample: emrt_augment_tiles' map, one thread per output pixel, with each sample's decisions read from its row of draws and its source
+ *   the th x tw window at (y0, x0) of scene `scene` (row pitch = the scene's W).  With the same decisions the output is bit-identical to
+ *   emrt_augment_tiles on a contiguous copy of the window.  Values of draws outside their ranges are clamped into them: no read leaves the bank.
+ * Both check on the host before any launch: pointers, B, the scale count, the tile against every scene (the message names scene and sizes), every
+ * scene inside bank_bytes, an increasing and consistent cumulative table, 0 <= flip_prob <= 1. */
+typedef struct EmrtSceneEntry {
+  long long img_off, lab_off;            /* byte offsets into bank */
+  int H, W;                              /* scene size */
+} EmrtSceneEntry;
+int emrt_scene_draw(const long long* step_counter, const EmrtSceneEntry* scenes, const long long* cum_origins, const EmrtSceneEntry* scenes_host, const long long* cum_origins_host, int n_scenes, size_t bank_bytes, long long key, int rank, int B, int th, int tw, int OH, int OW, double flip_prob, const int* scale_hw, int n_scales, int* draws, void* stream);
+int emrt_scene_sample(const unsigned char* bank, size_t bank_bytes, const EmrtSceneEntry* scenes, const EmrtSceneEntry* scenes_host, int n_scenes, const int* draws, int B, int th, int tw, int OH, int OW, const double* mean, const double* stdinv, const float* img_pad, int label_pad, const unsigned char* label_lut, float* out, long long out_bs, long long* labels, void* stream);
 
 /* ---- BatchNorm / SyncBatchNorm (train: fp64 sums [from the conv epilogue or emrt_bn_stats] -> [all-reduce of sums across
  * ranks] -> apply; eval: running statistics).  replaces nn.BatchNorm2D / nn.SyncBatchNorm (+ReLU, + residual add):
