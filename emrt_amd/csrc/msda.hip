@@ -33,13 +33,15 @@ struct MsdaArgs {
   float inv_h[4], inv_w[4];   // 1/H_l, 1/W_l: the offset normalisation off / (W, H) as a multiply (exact for power-of-two maps)
   // backward only
   const void* dout;
-  float* dvalue;      // fp32 [B][Lv][M*32] dense, accumulated with atomics (caller zeroes)
-  long long dv_bs;
+  int g_guard;        // zero guard pixels on both sides of a scatter slab (widest level + 2): corners whose weight is 0 are still ADDED
+                      // (branch-free inner loop) and may fall up to W + 1 pixels outside the block's range
+  int gmax_n;         // max |dout| partials per (batch, head) slice; 0: the scatter scans dout itself
+  float* gmax;        // [B*M][gmax_n], left by the gradient stage for the scatter
   void* doffw;        // [B*Lq][ldo] (offset + logit gradients), fully overwritten: fp32, or the compute dtype T when doffw_t
   int doffw_t;
   float* dref;        // fp32 [B][Lq][ref_L][2] or null, fully overwritten
   float* probs;       // fp32 [B*Lq][M*L*P] softmax probabilities (written by the gradient kernel, read by the LDS scatter)
-  void* dvalue_t;     // LDS path: [B][Lv][M*32] in the compute dtype, fully overwritten
+  void* dvalue_t;     // [B][Lv][M*32] in the compute dtype, fully overwritten by the scatter
   int Lv;
   int g_level[16], g_pix0[16], g_npix[16];   // scatter blocks: (level, first flat pixel, pixel count) of each LDS slab range
   int g_npix_max;                         // largest g_npix (+ the two guard bands): the per-half-wave sample records sit behind a slab of that size
@@ -48,10 +50,6 @@ struct MsdaArgs {
   int* part;                              // int32 partial slabs of the query-split blocks, [B * M][part_stride]
   long long part_stride;
   int f_n, f_pix0[8], f_npix[8], f_nqs[8], f_part[8];      // the ranges that were split: summed and written by msda_bwd_value_finalize_kernel
-  int g_guard;                            // zero guard pixels on both sides of a scatter slab (widest level + 2): corners whose weight is 0 are
-                                          // still ADDED (branch-free inner loop) and may fall up to W + 1 pixels outside the block's range
-  float* gmax;        // [B*M][gmax_n] per-block max |dout| of a (batch, head) slice, left by the LDS gradient kernel for the scatter
-  int gmax_n;         // 0: the scatter scans dout itself
 };
 
 template <class T>
@@ -643,10 +641,11 @@ __device__ __forceinline__ float quad_sum(float v) {  // sum over the 4 lanes th
   return v;
 }
 
-// Backward with recompute.  grad_value is scattered with fp32 atomics (v1; LDS-privatised slabs are the planned
-// follow-up); offset/logit gradients are written by lane sub==0 of each quad; the reference-point
-// gradient (decoder only) is reduced over the 8 heads of a query inside the wave.
-template <class T, int L, int P, bool ATOMIC_DV>
+// Gradient kernel with recompute, corners gathered from L2 (fp32 maps, slabs that do not fit, small calls, the decoder's dref): the
+// offset / logit gradients and the softmax probabilities are written by lane sub == 0 of each quad; the reference-point gradient
+// (decoder only) is reduced over the 8 heads of a query inside the wave.  The value gradient is NOT made here: the scatter kernels
+// (msda_bwd_value_mfma_kernel / msda_bwd_value_lds_kernel) build it from the probabilities this kernel leaves.
+template <class T, int L, int P>
 __global__ __launch_bounds__(256) void msda_bwd_kernel(MsdaArgs a) {
   constexpr int LP = L * P;
   const int lane = threadIdx.x & 63;
@@ -676,23 +675,12 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(MsdaArgs a) {
 #pragma unroll
   for (int i = 0; i < LP; ++i) pr[i] *= inv;
 
-  float go[8];
   typename Dot8<T>::Raw go_raw = Dot8<T>::zero();
-  if constexpr (ATOMIC_DV) {
-    load8<T>((const T*)a.dout + bq * (a.M * 32) + m * 32 + sub * 8, go);
-    if (!live) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) go[e] = 0.f;
-    }
-  } else {
-    if (live) go_raw = Dot8<T>::load((const T*)a.dout + bq * (a.M * 32) + m * 32 + sub * 8);
-  }
+  if (live) go_raw = Dot8<T>::load((const T*)a.dout + bq * (a.M * 32) + m * 32 + sub * 8);
 
   const T* vb = (const T*)a.value + (long long)b * a.v_bs + m * 32 + sub * 8;
-  float* gvb = a.dvalue + (long long)b * a.dv_bs + m * 32 + sub * 8;
   const float* refp = a.ref + (long long)b * a.ref_bs + (long long)q * a.ref_L * 2;
   const int rls = a.ref_L == 1 ? 0 : 2;
-  const int ldg = a.M * 32;
 
   float dA[LP];          // d loss / d attention prob
   float gx[LP], gy[LP];  // d loss / d pixel coordinate (== d offset)
@@ -701,7 +689,6 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(MsdaArgs a) {
     const int H = a.h[l], W = a.w[l];
     const float rx = refp[l * rls], ry = refp[l * rls + 1];
     const T* vl = vb + (long long)a.start[l] * a.ldv;
-    float* gl = gvb + (long long)a.start[l] * ldg;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       const int i = l * P + p;
@@ -715,43 +702,11 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(MsdaArgs a) {
       const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
       const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
       float d00 = 0.f, d01 = 0.f, d10 = 0.f, d11 = 0.f;   // <dout, v_corner> over this lane's 8 channels
-      if constexpr (!ATOMIC_DV) {
-        const long long o00 = (long long)y0 * W + x0;
-        if (vy0 && vx0) d00 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + o00 * a.ldv));
-        if (vy0 && vx1) d01 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + (o00 + 1) * a.ldv));
-        if (vy1 && vx0) d10 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + (o00 + W) * a.ldv));
-        if (vy1 && vx1) d11 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + (o00 + W + 1) * a.ldv));
-      } else {
-      float v[8];
-      if (vy0 && vx0) {
-        const long long off = (long long)y0 * W + x0;
-        load8<T>(vl + off * a.ldv, v);
-        const float c = aw * (1.f - ly) * (1.f - lx);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { d00 = fmaf(go[e], v[e], d00); if (live) atomicAdd(gl + off * ldg + e, c * go[e]); }
-      }
-      if (vy0 && vx1) {
-        const long long off = (long long)y0 * W + x0 + 1;
-        load8<T>(vl + off * a.ldv, v);
-        const float c = aw * (1.f - ly) * lx;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { d01 = fmaf(go[e], v[e], d01); if (live) atomicAdd(gl + off * ldg + e, c * go[e]); }
-      }
-      if (vy1 && vx0) {
-        const long long off = (long long)(y0 + 1) * W + x0;
-        load8<T>(vl + off * a.ldv, v);
-        const float c = aw * ly * (1.f - lx);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { d10 = fmaf(go[e], v[e], d10); if (live) atomicAdd(gl + off * ldg + e, c * go[e]); }
-      }
-      if (vy1 && vx1) {
-        const long long off = (long long)(y0 + 1) * W + x0 + 1;
-        load8<T>(vl + off * a.ldv, v);
-        const float c = aw * ly * lx;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { d11 = fmaf(go[e], v[e], d11); if (live) atomicAdd(gl + off * ldg + e, c * go[e]); }
-      }
-      }
+      const long long o00 = (long long)y0 * W + x0;
+      if (vy0 && vx0) d00 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + o00 * a.ldv));
+      if (vy0 && vx1) d01 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + (o00 + 1) * a.ldv));
+      if (vy1 && vx0) d10 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + (o00 + W) * a.ldv));
+      if (vy1 && vx1) d11 = Dot8<T>::dot(go_raw, Dot8<T>::load(vl + (o00 + W + 1) * a.ldv));
       // dA, gx, gy are linear in the corner dots: combine per lane first, then 3 quad reductions instead of 4
       dA[i] = quad_sum((1.f - ly) * ((1.f - lx) * d00 + lx * d01) + ly * ((1.f - lx) * d10 + lx * d11));
       gx[i] = aw * quad_sum((1.f - ly) * (d01 - d00) + ly * (d11 - d10));
@@ -762,7 +717,7 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(MsdaArgs a) {
   float dot = 0.f;
 #pragma unroll
   for (int i = 0; i < LP; ++i) dot = fmaf(pr[i], dA[i], dot);
-  if (!ATOMIC_DV && live && sub == 0) {
+  if (live && sub == 0) {
     float* pp = a.probs + bq * (a.M * LP) + m * LP;
 #pragma unroll
     for (int i = 0; i < LP; ++i) pp[i] = pr[i];
@@ -1569,31 +1524,17 @@ static bool msda_mf_plan(const MsdaArgs& a, int L, MsdaMfPlan& pl, int& nbands) 
   return nbands <= 65535;
 }
 
-// The (levels, points) pairs the MSDA kernels are built for, named ONCE: f(integral_constant<int, L>, integral_constant<int, P>) launches the
-// instantiation and returns the entry point's int; any other pair is the caller's error `unsupported` under the name fn.  ONE_LEVEL = false
-// leaves (1, 4) out (the band kernels are not built for it).  A `static` local of the generic lambda f exists once per (L, P) -- and once per
-// element type when the caller is itself a template: one "LDS limit raised" flag per kernel instantiation.
-template <bool ONE_LEVEL = true, class F>
-static int with_levels_points(int L, int P, const char* fn, const char* unsupported, F&& f) {
+
+// ---- host side: one plan per call, one launcher ------------------------------------------------------------------------------------------
+// The (levels, points) pairs the MSDA kernels are built for, named ONCE: f(integral_constant<int, L>, integral_constant<int, P>) runs on
+// the instantiation and returns the entry point's int; any other pair is the caller's error under the name fn.
+template <class F>
+static int with_levels_points(int L, int P, const char* fn, F&& f) {
   if (L == 3 && P == 6) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 6>{});
   if (L == 4 && P == 4) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
   if (L == 3 && P == 4) return f(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{});
-  if constexpr (ONE_LEVEL)
-    if (L == 1 && P == 4) return f(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
-  return fail(fn, unsupported);
-}
-
-static int msda_launch_mf(const MsdaArgs& a, int L, int P, const MsdaMfPlan& pl, int nbands, hipStream_t st) {
-  size_t lds = (size_t)2 * pl.npix_cap * MSDA_MF_PITCH * 4 + 2 * 32 * MSDA_MF_GP * 2 + 64 * 4;
-  const size_t epi = (size_t)pl.npix_cap * 33 * 4;          // the epilogue's fp32 image starts at the first weight tile
-  if (lds < epi) lds = epi;
-  return with_levels_points(L, P, "emrt_msda_bwd", "unsupported (levels, points) for the matrix-product scatter", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_value_mfma_kernel<LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
-    hipLaunchKernelGGL((msda_bwd_value_mfma_kernel<LL, PP>), dim3(a.B * a.M, nbands), dim3(512), lds, st, a, pl);
-    return check_launch("emrt_msda_bwd(matrix-product scatter)");
-  });
+  if (L == 1 && P == 4) return f(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
+  return fail(fn, "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)");
 }
 
 // pixels of a scatter range: (npix + 2 guard) * 33 * 4 B of slab + 20 480 B of sample records must fit the 160 KiB LDS
@@ -1695,95 +1636,10 @@ static int msda_ranges(MsdaArgs& a, int L, int bm, bool allow_split) {
 
 extern "C" int emrt_msda_bwd_uses_lds(const int* shapes_hw, int L) {
   (void)shapes_hw;
-  return (L >= 1 && L <= 4) ? 1 : 0;     // pixel-range slabs fit for every map size
+  return (L >= 1 && L <= 4) ? 1 : 0;     // every legal call takes the LDS path: the pixel-range slabs fit for every map size
 }
 
-static int msda_fill(MsdaArgs& a, const int* shapes_hw, int L, int Lv);
-// Whether the query-split scatter may be planned for a call: it needs the max |dout| partials some gradient kernel leaves (every
-// path with Lq >= 1024 or the LDS / band gradient kernels does) -- decided from the same quantities in both functions below.
-static bool msda_split_allowed(int B, int Lq, int M, int dtype_is_2byte) {
-  (void)B;
-  return dtype_is_2byte && Lq >= 1024 && M <= 8 && 256 % (M * 4) == 0;
-}
-
-static size_t msda_part_offset_floats(int B, int Lq, int M, int L, int P) {      // where the partial slabs start inside the workspace
-  // max |dout| partials per (batch, head): Lq / 64 from the separate scan, <= Lq / 128 chunks from the LDS gradient kernel, up to 64 row
-  // bands from the band kernel whatever Lq is (narrow maps: ADVICE r3)
-  const size_t gparts = (size_t)((Lq + 63) / 64 > 64 ? (Lq + 63) / 64 : 64);
-  return ((size_t)B * Lq * M * L * P + 512 + 2 * (size_t)B * M + (size_t)B * M * gparts + 3) & ~(size_t)3;      // 16-byte aligned
-}
-
-extern "C" size_t emrt_msda_bwd_workspace_bytes(int B, int Lq, int M, int L, int P, const int* shapes_hw, int dtype) {
-  // softmax probabilities + per-block max |dout| partials (the LDS gradient kernel leaves at most 256 / (B M) + 1 per (batch, head), the
-  // separate scan Lq / 64) + the integer partial slabs of a query-split scatter (the plan emrt_msda_bwd will make for these shapes)
-  if (!shapes_hw || L < 1 || L > 4 || B < 1 || Lq < 1 || M < 1 || P < 1) {      // (a size that left the partial slabs out would be written past)
-    fail("emrt_msda_bwd_workspace_bytes", "needs the level shapes (L = 1..4) and positive sizes; returns 0");
-    return 0;
-  }
-  size_t n = msda_part_offset_floats(B, Lq, M, L, P);
-  {
-    MsdaArgs a;
-    memset(&a, 0, sizeof(a));
-    int Lv = 0;
-    for (int l = 0; l < L; ++l) Lv += shapes_hw[2 * l] * shapes_hw[2 * l + 1];
-    if (msda_fill(a, shapes_hw, L, Lv) == 0) {
-      int wmax = 1;
-      for (int l = 0; l < L; ++l) wmax = a.w[l] > wmax ? a.w[l] : wmax;
-      a.g_guard = wmax + 2;
-      if (msda_ranges(a, L, B * M, msda_split_allowed(B, Lq, M, dtype != EMRT_F32)) > 0) n += (size_t)B * M * (size_t)a.part_stride;
-    }
-  }
-  return n * sizeof(float);
-}
-
-template <class T>
-static int msda_launch(const MsdaArgs& a, int L, int P, int mode /*0 fwd, 1 bwd atomic, 2 bwd grads only*/, hipStream_t st) {
-  const long long pairs = (long long)a.B * a.Lq * a.M;
-  const unsigned grid = (unsigned)((pairs + 63) / 64);
-  return with_levels_points(L, P, "emrt_msda", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    if (mode == 0) hipLaunchKernelGGL((msda_fwd_kernel<T, LL, PP>), dim3(grid), dim3(256), 0, st, a);
-    else if (mode == 1) hipLaunchKernelGGL((msda_bwd_kernel<T, LL, PP, true>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((msda_bwd_kernel<T, LL, PP, false>), dim3(grid), dim3(256), 0, st, a);
-    return check_launch(mode ? "emrt_msda_bwd" : "emrt_msda_fwd");
-  });
-}
-
-// forward only (the one MSDA kernel fp16 inference needs)
-template <class T>
-static int msda_launch_fwd(const MsdaArgs& a, int L, int P, hipStream_t st) {
-  const long long pairs = (long long)a.B * a.Lq * a.M;
-  const unsigned grid = (unsigned)((pairs + 63) / 64);
-  return with_levels_points(L, P, "emrt_msda_fwd", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    hipLaunchKernelGGL((msda_fwd_kernel<T, LL, PP>), dim3(grid), dim3(256), 0, st, a);
-    return check_launch("emrt_msda_fwd");
-  });
-}
-
-template <class T>
-static int msda_launch_fwd_lds(const MsdaArgs& a, int L, int P, int chunks, int qpb, int guard, size_t slab, hipStream_t st) {
-  int threads = g_tune.msda_fwd_threads;
-  if (threads < 64 || threads > 1024 || (threads & 63)) threads = 1024;
-  return with_levels_points(L, P, "emrt_msda_fwd", "unsupported (levels, points): built for (3,6), (4,4), (3,4), (1,4)", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_fwd_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
-    hipLaunchKernelGGL((msda_fwd_lds_kernel<T, LL, PP>), dim3(a.B * a.M * chunks), dim3(threads), slab, st, a, qpb, chunks, guard, g_tune.msda_fwd_probe);
-    return check_launch("emrt_msda_fwd(lds)");
-  });
-}
-
-template <class T>
-static int msda_launch_fwd_band(const MsdaArgs& a, int L, int P, int NB, int halo, int guard, size_t slab, hipStream_t st) {
-  return with_levels_points<false>(L, P, "emrt_msda_fwd", "unsupported (levels, points) for the band kernel", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_fwd_band_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
-    hipLaunchKernelGGL((msda_fwd_band_kernel<T, LL, PP>), dim3(a.B * a.M * NB), dim3(1024), slab, st, a, NB, halo, guard);
-    return check_launch("emrt_msda_fwd(band)");
-  });
-}
+#define MSDA_LDS_MAX (159 * 1024)      // most dynamic LDS a kernel is launched with (the limit msda_go raises an instantiation to)
 
 // Band plan for a pyramid whose whole slab does not fit: the number of bands NB (every level's height divisible by it) and the halo
 // (rows staged beyond a band on both sides, the same for every level) with the largest halo <= 7 whose slab fits 159 KB; NB as small as
@@ -1805,46 +1661,14 @@ static bool msda_band_plan(const MsdaArgs& a, int L, int bm, int guard, int& NB_
         npx = ((npx + 15) & ~15) + rows * a.w[l];
       }
       const size_t slab = (size_t)(((npx + guard + 15) >> 4) << 4) * MSDA_FWD_PITCH;
-      if (slab <= 159 * 1024) { NB_out = NB; halo_out = halo; slab_out = slab; return true; }
+      if (slab <= MSDA_LDS_MAX) { NB_out = NB; halo_out = halo; slab_out = slab; return true; }
     }
   }
   return false;
 }
 
-template <class T>
-static int msda_launch_bwd_grad_lds(const MsdaArgs& a, int L, int P, int chunks, int qpb, int guard, size_t slab, hipStream_t st) {
-  return with_levels_points(L, P, "emrt_msda_bwd", "unsupported (levels, points)", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
-    hipLaunchKernelGGL((msda_bwd_lds_kernel<T, LL, PP>), dim3(a.B * a.M * chunks), dim3(1024), slab, st, a, qpb, chunks, guard);
-    return check_launch("emrt_msda_bwd(lds gradients)");
-  });
-}
-
-template <class T>
-static int msda_launch_bwd_grad_band(const MsdaArgs& a, int L, int P, int NB, int halo, int guard, size_t slab, hipStream_t st) {
-  return with_levels_points<false>(L, P, "emrt_msda_bwd", "unsupported (levels, points) for the band kernel", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_lds_kernel<T, LL, PP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
-    hipLaunchKernelGGL((msda_bwd_lds_kernel<T, LL, PP, true>), dim3(a.B * a.M * NB), dim3(1024), slab, st, a, NB, halo, guard);
-    return check_launch("emrt_msda_bwd(band gradients)");
-  });
-}
-
-template <class T>
-static int msda_launch_lds(const MsdaArgs& a, int L, int P, int ngroups, size_t lds, hipStream_t st) {
-  return with_levels_points(L, P, "emrt_msda_bwd", "unsupported (levels, points) for the LDS scatter", [&](auto ll, auto pp) {
-    constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)msda_bwd_value_lds_kernel<T, LL, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); attr = true; }
-    hipLaunchKernelGGL((msda_bwd_value_lds_kernel<T, LL, PP>), dim3(a.B * a.M, ngroups), dim3(1024), lds, st, a, ((g_tune.msda_fwd_probe >> 4) & 127) | (g_tune.msda_scatter_merge ? 128 : 0));
-    return check_launch("emrt_msda_bwd(lds scatter)");
-  });
-}
-
-static int msda_fill(MsdaArgs& a, const int* shapes_hw, int L, int Lv) {
+// the level geometry of a call; returns sum(h * w)
+static int msda_fill(MsdaArgs& a, const int* shapes_hw, int L) {
   int start = 0;
   for (int l = 0; l < 4; ++l) { a.h[l] = 1; a.w[l] = 1; a.start[l] = 0; a.inv_h[l] = 1.f; a.inv_w[l] = 1.f; }
   for (int l = 0; l < L; ++l) {
@@ -1855,7 +1679,176 @@ static int msda_fill(MsdaArgs& a, const int* shapes_hw, int L, int Lv) {
     a.start[l] = start;
     start += a.h[l] * a.w[l];
   }
-  return start == Lv ? 0 : -1;
+  return start;
+}
+
+// One launch of a call: what msda_go launches and emrt_msda_plan reports.
+struct MsdaStep { int kind /* EMRT_MSDA_K_* */; dim3 grid; int threads; size_t lds; };
+
+// Everything a call decides before it launches, decided ONCE by msda_plan: emrt_msda_fwd, emrt_msda_bwd, emrt_msda_bwd_workspace_bytes
+// and emrt_msda_plan all read this and decide nothing themselves.
+struct MsdaPlan {
+  MsdaArgs a;               // the kernel arguments the plan decides -- level geometry, guard, scatter ranges, query split, gmax_n -- every pointer null
+  int guard;                // zero pixels on both sides of a staged slab: widest level + 2
+  int chunks, qpb;          // LDS first stage: blocks per (batch, head) and queries per block
+  int NB, halo;             // band first stage: row bands and the rows staged beyond a band on both sides
+  MsdaMfPlan mf;            // bands of the matrix-product scatter
+  size_t gmax_off, part_off, ws_bytes;      // backward workspace: probabilities at 0, max |dout| partials and partial slabs at these float offsets; total bytes
+  MsdaStep step[4];         // the launches, in order: first stage (+ max |dout| scan), then for the backward the value-gradient scatter (+ finalize)
+  int nsteps;
+};
+
+// The plan of a call, or the call's refusal under the name fn (non-zero).  ws_bytes is 0 for sizes nothing can be sized from and valid
+// from there on, also when the call itself is refused further down (emrt_msda_bwd_workspace_bytes reports it either way).
+static int msda_plan(MsdaPlan& p, const char* fn, bool backward, int B, int Lq, int M, int L, int P, const int* shapes_hw, int dtype, bool want_dref) {
+  p = MsdaPlan{};
+  if (!shapes_hw || B < 1 || Lq < 1) return fail(fn, "needs the level shapes and positive B, Lq");
+  if (M < 1 || L < 1 || L > 4 || P < 1) return fail(fn, "bad M/L/P");
+  if (want_dref && M != 8) return fail(fn, "reference-point gradient needs M == 8");
+  MsdaArgs& a = p.a;
+  a.B = B; a.Lq = Lq; a.M = M;
+  a.Lv = msda_fill(a, shapes_hw, L);
+  const int bm = B * M;
+  const long long pairs = (long long)bm * Lq;
+  int wmax = 1;
+  for (int l = 0; l < L; ++l) wmax = a.w[l] > wmax ? a.w[l] : wmax;
+  p.guard = wmax + 2;
+  const size_t slab = (size_t)(a.Lv + 2 * p.guard) * MSDA_FWD_PITCH;      // the whole (batch, head) slab of the LDS first stage
+  // long scans: the max |dout| partials exist on every path (the LDS / band gradient kernels leave them, behind the global one the extra
+  // launch costs ~3 us) -- which is all the query split of the scatter needs
+  const bool long_scan = Lq >= 1024 && M <= 8 && 256 % (M * 4) == 0;
+  int ng = 0;
+  if (backward) {
+    a.g_guard = p.guard;
+    ng = msda_ranges(a, L, bm, dtype != EMRT_F32 && long_scan);
+    // workspace: softmax probabilities | 512 + 2 B M spare | max |dout| partials per (batch, head): Lq / 64 from the separate scan, <= Lq / 128
+    // chunks from the LDS gradient kernel, up to 64 row bands from the band kernel whatever Lq is | the integer partial slabs of a query split
+    const size_t gparts = (size_t)((Lq + 63) / 64 > 64 ? (Lq + 63) / 64 : 64);
+    p.gmax_off = (size_t)B * Lq * M * L * P;
+    p.part_off = (p.gmax_off + 512 + 2 * (size_t)bm + (size_t)bm * gparts + 3) & ~(size_t)3;      // 16-byte aligned
+    p.ws_bytes = (p.part_off + (ng > 0 ? (size_t)bm * (size_t)a.part_stride : 0)) * sizeof(float);
+  }
+  if (int rc = with_levels_points(L, P, fn, [](auto, auto) { return 0; })) return rc;
+  if (backward && ng <= 0) return fail(fn, "value map rows too long for the LDS slab");
+  auto step = [&p](int kind, dim3 grid, int threads, size_t lds) { p.step[p.nsteps++] = MsdaStep{kind, grid, threads, lds}; };
+
+  // first stage (forward: the whole call; backward: offset / logit gradients and probabilities).  The LDS-staged kernels are built for the
+  // 16-bit types (backward: bf16) and take calls of at least msda_lds_min_pairs (batch, head, query) pairs.
+  const bool staged = (backward ? dtype == EMRT_BF16 && !g_tune.msda_bwd_global : dtype != EMRT_F32 && !g_tune.msda_fwd_global) && pairs >= g_tune.msda_lds_min_pairs;
+  size_t bslab = 0;
+  if (staged && slab <= MSDA_LDS_MAX && (!want_dref || g_tune.msda_bwd_dref_lds)) {
+    // one block per CU (the slab takes most of its LDS): as close to 256 blocks as whole chunks of >= 128 queries allow
+    int chunks = (256 + bm / 2) / bm;
+    if (!backward && g_tune.msda_fwd_chunks > 0) chunks = g_tune.msda_fwd_chunks;
+    if (chunks > (Lq + 127) / 128) chunks = (Lq + 127) / 128;
+    if (chunks < 1) chunks = 1;
+    p.qpb = (Lq + chunks - 1) / chunks;
+    p.chunks = (Lq + p.qpb - 1) / p.qpb;
+    int threads = backward ? 1024 : g_tune.msda_fwd_threads;
+    if (threads < 64 || threads > 1024 || (threads & 63)) threads = 1024;
+    step(backward ? EMRT_MSDA_K_GRAD_LDS : EMRT_MSDA_K_FWD_LDS, dim3(bm * p.chunks), threads, slab);
+    if (backward) a.gmax_n = p.chunks;
+  } else if (staged && slab > MSDA_LDS_MAX && Lq == a.Lv && L >= 2 && !want_dref && msda_band_plan(a, L, bm, p.guard, p.NB, p.halo, bslab)) {
+    // self-attention over a pyramid too large for one slab: row bands
+    step(backward ? EMRT_MSDA_K_GRAD_BAND : EMRT_MSDA_K_FWD_BAND, dim3(bm * p.NB), 1024, bslab);
+    if (backward) a.gmax_n = p.NB;
+  } else {
+    step(backward ? EMRT_MSDA_K_GRAD_GLOBAL : EMRT_MSDA_K_FWD_GLOBAL, dim3((unsigned)((pairs + 63) / 64)), 256, 0);
+    if (backward && long_scan) {
+      a.gmax_n = (Lq + 63) / 64;
+      step(EMRT_MSDA_K_ABSMAX, dim3(B * a.gmax_n), 256, 0);
+    }
+  }
+  if (!backward) return 0;
+
+  // value-gradient scatter.  Matrix product: every band of a level re-reads and re-derives ALL queries' samples of that level: worth it while at
+  // most one level is cut in two (cfg2: 32 x 32 | 16 x 16 | 8 x 8 = 4 bands, 256 blocks at batch 8: 45 vs 59 us; cfg3's 64 x 64 level would be
+  // 8 bands: 323 vs 199 us per call).  knob msda_scatter_mfma: 0 = never, 1 = this rule, 2 = whenever a plan exists (tests)
+  int nbands = 0;
+  if (dtype == EMRT_BF16 && g_tune.msda_scatter_mfma && msda_mf_plan(a, L, p.mf, nbands) && (nbands <= L + 1 || g_tune.msda_scatter_mfma >= 2)) {
+    size_t lds = (size_t)2 * p.mf.npix_cap * MSDA_MF_PITCH * 4 + 2 * 32 * MSDA_MF_GP * 2 + 64 * 4;
+    const size_t epi = (size_t)p.mf.npix_cap * 33 * 4;          // the epilogue's fp32 image starts at the first weight tile
+    step(EMRT_MSDA_K_SCATTER_MF, dim3(bm, nbands), 512, lds < epi ? epi : lds);
+    return 0;
+  }
+  int npix_max = 0;
+  for (int g = 0; g < ng; ++g) npix_max = a.g_npix[g] > npix_max ? a.g_npix[g] : npix_max;
+  a.g_npix_max = (npix_max + 2 * p.guard + 3) & ~3;          // slab + both guard bands; keeps the records 16-byte aligned
+  step(EMRT_MSDA_K_SCATTER_LDS, dim3(bm, ng), 1024, (size_t)a.g_npix_max * MSDA_SLAB_PITCH * sizeof(int) + 32 * 32 * (sizeof(float4) + sizeof(int)));
+  if (a.f_n) step(EMRT_MSDA_K_FINALIZE, dim3(bm, a.f_n, 8), 256, 0);
+  return 0;
+}
+
+// The one launcher: kernel K with the step's grid, block and dynamic LDS.  An instantiation that needs more LDS than a kernel gets by
+// default has its limit raised once (the flag exists once per K).
+template <auto K, class... Args>
+static int msda_go(const MsdaStep& s, const char* what, hipStream_t st, const Args&... args) {
+  static bool raised = false;
+  if (s.lds > 64 * 1024 && !raised) { (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, MSDA_LDS_MAX); raised = true; }
+  hipLaunchKernelGGL(K, s.grid, dim3(s.threads), s.lds, st, args...);
+  return check_launch(what);
+}
+
+static int msda_run_fwd(const MsdaPlan& p, const MsdaArgs& a, int L, int P, int dtype, hipStream_t st) {
+  const MsdaStep& s = p.step[0];
+  return with_fwd_dtype("emrt_msda_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    return with_levels_points(L, P, "emrt_msda_fwd", [&](auto ll, auto pp) {
+      constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+      if constexpr (sizeof(T) == 2) {      // the LDS-staged kernels are built for the 16-bit types only, the band kernel for two levels or more
+        if (s.kind == EMRT_MSDA_K_FWD_LDS) return msda_go<msda_fwd_lds_kernel<T, LL, PP>>(s, "emrt_msda_fwd(lds)", st, a, p.qpb, p.chunks, p.guard, g_tune.msda_fwd_probe);
+        if constexpr (LL >= 2)
+          if (s.kind == EMRT_MSDA_K_FWD_BAND) return msda_go<msda_fwd_band_kernel<T, LL, PP>>(s, "emrt_msda_fwd(band)", st, a, p.NB, p.halo, p.guard);
+      }
+      return msda_go<msda_fwd_kernel<T, LL, PP>>(s, "emrt_msda_fwd", st, a);
+    });
+  });
+}
+
+static int msda_run_bwd(const MsdaPlan& p, const MsdaArgs& a, int L, int P, int dtype, hipStream_t st) {
+  return with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    return with_levels_points(L, P, "emrt_msda_bwd", [&](auto ll, auto pp) {
+      constexpr int LL = decltype(ll)::value, PP = decltype(pp)::value;
+      for (int i = 0; i < p.nsteps; ++i) {
+        const MsdaStep& s = p.step[i];
+        int rc = 1;      // stays 1 for a kernel that is not built for T (msda_plan stages bf16 calls only)
+        if (s.kind == EMRT_MSDA_K_GRAD_GLOBAL) rc = msda_go<msda_bwd_kernel<T, LL, PP>>(s, "emrt_msda_bwd", st, a);
+        if (s.kind == EMRT_MSDA_K_ABSMAX) rc = msda_go<msda_absmax_kernel<T>>(s, "emrt_msda_bwd(max |dout|)", st, (const T*)a.dout, a.Lq, a.M, a.gmax_n, a.gmax);
+        if (s.kind == EMRT_MSDA_K_SCATTER_LDS)
+          rc = msda_go<msda_bwd_value_lds_kernel<T, LL, PP>>(s, "emrt_msda_bwd(lds scatter)", st, a, ((g_tune.msda_fwd_probe >> 4) & 127) | (g_tune.msda_scatter_merge ? 128 : 0));
+        if constexpr (std::is_same<T, bf16_t>::value) {
+          if (s.kind == EMRT_MSDA_K_GRAD_LDS) rc = msda_go<msda_bwd_lds_kernel<T, LL, PP>>(s, "emrt_msda_bwd(lds gradients)", st, a, p.qpb, p.chunks, p.guard);
+          if constexpr (LL >= 2)
+            if (s.kind == EMRT_MSDA_K_GRAD_BAND) rc = msda_go<msda_bwd_lds_kernel<T, LL, PP, true>>(s, "emrt_msda_bwd(band gradients)", st, a, p.NB, p.halo, p.guard);
+          if (s.kind == EMRT_MSDA_K_SCATTER_MF) rc = msda_go<msda_bwd_value_mfma_kernel<LL, PP>>(s, "emrt_msda_bwd(matrix-product scatter)", st, a, p.mf);
+          if (s.kind == EMRT_MSDA_K_FINALIZE) rc = msda_go<msda_bwd_value_finalize_kernel<T>>(s, "emrt_msda_bwd(scatter finalize)", st, a);
+        }
+        if (rc) return rc == 1 ? fail("emrt_msda_bwd", "planned a kernel that is not built for this element type") : rc;
+      }
+      return 0;
+    });
+  });
+}
+
+extern "C" size_t emrt_msda_bwd_workspace_bytes(int B, int Lq, int M, int L, int P, const int* shapes_hw, int dtype) {
+  MsdaPlan p;
+  (void)msda_plan(p, "emrt_msda_bwd_workspace_bytes", true, B, Lq, M, L, P, shapes_hw, dtype, false);
+  return p.ws_bytes;      // (0 with emrt_last_error() set: a size that left the partial slabs out would be written past)
+}
+
+extern "C" int emrt_msda_plan(int backward, int B, int Lq, int M, int L, int P, const int* shapes_hw, int want_dref, int dtype, int* out, int cap) {
+  EMRT_REQUIRE(dtype == EMRT_F32 || dtype == EMRT_BF16 || (dtype == EMRT_F16 && !backward), "dtype must be 0 (fp32), 1 (bf16) or, forward only, 2 (fp16)");
+  EMRT_REQUIRE(out && cap >= 0, "needs an output array");
+  MsdaPlan p;
+  if (int rc = msda_plan(p, "emrt_msda_plan", backward != 0, B, Lq, M, L, P, shapes_hw, dtype, backward && want_dref)) return rc;
+  EMRT_REQUIRE(cap >= 6 * p.nsteps, "output array holds fewer than 6 ints per launch");
+  for (int i = 0; i < p.nsteps; ++i) {
+    const MsdaStep& s = p.step[i];
+    const int rec[6] = {s.kind, (int)s.grid.x, (int)s.grid.y, (int)s.grid.z, s.threads, (int)s.lds};
+    memcpy(out + 6 * i, rec, sizeof(rec));
+  }
+  return 6 * p.nsteps;
 }
 
 extern "C" int emrt_msda_fwd(const void* value, int ldv, long long v_bs, const float* offw, int ldo, const float* ref,
@@ -1865,49 +1858,17 @@ extern "C" int emrt_msda_fwd(const void* value, int ldv, long long v_bs, const f
   EMRT_REQUIRE(ref_L == 1 || ref_L == L, "ref_L must be 1 or L");
   EMRT_REQUIRE(value && offw && ref && out && shapes_hw, "null pointer");
   EMRT_REQUIRE(D == 32, "head dim must be 32");
-  EMRT_REQUIRE(M >= 1 && L >= 1 && L <= 4 && P >= 1, "bad M/L/P");
   EMRT_REQUIRE(ldv % 8 == 0 && v_bs % 8 == 0 && ldo % 2 == 0, "value strides must be multiples of 8 elements");
+  MsdaPlan p;
+  if (int rc = msda_plan(p, "emrt_msda_fwd", false, B, Lq, M, L, P, shapes_hw, dtype, false)) return rc;
+  EMRT_REQUIRE(p.a.Lv == Lv, "sum(h*w) != Lv");
   EMRT_REQUIRE(ldo >= M * L * P * 3, "offw row too short");
   EMRT_REQUIRE(dtype == EMRT_F32 || ((long long)(B - 1) * v_bs + (long long)Lv * ldv) * 2 < (1ll << 31), "value tensor spans 2 GiB or more (32-bit buffer offsets)");
-  MsdaArgs a;
-  memset(&a, 0, sizeof(a));
+  MsdaArgs a = p.a;
   a.value = value; a.ldv = ldv; a.v_bs = v_bs; a.offw = offw; a.ldo = ldo; a.ref = ref; a.ref_bs = ref_bs; a.ref_L = ref_L; a.out = out;
-  a.B = B; a.Lq = Lq; a.M = M;
-  EMRT_REQUIRE(msda_fill(a, shapes_hw, L, Lv) == 0, "sum(h*w) != Lv");
-  hipStream_t st = (hipStream_t)stream;
-  a.Lv = Lv;
-  int wmax = 1;
-  for (int l = 0; l < L; ++l) wmax = a.w[l] > wmax ? a.w[l] : wmax;
-  const int guard = wmax + 2;                                  // zero rows on both sides of the staged slab (msda_fwd_lds_kernel)
-  const size_t slab = (size_t)(Lv + 2 * guard) * MSDA_FWD_PITCH;
-  return with_fwd_dtype("emrt_msda_fwd", dtype, [&](auto t) {
-    using T = decltype(t);
-    if constexpr (sizeof(T) == 2) {      // the LDS-staged kernels are built for the 16-bit types only
-      if (slab <= 159 * 1024 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs && !g_tune.msda_fwd_global) {
-        // one block per CU (the slab takes most of its LDS): as close to 256 blocks as whole chunks of >= 128 queries allow
-        int chunks = (256 + B * M / 2) / (B * M);
-        if (g_tune.msda_fwd_chunks > 0) chunks = g_tune.msda_fwd_chunks;
-        if (chunks > (Lq + 127) / 128) chunks = (Lq + 127) / 128;
-        if (chunks < 1) chunks = 1;
-        const int qpb = (Lq + chunks - 1) / chunks;
-        chunks = (Lq + qpb - 1) / qpb;
-        return msda_launch_fwd_lds<T>(a, L, P, chunks, qpb, guard, slab, st);
-      }
-      if (slab > 159 * 1024 && Lq == Lv && L >= 2 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs &&
-          !g_tune.msda_fwd_global) {
-        // self-attention over a pyramid too large for one slab: row bands (msda_fwd_band_kernel)
-        int NB = 0, halo = 0;
-        size_t bslab = 0;
-        if (msda_band_plan(a, L, B * M, guard, NB, halo, bslab))
-          return msda_launch_fwd_band<T>(a, L, P, NB, halo, guard, bslab, st);
-      }
-    }
-    return msda_launch_fwd<T>(a, L, P, st);
-  });
+  return msda_run_fwd(p, a, L, P, dtype, (hipStream_t)stream);
 }
 
-// dvalue: when emrt_msda_bwd_uses_lds(shapes) it is [B][Lv][M*D] in the COMPUTE dtype and fully overwritten (workspace
-// of emrt_msda_bwd_workspace_bytes required); otherwise fp32, pre-zeroed by the caller, accumulated with global atomics.
 extern "C" int emrt_msda_bwd(const void* value, int ldv, long long v_bs, const float* offw, int ldo, const float* ref,
                              long long ref_bs, int ref_L, const void* dout, void* dvalue, void* doffw, int doffw_compute_dtype, float* dref,
                              int B, int Lq, int Lv, int M, int D, int L, int P, const int* shapes_hw, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
@@ -1915,78 +1876,17 @@ extern "C" int emrt_msda_bwd(const void* value, int ldv, long long v_bs, const f
   EMRT_REQUIRE(ref_L == 1 || ref_L == L, "ref_L must be 1 or L");
   EMRT_REQUIRE(value && offw && ref && dout && dvalue && doffw && shapes_hw, "null pointer");
   EMRT_REQUIRE(D == 32, "head dim must be 32");
-  EMRT_REQUIRE(M >= 1 && L >= 1 && L <= 4 && P >= 1, "bad M/L/P");
-  EMRT_REQUIRE(!dref || M == 8, "reference-point gradient needs M == 8");
   EMRT_REQUIRE(ldv % 8 == 0 && v_bs % 8 == 0 && ldo % 2 == 0, "value strides must be multiples of 8 elements");
-  MsdaArgs a;
-  memset(&a, 0, sizeof(a));
+  MsdaPlan p;
+  if (int rc = msda_plan(p, "emrt_msda_bwd", true, B, Lq, M, L, P, shapes_hw, dtype, dref != nullptr)) return rc;
+  EMRT_REQUIRE(p.a.Lv == Lv, "sum(h*w) != Lv");
+  EMRT_REQUIRE(workspace, "LDS scatter path needs the probability workspace");
+  EMRT_REQUIRE(workspace_bytes >= p.ws_bytes, "workspace smaller than emrt_msda_bwd_workspace_bytes() for these arguments");
+  MsdaArgs a = p.a;
   a.value = value; a.ldv = ldv; a.v_bs = v_bs; a.offw = offw; a.ldo = ldo; a.ref = ref; a.ref_bs = ref_bs; a.ref_L = ref_L;
-  a.dout = dout; a.dv_bs = (long long)Lv * M * 32; a.doffw = doffw; a.doffw_t = (doffw_compute_dtype && dtype != EMRT_F32) ? 1 : 0; a.dref = dref;
-  a.B = B; a.Lq = Lq; a.M = M; a.Lv = Lv;
-  EMRT_REQUIRE(msda_fill(a, shapes_hw, L, Lv) == 0, "sum(h*w) != Lv");
-  hipStream_t st = (hipStream_t)stream;
-  const bool lds_ok = (L == 3 && P == 6) || (L == 4 && P == 4) || (L == 3 && P == 4) || (L == 1 && P == 4);
-  if (lds_ok) {
-    EMRT_REQUIRE(workspace, "LDS scatter path needs the probability workspace");
-    EMRT_REQUIRE(workspace_bytes >= emrt_msda_bwd_workspace_bytes(B, Lq, M, L, P, shapes_hw, dtype), "workspace smaller than emrt_msda_bwd_workspace_bytes() for these arguments");
-    a.probs = (float*)workspace;
-    a.dvalue_t = dvalue;
-    int wmax = 1;
-    for (int l = 0; l < L; ++l) wmax = a.w[l] > wmax ? a.w[l] : wmax;
-    const int guard = wmax + 2;
-    a.g_guard = guard;
-    const int ng = msda_ranges(a, L, B * M, msda_split_allowed(B, Lq, M, dtype != EMRT_F32));
-    EMRT_REQUIRE(ng > 0, "value map rows too long for the LDS slab");
-    a.part = (int*)((float*)workspace + msda_part_offset_floats(B, Lq, M, L, P));
-    int npix_max = 0;
-    for (int g = 0; g < ng; ++g) npix_max = a.g_npix[g] > npix_max ? a.g_npix[g] : npix_max;
-    // offset / logit gradients: from the LDS-staged slab when it fits (same conditions and launch shape as the forward)
-    const size_t slab = (size_t)(Lv + 2 * guard) * MSDA_FWD_PITCH;
-    size_t bslab = 0;
-    int rc;
-    if (dtype == EMRT_BF16 && (!dref || g_tune.msda_bwd_dref_lds) && slab <= 159 * 1024 && (long long)B * M * Lq >= g_tune.msda_lds_min_pairs && !g_tune.msda_bwd_global) {
-      int chunks = (256 + B * M / 2) / (B * M);
-      if (chunks > (Lq + 127) / 128) chunks = (Lq + 127) / 128;
-      if (chunks < 1) chunks = 1;
-      const int qpb = (Lq + chunks - 1) / chunks;
-      chunks = (Lq + qpb - 1) / qpb;
-      a.gmax = (float*)workspace + (size_t)B * Lq * M * L * P;
-      a.gmax_n = chunks;
-      rc = msda_launch_bwd_grad_lds<bf16_t>(a, L, P, chunks, qpb, guard, slab, st);
-    } else if (int NB = 0, halo = 0; dtype == EMRT_BF16 && !dref && slab > 159 * 1024 && Lq == Lv && L >= 2 && !g_tune.msda_bwd_global &&
-               (long long)B * M * Lq >= g_tune.msda_lds_min_pairs && msda_band_plan(a, L, B * M, guard, NB, halo, bslab)) {
-      // self-attention over a pyramid too large for one slab: row bands (msda_bwd_lds_kernel<BAND>), leaves max |dout| per block too
-      a.gmax = (float*)workspace + (size_t)B * Lq * M * L * P;
-      a.gmax_n = NB;
-      rc = msda_launch_bwd_grad_band<bf16_t>(a, L, P, NB, halo, guard, bslab, st);
-    } else {
-      rc = with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) { return msda_launch<decltype(t)>(a, L, P, 2, st); });
-      if (!rc && Lq >= 1024 && M <= 8 && 256 % (M * 4) == 0) {      // long scans only: the extra launch costs ~3 us
-        a.gmax = (float*)workspace + (size_t)B * Lq * M * L * P;
-        a.gmax_n = (Lq + 63) / 64;
-        rc = with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) {
-          using T = decltype(t);
-          hipLaunchKernelGGL((msda_absmax_kernel<T>), dim3(B * a.gmax_n), dim3(256), 0, st, (const T*)dout, Lq, M, a.gmax_n, a.gmax);
-          return 0;
-        });
-      }
-    }
-    if (rc) return rc;
-    if (MsdaMfPlan pl; dtype == EMRT_BF16 && g_tune.msda_scatter_mfma) {
-      // every band of a level re-reads and re-derives ALL queries' samples of that level: worth it while at most one level is cut in two
-      // (cfg2: 32 x 32 | 16 x 16 | 8 x 8 = 4 bands, 256 blocks at batch 8: 45 vs 59 us; cfg3's 64 x 64 level would be 8 bands: 323 vs 199 us per call).
-      // knob msda_scatter_mfma: 0 = never, 1 = this rule, 2 = whenever a plan exists (tests)
-      int nbands = 0;
-      if (msda_mf_plan(a, L, pl, nbands) && (nbands <= L + 1 || g_tune.msda_scatter_mfma >= 2)) return msda_launch_mf(a, L, P, pl, nbands, st);
-    }
-    a.g_npix_max = (npix_max + 2 * guard + 3) & ~3;          // slab + both guard bands; keeps the records 16-byte aligned
-    const size_t lds = (size_t)a.g_npix_max * MSDA_SLAB_PITCH * sizeof(int) + 32 * 32 * (sizeof(float4) + sizeof(int));
-    EMRT_REQUIRE(a.f_n == 0 || a.gmax_n > 0, "internal: query-split scatter planned without the max |dout| partials");
-    rc = with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) { return msda_launch_lds<decltype(t)>(a, L, P, ng, lds, st); });
-    if (rc || a.f_n == 0) return rc;
-    hipLaunchKernelGGL((msda_bwd_value_finalize_kernel<bf16_t>), dim3(B * M, a.f_n, 8), dim3(256), 0, st, a);
-    return check_launch("emrt_msda_bwd(scatter finalize)");
-  }
-  a.dvalue = (float*)dvalue;
-  return with_train_dtype("emrt_msda_bwd", dtype, [&](auto t) { return msda_launch<decltype(t)>(a, L, P, 1, st); });
+  a.dout = dout; a.dvalue_t = dvalue; a.doffw = doffw; a.doffw_t = (doffw_compute_dtype && dtype != EMRT_F32) ? 1 : 0; a.dref = dref;
+  a.probs = (float*)workspace;
+  if (a.gmax_n) a.gmax = (float*)workspace + p.gmax_off;
+  a.part = (int*)((float*)workspace + p.part_off);
+  return msda_run_bwd(p, a, L, P, dtype, (hipStream_t)stream);
 }

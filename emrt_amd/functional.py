@@ -1585,20 +1585,14 @@ def msda(value, offw, ref, shapes, n_heads, n_points, need_dref=False):
             if dy is None:
                 return
             assert dy.is_contiguous()
-            use_lds = bool(_L().query("emrt_msda_bwd_uses_lds", ctypes.cast(arr, ctypes.c_void_p), L))
             odt = None if c.dtype != F32 else torch.float32      # compute dtype: the projection's backward GEMM reads it directly
             doffw = c.zeros((B, Lq, ldo), odt) if ldo != M * L * Pn * 3 else c.empty((B, Lq, ldo), odt)
             dref = c.zeros((B, Lq, ref_L, 2), torch.float32) if need_dref else None      # zeroed: the LDS gradient kernel accumulates into it
-            if use_lds:
-                dvalue = c.empty((B, Lv, CC))          # compute dtype, fully overwritten by the LDS scatter
-                ws = c.empty((_L().query("emrt_msda_bwd_workspace_bytes", B, Lq, M, L, Pn, ctypes.cast(arr, ctypes.c_void_p), c.dtype) // 4,), torch.float32)
-            else:
-                dvalue = c.zeros((B, Lv, CC), torch.float32)
-                ws = None
+            dvalue = c.empty((B, Lv, CC))          # compute dtype, fully overwritten by the scatter
+            ws = c.empty((_L().query("emrt_msda_bwd_workspace_bytes", B, Lq, M, L, Pn, ctypes.cast(arr, ctypes.c_void_p), c.dtype) // 4,), torch.float32)
             _L().call("emrt_msda_bwd", P(value), value.stride(1), value.stride(0), P(offw), ldo, P(ref), ref_bs, ref_L, P(dy), P(dvalue), P(doffw),
-                      int(c.dtype != F32), P(dref), B, Lq, Lv, M, 32, L, Pn, ctypes.cast(arr, ctypes.c_void_p), P(ws), ws.numel() * 4 if ws is not None else 0,
-                      c.dtype, c.stream)
-            tape.add_grad(value, dvalue if use_lds else cast_from_f32(dvalue), owned=True)
+                      int(c.dtype != F32), P(dref), B, Lq, Lv, M, 32, L, Pn, ctypes.cast(arr, ctypes.c_void_p), P(ws), ws.numel() * 4, c.dtype, c.stream)
+            tape.add_grad(value, dvalue, owned=True)
             tape.add_grad(offw, doffw, owned=True)
             if need_dref:
                 if ref.shape[0] == 1 and B > 1:   # reference points shared by the batch: reduce over b

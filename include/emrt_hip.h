@@ -274,18 +274,32 @@ int emrt_layernorm_bwd(const void* z, const void* dy, void* dz, const float* gam
 int emrt_msda_fwd(const void* value, int ldv, long long v_bs, const float* offw, int ldo, const float* ref, long long ref_bs, int ref_L, void* out, int B, int Lq, int Lv, int M, int D, int L, int P, const int* shapes_hw, int dtype, void* stream);
 /* Backward.  doffw [B*Lq][ldo] (fp32, or the compute dtype when doffw_compute_dtype != 0 and dtype is a 2-byte type: what the
  * offsets|logits projection's backward GEMM reads) is overwritten; dref [B][Lq][ref_L][2] (nullable) must be ZEROED by the caller (the
- * LDS-staged gradient kernel adds the heads' contributions with atomics; the global-gather kernel overwrites it).  dvalue: when
- * emrt_msda_bwd_uses_lds(shapes_hw, L) == 1 (every level group's fp32 slab fits in LDS) it is [B][Lv][M*D] in the
- * compute dtype, fully overwritten by an LDS-privatised scatter (needs `workspace` of emrt_msda_bwd_workspace_bytes);
- * otherwise it is fp32, must be zeroed by the caller and is accumulated with global atomics.
+ * LDS-staged gradient kernel adds the heads' contributions with atomics; the global-gather kernel overwrites it).  dvalue is
+ * [B][Lv][M*D] in the compute dtype and fully overwritten by an LDS-privatised scatter; every call needs `workspace` of
+ * emrt_msda_bwd_workspace_bytes.  emrt_msda_bwd_uses_lds is 1 for L in 1..4: every legal call takes the LDS path (kept for bindings that ask).
  * emrt_msda_bwd_workspace_bytes (ABI 4: takes the level shapes and the dtype of the call it sizes): softmax probabilities, the
  * per-block max |dout| partials and -- for large pyramids, where the small levels' scatter blocks are split by queries -- the
- * integer partial slabs; it makes the same plan emrt_msda_bwd will make for these arguments.  ABI 5: shapes_hw == NULL (or L outside
+ * integer partial slabs; it reads the same plan emrt_msda_bwd launches from.  ABI 5: shapes_hw == NULL (or L outside
  * 1..4) is an error (returns 0, emrt_last_error() says why), and emrt_msda_bwd takes the size of the workspace it was given and
  * refuses one that is smaller than this function's answer. */
 int emrt_msda_bwd_uses_lds(const int* shapes_hw, int L);
 size_t emrt_msda_bwd_workspace_bytes(int B, int Lq, int M, int L, int P, const int* shapes_hw, int dtype);
 int emrt_msda_bwd(const void* value, int ldv, long long v_bs, const float* offw, int ldo, const float* ref, long long ref_bs, int ref_L, const void* dout, void* dvalue, void* doffw, int doffw_compute_dtype, float* dref, int B, int Lq, int Lv, int M, int D, int L, int P, const int* shapes_hw, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* The launches a call would make (ABI 9, additive; host only: launches nothing, touches no device memory).  Runs the planner emrt_msda_fwd
+ * (backward == 0) / emrt_msda_bwd read and writes six ints per launch, in launch order, to `out` (room for `cap` ints):
+ * {kernel kind, grid.x, grid.y, grid.z, threads, dynamic LDS bytes}; returns the number of ints written, or -1 (emrt_last_error() says why)
+ * for a call the entry point would refuse.  want_dref: the backward call passes dref. */
+#define EMRT_MSDA_K_FWD_GLOBAL 0   /* msda_fwd_kernel: corners gathered from L2 */
+#define EMRT_MSDA_K_FWD_LDS 1      /* msda_fwd_lds_kernel: the (batch, head) slab staged in LDS */
+#define EMRT_MSDA_K_FWD_BAND 2     /* msda_fwd_band_kernel: row bands of a pyramid too large for one slab */
+#define EMRT_MSDA_K_GRAD_GLOBAL 3  /* msda_bwd_kernel: offset / logit gradients and probabilities */
+#define EMRT_MSDA_K_GRAD_LDS 4     /* msda_bwd_lds_kernel */
+#define EMRT_MSDA_K_GRAD_BAND 5    /* msda_bwd_lds_kernel, row-band form */
+#define EMRT_MSDA_K_ABSMAX 6       /* msda_absmax_kernel: max |dout| partials behind the global gradient kernel */
+#define EMRT_MSDA_K_SCATTER_MF 7   /* msda_bwd_value_mfma_kernel: value gradient as a matrix product */
+#define EMRT_MSDA_K_SCATTER_LDS 8  /* msda_bwd_value_lds_kernel: value gradient by integer LDS scatter */
+#define EMRT_MSDA_K_FINALIZE 9     /* msda_bwd_value_finalize_kernel: sums the partial slabs of a query split */
+int emrt_msda_plan(int backward, int B, int Lq, int M, int L, int P, const int* shapes_hw, int want_dref, int dtype, int* out, int cap);
 
 /* ---- fused softmax(QK^T/sqrt(d)) V with dropout on the weights: EMRT_utils/layers.py:283-303 (L <= 128, D = 32).
  * ABI 8: emrt_mha_fwd reports through path_out (nullable) which kernel filled `probs` -- 0: the L x L probabilities (VALU kernel), 1: (row max,

@@ -9,6 +9,7 @@ Each is compared here with the oracle's torch-CPU expression of the same referen
 (reference arithmetic: EMRT_utils/utils.py:64-97, paddle_EMRT.py:134-138,201-209), the two MSDA forward kernels with each
 other bit for bit, and the whole bf16 model at batch 8 / 256x256 / ResNet-50 with the fp32 oracle under stated bounds.
 """
+import ctypes
 import math
 
 import pytest
@@ -76,9 +77,11 @@ def test_msda_bench_shape_bf16_vs_oracle(cfg):
     c.tape = None
     tape.watch(vd)
     tape.watch(od)
-    # which kernel ran is decided by the same rule the dispatcher uses (msda.hip: emrt_msda_fwd)
-    uses_lds = Lv * 80 <= 150 * 1024 and B * M * Lq >= 2048
-    assert uses_lds == cfg["lds"], "the test case no longer selects the kernel it was written for"
+    # which kernel ran: the library's own answer (emrt_msda_plan: the planner emrt_msda_fwd launches from; kinds EMRT_MSDA_K_FWD_*)
+    arr = (ctypes.c_int * (2 * L))(*[int(v) for hw in shapes for v in hw])
+    plan = (ctypes.c_int * 6)()
+    assert L_.query("emrt_msda_plan", 0, B, Lq, M, L, Pn, ctypes.cast(arr, ctypes.c_void_p), 0, BF16, ctypes.cast(plan, ctypes.c_void_p), 6) == 6, L_.last_error()
+    assert plan[0] == (1 if cfg["lds"] else 2 if cfg.get("band") else 0), "the test case no longer selects the kernel it was written for"
     # bf16 output of an fp32 accumulation over bf16 values: one rounding of the result (2^-9 relative) + accumulation noise
     close("msda fwd (bench shape)", host(y), out_r.detach(), BF16, atol=2e-2, rtol=1e-2)
     rel = ((host(y) - out_r.detach()).norm() / out_r.detach().norm()).item()
