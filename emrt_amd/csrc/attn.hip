@@ -622,6 +622,9 @@ extern "C" int emrt_mha_bwd(const void* q, int ldq, const void* k, int ldk, cons
     hipLaunchKernelGGL((mha_bwd_mfma_kernel<bf16_t>), dim3(B * M, g_tune.mha_bwd_split ? 2 : 1), dim3(64 * ((L + 15) / 16)), 0, st, a);
     return check_launch("emrt_mha_bwd");
   }
+  // the VALU kernel moves 8 elements per access, as the forward's does: the same requirement, here for all seven strides
+  EMRT_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0 && lddk % 8 == 0 && lddv % 8 == 0,
+               "row strides must be multiples of 8");
   return with_train_dtype("emrt_mha_bwd", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL((mha_bwd_kernel<T>), dim3(B * M), dim3(MHA_THREADS), lds, st, a);

@@ -304,7 +304,10 @@ int emrt_msda_plan(int backward, int B, int Lq, int M, int L, int P, const int* 
 /* ---- fused softmax(QK^T/sqrt(d)) V with dropout on the weights: EMRT_utils/layers.py:283-303 (L <= 128, D = 32).
  * ABI 8: emrt_mha_fwd reports through path_out (nullable) which kernel filled `probs` -- 0: the L x L probabilities (VALU kernel), 1: (row max,
  * 1 / row sum) in the first 2 L floats of each (batch, head) slab (MFMA kernel, bf16 / fp16) -- and emrt_mha_bwd takes that value as `path`: it runs the
- * matching backward or fails (it no longer re-derives the choice from its own operands). */
+ * matching backward or fails (it no longer re-derives the choice from its own operands).
+ * Row strides (in elements): emrt_mha_fwd wants ldq, ldk, ldv, ldo to be multiples of 8; emrt_mha_bwd with path 0 wants the same of all seven of
+ * ldq, ldk, ldv, lddo, lddq, lddk, lddv (its kernel moves 8 elements per access, as the forward's does) and fails before any launch otherwise; with
+ * path 1 it wants multiples of 8 for ldq, ldk, ldv, lddo and multiples of 4 for lddq, lddk, lddv. */
 int emrt_mha_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, float* probs, int B, int M, int L, int D, float scale, float pdrop, const unsigned long long* seed, unsigned salt, int* path_out, int dtype, void* stream);
 int emrt_mha_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* probs, const void* dout, int lddo, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int M, int L, int D, float scale, float pdrop, const unsigned long long* seed, unsigned salt, int path, int dtype, void* stream);
 

@@ -1,5 +1,6 @@
 """Seeded random case lists for the shape sweeps of csrc/norm.hip, csrc/spatial.hip and the inference glue
-(tests/test_gpu_norm_fuzz.py, tests/test_gpu_spatial_fuzz.py, tests/test_gpu_infer_glue.py), and the dispatchers' shape predicates
+(tests/test_gpu_norm_fuzz.py, tests/test_gpu_spatial_fuzz.py, tests/test_gpu_infer_glue.py) and of csrc/attn.hip
+(tests/test_gpu_mha_fuzz.py; its float64 reference and bounds are tests/mha_reference.py), and the dispatchers' shape predicates
 restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
 entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
 seed or a range cannot silently empty one.
@@ -67,6 +68,31 @@ Regime -> case ids (regime_table() renders this text; the CPU test compares):
   pyramid           one launch per direction, fp32 and bf16            py1808-{0,4,6,8}
   pyramid           one launch in fp32, per scale in bf16 (8-byte slices) py1808-{2,10}
   pyramid           per-scale fallback by the knob                     py1808-{1,3,5,7,9,11}
+  mha               L = 1 (VALU kernels in every dtype)                mha1909-{0,27}
+  mha               odd tile count (last k-step half padding)          mha1909-{1,2,3,4,5,6,10,11,12,16,19,20,21,22,23,28,29,30,31,32,33,37,38,39,43,46,47,48,49,50,56,57,60,61,62,63}
+  mha               L % 16 = 0                                         mha1909-{6,9,12,15,18,23,26,33,36,39,42,45,50,53,68,69}
+  mha               L % 16 = 1                                         mha1909-{7,10,13,16,19,24,34,37,40,43,46,51,54,55,56,57,58,59,64,65}
+  mha               L % 16 = 15                                        mha1909-{5,8,11,14,17,22,25,32,35,38,41,44,49,52,62,63,66,67}
+  mha               L % 4 != 0 (ragged lane quads)                     mha1909-{0,1,2,4,5,7,8,10,11,13,14,16,17,19,20,21,22,24,25,27,28,29,31,32,34,35,37,38,40,41,43,44,46,47,48,49,51,52,54,55,56,57,58,59,60,61,62,63,64,65,66,67}
+  mha               ragged last forward chunk                          mha1909-{10,11,12,13,14,16,17,19,20,21,22,23,24,25,37,38,39,40,41,43,44,46,47,48,49,50,51,52,56,57,58,59,60,61,62,63,64,65,66,67}
+  mha               VALU backward stages Pd in LDS                     mha1909-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,27,28,29,30,31,32,33,34,35,36,37,38,39,40,41,42,43,44,45,46,47,48,54,55,56,57,58,59,60,61}
+  mha               VALU backward re-derives Pd                        mha1909-{22,23,24,25,26,49,50,51,52,53,62,63,64,65,66,67,68,69}
+  mha               M = 1                                              mha1909-{4,14,18,28,30,32,55,66,68,69}
+  mha               M not in (1, 8)                                    mha1909-{0,1,2,3,5,6,8,9,11,12,13,15,16,20,21,22,23,24,26,27,29,31,33,34,35,37,38,40,41,43,44,45,46,47,50,51,52,53,54,56,60,61,62,63,64,65}
+  mha               B = 1                                              mha1909-{4,6,8,18,19,25,32,39,44,45,47,48,50,62,67}
+  mha               inputs: ordinary                                   mha1909-{0,4,8,12,16,20,24,28,32,36,40,44,48,52}
+  mha               inputs: peaked                                     mha1909-{1,5,9,13,17,21,25,29,33,37,41,45,49,53}
+  mha               inputs: negative                                   mha1909-{2,6,10,14,18,22,26,30,34,38,42,46,50}
+  mha               inputs: lastkey                                    mha1909-{3,7,11,15,19,23,27,31,35,39,43,47,51}
+  mha               dropout, Pd staged in LDS                          mha1909-{54,55,56,57,58,59,60,61}
+  mha               dropout, Pd re-derived                             mha1909-{62,63,64,65,66,67,68,69}
+  mha               dropout, odd tile count                            mha1909-{56,57,60,61,62,63}
+  mha               layout: fused                                      mha1909-{0,3,6,9,12,15,18,21,24,29,32,35,38,41,44,47,50,53,54,59,60,65,66}
+  mha               layout: split                                      mha1909-{1,4,7,10,13,16,19,22,25,27,30,33,36,39,42,45,48,51,55,56,61,62,67,68}
+  mha               layout: offset8                                    mha1909-{2,5,8,11,14,17,20,23,26,28,31,34,37,40,43,46,49,52,57,58,63,64,69}
+  mha               dropout, layout: fused                             mha1909-{54,59,60,65,66}
+  mha               dropout, layout: split                             mha1909-{55,56,61,62,67,68}
+  mha               dropout, layout: offset8                           mha1909-{57,58,63,64,69}
 
 Not reachable through the wrappers, on purpose:
   * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
@@ -564,17 +590,106 @@ def window_cover(origins_yx, H, W, ch, cw):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# attention: emrt_mha_fwd / emrt_mha_bwd (tests/test_gpu_mha_fuzz.py; the float64 reference and the bounds are tests/mha_reference.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+MHA_MAXL = 128
+
+
+def mha_path(is16bit, L, valu_knob, aligned):
+    """0: VALU kernels (`probs` = L x L probabilities), 1: MFMA kernels (`probs` = row statistics).  Mirrors `mfma` of emrt_mha_fwd
+    (csrc/attn.hip) for row strides that are multiples of 8; aligned: q, k, v on 16-byte and o on 8-byte boundaries."""
+    return int(bool(is16bit and not valu_knob and L >= 2 and aligned))
+
+
+def mha_bwd_stages_probs(L):
+    """Mirrors use_sp of emrt_mha_bwd: the VALU backward keeps the dropped probabilities in LDS (else it re-derives them from `probs`)."""
+    return (4 * L * 36 + 2 * L * (L + 1)) * 4 <= 159 * 1024
+
+
+def mha_tiles(L):
+    """16-row tiles of the MFMA kernels (nt); they walk k in pairs of tiles, so an odd count leaves the last k-step half padding"""
+    return (L + 15) // 16
+
+
+def mha_fwd_chunks(L):
+    """32-row chunks of the VALU forward (nchunk): blocks per (batch, head)"""
+    return (L + 31) // 32
+
+
+def mha_in_domain(case):
+    _, B, M, L, regime, p, layout, _ = case
+    return (B >= 1 and M >= 1 and 1 <= L <= MHA_MAXL and regime in MHA_INPUTS and layout in MHA_LAYOUTS and 0.0 <= p < 1.0
+            and (p == 0.0 or regime == "ordinary"))
+
+
+MHA_LS = (1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 95, 96, 97, 109, 110, 111, 112, 113, 127, 128)
+MHA_DROP_LS = (17, 33, 49, 110, 111, 113, 127, 128)
+MHA_MS = (1, 2, 3, 4, 8)
+MHA_INPUTS = ("ordinary", "peaked", "negative", "lastkey")          # tests/mha_reference.make_inputs
+# fused: through functional.mha (q | k in one buffer with ld = 2 E, the rest ld = E); split: the C entry points with q, k, v in three buffers
+# of row strides E, E + 8, 2 E + 16; offset8: the same with q 8 bytes off a 16-byte boundary in bf16 (path 0 by the alignment rule; an fp32
+# call has no such rule and runs the case as `split`).  Both direct layouts write o, dq, dk, dv into wider pre-filled buffers.
+MHA_LAYOUTS = ("fused", "split", "offset8")
+
+
+def mha_cases(seed=1909):
+    """(id, B, M, L, input regime, pdrop, layout, seed): every length of MHA_LS twice without dropout (another input regime and another
+    layout the second time), then MHA_DROP_LS x p in {0.1, 0.5} with ordinary inputs"""
+    rng = random.Random(seed)
+    out = []
+
+    def add(L, regime, p, layout):
+        while True:
+            B, M = rng.randint(1, 4), rng.choice(MHA_MS)
+            if B * M * L * L <= MAX_ELEMS:
+                break
+        out.append(("mha%d-%d" % (seed, len(out)), B, M, L, regime, p, layout, seed + len(out)))
+
+    n = len(MHA_LS)
+    for i in range(2 * n):
+        add(MHA_LS[i % n], MHA_INPUTS[i % 4], 0.0, MHA_LAYOUTS[(i + i // n) % 3])
+    for i, L in enumerate(MHA_DROP_LS):
+        for j, p in enumerate((0.1, 0.5)):
+            add(L, "ordinary", p, MHA_LAYOUTS[(i + j) % 3])
+    return out
+
+
+MHA_REGIMES = [
+    ("L = 1 (VALU kernels in every dtype)", lambda c: c[3] == 1),
+    ("odd tile count (last k-step half padding)", lambda c: c[3] >= 2 and mha_tiles(c[3]) % 2 == 1),
+    ("L % 16 = 0", lambda c: c[3] % 16 == 0),
+    ("L % 16 = 1", lambda c: c[3] % 16 == 1 and c[3] > 1),
+    ("L % 16 = 15", lambda c: c[3] % 16 == 15),
+    ("L % 4 != 0 (ragged lane quads)", lambda c: c[3] % 4 != 0),
+    ("ragged last forward chunk", lambda c: c[3] % 32 != 0 and mha_fwd_chunks(c[3]) > 1),
+    ("VALU backward stages Pd in LDS", lambda c: mha_bwd_stages_probs(c[3])),
+    ("VALU backward re-derives Pd", lambda c: not mha_bwd_stages_probs(c[3])),
+    ("M = 1", lambda c: c[2] == 1),
+    ("M not in (1, 8)", lambda c: c[2] not in (1, 8)),
+    ("B = 1", lambda c: c[1] == 1),
+] + [("inputs: %s" % r, (lambda r_: lambda c: c[4] == r_ and c[5] == 0.0)(r)) for r in MHA_INPUTS] + [
+    ("dropout, Pd staged in LDS", lambda c: c[5] > 0 and mha_bwd_stages_probs(c[3])),
+    ("dropout, Pd re-derived", lambda c: c[5] > 0 and not mha_bwd_stages_probs(c[3])),
+    ("dropout, odd tile count", lambda c: c[5] > 0 and mha_tiles(c[3]) % 2 == 1),
+] + [("layout: %s" % l, (lambda l_: lambda c: c[6] == l_)(l)) for l in MHA_LAYOUTS] + [
+    ("dropout, layout: %s" % l, (lambda l_: lambda c: c[5] > 0 and c[6] == l_)(l)) for l in MHA_LAYOUTS]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 CASES = {
     "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
     "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
+    "mha": mha_cases(),
 }
 REGIMES = {
     "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
     "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
+    "mha": MHA_REGIMES,
 }
 IN_DOMAIN = {
     "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
     "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
+    "mha": mha_in_domain,
 }
 
 

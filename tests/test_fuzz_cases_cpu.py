@@ -46,6 +46,19 @@ def test_case_sizes_stay_small():
         assert c[1] * c[2] * c[3] * c[5] <= fc.MAX_ELEMS
     for c in fc.CASES["pyramid"]:
         assert c[1] * c[4] * c[5] * c[2] * (len(c[3]) + 1) <= fc.MAX_ELEMS
+    for c in fc.CASES["mha"]:
+        assert c[1] * c[2] * c[3] * c[3] <= fc.MAX_ELEMS and 1 <= c[1] <= 4 and c[2] in fc.MHA_MS and c[3] in fc.MHA_LS
+
+
+def test_mha_sweep_covers_what_it_was_written_for():
+    """every length of the list without dropout; dropout at p in {0.1, 0.5} on both sides of the LDS threshold of the VALU backward and at the
+    lengths the sweep was asked to hold; ordinary inputs under dropout (no probability underflows there: kept == read back > 0)"""
+    cases = fc.CASES["mha"]
+    assert {c[3] for c in cases if c[5] == 0.0} == set(fc.MHA_LS)
+    drop = [c for c in cases if c[5] > 0.0]
+    assert {17, 33, 110, 111, 128} <= {c[3] for c in drop} and {c[5] for c in drop} == {0.1, 0.5}
+    assert all(c[4] == "ordinary" for c in drop)
+    assert fc.mha_cases() == cases
 
 
 def test_mirrored_predicates_at_known_points():
@@ -61,6 +74,11 @@ def test_mirrored_predicates_at_known_points():
     assert fc.pyramid_grouped(256, (1, 3, 6, 8), 32, 32, 2, True) and not fc.pyramid_grouped(256, (1, 3, 6, 8), 32, 32, 2, False)
     assert fc.pyramid_grouped(12, (5, 6), 26, 27, 4, True) and not fc.pyramid_grouped(12, (5, 6), 26, 27, 2, True)
     assert fc.resize_bwd_wide(256, 8, 8, 32, 32) and not fc.resize_bwd_wide(256, 8, 8, 31, 32) and not fc.resize_bwd_wide(6, 1, 1, 32, 32)
+    assert fc.mha_bwd_stages_probs(110) and not fc.mha_bwd_stages_probs(111) and fc.mha_bwd_stages_probs(1) and not fc.mha_bwd_stages_probs(128)
+    assert fc.mha_path(True, 110, 0, True) == 1 and fc.mha_path(False, 110, 0, True) == 0 and fc.mha_path(True, 1, 0, True) == 0
+    assert fc.mha_path(True, 110, 1, True) == 0 and fc.mha_path(True, 110, 0, False) == 0 and fc.mha_path(True, 2, 0, True) == 1
+    assert [fc.mha_tiles(L) for L in (1, 16, 17, 110, 113, 128)] == [1, 1, 2, 7, 8, 8]
+    assert [fc.mha_fwd_chunks(L) for L in (1, 32, 33, 110, 128)] == [1, 1, 2, 4, 4]
 
 
 def test_window_cases():
