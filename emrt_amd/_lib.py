@@ -1,9 +1,11 @@
-"""ctypes binding of libemrt_hip.so, generated from include/emrt_hip.h (single source of truth).
+"""ctypes binding of libemrt_hip.so, generated from include/emrt_hip.h (single source of truth): the prototypes (parse_header) and the
+descriptor structs (parse_structs / struct) alike.
 
 The product path has NO fallback: if the shared library is missing or a symbol is absent this module raises, and
 every op in emrt_amd.functional raises with it.  (INTEGRATION.md shows this same stub as the reference-side binding.)
 """
 import ctypes
+import keyword
 import os
 import re
 
@@ -46,10 +48,76 @@ def parse_header(path=HEADER):
 def _ctype_of(t):
     t = t.replace("const ", "").strip()
     if t.endswith("*"):
-        return ctypes.c_char_p if t == "char*" and False else ctypes.c_void_p
+        return ctypes.c_void_p
     if t in _CTYPES:
         return _CTYPES[t]
     raise EmrtHipError("emrt_hip.h: unknown C type %r" % t)
+
+
+_MEMBER_RENAMES = {"in": "inp"}      # C member names that are Python keywords -> the attribute name the ctypes class gets
+_POINTEES = ("void", "char", "unsigned char")      # what a pointer member may point to besides the scalars of _CTYPES
+
+
+def member_name(struct_name, member):
+    """The Python attribute of a struct member: its C name, unless that is a keyword (then the rename table must hold it)."""
+    if member in _MEMBER_RENAMES:
+        return _MEMBER_RENAMES[member]
+    if keyword.iskeyword(member):
+        raise EmrtHipError("emrt_hip.h: %s.%s: a Python keyword without an entry in the rename table" % (struct_name, member))
+    return member
+
+
+def parse_structs(path=HEADER):
+    """-> {name: [(type_str, member, array_length or None), ...]} for every `typedef struct Name { ... } Name;` in the header, members in
+    declaration order under their C names.  Anything that is not understood raises EmrtHipError naming struct and member."""
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    structs = {}
+    found = list(re.finditer(r"\btypedef\s+struct\b\s*(\w*)\s*\{(.*?)\}\s*(\w*)\s*;", text, flags=re.S))
+    if len(found) != len(re.findall(r"\btypedef\s+struct\b", text)):
+        raise EmrtHipError("emrt_hip.h: a `typedef struct` that is not of the form `typedef struct Name { ... } Name;`")
+    for m in found:
+        tag, body, name = m.group(1), m.group(2), m.group(3)
+        if tag != name or not name:
+            raise EmrtHipError("emrt_hip.h: struct tag %r and typedef name %r differ" % (tag, name))
+        members = []
+        for decl in body.split(";"):
+            decl = " ".join(decl.split())
+            if not decl:
+                continue
+            first, *more = [d.strip() for d in decl.split(",")]
+            mm = re.match(r"^([\w\s\*]+?)\s*\b(\w+)\s*(?:\[\s*(\d+)\s*\])?$", first)
+            if mm is None:          # a nested struct / union body, a bit-field, a function pointer, ...
+                raise EmrtHipError("emrt_hip.h: %s: cannot parse the member declaration %r" % (name, decl))
+            ctype = re.sub(r"\s*\*\s*", "*", mm.group(1).strip())
+            declared = [(mm.group(2), mm.group(3))]
+            for d in more:
+                md = re.match(r"^(\w+)\s*(?:\[\s*(\d+)\s*\])?$", d)
+                if md is None or ctype.endswith("*"):      # `T *a, *b` (and `T* a, b`, whose b is no pointer)
+                    raise EmrtHipError("emrt_hip.h: %s.%s: one pointer member per declaration, written `T* name`" % (name, d.lstrip("* ")))
+                declared.append((md.group(1), md.group(2)))
+            base = ctype.replace("const ", "").rstrip("*").strip()
+            if base not in _CTYPES and not (ctype.endswith("*") and (base in _POINTEES or base in structs)):
+                raise EmrtHipError("emrt_hip.h: %s.%s: unknown C type %r" % (name, declared[0][0], ctype))
+            for member, count in declared:
+                member_name(name, member)
+                members.append((ctype, member, int(count) if count else None))
+        structs[name] = members
+    return structs
+
+
+_STRUCTS = {}      # name -> the one ctypes.Structure subclass of that header struct
+
+
+def struct(name):
+    """The ctypes.Structure subclass of a descriptor struct of the header, generated once: (struct(n) * k) is the same array type in every
+    module.  Pointer members are c_void_p (None, an int address or data_ptr() all assign)."""
+    if not _STRUCTS:
+        for sname, members in parse_structs().items():
+            fields = [(member_name(sname, m), _ctype_of(t) * n if n else _ctype_of(t)) for t, m, n in members]
+            _STRUCTS[sname] = type(sname, (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s of include/emrt_hip.h" % sname})
+    if name not in _STRUCTS:
+        raise EmrtHipError("emrt_hip.h declares no struct %s" % name)
+    return _STRUCTS[name]
 
 
 class _Lib:

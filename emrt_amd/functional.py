@@ -288,12 +288,35 @@ class GemmWeight:
         self.need_bwd = True
 
 
-class _WgradDesc(ctypes.Structure):       # EmrtWgradDesc (include/emrt_hip.h)
-    _fields_ = [("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("dbias", ctypes.c_void_p),
-                ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int), ("ldx", ctypes.c_int),
-                ("x_bs", ctypes.c_longlong), ("OH", ctypes.c_int), ("OW", ctypes.c_int), ("OC", ctypes.c_int), ("lddy", ctypes.c_int),
-                ("dy_bs", ctypes.c_longlong), ("KH", ctypes.c_int), ("KW", ctypes.c_int), ("stride", ctypes.c_int), ("pad", ctypes.c_int),
-                ("dilation", ctypes.c_int), ("dw_is_zero", ctypes.c_int)]
+# the descriptor structs of include/emrt_hip.h: generated from the header, one class per struct for every module (_lib.struct)
+_ConvDesc, _ConvBwdDesc, _DgradDesc = _lib.struct("EmrtConvDesc"), _lib.struct("EmrtConvBwdDesc"), _lib.struct("EmrtConvDgradDesc")
+_WgradDesc, _BnGroupDesc, _AugDesc = _lib.struct("EmrtWgradDesc"), _lib.struct("EmrtBnGroupDesc"), _lib.struct("EmrtAugDesc")
+
+
+def _dp(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _fill_conv_desc(d, x_ptr, x_geom, w, out_ptr, out_geom, stride, pad, bn_stats=None, out_f32=False):
+    """One problem of emrt_conv2d_group (EmrtConvDesc): the input map at x_ptr with x_geom = (N, H, W, C, ldin, in_bs) as _check_map gives it, the
+    GemmWeight w (its bias, if it has one), the output at out_ptr with out_geom = (OH, OW, ldout, out_bs); bn_stats: address of the fp64 batch sums.
+    No grouped problem has a residual or a ReLU."""
+    d.inp, d.w_packed, d.out, d.bias, d.residual, d.bn_stats = x_ptr, w.fwd_ptr, out_ptr, _dp(w.bias), None, bn_stats
+    d.N, d.H, d.W, d.C, d.ldin, d.in_bs = x_geom
+    d.OH, d.OW, d.ldout, d.out_bs = out_geom
+    d.OC, d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu, d.out_f32 = w.OC, 0, 0, w.KH, w.KW, stride, pad, 0, int(bool(out_f32))
+
+
+def _fill_conv_bwd_desc(d, x_ptr, x_geom, w, dy_ptr, dy_geom, dx_ptr, dx_strides, accumulate, stride, pad, wgrad=False):
+    """One problem of emrt_conv2d_bwd_group (EmrtConvBwdDesc): x_geom = (N, H, W, C, ldx, x_bs) of the forward input, dy_geom = (OH, OW, lddy, dy_bs)
+    of the output's gradient, dx_strides = (lddx, dx_bs) of the data gradient, written or (accumulate) added to.  wgrad: this launch also
+    accumulates dW (and dbias); otherwise the weight gradient is batched (defer_wgrad)."""
+    d.x, d.dy, d.w_bwd_packed, d.dx = x_ptr, dy_ptr, w.bwd_ptr, dx_ptr
+    d.lddx, d.dx_bs = dx_strides
+    d.accumulate, d.dw, d.dbias = int(accumulate), (w.grad.data_ptr() if wgrad else None), (_dp(w.bias_grad) if wgrad and w.bias is not None else None)
+    d.N, d.H, d.W, d.C, d.ldx, d.x_bs = x_geom
+    d.OH, d.OW, d.lddy, d.dy_bs = dy_geom
+    d.OC, d.KH, d.KW, d.stride, d.pad = w.OC, w.KH, w.KW, stride, pad
 
 
 def wgrad_deferred(w):
@@ -312,30 +335,22 @@ def defer_wgrad(tape, x, dy, w, geom, stride, pad, dil):
     # a weight used twice in one step (a shared layer): its earlier contribution may be queued as "dW is zero: store the tile"; that
     # launch must be on the stream before this one's adds are (emrt_conv2d_wgrad_group also drops the store for aliased problems)
     dwp = w.grad.data_ptr()
-    if any(f[2] == dwp for f, _keep in tape.wgrads):
+    if any(q.dw == dwp for q, _keep in tape.wgrads):
         tape.flush_wgrads()
-    tape.wgrads.append(((x.data_ptr(), dy.data_ptr(), w.grad.data_ptr(), w.bias_grad.data_ptr() if w.bias is not None else None,
-                         N, H, Wd, C, ldx, x_bs, OH, OW, w.OC, lddy, dy_bs, w.KH, w.KW, stride, pad, dil, fresh), (x, dy)))
+    d = _WgradDesc()
+    d.x, d.dy, d.dw, d.dbias = x.data_ptr(), dy.data_ptr(), dwp, (w.bias_grad.data_ptr() if w.bias is not None else None)
+    d.N, d.H, d.W, d.C, d.ldx, d.x_bs, d.OH, d.OW, d.OC, d.lddy, d.dy_bs = N, H, Wd, C, ldx, x_bs, OH, OW, w.OC, lddy, dy_bs
+    d.KH, d.KW, d.stride, d.pad, d.dilation, d.dw_is_zero = w.KH, w.KW, stride, pad, dil, fresh
+    tape.wgrads.append((d, (x, dy)))
     if len(tape.wgrads) >= ctx().wgrad_batch:
         tape.flush_wgrads()
 
 
 def launch_wgrads(pending):
     c = ctx()
-    arr = (_WgradDesc * len(pending))()
-    for d, (f, _keep) in zip(arr, pending):
-        (d.x, d.dy, d.dw, d.dbias, d.N, d.H, d.W, d.C, d.ldx, d.x_bs, d.OH, d.OW, d.OC, d.lddy, d.dy_bs, d.KH, d.KW, d.stride, d.pad, d.dilation, d.dw_is_zero) = f
+    arr = (_WgradDesc * len(pending))(*[d for d, _keep in pending])
     stream = c.wgrad_fork([t for _f, keep in pending for t in keep]) if c.wgrad_side else c.stream
     _L().call("emrt_conv2d_wgrad_group", arr, len(pending), c.dtype, stream)
-
-
-class _DgradDesc(ctypes.Structure):       # EmrtConvDgradDesc (include/emrt_hip.h)
-    _fields_ = [("dy", ctypes.c_void_p), ("w_bwd_packed", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("lddx", ctypes.c_int), ("dx_bs", ctypes.c_longlong),
-                ("accumulate", ctypes.c_int), ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int), ("OH", ctypes.c_int),
-                ("OW", ctypes.c_int), ("OC", ctypes.c_int), ("lddy", ctypes.c_int), ("dy_bs", ctypes.c_longlong), ("KH", ctypes.c_int), ("KW", ctypes.c_int),
-                ("stride", ctypes.c_int), ("pad", ctypes.c_int), ("dilation", ctypes.c_int), ("bn_stats", ctypes.c_void_p), ("mask_y", ctypes.c_void_p),
-                ("ldy", ctypes.c_int), ("y_bs", ctypes.c_longlong), ("mask_scale", ctypes.c_float), ("stat_x", ctypes.c_void_p), ("ldsx", ctypes.c_int),
-                ("sx_bs", ctypes.c_longlong), ("addend", ctypes.c_void_p), ("ldadd", ctypes.c_int), ("add_bs", ctypes.c_longlong)]
 
 
 _PAIR_IDS = [0]
@@ -840,13 +855,14 @@ def conv_bn(conv, bn, x, relu=False, residual=None, out=None, defer=False):
     return _bn_tail(y, bn, sums, relu, residual, out, defer)
 
 
-class _BnGroupDesc(ctypes.Structure):      # EmrtBnGroupDesc (include/emrt_hip.h)
-    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("sums", ctypes.c_void_p),
-                ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p), ("run_mean", ctypes.c_void_p), ("run_var", ctypes.c_void_p),
-                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
-                ("count", ctypes.c_double), ("eps", ctypes.c_float), ("momentum", ctypes.c_float),
-                ("M", ctypes.c_int), ("C", ctypes.c_int), ("ldx", ctypes.c_int), ("ldy", ctypes.c_int), ("lddy", ctypes.c_int), ("lddx", ctypes.c_int),
-                ("relu", ctypes.c_int), ("res", ctypes.c_void_p), ("ldres", ctypes.c_int), ("res_hw", ctypes.c_int), ("res_bs", ctypes.c_longlong)]
+def _group_conv_ok(cv, bn_state, x, x_geom):
+    """what every grouped conv -> BatchNorm form asks of one of its problems (the vector path of emrt_conv2d_group with the statistics in its epilogue):
+    no dilation, no bias, more than 32 output channels, channels and strides in whole 16-byte vectors from an aligned base, one rank's statistics"""
+    w = cv.gw
+    N, H, W, C, ld, bs = x_geom
+    per16 = 4 if ctx().dtype == F32 else 8
+    return (getattr(cv, "dilation", 1) == 1 and w.bias is None and w.OC > 32 and w.C == C and C % per16 == 0 and w.OC % per16 == 0 and ld % per16 == 0
+            and bs % per16 == 0 and x.data_ptr() % 16 == 0 and not _sync_active(bn_state))
 
 
 def _small_group_ok(convs, bns, xs, post_adds=None):
@@ -854,17 +870,14 @@ def _small_group_ok(convs, bns, xs, post_adds=None):
     c = ctx()
     if not (c.training and c.bn_small_group and 2 <= len(convs) <= 4 and c.tape is not None and not c.overlap):
         return False
-    per16 = 4 if c.dtype == F32 else 8
     tiles = 0
     for i, (cv, b, x) in enumerate(zip(convs, bns, xs)):
         w = cv.gw
         if isinstance(x, PendingBN) or x.dim() not in (3, 4) or x.stride(-1) != 1:
             return False
         N, H, W, C, ld, bs = _check_map(x)
-        pad = cv.padding
-        if not (w.KH == w.KW and w.KH in (1, 3) and cv.stride == 1 and pad == w.KH // 2 and getattr(cv, "dilation", 1) == 1 and w.bias is None
-                and w.OC > 32 and C == w.C and C % per16 == 0 and w.OC % per16 == 0 and ld % per16 == 0 and bs % per16 == 0 and x.data_ptr() % 16 == 0
-                and w.OC % 4 == 0 and 256 % (w.OC // 4) == 0 and N * H * W <= 16384 and cv.need_dx and b.C == w.OC and not _sync_active(b.state)):
+        if not (w.KH == w.KW and w.KH in (1, 3) and cv.stride == 1 and cv.padding == w.KH // 2 and _group_conv_ok(cv, b.state, x, (N, H, W, C, ld, bs))
+                and w.OC % 4 == 0 and 256 % (w.OC // 4) == 0 and N * H * W <= 16384 and cv.need_dx and b.C == w.OC):
             return False
         if post_adds is not None and post_adds[i] is not None:
             r = post_adds[i]
@@ -903,10 +916,7 @@ def conv_bn_small_group(convs, bns, xs, relu=True, post_adds=None):
         sm = c.zeros_f64(BN_REPLICAS * 2 * w.OC)
         mean, invstd = c.empty((w.OC,), torch.float32), c.empty((w.OC,), torch.float32)
         M = N * H * W
-        d.inp, d.w_packed, d.out, d.bias, d.residual, d.bn_stats = x.data_ptr(), w.fwd_ptr, raw.data_ptr(), None, None, sm.data_ptr()
-        d.N, d.H, d.W, d.C, d.ldin, d.in_bs = N, H, W, C, ld, bs
-        d.OH, d.OW, d.OC, d.ldout, d.out_bs = H, W, w.OC, w.OC, H * W * w.OC
-        d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu, d.out_f32 = 0, 0, w.KH, w.KW, 1, cv.padding, 0, 0
+        _fill_conv_desc(d, x.data_ptr(), (N, H, W, C, ld, bs), w, raw.data_ptr(), (H, W, w.OC, H * W * w.OC), 1, cv.padding, bn_stats=sm.data_ptr())
         r = post_adds[i] if post_adds is not None else None
         q.x, q.y, q.dy, q.dx, q.sums = raw.data_ptr(), out.data_ptr(), None, None, sm.data_ptr()
         q.mean, q.invstd, q.run_mean, q.run_var = mean.data_ptr(), invstd.data_ptr(), _dp(st.run_mean), _dp(st.run_var)
@@ -957,12 +967,8 @@ def conv_bn_small_group(convs, bns, xs, relu=True, post_adds=None):
                 defer_wgrad(tape, x, draw, w, (N, H, W, C, ld, bs, H, W, w.OC, H * W * w.OC), 1, cv.padding, 1)
             slot = tape.grad_slot(x)
             dx = slot if slot is not None else c.empty(tuple(x.shape))
-            _, _, _, _, lddx, dx_bs = _check_map(dx)
-            d.x, d.dy, d.w_bwd_packed, d.dx = x.data_ptr(), draw.data_ptr(), w.bwd_ptr, dx.data_ptr()
-            d.lddx, d.dx_bs, d.accumulate, d.dw, d.dbias = lddx, dx_bs, int(slot is not None), None, None
-            d.N, d.H, d.W, d.C, d.ldx, d.x_bs = N, H, W, C, ld, bs
-            d.OH, d.OW, d.OC, d.lddy, d.dy_bs = H, W, w.OC, w.OC, H * W * w.OC
-            d.KH, d.KW, d.stride, d.pad = w.KH, w.KW, 1, cv.padding
+            _fill_conv_bwd_desc(d, x.data_ptr(), (N, H, W, C, ld, bs), w, draw.data_ptr(), (H, W, w.OC, H * W * w.OC), dx.data_ptr(), _check_map(dx)[4:6],
+                                slot is not None, 1, cv.padding)
             keep.append((draw, sm2, deferred))
             if slot is None:
                 fresh.append((x, dx))
@@ -1037,15 +1043,13 @@ def conv_bn_many(items, host_tiles=128):
     n = len(items)
     if not (c.training and c.bn_defer and c.tape is not None and 2 <= n <= 6 and not c.overlap):
         return None
-    per16 = 4 if c.dtype == F32 else 8
     tiles, geo = [], []
     for cv, bn, x, relu, defer, out in items:
         w = cv.gw
         if isinstance(x, PendingBN) or x.dim() != 4 or (defer == "conv" and not c.bn_conv):
             return None
         N, H, W, C, ld, bs = _check_map(x)
-        if not (w.KH == w.KW and w.KH in (1, 3) and getattr(cv, "dilation", 1) == 1 and w.bias is None and w.OC > 32 and w.C == C and C % per16 == 0
-                and w.OC % per16 == 0 and ld % per16 == 0 and bs % per16 == 0 and x.data_ptr() % 16 == 0 and not _sync_active(bn.state)):
+        if not (w.KH == w.KW and w.KH in (1, 3) and _group_conv_ok(cv, bn.state, x, (N, H, W, C, ld, bs))):
             return None
         OH, OW = (H + 2 * cv.padding - w.KH) // cv.stride + 1, (W + 2 * cv.padding - w.KW) // cv.stride + 1
         tiles.append(((N * OH * OW + 63) // 64) * ((w.OC + 63) // 64))
@@ -1058,10 +1062,7 @@ def conv_bn_many(items, host_tiles=128):
         w = cv.gw
         y = c.empty((N, OH, OW, w.OC))
         sm = c.zeros_f64(BN_REPLICAS * 2 * bn.C)
-        d.inp, d.w_packed, d.out, d.bias, d.residual, d.bn_stats = x.data_ptr(), w.fwd_ptr, y.data_ptr(), None, None, sm.data_ptr()
-        d.N, d.H, d.W, d.C, d.ldin, d.in_bs = N, H, W, C, ld, bs
-        d.OH, d.OW, d.OC, d.ldout, d.out_bs = OH, OW, w.OC, w.OC, OH * OW * w.OC
-        d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu, d.out_f32 = 0, 0, w.KH, w.KW, cv.stride, cv.padding, 0, 0
+        _fill_conv_desc(d, x.data_ptr(), (N, H, W, C, ld, bs), w, y.data_ptr(), (OH, OW, w.OC, OH * OW * w.OC), cv.stride, cv.padding, bn_stats=sm.data_ptr())
         ys.append(y); sums.append(sm)
     _L().call("emrt_conv2d_group", fd, n, c.dtype, c.stream)
     _PAIR_IDS[0] += 1
@@ -1084,15 +1085,13 @@ def conv_bn_pair(items, x):
     n = len(items)
     if not (c.training and c.bn_defer and c.conv_pair and 2 <= n <= 4 and not isinstance(x, PendingBN) and x.dim() == 4):
         return None
-    per16 = 4 if c.dtype == F32 else 8
     N, H, W, C, ld, bs = _check_map(x)
     tiles = 0
     for cv, bn, relu, defer in items:
         w = cv.gw
         if defer == "conv" and not c.bn_conv:
             return None
-        if not (w.KH == w.KW == 1 and cv.padding == 0 and getattr(cv, "dilation", 1) == 1 and w.bias is None and w.OC > 32 and w.C == C and C % per16 == 0
-                and w.OC % per16 == 0 and ld % per16 == 0 and bs % per16 == 0 and x.data_ptr() % 16 == 0 and not _sync_active(bn.state)):
+        if not (w.KH == w.KW == 1 and cv.padding == 0 and _group_conv_ok(cv, bn.state, x, (N, H, W, C, ld, bs))):
             return None
         OH, OW = (H - 1) // cv.stride + 1, (W - 1) // cv.stride + 1
         tiles += ((N * OH * OW + 63) // 64) * ((w.OC + 63) // 64)
@@ -1105,10 +1104,7 @@ def conv_bn_pair(items, x):
         OH, OW = (H - 1) // cv.stride + 1, (W - 1) // cv.stride + 1
         y = c.empty((N, OH, OW, w.OC))
         sm = c.zeros_f64(BN_REPLICAS * 2 * bn.C)
-        d.inp, d.w_packed, d.out, d.bias, d.residual, d.bn_stats = x.data_ptr(), w.fwd_ptr, y.data_ptr(), None, None, sm.data_ptr()
-        d.N, d.H, d.W, d.C, d.ldin, d.in_bs = N, H, W, C, ld, bs
-        d.OH, d.OW, d.OC, d.ldout, d.out_bs = OH, OW, w.OC, w.OC, OH * OW * w.OC
-        d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu, d.out_f32 = 0, 0, 1, 1, cv.stride, 0, 0, 0
+        _fill_conv_desc(d, x.data_ptr(), (N, H, W, C, ld, bs), w, y.data_ptr(), (OH, OW, w.OC, OH * OW * w.OC), cv.stride, 0, bn_stats=sm.data_ptr())
         ys.append(y); sums.append(sm)
     _L().call("emrt_conv2d_group", fd, n, c.dtype, c.stream)
     res = []
@@ -1216,28 +1212,6 @@ def group_norm(x, gamma, beta, dgamma, dbeta, G=32, eps=1e-5, gelu=False, residu
     return out
 
 
-class _ConvDesc(ctypes.Structure):        # EmrtConvDesc (include/emrt_hip.h)
-    _fields_ = [("inp", ctypes.c_void_p), ("w_packed", ctypes.c_void_p), ("out", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("residual", ctypes.c_void_p), ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int),
-                ("ldin", ctypes.c_int), ("in_bs", ctypes.c_longlong), ("OH", ctypes.c_int), ("OW", ctypes.c_int), ("OC", ctypes.c_int),
-                ("ldout", ctypes.c_int), ("out_bs", ctypes.c_longlong), ("ldres", ctypes.c_int), ("res_bs", ctypes.c_longlong),
-                ("KH", ctypes.c_int), ("KW", ctypes.c_int), ("stride", ctypes.c_int), ("pad", ctypes.c_int), ("relu", ctypes.c_int),
-                ("bn_stats", ctypes.c_void_p), ("out_f32", ctypes.c_int)]
-
-
-class _ConvBwdDesc(ctypes.Structure):     # EmrtConvBwdDesc
-    _fields_ = [("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("w_bwd_packed", ctypes.c_void_p), ("dx", ctypes.c_void_p),
-                ("lddx", ctypes.c_int), ("dx_bs", ctypes.c_longlong), ("accumulate", ctypes.c_int), ("dw", ctypes.c_void_p),
-                ("dbias", ctypes.c_void_p), ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int),
-                ("ldx", ctypes.c_int), ("x_bs", ctypes.c_longlong), ("OH", ctypes.c_int), ("OW", ctypes.c_int), ("OC", ctypes.c_int),
-                ("lddy", ctypes.c_int), ("dy_bs", ctypes.c_longlong), ("KH", ctypes.c_int), ("KW", ctypes.c_int), ("stride", ctypes.c_int),
-                ("pad", ctypes.c_int)]
-
-
-def _dp(t):
-    return t.data_ptr() if t is not None else None
-
-
 def level_conv_gn_takes_linears(src, convs, linears):
     """True when level_conv_gn(linears=) can put the projections into the level convolutions' forward launch: the grouped kernel's limits (6 problems,
     4096 tiles of 64 x 64 in all -- beyond that emrt_conv2d_group falls back to one launch per problem)"""
@@ -1277,12 +1251,8 @@ def level_conv_gn(src, convs, gns, spatial_shapes, level_spans, G=32, eps=1e-5, 
         lin_geo.append(tuple(linears[j][0].shape))
     for l, (w, (h, wd), (s0, n)) in enumerate(zip(convs, spatial_shapes, level_spans)):
         assert n == h * wd
-        d = fd[l]
-        d.inp, d.w_packed, d.out = src.data_ptr() + s0 * C * esz, w.fwd_ptr, y.data_ptr() + s0 * C * esz
-        d.bias = d.residual = d.bn_stats = None
-        d.N, d.H, d.W, d.C, d.ldin, d.in_bs = B, h, wd, C, C, Lv * C
-        d.OH, d.OW, d.OC, d.ldout, d.out_bs = h, wd, C, C, Lv * C
-        d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu = 0, 0, 3, 3, 1, 1, 0
+        off = s0 * C * esz
+        _fill_conv_desc(fd[l], src.data_ptr() + off, (B, h, wd, C, C, Lv * C), w, y.data_ptr() + off, (h, wd, C, Lv * C), 1, 1)
     _L().call("emrt_conv2d_group", fd, L + nl, c.dtype, c.stream)
     if nl and c.tape is not None:
         _record_linear_group_bwd(linears, lin_outs, lin_geo)
@@ -1315,16 +1285,12 @@ def level_conv_gn(src, convs, gns, spatial_shapes, level_spans, G=32, eps=1e-5, 
                 for w in convs:
                     w.grad_is_zero = False
             for l, (w, (h, wd), (s0, n)) in enumerate(zip(convs, spatial_shapes, level_spans)):
-                d = bd[l]
                 off = s0 * C * esz
-                d.x, d.dy, d.w_bwd_packed, d.dx = src.data_ptr() + off, dy.data_ptr() + off, w.bwd_ptr, dx.data_ptr() + off
-                d.lddx, d.dx_bs, d.accumulate, d.dw, d.dbias = C, Lv * C, int(slot is not None), None if deferred else w.grad.data_ptr(), None
                 if deferred:
                     xs, dys = src.narrow(1, s0, n), dy.narrow(1, s0, n)
                     defer_wgrad(tape, xs, dys, w, (B, h, wd, C, C, Lv * C, h, wd, C, Lv * C), 1, 1, 1)
-                d.N, d.H, d.W, d.C, d.ldx, d.x_bs = B, h, wd, C, C, Lv * C
-                d.OH, d.OW, d.OC, d.lddy, d.dy_bs = h, wd, C, C, Lv * C
-                d.KH, d.KW, d.stride, d.pad = 3, 3, 1, 1
+                _fill_conv_bwd_desc(bd[l], src.data_ptr() + off, (B, h, wd, C, C, Lv * C), w, dy.data_ptr() + off, (h, wd, C, Lv * C), dx.data_ptr() + off,
+                                    (C, Lv * C), slot is not None, 1, 1, wgrad=not deferred)
             _L().call("emrt_conv2d_bwd_group", bd, L, c.dtype, c.stream)
             if slot is None:
                 tape.add_grad(src, dx, owned=True)
@@ -1345,10 +1311,7 @@ def _linear_desc(d, x, w, out_f32):
     assert x.is_contiguous() and x.dim() == 3 and w.KH == w.KW == 1 and x.shape[2] == w.C
     B, L_, C = x.shape
     out = c.empty((B, L_, w.OC), torch.float32 if out_f32 else None)
-    d.inp, d.w_packed, d.out, d.bias, d.residual, d.bn_stats = x.data_ptr(), w.fwd_ptr, out.data_ptr(), _dp(w.bias), None, None
-    d.N, d.H, d.W, d.C, d.ldin, d.in_bs = B, 1, L_, C, C, L_ * C
-    d.OH, d.OW, d.OC, d.ldout, d.out_bs = 1, L_, w.OC, w.OC, L_ * w.OC
-    d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu, d.out_f32 = 0, 0, 1, 1, 1, 0, 0, int(bool(out_f32))
+    _fill_conv_desc(d, x.data_ptr(), (B, 1, L_, C, C, L_ * C), w, out.data_ptr(), (1, L_, w.OC, L_ * w.OC), 1, 0, out_f32=out_f32)
     return out
 
 
@@ -1402,11 +1365,8 @@ def _record_linear_group_bwd(items, outs, geo):
             slot = tape.grad_slot(x)
             dx = slot if slot is not None else c.empty((B, L_, C))
             assert dx.is_contiguous()
-            d.x, d.dy, d.w_bwd_packed, d.dx = x.data_ptr(), dy.data_ptr(), w.bwd_ptr, dx.data_ptr()
-            d.lddx, d.dx_bs, d.accumulate, d.dw, d.dbias = C, L_ * C, int(slot is not None), None, None
-            d.N, d.H, d.W, d.C, d.ldx, d.x_bs = B, 1, L_, C, C, L_ * C
-            d.OH, d.OW, d.OC, d.lddy, d.dy_bs = 1, L_, w.OC, w.OC, L_ * w.OC
-            d.KH, d.KW, d.stride, d.pad = 1, 1, 1, 0
+            _fill_conv_bwd_desc(d, x.data_ptr(), (B, 1, L_, C, C, L_ * C), w, dy.data_ptr(), (1, L_, w.OC, L_ * w.OC), dx.data_ptr(), (C, L_ * C),
+                                slot is not None, 1, 0)
             if slot is None:
                 fresh.append((x, dx))
         _L().call("emrt_conv2d_bwd_group", bd, len(live), c.dtype, c.stream)
@@ -1437,12 +1397,7 @@ def level_proj_gn(feats, convs, gns, G=32, eps=1e-5):
     fd = (_ConvDesc * L)()
     for l, (w, f, (a, n)) in enumerate(zip(convs, feats, spans)):
         _, h, wd, Cl = f.shape
-        d = fd[l]
-        d.inp, d.w_packed, d.out, d.bias = f.data_ptr(), w.fwd_ptr, y.data_ptr() + a * OC * esz, _dp(w.bias)
-        d.residual = d.bn_stats = None
-        d.N, d.H, d.W, d.C, d.ldin, d.in_bs = B, h, wd, Cl, Cl, h * wd * Cl
-        d.OH, d.OW, d.OC, d.ldout, d.out_bs = h, wd, OC, OC, Lv * OC
-        d.ldres, d.res_bs, d.KH, d.KW, d.stride, d.pad, d.relu = 0, 0, 1, 1, 1, 0, 0
+        _fill_conv_desc(fd[l], f.data_ptr(), (B, h, wd, Cl, Cl, h * wd * Cl), w, y.data_ptr() + a * OC * esz, (h, wd, OC, Lv * OC), 1, 0)
     _L().call("emrt_conv2d_group", fd, L, c.dtype, c.stream)
     starts = (ctypes.c_int * L)(*[a for a, _ in spans])
     hws = (ctypes.c_int * L)(*[n for _, n in spans])
@@ -1473,17 +1428,10 @@ def level_proj_gn(feats, convs, gns, G=32, eps=1e-5):
                     w.grad_is_zero = False
             for l, (w, f, (a, n), dx) in enumerate(zip(convs, feats, spans, dxs)):
                 _, h, wd, Cl = f.shape
-                _, _, _, _, lddx, dx_bs = _check_map(dx)
-                d = bd[l]
-                d.x, d.dy, d.w_bwd_packed, d.dx = f.data_ptr(), dy.data_ptr() + a * OC * esz, w.bwd_ptr, dx.data_ptr()
-                d.lddx, d.dx_bs, d.accumulate = lddx, dx_bs, int(slots[l] is not None)
-                d.dw = None if deferred else w.grad.data_ptr()
-                d.dbias = None if deferred else (_dp(w.bias_grad) if w.bias is not None else None)
                 if deferred:
                     defer_wgrad(tape, f, dy.narrow(1, a, n), w, (B, h, wd, Cl, Cl, h * wd * Cl, h, wd, OC, Lv * OC), 1, 0, 1)
-                d.N, d.H, d.W, d.C, d.ldx, d.x_bs = B, h, wd, Cl, Cl, h * wd * Cl
-                d.OH, d.OW, d.OC, d.lddy, d.dy_bs = h, wd, OC, OC, Lv * OC
-                d.KH, d.KW, d.stride, d.pad = 1, 1, 1, 0
+                _fill_conv_bwd_desc(bd[l], f.data_ptr(), (B, h, wd, Cl, Cl, h * wd * Cl), w, dy.data_ptr() + a * OC * esz, (h, wd, OC, Lv * OC), dx.data_ptr(),
+                                    _check_map(dx)[4:6], slots[l] is not None, 1, 0, wgrad=not deferred)
             _L().call("emrt_conv2d_bwd_group", bd, L, c.dtype, c.stream)
             for s_, f, dx in zip(slots, feats, dxs):
                 if s_ is None:
@@ -1976,11 +1924,6 @@ def ohem_ce_pair(logits_a, logits_b, labels, ignore_index, thresh, min_kept, wa,
             tape.add_grad(logits_b, db, owned=True)
         tape.record(bwd)
     return res_a, res_b, total, prob_a, prob_b
-
-
-class _AugDesc(ctypes.Structure):         # EmrtAugDesc (include/emrt_hip.h)
-    _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int), ("h", ctypes.c_int),
-                ("w", ctypes.c_int), ("off_y", ctypes.c_int), ("off_x", ctypes.c_int), ("flip", ctypes.c_int)]
 
 
 def augment_tiles(src, samples, out_size, mean, stdinv, img_pad, label_pad, label_lut=None, labels=True):

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from ... import _lib
 from ..transforms import Compose, DevicePlan
 
 
@@ -270,8 +271,7 @@ class DeviceTileLoader(TileLoader):
 
 # ---- whole scenes resident in device memory (train.py --data scenes) -----------------------------------------------------------
 
-class _SceneEntry(ctypes.Structure):       # EmrtSceneEntry (include/emrt_hip.h)
-    _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+_SceneEntry = _lib.struct("EmrtSceneEntry")      # generated from include/emrt_hip.h
 
 
 MAX_SCALES = 16           # csrc/augment.hip SCENE_MAX_SCALES: scale entries of one emrt_scene_draw launch

@@ -31,12 +31,9 @@ class PolynomialDecay:
         return EmrtLrSchedule(kind=0, base_lr=self.base_lr, end_lr=self.end_lr, power=self.power, total_steps=int(self.decay_steps))
 
 
-class EmrtLrSchedule(ctypes.Structure):
-    """include/emrt_hip.h: EmrtLrSchedule, the host descriptor the schedule-driven optimizer kernels evaluate on the device."""
-    KINDS = ("PolynomialDecay", "WarmupPolyLR", "WarmupCosineLR", "WarmupMultiStepLR")
-    _fields_ = [("kind", ctypes.c_int), ("base_lr", ctypes.c_float), ("end_lr", ctypes.c_float), ("power", ctypes.c_float),
-                ("warmup_lr_init", ctypes.c_float), ("gamma", ctypes.c_float), ("total_steps", ctypes.c_longlong),
-                ("warmup_steps", ctypes.c_longlong), ("nmilestones", ctypes.c_int), ("milestones", ctypes.c_longlong * 16)]
+EmrtLrSchedule = _lib.struct("EmrtLrSchedule")      # generated from include/emrt_hip.h
+EmrtLrSchedule.__doc__ = "include/emrt_hip.h: EmrtLrSchedule, the host descriptor the schedule-driven optimizer kernels evaluate on the device."
+EmrtLrSchedule.KINDS = ("PolynomialDecay", "WarmupPolyLR", "WarmupCosineLR", "WarmupMultiStepLR")
 
 
 class _Schedule:

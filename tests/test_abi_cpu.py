@@ -1,9 +1,11 @@
 """CPU: the C-ABI shared library loads and exports exactly what include/emrt_hip.h declares; the header's prototypes are
-the definitions' prototypes (no compute calls -- there is no GPU here)."""
+the definitions' prototypes and the generated descriptor classes have the compiled layout (no compute calls -- there is no GPU here)."""
+import ast
 import ctypes
 import glob
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -44,6 +46,95 @@ def test_header_matches_definitions():
     assert set(defs) == set(protos)
     for name, (ret, args) in protos.items():
         assert [t for t, _ in args] == defs[name], name
+
+
+def _host_cxx():
+    """the clang++ that sits beside the hipcc build_ext uses (host-only compiles: no offload arch, nothing GPU)"""
+    from emrt_amd import build_ext
+    hipcc = shutil.which(build_ext._hipcc())
+    assert hipcc, "hipcc not found"
+    d = os.path.dirname(os.path.realpath(hipcc))
+    for cand in ("amdclang++", "../llvm/bin/clang++", "../lib/llvm/bin/clang++", "clang++"):
+        if os.path.exists(os.path.join(d, cand)):
+            return os.path.normpath(os.path.join(d, cand))
+    raise AssertionError("no clang++ beside %s" % hipcc)
+
+
+def test_generated_structs_have_the_compiled_layout(tmp_path):
+    """sizeof and every offsetof, as the C++ compiler lays include/emrt_hip.h out, against the ctypes classes generated from the same header"""
+    from emrt_amd import _lib
+    structs = _lib.parse_structs()
+    lines = ["#include <cstddef>", "#include <cstdio>", '#include "emrt_hip.h"', "int main() {"]
+    for name, members in structs.items():
+        lines.append('  std::printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        lines += ['  std::printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (name, m, name, m) for _, m, _ in members]
+    (tmp_path / "layout.cpp").write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([_host_cxx(), "-std=c++17", "-I", os.path.dirname(_lib.HEADER), str(tmp_path / "layout.cpp"), "-o", exe], check=True, capture_output=True, text=True)
+    compiled = dict(line.split() for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
+    generated = {}
+    for name, members in structs.items():
+        S = _lib.struct(name)
+        generated[name] = str(ctypes.sizeof(S))
+        generated.update({"%s.%s" % (name, m): str(getattr(S, _lib.member_name(name, m)).offset) for _, m, _ in members})
+    assert len(generated) == 8 + 151 and generated == compiled
+
+
+def test_no_struct_of_the_header_escapes_the_parser():
+    from emrt_amd import _lib
+    structs = _lib.parse_structs()
+    assert len(structs) == len(re.findall(r"typedef\s+struct", open(_lib.HEADER).read())) == 8
+    # a prototype parameter is a scalar, a pointer to one (or to void / char), or a pointer to a parsed struct
+    builtin = {"void", "char", "short", "int", "long", "unsigned", "signed", "float", "double", "size_t"}
+    named = set()
+    for name, (ret, args) in _lib.parse_header().items():
+        for t, a in args:
+            base = t.replace("const", "").replace("*", "").strip()
+            if not set(base.split()) <= builtin:
+                assert base in structs and t.endswith("*"), "%s.%s: %r" % (name, a, t)
+                named.add(base)
+    assert named == set(structs)
+    assert len(_lib.parse_header()) == 109
+
+
+@pytest.mark.parametrize("body, offender", [
+    ("typedef struct A { int n; half x; } A;", r"A\.x.*half"),                        # an unknown member type
+    ("typedef struct A { int n; float lambda; } A;", r"A\.lambda"),                   # a keyword member other than `in`
+    ("typedef struct A { int n; } B;", r"'A'.*'B'"),                                  # tag and typedef name differ
+    ("typedef struct A { float *a, *b; int n; } A;", r"A\.b"),                        # the `T *a, *b` form
+    ("typedef struct A { int n; unsigned flags : 3; } A;", r"A: .*flags"),            # a bit-field
+    ("typedef struct A { struct { int a; } inner; int n; } A;", r"A"),                # a nested struct
+])
+def test_struct_parser_refuses_what_it_does_not_understand(tmp_path, body, offender):
+    from emrt_amd import _lib
+    h = tmp_path / "snippet.h"
+    h.write_text("/* a header */\ntypedef struct Ok { const void* in; long long m[4]; int a, b; } Ok;\n" + body + "\n")
+    with pytest.raises(_lib.EmrtHipError, match=offender):
+        _lib.parse_structs(str(h))
+    h.write_text("typedef struct Ok { const void* in; long long m[4]; int a, b; } Ok;\n")
+    assert _lib.parse_structs(str(h)) == {"Ok": [("const void*", "in", None), ("long long", "m", 4), ("int", "a", None), ("int", "b", None)]}
+    assert _lib.member_name("Ok", "in") == "inp"
+
+
+def test_one_class_per_struct_everywhere():
+    from emrt_amd import _lib
+    from emrt_amd import functional as Fn
+    from emrt_amd.src import datasets
+    from emrt_amd.src.models import solver
+    for n in _lib.parse_structs():
+        assert _lib.struct(n) is _lib.struct(n) and issubclass(_lib.struct(n), ctypes.Structure)
+    assert (_lib.struct("EmrtConvDesc") * 3) is (Fn._ConvDesc * 3)
+    users = {"EmrtConvDesc": Fn._ConvDesc, "EmrtConvBwdDesc": Fn._ConvBwdDesc, "EmrtConvDgradDesc": Fn._DgradDesc, "EmrtWgradDesc": Fn._WgradDesc,
+             "EmrtBnGroupDesc": Fn._BnGroupDesc, "EmrtAugDesc": Fn._AugDesc, "EmrtSceneEntry": datasets._SceneEntry, "EmrtLrSchedule": solver.EmrtLrSchedule}
+    # tools/bench_conv.py opens the GPU on import: the right-hand side of its `_WD = ...` line is evaluated instead
+    tree = ast.parse(open(os.path.join(ROOT, "tools", "bench_conv.py")).read())
+    (wd,) = [n.value for n in tree.body if isinstance(n, ast.Assign) and [t.id for t in n.targets if isinstance(t, ast.Name)] == ["_WD"]]
+    assert eval(compile(ast.Expression(wd), "bench_conv.py", "eval"), {"_lib": _lib}) is _lib.struct("EmrtWgradDesc")
+    for n, cls in users.items():
+        assert cls is _lib.struct(n), n
+    assert set(users) == set(_lib.parse_structs())
+    with pytest.raises(_lib.EmrtHipError, match="EmrtNoSuchDesc"):
+        _lib.struct("EmrtNoSuchDesc")
 
 
 def test_loader_binds_all_entry_points(built):

@@ -160,15 +160,11 @@ def test_label_lut_is_lovedas_shift():
     assert np.array_equal(lut, want) and lut[0] == 255 and lut[255] == 255 and lut[1] == 0
 
 
-class _Desc(ctypes.Structure):
-    _fields_ = [("img_off", ctypes.c_longlong), ("lab_off", ctypes.c_longlong), ("H", ctypes.c_int), ("W", ctypes.c_int), ("h", ctypes.c_int),
-                ("w", ctypes.c_int), ("off_y", ctypes.c_int), ("off_x", ctypes.c_int), ("flip", ctypes.c_int)]
-
-
 def test_entry_point_refuses_bad_descriptors_before_any_launch():
     """Against the real library, no GPU: every bad call returns non-zero with a message before anything touches a device (the pointers
     are never dereferenced)."""
     from emrt_amd import _lib, build_ext
+    _Desc = _lib.struct("EmrtAugDesc")
     build_ext.build(verbose=False)
     _lib._LIB = None
     L = _lib.lib()

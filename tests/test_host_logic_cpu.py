@@ -27,6 +27,23 @@ def _place(model):
     return model
 
 
+def test_fake_abi_checks_descriptor_tables_and_logs_them_member_by_member(fake):
+    import ctypes
+    from emrt_amd import _lib
+    arr = (_lib.struct("EmrtWgradDesc") * 2)()
+    arr[0].dw, arr[0].N, arr[1].dy = 0x1008, 3, 0x2004
+    fake.call("emrt_conv2d_wgrad_group", arr, 2, 0, ctypes.c_void_p(0))
+    fake.call("emrt_conv2d_wgrad_group", 0x3000, 1, 0, None)              # a plain address: a table that lives somewhere else
+    fake.call("emrt_cast", ctypes.c_void_p(0x4010), None, 5, True, 0, None)
+    with pytest.raises(AssertionError, match="expected an array of EmrtWgradDesc"):
+        fake.call("emrt_conv2d_wgrad_group", (_lib.struct("EmrtConvBwdDesc") * 1)(), 1, 0, None)
+    first, second, third = fake.canonical_log().splitlines()
+    assert first.startswith("emrt_conv2d_wgrad_group(descs=[{x=null, dy=null, dw=ptr%16=8, dbias=null, N=3, H=0, ") and first.count("{") == 2
+    assert "}, {x=null, dy=ptr%16=4, dw=null, " in first and first.endswith("dw_is_zero=0}], n=2, dtype=0, stream=null)")
+    assert second == "emrt_conv2d_wgrad_group(descs=ptr%16=0, n=1, dtype=0, stream=null)"
+    assert third.startswith("emrt_cast(") and "=ptr%16=0, " in third and "=null, " in third and "=5, " in third and "=1, " in third
+
+
 @pytest.mark.parametrize("backbone", ["resnet18", "resnet50"])
 def test_train_step_launch_sequence(fake, backbone):
     from emrt_amd.src.models.emrt import EMRT

@@ -164,12 +164,7 @@ def wbig():
         print(line, flush=True)
 
 
-class _WD(ctypes.Structure):       # EmrtWgradDesc
-    _fields_ = [("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("dbias", ctypes.c_void_p),
-                ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int), ("ldx", ctypes.c_int),
-                ("x_bs", ctypes.c_longlong), ("OH", ctypes.c_int), ("OW", ctypes.c_int), ("OC", ctypes.c_int), ("lddy", ctypes.c_int),
-                ("dy_bs", ctypes.c_longlong), ("KH", ctypes.c_int), ("KW", ctypes.c_int), ("stride", ctypes.c_int), ("pad", ctypes.c_int),
-                ("dilation", ctypes.c_int), ("dw_is_zero", ctypes.c_int)]
+_WD = _lib.struct("EmrtWgradDesc")
 
 
 def wgroup8():
