@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libemrt_hip.so")
-SOURCES = ["conv.hip", "norm.hip", "msda.hip", "attn.hip", "spatial.hip", "loss_optim.hip", "elementwise.hip", "gconv.hip", "augment.hip", "ohem.hip", "scene.hip"]
+SOURCES = ["conv.hip", "norm.hip", "msda.hip", "attn.hip", "spatial.hip", "loss.hip", "optim.hip", "elementwise.hip", "gconv.hip", "augment.hip", "scene.hip"]
 HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip.h")      # the public C-ABI: csrc/common.hpp includes it, so it is an input of every object
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]

@@ -278,6 +278,44 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// K partial sums per thread -> out[0..K) = the K sums of a 256-thread block, in ONE order (the streaming loss kernels promise each other's bits):
+// wave sum, lane 0 to slot [wave][k], thread 0 adds the four waves in order 0..3.  red: K * 4 floats of LDS.
+template <int K>
+__device__ __forceinline__ void block_sum_256(const float (&v)[K], float* red, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float s[K];
+  // (the K wave sums first, the stores behind them: the shuffles of the K chains then overlap instead of waiting for one another)
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = wave_sum(v[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wv * K + k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float a = 0.f;
+      for (int w = 0; w < 4; ++w) a += red[w * K + k];
+      out[k] = a;
+    }
+  }
+}
+// the fp64 tree behind every one-block finalize launch: K values per thread of a 256-thread block -> r[k][0], o = 128 ... 1 (a single-thread
+// loop over up to 4096 partials took 70 us of dependent loads).  Ends on a barrier; a caller that reuses r puts one behind its read of r[k][0].
+template <int K>
+__device__ __forceinline__ void block_tree_sum_f64(const double (&a)[K], double (*r)[256]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) r[k][threadIdx.x] = a[k];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) r[k][threadIdx.x] += r[k][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+}
 
 // counter-based RNG for dropout: one 32-bit hash of (seed, salt, index).  keep iff u >= p.
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {

@@ -1,5 +1,9 @@
-// Hard-pixel mining and class-weighted cross entropy for gfx950.
+// The loss kernels for gfx950: softmax cross entropy, its class-weighted form and hard-pixel mining, all HBM-bound streaming
+// passes over fp32 NCHW logits.  ONE copy of the per-pixel arithmetic (pixel_stats / pixel_ce / pixel_grad_store / pixel_zero_store) serves every
+// kernel here, so "pair == two singles", "unit weights == plain" and "OHEM pair == singles" hold to the last bit by construction.
 //
+//  * softmax cross entropy with ignore_index (reference: losses/mix_softmax_cross_entropy_loss.py:27-35 -> paddle
+//    nn.CrossEntropyLoss(ignore_index=255, axis=1)): the class-weighted family below with the weight compiled out.
 //  * OhemCrossEntropyLoss (reference: losses/ohem_cross_entropy_loss.py:41-79).  The reference finds its threshold with an argsort over every
 //    pixel and a device-to-host read in the middle of the loss; here the min_kept-th smallest probability is found by an exact radix select
 //    (11 + 11 + 10 bits, most significant digit first) over the fp32 bit patterns, entirely on the device: a captured step stays one graph.
@@ -50,9 +54,41 @@ inline OhemWs ohem_ws(void* workspace, int heads) {
   return w;
 }
 
+// ---- the pixel core: every loss kernel's index split and softmax arithmetic, written once ------------------------------------------
 __device__ __forceinline__ void pixel_of(long long idx, long long total, long long HW, long long& n, long long& p) {
   n = total <= 0xffffffffll ? (long long)((unsigned)idx / (unsigned)HW) : idx / HW;      // (32-bit division when it can be)
   p = idx - n * HW;
+}
+
+struct PixelStats {
+  float mx, den;      // max logit over the classes, sum of exp(logit - max)
+};
+__device__ __forceinline__ PixelStats pixel_stats(const float* __restrict__ lp, int C, long long HW) {
+  PixelStats s;
+  s.mx = -3.0e38f;
+  for (int c = 0; c < C; ++c) s.mx = fmaxf(s.mx, lp[c * HW]);
+  s.den = 0.f;
+  for (int c = 0; c < C; ++c) s.den += __expf(lp[c * HW] - s.mx);
+  return s;
+}
+// the pixel's CE; pr = softmax probability of its own class (a label outside [0, C) that is not ignore_index picks logit 0, as it always did)
+__device__ __forceinline__ float pixel_ce(const float* __restrict__ lp, int C, long long HW, long long lab, const PixelStats& s, float& pr) {
+  const float picked = (lab >= 0 && lab < C) ? lp[lab * HW] : 0.f;
+  pr = __expf(picked - s.mx) / s.den;
+  return logf(s.den) + s.mx - picked;
+}
+__device__ __forceinline__ float pixel_ce(const float* __restrict__ lp, int C, long long HW, long long lab) {
+  float pr;
+  return pixel_ce(lp, C, HW, lab, pixel_stats(lp, C, HW), pr);
+}
+// dp[c] = g * (softmax_c - onehot_c)
+__device__ __forceinline__ void pixel_grad_store(const float* __restrict__ lp, float* __restrict__ dp, int C, long long HW, long long lab, float g) {
+  const PixelStats s = pixel_stats(lp, C, HW);
+  const float inv = 1.f / s.den;
+  for (int c = 0; c < C; ++c) dp[c * HW] = g * (__expf(lp[c * HW] - s.mx) * inv - (c == lab ? 1.f : 0.f));
+}
+__device__ __forceinline__ void pixel_zero_store(float* __restrict__ dp, int C, long long HW) {
+  for (int c = 0; c < C; ++c) dp[c * HW] = 0.f;
 }
 
 // the block's LDS histogram -> the global bins: one integer atomic per non-empty bin
@@ -64,7 +100,7 @@ __device__ __forceinline__ void flush_bins(const unsigned* lh, unsigned* __restr
   }
 }
 
-// pass over the logits: p = softmax probability of the pixel's own class (the arithmetic of loss_optim.hip's ce_pixel) and its CE, both stored;
+// pass over the logits: p = softmax probability of the pixel's own class and its CE, both stored;
 // histogram of the keys' first digit over the non-ignored pixels (its total is num_valid)
 template <int NH>
 __global__ __launch_bounds__(256) void ohem_prob_kernel(OhemHeads<NH> hd, const long long* __restrict__ labels, int N, int C, long long HW, int ignore_index,
@@ -87,14 +123,10 @@ __global__ __launch_bounds__(256) void ohem_prob_kernel(OhemHeads<NH> hd, const 
     long long n, p;
     pixel_of(idx, total, HW, n, p);
     const float* lp = logits + n * C * HW + p;
-    float mx = -3.0e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lp[c * HW]);
-    float den = 0.f;
-    for (int c = 0; c < C; ++c) den += __expf(lp[c * HW] - mx);
-    const float picked = (lab >= 0 && lab < C) ? lp[lab * HW] : 0.f;
-    const float pr = __expf(picked - mx) / den;
+    float pr;
+    const float v = pixel_ce(lp, C, HW, lab, pixel_stats(lp, C, HW), pr);
     prob[idx] = pr;
-    ce[idx] = logf(den) + mx - picked;
+    ce[idx] = v;
     atomicAdd(&lh[__float_as_uint(pr) >> 21], 1u);
   }
   flush_bins(lh, ws.hist + h * OH_SEL_WORDS, OH_BINS);
@@ -191,48 +223,32 @@ __global__ __launch_bounds__(256) void ohem_sum_kernel(OhemHeads<NH> hd, long lo
   const float* __restrict__ ce = ws.ce + h * total;
   float* partial = ws.partial + h * OH_MAX_BLOCKS * 2;
   const float thr = hd.result[h][2];
-  float ls = 0.f, cnt = 0.f;
+  float acc[2] = {0.f, 0.f};      // loss, kept count
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-    if (prob[idx] < thr) { ls += ce[idx]; cnt += 1.f; }
+    if (prob[idx] < thr) { acc[0] += ce[idx]; acc[1] += 1.f; }
   }
-  ls = wave_sum(ls);
-  cnt = wave_sum(cnt);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) { red[wv * 2] = ls; red[wv * 2 + 1] = cnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.f, b = 0.f;
-    for (int w = 0; w < 4; ++w) { a += red[w * 2]; b += red[w * 2 + 1]; }
-    partial[blockIdx.x * 2] = a;
-    partial[blockIdx.x * 2 + 1] = b;
-  }
+  block_sum_256<2>(acc, red, partial + blockIdx.x * 2);
 }
 
 // one block; per head: result = {loss, kept count, threshold (written by the scan), non-ignored count, 1 / (kept + 1e-5 npix) or 0 when nothing is
 // kept}; total[0] = sum of w_h * loss_h (null: not wanted)
 template <int NH>
 __global__ __launch_bounds__(256) void ohem_finalize_kernel(OhemHeads<NH> hd, OhemWs ws, int nblk, double npix, float* __restrict__ total) {
-  __shared__ double ra[256], rb[256];
+  __shared__ double r[2][256];
   float t = 0.f;
   for (int h = 0; h < NH; ++h) {
     const float* partial = ws.partial + h * OH_MAX_BLOCKS * 2;
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) { a += partial[i * 2]; b += partial[i * 2 + 1]; }
-    ra[threadIdx.x] = a;
-    rb[threadIdx.x] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) { ra[threadIdx.x] += ra[threadIdx.x + o]; rb[threadIdx.x] += rb[threadIdx.x + o]; }
-      __syncthreads();
-    }
+    double a[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < nblk; i += 256) { a[0] += partial[i * 2]; a[1] += partial[i * 2 + 1]; }
+    block_tree_sum_f64<2>(a, r);
     if (threadIdx.x == 0) {
       // mean(loss * mask) / (mean(mask) + 1e-5) of the reference, numerator and denominator times npix (npix counts the ignored pixels too)
-      const double den = rb[0] + 1e-5 * npix;
+      const double den = r[1][0] + 1e-5 * npix;
       float* result = hd.result[h];
-      result[0] = (float)(ra[0] / den);
-      result[1] = (float)rb[0];
+      result[0] = (float)(r[0][0] / den);
+      result[1] = (float)r[1][0];
       result[3] = (float)ws.hist[h * OH_SEL_WORDS + 3 * OH_BINS + ST_VALID];
-      result[4] = rb[0] > 0.0 ? (float)(1.0 / den) : 0.f;
+      result[4] = r[1][0] > 0.0 ? (float)(1.0 / den) : 0.f;
       t += hd.w[h] * result[0];
     }
     __syncthreads();
@@ -256,38 +272,28 @@ __global__ __launch_bounds__(256) void ohem_bwd_kernel(OhemHeads<NH> hd, const l
     pixel_of(idx, total, HW, n, p);
     const float* lp = logits + n * C * HW + p;
     float* dp = dlogits + n * C * HW + p;
-    if (lab == ignore_index || !(prob[idx] < thr)) {
-      for (int c = 0; c < C; ++c) dp[c * HW] = 0.f;
-      continue;
-    }
-    float mx = -3.0e38f;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lp[c * HW]);
-    float den = 0.f;
-    for (int c = 0; c < C; ++c) den += __expf(lp[c * HW] - mx);
-    const float inv = 1.f / den;
-    for (int c = 0; c < C; ++c) dp[c * HW] = g * (__expf(lp[c * HW] - mx) * inv - (c == lab ? 1.f : 0.f));
+    if (lab == ignore_index || !(prob[idx] < thr)) pixel_zero_store(dp, C, HW);
+    else pixel_grad_store(lp, dp, C, HW, lab, g);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// class-weighted cross entropy, NH = 1 head or the 2 heads of the Mix loss
+// cross entropy, NH = 1 head or the 2 heads of the Mix loss (mix_softmax_cross_entropy_loss.py:29-35,44-51: CE(main) + 0.4 CE(aux) on the SAME
+// labels, read once).  CW = true: class-weighted, cw[C] on the device; CW = false: the plain CE -- no weight load, no multiply: what
+// emrt_softmax_ce_* runs, and emrt_wce_* with class_weight == NULL.
 // ------------------------------------------------------------------------------------------------
-template <int NH>
-struct WceHeads {
-  const float* logits[NH];
-  float* out[NH];          // forward: result[2] per head; backward: dlogits
-  const float* up[NH];
-  float w[NH];
-};
-
+// The kernels take the heads as plain __restrict__ pointer and scalar arguments (head b unused when NH = 1), as the plain CE kernels always
+// did: handed over as a by-value record the plain forward measured 0.6 us slower at 8 x 6 x 256 x 256.
+template <bool CW>
 __device__ __forceinline__ float class_weight_of(const float* __restrict__ cw, long long lab, int C) {
-  return cw ? ((lab >= 0 && lab < C) ? cw[lab] : 0.f) : 1.f;
+  return CW ? ((lab >= 0 && lab < C) ? cw[lab] : 0.f) : 1.f;
 }
 
-// partial[block] = {sum w[y] CE of head 0, (of head 1,) sum w[y]}
-template <int NH>
-__global__ __launch_bounds__(256) void wce_fwd_kernel(WceHeads<NH> hd, const long long* __restrict__ labels, const float* __restrict__ cw, int N, int C,
-                                                      long long HW, int ignore_index, float* __restrict__ partial) {
+// partial[block] = {sum w[y] CE of head a, (of head b,) sum w[y]}
+template <int NH, bool CW>
+__global__ __launch_bounds__(256) void wce_fwd_kernel(const float* __restrict__ la, const float* __restrict__ lb, const long long* __restrict__ labels,
+                                                      const float* __restrict__ cw, int N, int C, long long HW, int ignore_index,
+                                                      float* __restrict__ partial) {
   __shared__ float red[(NH + 1) * 4];
   const long long total = (long long)N * HW;
   float acc[NH + 1];
@@ -298,36 +304,22 @@ __global__ __launch_bounds__(256) void wce_fwd_kernel(WceHeads<NH> hd, const lon
     if (lab == ignore_index) continue;
     long long n, p;
     pixel_of(idx, total, HW, n, p);
-    const float w = class_weight_of(cw, lab, C);
+    const float w = class_weight_of<CW>(cw, lab, C);
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
-      const float* lp = hd.logits[h] + n * C * HW + p;
-      float mx = -3.0e38f;
-      for (int c = 0; c < C; ++c) mx = fmaxf(mx, lp[c * HW]);
-      float den = 0.f;
-      for (int c = 0; c < C; ++c) den += __expf(lp[c * HW] - mx);
-      const float picked = (lab >= 0 && lab < C) ? lp[lab * HW] : 0.f;
-      acc[h] += w * (logf(den) + mx - picked);
+      const float ce = pixel_ce((h ? lb : la) + n * C * HW + p, C, HW, lab);
+      acc[h] += CW ? w * ce : ce;
     }
     acc[NH] += w;
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int h = 0; h <= NH; ++h) {
-    const float v = wave_sum(acc[h]);
-    if (lane == 0) red[wv * (NH + 1) + h] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x <= NH) {
-    float a = 0.f;
-    for (int w = 0; w < 4; ++w) a += red[w * (NH + 1) + threadIdx.x];
-    partial[blockIdx.x * (NH + 1) + threadIdx.x] = a;
-  }
+  block_sum_256<NH + 1>(acc, red, partial + blockIdx.x * (NH + 1));
 }
 
-// result of head h = {sum w CE / sum w, sum w}; two heads: total[0] = wa * loss_a + wb * loss_b
+// result of head h = {sum w CE / sum w, sum w} (plain: {mean loss over the non-ignored pixels, their count}); two heads: total[0] = wa * loss_a +
+// wb * loss_b
 template <int NH>
-__global__ __launch_bounds__(256) void wce_finalize_kernel(const float* __restrict__ partial, int nblk, WceHeads<NH> hd, float* __restrict__ total) {
+__global__ __launch_bounds__(256) void wce_finalize_kernel(const float* __restrict__ partial, int nblk, float wa, float wb, float* __restrict__ res_a,
+                                                           float* __restrict__ res_b, float* __restrict__ total) {
   __shared__ double r[NH + 1][256];
   double a[NH + 1];
 #pragma unroll
@@ -336,70 +328,103 @@ __global__ __launch_bounds__(256) void wce_finalize_kernel(const float* __restri
 #pragma unroll
     for (int h = 0; h <= NH; ++h) a[h] += partial[i * (NH + 1) + h];
   }
-#pragma unroll
-  for (int h = 0; h <= NH; ++h) r[h][threadIdx.x] = a[h];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-#pragma unroll
-      for (int h = 0; h <= NH; ++h) r[h][threadIdx.x] += r[h][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  block_tree_sum_f64<NH + 1>(a, r);
   if (threadIdx.x == 0) {
-    const double den = r[NH][0] > 0.0 ? r[NH][0] : 1.0;      // every pixel ignored (or of weight 0): loss 0, not 0 / 0
-    float t = 0.f;
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-      hd.out[h][0] = (float)(r[h][0] / den);
-      hd.out[h][1] = (float)r[NH][0];
-      t += hd.w[h] * hd.out[h][0];
+    // Paddle's cross_entropy divides by count + (count == 0): every pixel ignored (or of weight 0) gives loss 0, not 0 / 0
+    const double den = r[NH][0] > 0.0 ? r[NH][0] : 1.0;
+    res_a[0] = (float)(r[0][0] / den); res_a[1] = (float)r[NH][0];
+    if (NH == 2) {
+      res_b[0] = (float)(r[NH - 1][0] / den); res_b[1] = (float)r[NH][0];
+      // two products and one add in the compiled kernel (no fused multiply-add), for the plain and the weighted pair alike; the weighted pair used
+      // to start the sum from 0.f, which differs only in the sign of a zero total under negative head weights
+      total[0] = wa * res_a[0] + wb * res_b[0];
     }
-    if (total) total[0] = t;
   }
 }
 
-// dlogits_h = w_h * up_h * w[y] * (softmax - onehot) / sum w[y]
-template <int NH>
-__global__ __launch_bounds__(256) void wce_bwd_kernel(WceHeads<NH> hd, const long long* __restrict__ labels, const float* __restrict__ cw,
-                                                      const float* __restrict__ res, int N, int C, long long HW, int ignore_index) {
+// dlogits_h = w_h * up_h * w[y] * (softmax - onehot) / sum w[y]     (up_h: device scalar or null == 1; all ignored: zero gradient)
+template <int NH, bool CW>
+__global__ __launch_bounds__(256) void wce_bwd_kernel(const float* __restrict__ la, const float* __restrict__ lb, const long long* __restrict__ labels,
+                                                      const float* __restrict__ cw, const float* __restrict__ res, const float* __restrict__ up_a,
+                                                      const float* __restrict__ up_b, float wa, float wb, int N, int C, long long HW, int ignore_index,
+                                                      float* __restrict__ da, float* __restrict__ db) {
   const long long total = (long long)N * HW;
   const float den_w = res[1] > 0.f ? res[1] : 1.f, inv_den = 1.f / den_w;
-  float gh[NH];
-  // (the quotient / reciprocal forms of emrt_softmax_ce_bwd / _pair_bwd: unit class weights give their bits)
-#pragma unroll
-  for (int h = 0; h < NH; ++h) gh[h] = NH == 1 ? hd.w[h] * (hd.up[h] ? hd.up[h][0] : 1.f) / den_w : hd.w[h] * (hd.up[h] ? hd.up[h][0] : 1.f) * inv_den;
+  // (one head divides, two heads multiply by the reciprocal: the two forms the single and the pair entry points have always had)
+  const float ga = NH == 1 ? wa * (up_a ? up_a[0] : 1.f) / den_w : wa * (up_a ? up_a[0] : 1.f) * inv_den;
+  const float gb = NH == 1 ? 0.f : wb * (up_b ? up_b[0] : 1.f) * inv_den;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
     const long long lab = labels[idx];
     long long n, p;
     pixel_of(idx, total, HW, n, p);
-    const float w = lab == ignore_index ? 0.f : class_weight_of(cw, lab, C);
+    const float w = lab == ignore_index ? 0.f : class_weight_of<CW>(cw, lab, C);
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
-      const float* lp = hd.logits[h] + n * C * HW + p;
-      float* dp = hd.out[h] + n * C * HW + p;
-      if (lab == ignore_index) {
-        for (int c = 0; c < C; ++c) dp[c * HW] = 0.f;
-        continue;
-      }
-      const float g = gh[h] * w;
-      float mx = -3.0e38f;
-      for (int c = 0; c < C; ++c) mx = fmaxf(mx, lp[c * HW]);
-      float den = 0.f;
-      for (int c = 0; c < C; ++c) den += __expf(lp[c * HW] - mx);
-      const float inv = 1.f / den;
-      for (int c = 0; c < C; ++c) dp[c * HW] = g * (__expf(lp[c * HW] - mx) * inv - (c == lab ? 1.f : 0.f));
+      const float* lp = (h ? lb : la) + n * C * HW + p;
+      float* dp = (h ? db : da) + n * C * HW + p;
+      const float g = h ? gb : ga;
+      if (lab == ignore_index) pixel_zero_store(dp, C, HW);
+      else pixel_grad_store(lp, dp, C, HW, lab, CW ? g * w : g);
     }
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// host side.  Grids: one thread per pixel, capped (1024 blocks forward -- the partials' workspace --, 4096 backward, 128 for the digit histograms).
+// ------------------------------------------------------------------------------------------------
 inline int stream_grid(long long npix, int cap) {
   long long g = (npix + 255) / 256;
   return (int)(g > cap ? cap : g < 1 ? 1 : g);
 }
 
 inline bool shape_ok(int N, int C, int H, int W) { return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N * H * W < (1ll << 31); }
+#define SHAPE_MSG "N, C, H, W >= 1 and N * H * W < 2^31"
 
+// the one filler of the OHEM head record: every array is per head, in head order
+template <int NH>
+OhemHeads<NH> ohem_heads(const float* const (&logits)[NH], const float* const (&prob)[NH], const float* const (&result)[NH], float* const (&dlogits)[NH],
+                         const float* const (&up)[NH], const float (&w)[NH]) {
+  OhemHeads<NH> hd;
+  for (int h = 0; h < NH; ++h) {
+    hd.logits[h] = logits[h]; hd.prob[h] = (float*)prob[h]; hd.result[h] = (float*)result[h]; hd.dlogits[h] = dlogits[h]; hd.up[h] = up[h]; hd.w[h] = w[h];
+  }
+  return hd;
+}
+
+// the heads of a CE call on the host, a = [0], b = [1] (null / 0 when NH = 1)
+struct WceHeads {
+  const float* logits[2];
+  float* out[2];          // forward: result[2] per head; backward: dlogits
+  const float* up[2];
+  float w[2];
+};
+
+// forward of the CE family: the streaming launch + the one-block finalize; cw == nullptr takes the plain kernels
+template <int NH>
+int wce_forward(const char* fn, const WceHeads& hd, const long long* labels, const float* cw, int N, int C, int H, int W, int ignore_index, float* total,
+                void* workspace, void* stream) {
+  const int grid = stream_grid((long long)N * H * W, 1024);
+  hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, hd.logits[0], hd.logits[1], labels, cw, N, C, (long long)H * W, ignore_index, (float*)workspace);
+  };
+  if (cw) launch(wce_fwd_kernel<NH, true>);
+  else launch(wce_fwd_kernel<NH, false>);
+  hipLaunchKernelGGL(wce_finalize_kernel<NH>, dim3(1), dim3(256), 0, st, (const float*)workspace, grid, hd.w[0], hd.w[1], hd.out[0], hd.out[1], total);
+  return check_launch(fn);
+}
+template <int NH>
+int wce_backward(const char* fn, const WceHeads& hd, const long long* labels, const float* cw, const float* res, int N, int C, int H, int W,
+                 int ignore_index, void* stream) {
+  const int grid = stream_grid((long long)N * H * W, 4096);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, hd.logits[0], hd.logits[1], labels, cw, res, hd.up[0], hd.up[1], hd.w[0], hd.w[1],
+                       N, C, (long long)H * W, ignore_index, hd.out[0], hd.out[1]);
+  };
+  if (cw) launch(wce_bwd_kernel<NH, true>);
+  else launch(wce_bwd_kernel<NH, false>);
+  return check_launch(fn);
+}
 
 template <int NH>
 int ohem_forward(const char* fn, const OhemHeads<NH>& hd, const long long* labels, int N, int C, int H, int W, int ignore_index, float thresh,
@@ -423,6 +448,13 @@ int ohem_forward(const char* fn, const OhemHeads<NH>& hd, const long long* label
   return check_launch(fn);
 }
 
+template <int NH>
+int ohem_backward(const char* fn, const OhemHeads<NH>& hd, const long long* labels, int N, int C, int H, int W, int ignore_index, void* stream) {
+  hipLaunchKernelGGL(ohem_bwd_kernel<NH>, dim3(stream_grid((long long)N * H * W, 4096), NH), dim3(256), 0, (hipStream_t)stream, hd, labels, N, C,
+                     (long long)H * W, ignore_index);
+  return check_launch(fn);
+}
+
 }  // namespace
 
 // workspace of one OHEM forward over `heads` (1 or 2) heads of npix = N * H * W pixels: per head three digit histograms, the selection state, the
@@ -435,98 +467,102 @@ extern "C" size_t emrt_ohem_workspace_bytes(long long npix, int heads) {
 extern "C" int emrt_ohem_ce_fwd(const float* logits, const long long* labels, int N, int C, int H, int W, int ignore_index, float thresh,
                                 long long min_kept, float* prob, float* result, void* workspace, void* stream) {
   EMRT_REQUIRE(logits && labels && prob && result && workspace, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
   EMRT_REQUIRE(min_kept >= 0, "min_kept >= 0");
   EMRT_REQUIRE(thresh == thresh, "thresh is NaN");
-  OhemHeads<1> hd = {};
-  hd.logits[0] = logits; hd.prob[0] = prob; hd.result[0] = result; hd.w[0] = 1.f;
-  return ohem_forward<1>("emrt_ohem_ce_fwd", hd, labels, N, C, H, W, ignore_index, thresh, min_kept, nullptr, workspace, stream);
+  return ohem_forward<1>(__func__, ohem_heads<1>({logits}, {prob}, {result}, {nullptr}, {nullptr}, {1.f}), labels, N, C, H, W, ignore_index, thresh, min_kept,
+                         nullptr, workspace, stream);
 }
 
 extern "C" int emrt_ohem_ce_bwd(const float* logits, const long long* labels, const float* prob, const float* result, const float* upstream,
                                 float weight, int N, int C, int H, int W, int ignore_index, float* dlogits, void* stream) {
   EMRT_REQUIRE(logits && labels && prob && result && dlogits, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
-  OhemHeads<1> hd = {};
-  hd.logits[0] = logits; hd.prob[0] = (float*)prob; hd.result[0] = (float*)result; hd.dlogits[0] = dlogits; hd.up[0] = upstream; hd.w[0] = weight;
-  hipLaunchKernelGGL(ohem_bwd_kernel<1>, dim3(stream_grid((long long)N * H * W, 4096)), dim3(256), 0, (hipStream_t)stream, hd, labels, N, C,
-                     (long long)H * W, ignore_index);
-  return check_launch("emrt_ohem_ce_bwd");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
+  return ohem_backward<1>(__func__, ohem_heads<1>({logits}, {prob}, {result}, {dlogits}, {upstream}, {weight}), labels, N, C, H, W, ignore_index, stream);
 }
 
 extern "C" int emrt_ohem_ce_pair_fwd(const float* logits_a, const float* logits_b, const long long* labels, int N, int C, int H, int W, int ignore_index,
                                      float thresh, long long min_kept, float wa, float wb, float* prob_a, float* prob_b, float* res_a, float* res_b,
                                      float* total, void* workspace, void* stream) {
   EMRT_REQUIRE(logits_a && logits_b && labels && prob_a && prob_b && res_a && res_b && total && workspace, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
   EMRT_REQUIRE(min_kept >= 0, "min_kept >= 0");
   EMRT_REQUIRE(thresh == thresh, "thresh is NaN");
-  OhemHeads<2> hd = {};
-  hd.logits[0] = logits_a; hd.prob[0] = prob_a; hd.result[0] = res_a; hd.w[0] = wa;
-  hd.logits[1] = logits_b; hd.prob[1] = prob_b; hd.result[1] = res_b; hd.w[1] = wb;
-  return ohem_forward<2>("emrt_ohem_ce_pair_fwd", hd, labels, N, C, H, W, ignore_index, thresh, min_kept, total, workspace, stream);
+  return ohem_forward<2>(__func__, ohem_heads<2>({logits_a, logits_b}, {prob_a, prob_b}, {res_a, res_b}, {nullptr, nullptr}, {nullptr, nullptr}, {wa, wb}),
+                         labels, N, C, H, W, ignore_index, thresh, min_kept, total, workspace, stream);
 }
 
 extern "C" int emrt_ohem_ce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* prob_a, const float* prob_b,
                                      const float* res_a, const float* res_b, const float* up_a, const float* up_b, float wa, float wb, int N, int C,
                                      int H, int W, int ignore_index, float* dlogits_a, float* dlogits_b, void* stream) {
   EMRT_REQUIRE(logits_a && logits_b && labels && prob_a && prob_b && res_a && res_b && dlogits_a && dlogits_b, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
-  OhemHeads<2> hd = {};
-  hd.logits[0] = logits_a; hd.prob[0] = (float*)prob_a; hd.result[0] = (float*)res_a; hd.dlogits[0] = dlogits_a; hd.up[0] = up_a; hd.w[0] = wa;
-  hd.logits[1] = logits_b; hd.prob[1] = (float*)prob_b; hd.result[1] = (float*)res_b; hd.dlogits[1] = dlogits_b; hd.up[1] = up_b; hd.w[1] = wb;
-  hipLaunchKernelGGL(ohem_bwd_kernel<2>, dim3(stream_grid((long long)N * H * W, 4096), 2), dim3(256), 0, (hipStream_t)stream, hd, labels, N, C,
-                     (long long)H * W, ignore_index);
-  return check_launch("emrt_ohem_ce_pair_bwd");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
+  return ohem_backward<2>(__func__, ohem_heads<2>({logits_a, logits_b}, {prob_a, prob_b}, {res_a, res_b}, {dlogits_a, dlogits_b}, {up_a, up_b}, {wa, wb}),
+                          labels, N, C, H, W, ignore_index, stream);
 }
 
+// ---- plain CE: the family with the weight compiled out (no shape refusal: these entry points never had one).  workspace: emrt_ce_workspace_bytes()
+extern "C" size_t emrt_ce_workspace_bytes(void) { return 1024 * 3 * sizeof(float); }
+
+// result[2] (device): {mean loss, non-ignored count}
+extern "C" int emrt_softmax_ce_fwd(const float* logits, const long long* labels, int N, int C, int H, int W, int ignore_index,
+                                   float* result, void* workspace, void* stream) {
+  EMRT_REQUIRE(logits && labels && result && workspace, "null pointer");
+  return wce_forward<1>(__func__, WceHeads{{logits}, {result}, {}, {1.f}}, labels, nullptr, N, C, H, W, ignore_index, nullptr, workspace, stream);
+}
+
+// dlogits = weight * upstream * (softmax - onehot) / count     (upstream: device scalar or null == 1)
+extern "C" int emrt_softmax_ce_bwd(const float* logits, const long long* labels, const float* result, const float* upstream,
+                                   float weight, int N, int C, int H, int W, int ignore_index, float* dlogits, void* stream) {
+  EMRT_REQUIRE(logits && labels && result && dlogits, "null pointer");
+  return wce_backward<1>(__func__, WceHeads{{logits}, {dlogits}, {upstream}, {weight}}, labels, nullptr, result, N, C, H, W, ignore_index, stream);
+}
+
+// both heads at once: res_a / res_b (device float[2] each: {mean loss, non-ignored count}), total[0] = wa * loss_a + wb * loss_b
+extern "C" int emrt_softmax_ce_pair_fwd(const float* logits_a, const float* logits_b, const long long* labels, int N, int C, int H, int W,
+                                        int ignore_index, float wa, float wb, float* res_a, float* res_b, float* total, void* workspace, void* stream) {
+  EMRT_REQUIRE(logits_a && logits_b && labels && res_a && res_b && total && workspace, "null pointer");
+  return wce_forward<2>(__func__, WceHeads{{logits_a, logits_b}, {res_a, res_b}, {}, {wa, wb}}, labels, nullptr, N, C, H, W, ignore_index,
+                        total, workspace, stream);
+}
+
+// d logits_a = wa * up_a * (softmax - onehot) / count, d logits_b likewise (up_*: device scalars or NULL == 1); res_a from the forward
+extern "C" int emrt_softmax_ce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* res_a, const float* up_a,
+                                        const float* up_b, float wa, float wb, int N, int C, int H, int W, int ignore_index, float* dlogits_a,
+                                        float* dlogits_b, void* stream) {
+  EMRT_REQUIRE(logits_a && logits_b && labels && res_a && dlogits_a && dlogits_b, "null pointer");
+  return wce_backward<2>(__func__, WceHeads{{logits_a, logits_b}, {dlogits_a, dlogits_b}, {up_a, up_b}, {wa, wb}}, labels, nullptr, res_a, N, C, H, W,
+                         ignore_index, stream);
+}
+
+// ---- class-weighted CE: class_weight == NULL is the plain CE above, kernel for kernel
 extern "C" int emrt_wce_fwd(const float* logits, const long long* labels, const float* class_weight, int N, int C, int H, int W, int ignore_index,
                             float* result, void* workspace, void* stream) {
   EMRT_REQUIRE(logits && labels && result && workspace, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
-  const int grid = stream_grid((long long)N * H * W, 1024);
-  hipStream_t st = (hipStream_t)stream;
-  WceHeads<1> hd;
-  hd.logits[0] = logits; hd.out[0] = result; hd.up[0] = nullptr; hd.w[0] = 1.f;
-  hipLaunchKernelGGL(wce_fwd_kernel<1>, dim3(grid), dim3(256), 0, st, hd, labels, class_weight, N, C, (long long)H * W, ignore_index, (float*)workspace);
-  hipLaunchKernelGGL(wce_finalize_kernel<1>, dim3(1), dim3(256), 0, st, (const float*)workspace, grid, hd, (float*)nullptr);
-  return check_launch("emrt_wce_fwd");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
+  return wce_forward<1>(__func__, WceHeads{{logits}, {result}, {}, {1.f}}, labels, class_weight, N, C, H, W, ignore_index, nullptr, workspace, stream);
 }
 
 extern "C" int emrt_wce_bwd(const float* logits, const long long* labels, const float* class_weight, const float* result, const float* upstream,
                             float weight, int N, int C, int H, int W, int ignore_index, float* dlogits, void* stream) {
   EMRT_REQUIRE(logits && labels && result && dlogits, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
-  WceHeads<1> hd;
-  hd.logits[0] = logits; hd.out[0] = dlogits; hd.up[0] = upstream; hd.w[0] = weight;
-  hipLaunchKernelGGL(wce_bwd_kernel<1>, dim3(stream_grid((long long)N * H * W, 4096)), dim3(256), 0, (hipStream_t)stream, hd, labels, class_weight, result, N,
-                     C, (long long)H * W, ignore_index);
-  return check_launch("emrt_wce_bwd");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
+  return wce_backward<1>(__func__, WceHeads{{logits}, {dlogits}, {upstream}, {weight}}, labels, class_weight, result, N, C, H, W, ignore_index, stream);
 }
 
 extern "C" int emrt_wce_pair_fwd(const float* logits_a, const float* logits_b, const long long* labels, const float* class_weight, int N, int C, int H,
                                  int W, int ignore_index, float wa, float wb, float* res_a, float* res_b, float* total, void* workspace, void* stream) {
   EMRT_REQUIRE(logits_a && logits_b && labels && res_a && res_b && total && workspace, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
-  const int grid = stream_grid((long long)N * H * W, 1024);
-  hipStream_t st = (hipStream_t)stream;
-  WceHeads<2> hd;
-  hd.logits[0] = logits_a; hd.out[0] = res_a; hd.up[0] = nullptr; hd.w[0] = wa;
-  hd.logits[1] = logits_b; hd.out[1] = res_b; hd.up[1] = nullptr; hd.w[1] = wb;
-  hipLaunchKernelGGL(wce_fwd_kernel<2>, dim3(grid), dim3(256), 0, st, hd, labels, class_weight, N, C, (long long)H * W, ignore_index, (float*)workspace);
-  hipLaunchKernelGGL(wce_finalize_kernel<2>, dim3(1), dim3(256), 0, st, (const float*)workspace, grid, hd, total);
-  return check_launch("emrt_wce_pair_fwd");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
+  return wce_forward<2>(__func__, WceHeads{{logits_a, logits_b}, {res_a, res_b}, {}, {wa, wb}}, labels, class_weight, N, C, H, W,
+                        ignore_index, total, workspace, stream);
 }
 
 extern "C" int emrt_wce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* class_weight, const float* res_a,
                                  const float* up_a, const float* up_b, float wa, float wb, int N, int C, int H, int W, int ignore_index,
                                  float* dlogits_a, float* dlogits_b, void* stream) {
   EMRT_REQUIRE(logits_a && logits_b && labels && res_a && dlogits_a && dlogits_b, "null pointer");
-  EMRT_REQUIRE(shape_ok(N, C, H, W), "N, C, H, W >= 1 and N * H * W < 2^31");
-  WceHeads<2> hd;
-  hd.logits[0] = logits_a; hd.out[0] = dlogits_a; hd.up[0] = up_a; hd.w[0] = wa;
-  hd.logits[1] = logits_b; hd.out[1] = dlogits_b; hd.up[1] = up_b; hd.w[1] = wb;
-  hipLaunchKernelGGL(wce_bwd_kernel<2>, dim3(stream_grid((long long)N * H * W, 4096)), dim3(256), 0, (hipStream_t)stream, hd, labels, class_weight, res_a, N,
-                     C, (long long)H * W, ignore_index);
-  return check_launch("emrt_wce_pair_bwd");
+  EMRT_REQUIRE(shape_ok(N, C, H, W), SHAPE_MSG);
+  return wce_backward<2>(__func__, WceHeads{{logits_a, logits_b}, {dlogits_a, dlogits_b}, {up_a, up_b}, {wa, wb}}, labels, class_weight, res_a, N, C, H, W,
+                         ignore_index, stream);
 }

@@ -1798,8 +1798,12 @@ def sigmoid_f32(x):
 # ---------------------------------------------------------------------------------------------------
 # loss
 # ---------------------------------------------------------------------------------------------------
-def _class_weight_ok(class_weight, C):
+def _ce_entry(class_weight, C):
+    """-> (entry-point family, its extra tensor argument behind labels): emrt_wce_* with the class weights, or the plain emrt_softmax_ce_*"""
+    if class_weight is None:
+        return "emrt_softmax_ce", ()
     assert class_weight.dtype == torch.float32 and class_weight.is_contiguous() and class_weight.numel() == C
+    return "emrt_wce", (class_weight,)
 
 
 def softmax_ce_pair(logits_a, logits_b, labels, ignore_index, wa, wb, class_weight=None):
@@ -1812,29 +1816,15 @@ def softmax_ce_pair(logits_a, logits_b, labels, ignore_index, wa, wb, class_weig
     assert labels.dtype == torch.int64 and labels.is_contiguous()
     res_a, res_b, total = c.empty((2,), torch.float32), c.empty((2,), torch.float32), c.empty((1,), torch.float32)
     ws = c.workspace(_L().query("emrt_ce_workspace_bytes"))
-    if class_weight is not None:
-        _class_weight_ok(class_weight, C)
-        _L().call("emrt_wce_pair_fwd", P(logits_a), P(logits_b), P(labels), P(class_weight), N, C, H, W, ignore_index, float(wa), float(wb), P(res_a),
-                  P(res_b), P(total), P(ws), c.stream)
-        tape = c.tape
-        if tape is not None:
-            def bwd_w():
-                up_a, up_b = tape.pop_grad(res_a), tape.pop_grad(res_b)
-                da, db = c.empty((N, C, H, W), torch.float32), c.empty((N, C, H, W), torch.float32)
-                _L().call("emrt_wce_pair_bwd", P(logits_a), P(logits_b), P(labels), P(class_weight), P(res_a), P(up_a), P(up_b), float(wa), float(wb),
-                          N, C, H, W, ignore_index, P(da), P(db), c.stream)
-                tape.add_grad(logits_a, da, owned=True)
-                tape.add_grad(logits_b, db, owned=True)
-            tape.record(bwd_w)
-        return res_a, res_b, total
-    _L().call("emrt_softmax_ce_pair_fwd", P(logits_a), P(logits_b), P(labels), N, C, H, W, ignore_index, float(wa), float(wb), P(res_a), P(res_b), P(total),
+    entry, cw = _ce_entry(class_weight, C)
+    _L().call(entry + "_pair_fwd", P(logits_a), P(logits_b), P(labels), *map(P, cw), N, C, H, W, ignore_index, float(wa), float(wb), P(res_a), P(res_b), P(total),
               P(ws), c.stream)
     tape = c.tape
     if tape is not None:
         def bwd():
             up_a, up_b = tape.pop_grad(res_a), tape.pop_grad(res_b)      # device scalars or None (== 1)
             da, db = c.empty((N, C, H, W), torch.float32), c.empty((N, C, H, W), torch.float32)
-            _L().call("emrt_softmax_ce_pair_bwd", P(logits_a), P(logits_b), P(labels), P(res_a), P(up_a), P(up_b), float(wa), float(wb), N, C, H, W,
+            _L().call(entry + "_pair_bwd", P(logits_a), P(logits_b), P(labels), *map(P, cw), P(res_a), P(up_a), P(up_b), float(wa), float(wb), N, C, H, W,
                       ignore_index, P(da), P(db), c.stream)
             tape.add_grad(logits_a, da, owned=True)
             tape.add_grad(logits_b, db, owned=True)
@@ -1851,25 +1841,14 @@ def softmax_ce(logits, labels, ignore_index, weight=1.0, class_weight=None):
     assert logits.dtype == torch.float32 and logits.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous()
     res = c.empty((2,), torch.float32)
     ws = c.workspace(_L().query("emrt_ce_workspace_bytes"))
-    if class_weight is not None:
-        _class_weight_ok(class_weight, C)
-        _L().call("emrt_wce_fwd", P(logits), P(labels), P(class_weight), N, C, H, W, ignore_index, P(res), P(ws), c.stream)
-        tape = c.tape
-        if tape is not None:
-            def bwd_w():
-                up = tape.pop_grad(res)
-                dl = c.empty((N, C, H, W), torch.float32)
-                _L().call("emrt_wce_bwd", P(logits), P(labels), P(class_weight), P(res), P(up), float(weight), N, C, H, W, ignore_index, P(dl), c.stream)
-                tape.add_grad(logits, dl, owned=True)
-            tape.record(bwd_w)
-        return res
-    _L().call("emrt_softmax_ce_fwd", P(logits), P(labels), N, C, H, W, ignore_index, P(res), P(ws), c.stream)
+    entry, cw = _ce_entry(class_weight, C)
+    _L().call(entry + "_fwd", P(logits), P(labels), *map(P, cw), N, C, H, W, ignore_index, P(res), P(ws), c.stream)
     tape = c.tape
     if tape is not None:
         def bwd():
             up = tape.pop_grad(res)   # device scalar or None (== 1)
             dl = c.empty((N, C, H, W), torch.float32)
-            _L().call("emrt_softmax_ce_bwd", P(logits), P(labels), P(res), P(up), float(weight), N, C, H, W, ignore_index, P(dl), c.stream)
+            _L().call(entry + "_bwd", P(logits), P(labels), *map(P, cw), P(res), P(up), float(weight), N, C, H, W, ignore_index, P(dl), c.stream)
             tape.add_grad(logits, dl, owned=True)
         tape.record(bwd)
     return res

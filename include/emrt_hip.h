@@ -401,7 +401,7 @@ int emrt_ohem_ce_pair_fwd(const float* logits_a, const float* logits_b, const lo
 int emrt_ohem_ce_pair_bwd(const float* logits_a, const float* logits_b, const long long* labels, const float* prob_a, const float* prob_b, const float* res_a, const float* res_b, const float* up_a, const float* up_b, float wa, float wb, int N, int C, int H, int W, int ignore_index, float* dlogits_a, float* dlogits_b, void* stream);
 /* ---- nn.CrossEntropyLoss(weight = class_weight, ignore_index) (losses/cross_entropy_loss.py:30-35, the class-weight option): loss = sum w[y] CE /
  * sum w[y] over the non-ignored pixels, dlogits = weight * upstream * w[y] * (softmax - onehot) / sum w[y].  class_weight: DEVICE float[C], or NULL
- * == all ones (then the results of emrt_softmax_ce_* to the last bits).  result / res_a / res_b (device float[2]) = {loss, sum w[y]}; the pair form is
+ * == all ones (then the kernels of emrt_softmax_ce_* themselves: their results to the last bits).  result / res_a / res_b (device float[2]) = {loss, sum w[y]}; the pair form is
  * emrt_softmax_ce_pair_* with the weights: one forward and one backward launch for both heads.  workspace: emrt_ce_workspace_bytes(). */
 int emrt_wce_fwd(const float* logits, const long long* labels, const float* class_weight, int N, int C, int H, int W, int ignore_index, float* result, void* workspace, void* stream);
 int emrt_wce_bwd(const float* logits, const long long* labels, const float* class_weight, const float* result, const float* upstream, float weight, int N, int C, int H, int W, int ignore_index, float* dlogits, void* stream);
@@ -436,7 +436,8 @@ typedef struct EmrtLrSchedule {
   int nmilestones;
   long long milestones[16];
 } EmrtLrSchedule;
-/* emrt_sgd_momentum_step with lr = the schedule's value in place of the built-in polynomial: same element arithmetic (kind 0 gives the same bits). */
+/* emrt_sgd_momentum_step with lr = the schedule's value in place of the built-in polynomial; emrt_sgd_momentum_step is that entry point with a kind-0
+ * descriptor (base_lr, end_lr, power, total_steps = decay_steps): one kernel, the same bits. */
 int emrt_sgd_momentum_step_sched(float* params, const float* grads, float* velocity, long long n, const float* clip_state, const long long* step, const EmrtLrSchedule* sched, float momentum, float weight_decay, const long long* ranges, int nranges, float range_mult, float* lr_out, void* mirror, int mirror_dtype, void* stream);
 /* One streaming pass of Adam (decoupled = 0: g += weight_decay * p, paddle.optimizer.Adam) or AdamW (decoupled = 1: p *= 1 - lr_e * weight_decay) with
  * t = step[0] + 1, lr_e = lr * range_mult inside `ranges` (else lr), g = grad * clip_state[0] (clip_state NULL == 1):

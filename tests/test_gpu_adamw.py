@@ -216,30 +216,37 @@ def test_schedules_on_the_device(L, kind):
 
 def test_sched_kind0_is_the_builtin_sgd_bit_for_bit(L):
     """emrt_sgd_momentum_step_sched with a kind-0 descriptor against emrt_sgd_momentum_step on the same buffers: master, velocity, mirror
-    and the reported learning rate are the same bits (the two kernels share the element body; only where lr comes from differs)."""
+    and the reported learning rate are the same bits (the built-in entry point is the schedule-driven one with a kind-0 descriptor), for every
+    mirror type and both settings of the sgd_nt knob."""
     g_ = torch.Generator().manual_seed(9)
     p0, v0, gr = torch.randn(N, generator=g_), torch.randn(N, generator=g_) * 0.1, torch.randn(N, generator=g_)
     rng = (ctypes.c_longlong * 2)(*RANGE)
     desc = solver.PolynomialDecay(0.01, 100, 1e-4, 0.9).descriptor()
-    for s in (0, 37, 100, 250):
-        res = []
-        for which in ("builtin", "sched"):
-            p, v, gd = p0.cuda(), v0.cuda(), gr.cuda()
-            mirror = torch.empty(N, dtype=torch.bfloat16, device="cuda")
-            state = torch.tensor([0.37, 0.0], dtype=torch.float32, device="cuda")
-            cnt = torch.tensor([s], dtype=torch.int64, device="cuda")
-            lr = torch.zeros(1, dtype=torch.float32, device="cuda")
-            if which == "builtin":
-                L.call("emrt_sgd_momentum_step", P(p), P(gd), P(v), N, P(state), P(cnt), 0.01, 1e-4, 0.9, 100, 0.9, 1e-4,
-                       ctypes.cast(rng, ctypes.c_void_p), 1, MULT, P(lr), P(mirror), 1, ctx().stream)
-            else:
-                L.call("emrt_sgd_momentum_step_sched", P(p), P(gd), P(v), N, P(state), P(cnt), sched_ptr(desc), 0.9, 1e-4,
-                       ctypes.cast(rng, ctypes.c_void_p), 1, MULT, P(lr), P(mirror), 1, ctx().stream)
-            torch.cuda.synchronize()
-            res.append((p.cpu(), v.cpu(), mirror.cpu(), lr.cpu()))
-        for a, b, name in zip(res[0], res[1], ("master", "velocity", "mirror", "lr")):
-            assert torch.equal(a, b), (s, name, int((a != b).sum()))
-        assert not torch.equal(res[0][0], p0)
+    for nt in (1, 0):
+        old = L.set_tuning("sgd_nt", nt)
+        try:
+            for mdt, mtype in ((0, None), (1, torch.bfloat16), (2, torch.float16)):
+                for s in (0, 37, 100, 250):
+                    res = []
+                    for which in ("builtin", "sched"):
+                        p, v, gd = p0.cuda(), v0.cuda(), gr.cuda()
+                        mirror = None if mtype is None else torch.empty(N, dtype=mtype, device="cuda")
+                        state = torch.tensor([0.37, 0.0], dtype=torch.float32, device="cuda")
+                        cnt = torch.tensor([s], dtype=torch.int64, device="cuda")
+                        lr = torch.zeros(1, dtype=torch.float32, device="cuda")
+                        if which == "builtin":
+                            L.call("emrt_sgd_momentum_step", P(p), P(gd), P(v), N, P(state), P(cnt), 0.01, 1e-4, 0.9, 100, 0.9, 1e-4,
+                                   ctypes.cast(rng, ctypes.c_void_p), 1, MULT, P(lr), P(mirror), mdt, ctx().stream)
+                        else:
+                            L.call("emrt_sgd_momentum_step_sched", P(p), P(gd), P(v), N, P(state), P(cnt), sched_ptr(desc), 0.9, 1e-4,
+                                   ctypes.cast(rng, ctypes.c_void_p), 1, MULT, P(lr), P(mirror), mdt, ctx().stream)
+                        torch.cuda.synchronize()
+                        res.append((p.cpu(), v.cpu(), lr.cpu()) + (() if mirror is None else (mirror.cpu(),)))
+                    for a, b, name in zip(res[0], res[1], ("master", "velocity", "lr", "mirror")):
+                        assert torch.equal(a, b), (nt, mdt, s, name, int((a != b).sum()))
+                    assert not torch.equal(res[0][0], p0)
+        finally:
+            L.set_tuning("sgd_nt", old)
 
 
 # ---- the optimizer class on a model --------------------------------------------------------------------------------------------------------------

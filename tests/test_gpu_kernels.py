@@ -1646,7 +1646,7 @@ def test_sgd_momentum_matches_reference_optimizer():
 
 
 def test_optimizer_pass_non_temporal_arm_is_bit_identical():
-    """Knob sgd_nt (csrc/loss_optim.hip): the non-temporal loads / stores of the fp32 streams change caching, not arithmetic -- master weights, velocity
+    """Knob sgd_nt (csrc/optim.hip): the non-temporal loads / stores of the fp32 streams change caching, not arithmetic -- master weights, velocity
     and the bf16 mirror after two steps are bit-identical with the knob on and off (odd length: the scalar tail runs too)."""
     import ctypes
     from emrt_amd import _lib

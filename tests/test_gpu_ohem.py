@@ -1,4 +1,4 @@
-"""-m gpu: OhemCrossEntropyLoss with the threshold selected on the device, and class-weighted cross entropy (csrc/ohem.hip), kernel and
+"""-m gpu: OhemCrossEntropyLoss with the threshold selected on the device, and class-weighted cross entropy (csrc/loss.hip), kernel and
 model level.  The OHEM reference is a float64 restatement of the reference's formulae (losses/ohem_cross_entropy_loss.py:41-79), written
 below; the yardstick of the weighted cross entropy is float64 torch.nn.functional.cross_entropy(weight=...).
 
@@ -392,6 +392,47 @@ def test_weighted_cross_entropy(shape, seed, ignored):
     # every pixel ignored: 0, not 0 / 0
     got = _run_ce(la, lb, torch.full_like(labels, IGN), w, True)
     assert got[0][0].item() == got[1][0].item() == got[4].item() == 0.0 and not got[2].any() and not got[3].any()
+
+
+def _abi_ce(family, la, lb, lab, pair, up):
+    """The C-ABI itself, family "softmax_ce" or "wce" with class_weight = NULL (functional never passes a null weight to emrt_wce_*):
+    -> [result a, result b, dlogits a, dlogits b(, total)], head weights 1.0 / 0.4, upstream `up` (device scalar or None)."""
+    import ctypes
+    from emrt_amd import _lib
+    L, c = _lib.lib(), ctx()
+    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    cw = (None,) if family == "wce" else ()                      # the extra argument of emrt_wce_*: behind labels
+    N, C, H, W = la.shape
+    ws = torch.empty(L.query("emrt_ce_workspace_bytes"), dtype=torch.uint8, device="cuda")
+    ra, rb, total = (torch.full((2,), -1.0, device="cuda") for _ in range(3))
+    da, db = torch.full_like(la, 7.0), torch.full_like(lb, 7.0)
+    if pair:
+        L.call("emrt_%s_pair_fwd" % family, P(la), P(lb), P(lab), *cw, N, C, H, W, IGN, 1.0, 0.4, P(ra), P(rb), P(total), P(ws), c.stream)
+        L.call("emrt_%s_pair_bwd" % family, P(la), P(lb), P(lab), *cw, P(ra), P(up), P(up), 1.0, 0.4, N, C, H, W, IGN, P(da), P(db), c.stream)
+    else:
+        for lg, r, d, wgt in ((la, ra, da, 1.0), (lb, rb, db, 0.4)):
+            L.call("emrt_%s_fwd" % family, P(lg), P(lab), *cw, N, C, H, W, IGN, P(r), P(ws), c.stream)
+            L.call("emrt_%s_bwd" % family, P(lg), P(lab), *cw, P(r), P(up), wgt, N, C, H, W, IGN, P(d), c.stream)
+    torch.cuda.synchronize()
+    return [ra.cpu(), rb.cpu(), da.cpu(), db.cpu()] + ([total.cpu()] if pair else [])
+
+
+@pytest.mark.parametrize("shape,seed,ignored", [((3, 6, 16, 20), 34, 0.1), ((4, 7, 24, 40), 35, 0.15), ((3, 6, 16, 20), 36, 1.0)],
+                         ids=["3x6x16x20", "4x7x24x40", "all_ignored"])
+def test_null_class_weight_takes_the_plain_kernels(shape, seed, ignored):
+    """emrt_wce_* with class_weight = NULL against emrt_softmax_ce_*, single and pair form: results, total and both gradients are the same
+    bits (they are the same kernels)."""
+    init(F32)
+    la, lb, labels, _ = _ce_inputs(shape, seed, ignored)
+    assert bool((labels == IGN).all()) == (ignored == 1.0)
+    la, lb, lab = la.cuda(), lb.cuda(), labels.cuda()
+    up = torch.tensor([0.37], device="cuda")
+    for pair in (False, True):
+        for u in (None, up):
+            plain, null_w = _abi_ce("softmax_ce", la, lb, lab, pair, u), _abi_ce("wce", la, lb, lab, pair, u)
+            for a, b, name in zip(null_w, plain, ("result a", "result b", "dlogits a", "dlogits b", "total")):
+                assert torch.equal(a, b), (pair, u is not None, name, int((a != b).sum()))
+            assert not bool((plain[2] == 7.0).any()) and bool(plain[2].any()) != (ignored == 1.0)      # the gradient was written, and is zero only when all is ignored
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

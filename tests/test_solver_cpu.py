@@ -1,6 +1,6 @@
 """CPU: the solver's host layer -- the four learning-rate schedules against independent values, the optimizer / schedule factories from the
 shipped AdamW yaml, the launch sequences of one optimizer step on the recording stand-in (tests/fake_abi.py), and the argument refusals of
-emrt_adamw_step / emrt_sgd_momentum_step_sched, which run on the host before anything is launched (no GPU here)."""
+emrt_adamw_step / emrt_sgd_momentum_step_sched / emrt_sgd_momentum_step (and the null-pointer refusals of the loss entry points), which run on the host before anything is launched (no GPU here)."""
 import argparse
 import ctypes
 import os
@@ -391,6 +391,48 @@ def test_sgd_step_sched_refuses_bad_arguments_before_any_launch(real_lib, change
     from emrt_amd import _lib
     with pytest.raises(_lib.EmrtHipError, match="emrt_sgd_momentum_step_sched.*" + match):
         _call(real_lib, "emrt_sgd_momentum_step_sched", _sgd_args(**change))
+
+
+def _builtin_sgd_args(**kw):
+    a = dict(params=P_OK, grads=P_OK, velocity=P_OK, n=64, clip_state=P_OK, step=P_OK, base_lr=0.01, end_lr=0.0, power=0.9, decay_steps=100, momentum=0.9,
+             weight_decay=1e-4, ranges=None, nranges=0, range_mult=0.1, lr_out=None, mirror=None, mirror_dtype=0, stream=None)
+    a.update(kw)
+    return a
+
+
+# (the entry point with the built-in polynomial shares its checks with the other two: the messages must still carry ITS name)
+@pytest.mark.parametrize("change,match", [
+    (dict(velocity=None), "null pointer"),
+    (dict(params=P_ODD), "16-byte aligned"),
+    (dict(mirror=P_OK, mirror_dtype=3), "mirror is bf16 or fp16"),
+    (dict(nranges=-1), "lr-mult ranges"),
+    (dict(decay_steps=0), "decay_steps must be positive"),
+], ids=lambda v: None if isinstance(v, dict) else v.replace(" ", "_"))
+def test_sgd_step_refuses_bad_arguments_before_any_launch(real_lib, change, match):
+    from emrt_amd import _lib
+    args = _builtin_sgd_args(**change)
+    assert [k for k in args] == [a for _, a in real_lib.protos["emrt_sgd_momentum_step"][1]]
+    with pytest.raises(_lib.EmrtHipError, match="emrt_sgd_momentum_step: .*" + match):
+        real_lib.call("emrt_sgd_momentum_step", *args.values())
+
+
+# one null required pointer per loss entry point that tests/test_losses_cpu.py does not refuse with one (shapes 2 x 6 x 8 x 8, ignore_index 255)
+LOSS_NULL_REFUSALS = [
+    ("emrt_softmax_ce_fwd", (P_OK, P_OK, 2, 6, 8, 8, 255, None, P_OK, None)),                                       # result
+    ("emrt_softmax_ce_bwd", (P_OK, None, P_OK, None, 1.0, 2, 6, 8, 8, 255, P_OK, None)),                            # labels
+    ("emrt_softmax_ce_pair_fwd", (P_OK, P_OK, P_OK, 2, 6, 8, 8, 255, 1.0, 0.4, P_OK, P_OK, None, P_OK, None)),               # total
+    ("emrt_softmax_ce_pair_bwd", (P_OK, P_OK, P_OK, P_OK, None, None, 1.0, 0.4, 2, 6, 8, 8, 255, P_OK, None, None)),      # dlogits_b
+    ("emrt_wce_bwd", (P_OK, P_OK, None, P_OK, None, 1.0, 2, 6, 8, 8, 255, None, None)),                             # dlogits (class_weight may be null)
+    ("emrt_wce_pair_bwd", (P_OK, P_OK, P_OK, None, None, None, None, 1.0, 0.4, 2, 6, 8, 8, 255, P_OK, P_OK, None)),       # res_a
+]
+
+
+@pytest.mark.parametrize("name,args", LOSS_NULL_REFUSALS, ids=[n for n, _ in LOSS_NULL_REFUSALS])
+def test_loss_entry_points_refuse_a_null_pointer_under_their_own_name(real_lib, name, args):
+    from emrt_amd import _lib
+    assert len(args) == len(real_lib.protos[name][1])
+    with pytest.raises(_lib.EmrtHipError, match=name + ": null pointer"):
+        real_lib.call(name, *args)
 
 
 def test_abi_is_still_version_9_with_the_new_entry_points(real_lib):

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = [(8, 6, 256, 256), (4, 7, 512, 512)]
-# GPU launches of one forward + backward pass (csrc/loss_optim.hip, csrc/ohem.hip)
+# GPU launches of one forward + backward pass (csrc/loss.hip)
 LAUNCHES = {"mix": 2 + 1, "weighted_mix": 2 + 1, "ohem": 9 + 1}
 
 
