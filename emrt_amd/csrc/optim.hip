@@ -271,12 +271,16 @@ extern "C" int emrt_segmentation_areas(const int* pred, const void* label, int l
                                        long long* out, void* stream) {
   EMRT_REQUIRE(pred && label && out, "null pointer");
   EMRT_REQUIRE(num_classes >= 1 && num_classes <= 256 && n >= 0, "1..256 classes");
+  EMRT_REQUIRE(label_is_int64 >= 0 && label_is_int64 <= 2, "label_is_int64 selects the label type: 0 = int32, 1 = int64, 2 = uint8");
   if (n == 0) return 0;
   long long grid = (n + 256 * 16 - 1) / (256 * 16);
   if (grid > 1024) grid = 1024;
   hipStream_t st = (hipStream_t)stream;
-  if (label_is_int64) hipLaunchKernelGGL((seg_areas_kernel<long long>), dim3((unsigned)grid), dim3(256), 0, st, pred, (const long long*)label, n, num_classes, ignore_index, (unsigned long long*)out);
-  else hipLaunchKernelGGL((seg_areas_kernel<int>), dim3((unsigned)grid), dim3(256), 0, st, pred, (const int*)label, n, num_classes, ignore_index, (unsigned long long*)out);
+  unsigned long long* o = (unsigned long long*)out;
+  // uint8 (the label maps of a scene bank, at any byte offset): one byte per lane, so nothing is assumed about the pointer's alignment
+  if (label_is_int64 == 2) hipLaunchKernelGGL((seg_areas_kernel<unsigned char>), dim3((unsigned)grid), dim3(256), 0, st, pred, (const unsigned char*)label, n, num_classes, ignore_index, o);
+  else if (label_is_int64 == 1) hipLaunchKernelGGL((seg_areas_kernel<long long>), dim3((unsigned)grid), dim3(256), 0, st, pred, (const long long*)label, n, num_classes, ignore_index, o);
+  else hipLaunchKernelGGL((seg_areas_kernel<int>), dim3((unsigned)grid), dim3(256), 0, st, pred, (const int*)label, n, num_classes, ignore_index, o);
   return check_launch("emrt_segmentation_areas");
 }
 

@@ -8,6 +8,9 @@
 
 Nothing is resized: a scene is predicted at its own resolution with the configured crop and stride.  With `scales`, the softmax sums of
 infer.ms_accumulate (multi-scale + horizontal flip) are finished instead.
+
+SceneEvaluator runs the same windows over the scenes of a resident validation bank (datasets.SceneBank) and counts the metric areas
+against the bank's uint8 label maps where they lie: emrt_window_normalise, emrt_argmax_nchw and emrt_segmentation_areas stand where the finish stands.
 """
 import ctypes
 from collections import namedtuple
@@ -31,6 +34,48 @@ def _origins(org):
     return arr, ctypes.cast(arr, ctypes.c_void_p)
 
 
+def check_windows(crop_size, stride_size):
+    """-> (crop, stride) as int (w, h) pairs; a stride larger than the crop is refused"""
+    crop, stride = tuple(int(v) for v in crop_size), tuple(int(v) for v in stride_size)
+    if len(crop) != 2 or len(stride) != 2 or min(crop + stride) < 1:
+        raise ValueError("crop_size and stride_size are positive (w, h) pairs, got %r and %r" % (crop_size, stride_size))
+    if stride[0] > crop[0] or stride[1] > crop[1]:
+        raise ValueError("stride %r is larger than the crop %r: the windows would leave uncovered stripes (NaN logits in the reference)"
+                         % (stride, crop))
+    return crop, stride
+
+
+def check_normalise(mean, std):
+    """-> (mean, 1 / std) as lists of Python floats, as transforms.Normalize computes them"""
+    if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
+        raise ValueError("mean / std need 3 channels and a non-zero std, got %r / %r" % (mean, std))
+    return [float(v) for v in np.asarray(mean, dtype=np.float64)], [float(v) for v in 1.0 / np.asarray(std, dtype=np.float64)]
+
+
+def crop_windows(scene, H, W, org, ch, cw, mean, stdinv):
+    """windows at `org` of the uint8 [H, W, 3] scene -> normalised fp32 [n, 3, ch, cw] (+ the origins' pointer and the array that owns it)"""
+    c = ctx()
+    arr, ptr = _origins(org)
+    batch = c.empty((len(org), 3, ch, cw), torch.float32)
+    Fn._L().call("emrt_scene_crop_windows_u8", Fn.P(scene), Fn.P(batch), ptr, len(org), H, W, ch, cw, *mean, *stdinv, c.stream)
+    return batch, ptr, arr
+
+
+def accumulate_windows(model, scene, H, W, crop, stride, ncls, max_batch, mean, stdinv, final, count):
+    """The single-scale pass both classes share: the windows of infer.window_grid(H, W, crop, stride) in that order, max_batch per model call
+    (chunked exactly as infer.slide_inference: the same logits, bit for bit), cropped and normalised from the uint8 scene, their logits added to
+    `final` [1, ncls, H, W] and their hits to `count` [1, 1, H, W]; both fp32 and zeroed by the caller."""
+    L, c = Fn._L(), ctx()
+    w_crop, h_crop = crop
+    wins = infer.window_grid(H, W, crop, stride)
+    for i in range(0, len(wins), max_batch):
+        chunk = wins[i:i + max_batch]
+        batch, ptr, _keep = crop_windows(scene, H, W, [(a, b) for (a, b, _, _) in chunk], h_crop, w_crop, mean, stdinv)
+        logits = model(batch)[0]
+        assert logits.dtype == torch.float32 and logits.is_contiguous()
+        L.call("emrt_window_accumulate", Fn.P(logits), Fn.P(final), Fn.P(count), ptr, len(chunk), ncls, H, W, h_crop, w_crop, c.stream)
+
+
 class ScenePredictor:
     """p = ScenePredictor(model, num_classes, crop_size, stride_size, palette, mean, std, overlay=None, max_batch=32, scales=None)
     p(scene_u8)            torch.uint8 [H, W, 3] RGB on the device -> SceneResult
@@ -42,22 +87,14 @@ class ScenePredictor:
     def __init__(self, model, num_classes, crop_size, stride_size, palette, mean, std, overlay=None, max_batch=32, scales=None,
                  flip_horizontal=True):
         self.model, self.ncls = model, int(num_classes)
-        self.crop, self.stride = tuple(int(v) for v in crop_size), tuple(int(v) for v in stride_size)
-        if len(self.crop) != 2 or len(self.stride) != 2 or min(self.crop + self.stride) < 1:
-            raise ValueError("crop_size and stride_size are positive (w, h) pairs, got %r and %r" % (crop_size, stride_size))
-        if self.stride[0] > self.crop[0] or self.stride[1] > self.crop[1]:
-            raise ValueError("stride %r is larger than the crop %r: the windows would leave uncovered stripes (NaN logits in the reference)"
-                             % (self.stride, self.crop))
+        self.crop, self.stride = check_windows(crop_size, stride_size)
         pal = np.ascontiguousarray(np.asarray(palette))
         if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] != 3 or pal.shape[0] != self.ncls:
             raise ValueError("palette must be uint8 [%d, 3] (one RGB colour per class), got %s %s" % (self.ncls, pal.dtype, pal.shape))
         if not 1 <= self.ncls <= 256:
             raise ValueError("num_classes must be 1..256 (the index map is uint8), got %d" % self.ncls)
         self._pal = (ctypes.c_ubyte * pal.size)(*pal.reshape(-1).tolist())
-        if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
-            raise ValueError("mean / std need 3 channels and a non-zero std, got %r / %r" % (mean, std))
-        self.mean = [float(v) for v in np.asarray(mean, dtype=np.float64)]
-        self.stdinv = [float(v) for v in 1.0 / np.asarray(std, dtype=np.float64)]          # as Normalize computes it
+        self.mean, self.stdinv = check_normalise(mean, std)
         if overlay is not None and not 0.0 <= float(overlay) <= 1.0:
             raise ValueError("overlay alpha must be in [0, 1], got %r" % (overlay,))
         self.alpha = None if overlay is None else float(overlay)
@@ -70,11 +107,7 @@ class ScenePredictor:
     # ---- kernels ---------------------------------------------------------------------------------------------------
     def _crop(self, scene, H, W, org, ch, cw):
         """windows at `org` of the uint8 [H, W, 3] scene -> normalised fp32 [n, 3, ch, cw]"""
-        c = ctx()
-        arr, ptr = _origins(org)
-        batch = c.empty((len(org), 3, ch, cw), torch.float32)
-        Fn._L().call("emrt_scene_crop_windows_u8", Fn.P(scene), Fn.P(batch), ptr, len(org), H, W, ch, cw, *self.mean, *self.stdinv, c.stream)
-        return batch, ptr, arr
+        return crop_windows(scene, H, W, org, ch, cw, self.mean, self.stdinv)
 
     def _finish(self, values, count, scene, out, j0, N, H, W):
         """values [N, ncls, H, W] (+ count) -> maps j0 .. j0 + N of `out`; the areas are added to out.areas"""
@@ -101,7 +134,7 @@ class ScenePredictor:
         w_crop, h_crop = self.crop
         if H < h_crop or W < w_crop:
             raise ValueError("scene %dx%d (h x w) is smaller than the crop %dx%d: nothing is resized or padded" % (H, W, h_crop, w_crop))
-        L, c = Fn._L(), ctx()
+        c = ctx()
         out = self._outputs(1, H, W)
         if self.scales is not None:
             img, _, _ = self._crop(scene, H, W, [(0, 0)], H, W)          # the whole scene as normalised fp32 CHW: one window
@@ -109,15 +142,9 @@ class ScenePredictor:
                                         flip_horizontal=self.flip_horizontal)
             self._finish(final, None, scene, out, 0, 1, H, W)
         else:
-            wins = infer.window_grid(H, W, self.crop, self.stride)
             final = c.zeros((1, self.ncls, H, W), torch.float32)
             count = c.zeros((1, 1, H, W), torch.float32)
-            for i in range(0, len(wins), self.max_batch):          # chunked exactly as infer.slide_inference: the same logits, bit for bit
-                chunk = wins[i:i + self.max_batch]
-                batch, ptr, _keep = self._crop(scene, H, W, [(a, b) for (a, b, _, _) in chunk], h_crop, w_crop)
-                logits = self.model(batch)[0]
-                assert logits.dtype == torch.float32 and logits.is_contiguous()
-                L.call("emrt_window_accumulate", Fn.P(logits), Fn.P(final), Fn.P(count), ptr, len(chunk), self.ncls, H, W, h_crop, w_crop, c.stream)
+            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count)
             self._finish(final, count, scene, out, 0, 1, H, W)
         return SceneResult(out.index[0], out.color[0], None if out.overlay is None else out.overlay[0], out.areas)
 
@@ -137,3 +164,74 @@ class ScenePredictor:
             assert logits.dtype == torch.float32 and logits.is_contiguous() and tuple(logits.shape) == (m, self.ncls, h, w)
             self._finish(logits, None, tiles[j0:j0 + m], out, j0, m, h, w)
         return out
+
+
+class SceneEvaluator:
+    """ev = SceneEvaluator(model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None)
+    tot = ev.evaluate(rank=0, nranks=1)     int64 [3, ncls] on the device: intersect, prediction and label areas of this rank's scenes
+    ev.per_scene                            int64 [n_scenes, 3, ncls] on the device: the same per scene, rows of other ranks' scenes zero
+
+    `bank` is a datasets.SceneBank whose label maps are stored as they are to be counted (a validation bank: shift_on_upload=True).  Scene i of
+    range(rank, len(bank), nranks) is predicted at its own size from the bank's uint8 view -- accumulate_windows, emrt_window_normalise,
+    emrt_argmax_nchw: the prediction of infer.ss_inference on the CPU-normalised scene, bit for bit (with `scales`: infer.ms_accumulate on the
+    normalised scene and the argmax, infer.ms_inference's) -- and emrt_segmentation_areas counts it against the uint8 label view into the scene's
+    row.  Everything is enqueued on the current stream: no host copy of a pixel, no synchronisation.  Sums, counts, normalised logits and the
+    prediction are allocated once per distinct scene shape and reused by every scene of that shape and by every later evaluation.
+    crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); mean / std as transforms.Normalize takes them."""
+
+    def __init__(self, model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None,
+                 flip_horizontal=True):
+        self.model, self.bank, self.ncls = model, bank, int(num_classes)
+        self.crop, self.stride = check_windows(crop_size, stride_size)
+        for i, (H, W) in enumerate(bank.sizes):
+            if H < self.crop[1] or W < self.crop[0]:
+                raise ValueError("scene %d (%s) is %dx%d (h x w), smaller than the crop %dx%d: nothing is resized or padded"
+                                 % (i, bank.names[i], H, W, self.crop[1], self.crop[0]))
+        if not 1 <= self.ncls <= 256:
+            raise ValueError("num_classes must be 1..256 (the label maps are uint8), got %d" % self.ncls)
+        if not 1 <= int(max_batch) <= MAX_WINDOWS:
+            raise ValueError("max_batch must be 1..%d, got %r" % (MAX_WINDOWS, max_batch))
+        self.max_batch = int(max_batch)
+        self.mean, self.stdinv = check_normalise(mean, std)
+        self.ignore_index = int(ignore_index)
+        self.scales = None if scales is None else tuple(scales)
+        self.flip_horizontal = flip_horizontal
+        self.per_scene = torch.empty((len(bank), 3, self.ncls), dtype=torch.int64, device=bank.device)
+        self._scratch = {}          # (H, W) -> (sums, counts, normalised logits, prediction)
+
+    def _buffers(self, H, W):
+        if (H, W) not in self._scratch:
+            dev, single = self.bank.device, self.scales is None
+            self._scratch[(H, W)] = (torch.empty((1, self.ncls, H, W), dtype=torch.float32, device=dev) if single else None,
+                                     torch.empty((1, 1, H, W), dtype=torch.float32, device=dev) if single else None,
+                                     torch.empty((1, self.ncls, H, W), dtype=torch.float32, device=dev) if single else None,
+                                     torch.empty((1, 1, H, W), dtype=torch.int32, device=dev))
+        return self._scratch[(H, W)]
+
+    def predict(self, i):
+        """Scene i -> its int32 [1, 1, H, W] prediction in the scratch of its shape (overwritten by the next scene of that shape)."""
+        L, c = Fn._L(), ctx()
+        scene, _ = self.bank.scene(i)
+        H, W = self.bank.sizes[i]
+        final, count, logits, pred = self._buffers(H, W)
+        if self.scales is not None:
+            img, _, _keep = crop_windows(scene, H, W, [(0, 0)], H, W, self.mean, self.stdinv)          # the whole scene as normalised fp32 CHW: one window
+            logits = infer.ms_accumulate(self.model, img[0], (H, W), True, None, self.stride, self.crop, self.ncls, scales=list(self.scales),
+                                         flip_horizontal=self.flip_horizontal)
+        else:
+            L.call("emrt_memset", Fn.P(final), 0, final.numel() * 4, c.stream)
+            L.call("emrt_memset", Fn.P(count), 0, count.numel() * 4, c.stream)
+            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count)
+            L.call("emrt_window_normalise", Fn.P(final), Fn.P(count), Fn.P(logits), self.ncls, H, W, c.stream)
+        L.call("emrt_argmax_nchw", Fn.P(logits), Fn.P(pred), 1, self.ncls, H, W, c.stream)
+        return pred
+
+    def evaluate(self, rank=0, nranks=1):
+        L, c = Fn._L(), ctx()
+        self.model.eval()
+        L.call("emrt_memset", Fn.P(self.per_scene), 0, self.per_scene.numel() * 8, c.stream)
+        for i in range(rank, len(self.bank), nranks):
+            pred = self.predict(i)
+            _, label = self.bank.scene(i)
+            L.call("emrt_segmentation_areas", Fn.P(pred), Fn.P(label), 2, pred.numel(), self.ncls, self.ignore_index, Fn.P(self.per_scene[i]), c.stream)
+        return self.per_scene.sum(0)

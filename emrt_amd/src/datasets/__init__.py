@@ -323,11 +323,18 @@ class SceneBank:
     bank.sizes      [(H, W)] per scene, bank.names their file stems, bank.offsets [(img_off, lab_off)]
     bank.tables(th, tw) -> the scene table and the cumulative table of tile origins, on the device and as the host mirrors the entry points
                     check (emrt_scene_draw / emrt_scene_sample)
-    label_shift     the dataset's label shift (LoveDA: 1), applied by the sampler through label_lut"""
+    bank.scene(i)   -> (uint8 [H, W, 3], uint8 [H, W]): scene i and its label map as views of bank.buffer (no copy)
+    label_shift     the dataset's label shift (LoveDA: 1), applied by the sampler through label_lut
 
-    def __init__(self, root, device, label_shift=0):
+    sub             the two directories under `root`; a validation bank is SceneBank(root, device, label_shift, sub=("val_images", "val_labels"),
+                    shift_on_upload=True)
+    shift_on_upload the label maps are stored as `label - np.uint8(label_shift)` with uint8 wrap, what Dataset.__getitem__ does in `val` mode
+                    (LoveDA's class 0 becomes 255): an evaluator counts the stored bytes as they lie.  False: stored as decoded."""
+
+    def __init__(self, root, device, label_shift=0, sub=("images", "labels"), shift_on_upload=False):
         self.root, self.device, self.label_shift = root, torch.device(device), int(label_shift)
-        files = scene_files(os.path.join(root, "images"), os.path.join(root, "labels"))
+        self.sub, self.shift_on_upload = tuple(sub), bool(shift_on_upload)
+        files = scene_files(os.path.join(root, self.sub[0]), os.path.join(root, self.sub[1]))
         self.names, self.sizes, self.offsets = [], [], []
         total = 0
         with _no_pixel_limit():
@@ -352,12 +359,19 @@ class SceneBank:
             for (name, ip, lp), (io, lo), (H, W) in zip(files, self.offsets, self.sizes):
                 img = np.array(Image.open(ip).convert("RGB"), dtype=np.uint8)         # read_image's / read_label's calls, kept in uint8
                 lab = np.array(Image.open(lp).convert("P"), dtype=np.uint8)
+                if self.shift_on_upload and self.label_shift:
+                    lab = lab - np.uint8(self.label_shift)          # uint8 wrap: class 0 (ignore) -> 255
                 self.buffer[io:lo].copy_(torch.from_numpy(img.reshape(-1)))
                 self.buffer[lo:lo + H * W].copy_(torch.from_numpy(lab.reshape(-1)))
         self._tables = {}
 
     def __len__(self):
         return len(self.sizes)
+
+    def scene(self, i):
+        """Scene i and its label map, uint8 [H, W, 3] and uint8 [H, W]: views of bank.buffer."""
+        (io, lo), (H, W) = self.offsets[i], self.sizes[i]
+        return self.buffer[io:lo].view(H, W, 3), self.buffer[lo:lo + H * W].view(H, W)
 
     def origins(self, th, tw):
         """Tile origins per scene, (H - th + 1) * (W - tw + 1); a tile larger than a scene is an error naming both."""

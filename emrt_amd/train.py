@@ -14,6 +14,8 @@ random tiles of DATA.CROP_SIZE, resident on the device) or from an .npz of pre-c
 --device_transforms then runs its training transforms on the GPU (DeviceTileLoader) instead of in the reader threads.
 --data scenes uploads the whole scenes of <DATA.DATA_PATH>/images + /labels once (SceneBank) and cuts every training tile out of device memory
 inside the captured step (SceneSampler): no reader threads, no per-step copy; periodic evaluation reads <root>/val_images + /val_labels.
+--eval_scenes native (with --data scenes) uploads those validation scenes once as well and evaluates them at their own resolution on the device
+(api.scene.SceneEvaluator) instead of resizing each to VAL.IMAGE_BASE_SIZE on the host.
 """
 import argparse
 import os
@@ -54,6 +56,9 @@ def parse_args(argv=None):
                    "processes, one per GPU (the reference gets its ranks from paddle.distributed.launch, train.py:116-123)")
     p.add_argument("--device_transforms", action="store_true", help="--data dataset only: reader threads just decode tiles; the "
                    "training transforms run as one HIP kernel per batch on the GPU (DeviceTileLoader)")
+    p.add_argument("--eval_scenes", default="resized", choices=["resized", "native"], help="--data scenes only: how the periodic evaluation sees the "
+                   "validation scenes.  'resized': decoded on the host and resized to VAL.IMAGE_BASE_SIZE (the tile chain of get_val_transforms); "
+                   "'native': resident on the GPU as uint8 and evaluated at their own resolution with VAL.CROP_SIZE / VAL.STRIDE_SIZE windows")
     p.add_argument("--val_tiles", type=int, default=16, help="--data synthetic / .npz without val arrays: how many held-out tiles to evaluate on")
     return p.parse_args(argv)
 
@@ -131,6 +136,10 @@ def main(argv=None):
                          "--data scenes already runs the transforms on the GPU, on tiles cut from the resident scenes")
     if args.device_transforms and args.data != "dataset":
         raise SystemExit("[train] --device_transforms needs --data dataset (it augments decoded tiles; --data %s has none)" % args.data)
+    if args.eval_scenes == "native" and args.data != "scenes":
+        raise SystemExit("[train] --eval_scenes native needs --data scenes (it evaluates the scene tree's val_images/ + val_labels/; --data %s has none)" % args.data)
+    if args.eval_scenes == "native" and args.no_eval:
+        raise SystemExit("[train] --eval_scenes native cannot be combined with --no-eval: there is no evaluation to run on the scenes")
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     if args.gpus > 1 and not launched:          # pure parent: no GPU call in this process, N fresh rank processes
         import sys
@@ -236,9 +245,11 @@ def main(argv=None):
             config.SAVE_DIR = fallback
         print("train_cfg: {}\ntrain_model_name: {}\ntrain_datatset: {}".format(args.cfg, config.MODEL.NAME, config.DATA.DATASET))
     # ---- validation set for the periodic evaluation (train.py:88-100, 187-195; val_in_train.py:19-125) ---------------------
-    val_images = val_labels = None
+    val_images = val_labels = scene_eval = None
     if not args.no_eval:
-        if args.data in ("dataset", "scenes"):
+        if args.eval_scenes == "native":
+            pass                    # the evaluator is built below, once the stride is settled
+        elif args.data in ("dataset", "scenes"):
             from .src.transforms import get_val_transforms
             if args.data == "scenes":
                 from .src.datasets import SceneVal
@@ -257,6 +268,13 @@ def main(argv=None):
             val_images, val_labels = list(vi), list(vl)
         if list(config.VAL.STRIDE_SIZE) == [320, 320] and list(config.VAL.CROP_SIZE)[0] < 320:
             config.VAL.STRIDE_SIZE = list(config.VAL.CROP_SIZE)   # the default stride > crop leaves NaN stripes
+        if args.eval_scenes == "native":        # the validation scenes uploaded once, beside the training bank
+            from .val import scene_evaluator
+            scene_eval = scene_evaluator(model, config, dev)
+            val_images = scene_eval.bank.names
+            if rank == 0:
+                print("[train] eval: %d validation scenes resident on the GPU (%.1f MB), evaluated at their own resolution" % (
+                    len(scene_eval.bank), scene_eval.bank.nbytes / 1e6), flush=True)
     best_mean_iou, best_acc, best_model_iter = -1.0, -1.0, -1
     iters_per_epoch = max(len(sampler), 1)
     total_epoch = iters // iters_per_epoch
@@ -297,9 +315,16 @@ def main(argv=None):
             checkpoint_now = cur_iter % config.SAVE_FREQ_CHECKPOINT == 0 or cur_iter == iters
             mean_iou = None
             if checkpoint_now and val_images is not None:       # every rank takes part (train.py:187-195)
-                from .val import evaluate
-                val_time_cost, mean_iou, acc, kap, class_iou, class_acc, class_f1, mean_f1 = evaluate(model, val_images, val_labels, config, rank, nranks)
+                from .val import evaluate, evaluate_scenes, scene_lines
+                if scene_eval is not None:
+                    val_time_cost, mean_iou, acc, kap, class_iou, class_acc, class_f1, mean_f1 = evaluate_scenes(scene_eval, rank, nranks)
+                    lines = scene_lines(scene_eval, nranks)
+                else:
+                    val_time_cost, mean_iou, acc, kap, class_iou, class_acc, class_f1, mean_f1 = evaluate(model, val_images, val_labels, config, rank, nranks)
+                    lines = []
                 if rank == 0:
+                    for line in lines:
+                        print(line)
                     print("Val_time_cost:   {}".format(val_time_cost))
                     print("In this val: mIoU {:.4f},  Acc: {:.4f}, F1-Score:{:.4f}".format(mean_iou, acc, mean_f1))
                     print("Current best_mIoU: {:.4f},  Acc: {:.4f}, iter: {}".format(best_mean_iou, best_acc, best_model_iter), flush=True)

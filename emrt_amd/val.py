@@ -1,10 +1,14 @@
 """Evaluation entry point (reference: semantic_segmentation/val.py:34-231, val_in_train.py:19-125).
 
     python -m emrt_amd.val --config <yaml> --model_path <iter_N_state.pt> [--data tiles.npz]
+    python -m emrt_amd.val --config <yaml> --model_path <...> --data scenes [--data_path ROOT]
 
 Single-scale sliding-window inference (src/api/infer.py) over a set of tiles, per-image area accumulation, one
 all-reduce of the [3, ncls] int64 areas at the end when WORLD_SIZE > 1 (the reference all-gathers three tensors per
 image, val.py:164-170), then mIoU / Acc / Kappa / per-class F1 exactly as val.py:197-209 prints them.
+
+--data scenes evaluates the whole scenes of <DATA.DATA_PATH>/val_images + /val_labels at their own resolution: they are uploaded once as uint8
+(datasets.SceneBank) and api.scene.SceneEvaluator cuts, normalises, predicts and counts them on the device; one more line per scene.
 """
 import argparse
 import os
@@ -27,7 +31,8 @@ def parse_args(argv=None):
                    default=os.path.join(os.path.dirname(__file__), "configs/EMRT/EMRT_256x256_160k_potsdam.yaml"))
     p.add_argument("--model_path", default=None, type=str)
     p.add_argument("--multi_scales", action="store_true", help="multi-scale (VAL.SCALE_RATIOS) + horizontal-flip inference, infer.py:160-260")
-    p.add_argument("--data", default="synthetic", help="'synthetic', 'dataset' (DATA.DATASET under DATA.DATA_PATH) or a .npz")
+    p.add_argument("--data", default="synthetic", help="'synthetic', 'dataset' (DATA.DATASET under DATA.DATA_PATH), 'scenes' (the whole scenes of "
+                   "DATA.DATA_PATH/val_images + /val_labels, resident on the GPU and evaluated at their own resolution) or a .npz")
     p.add_argument("--data_path", default=None, help="override DATA.DATA_PATH of the yaml")
     p.add_argument("--dtype", default="fp32", choices=["bf16", "fp16", "fp32"])
     return p.parse_args(argv)
@@ -97,12 +102,54 @@ def evaluate(model, images, labels, config, rank=0, nranks=1, multi_scales=False
         tot[2] += la
     if nranks > 1:
         torch.distributed.all_reduce(tot)
+    return (time.time() - t0,) + metric_tuple(tot)
+
+
+def metric_tuple(tot):
+    """int64 [3, ncls] intersect / prediction / label areas (after the all-reduce, if any) -> (mIoU, Acc, kappa, class IoU, class Acc, class F1,
+    mean F1): what evaluate() returns after its time."""
     class_iou, miou = metrics.mean_iou(tot[0], tot[1], tot[2])
     acc, class_acc, class_rec = metrics.accuracy(tot[0], tot[1], tot[2])
     kap = metrics.kappa(tot[0], tot[1], tot[2])
     with np.errstate(divide="ignore", invalid="ignore"):
         class_f1 = np.nan_to_num(2 * class_acc * class_rec / (class_acc + class_rec))
-    return time.time() - t0, miou, acc, kap, class_iou, class_acc, class_f1, float(np.mean(class_f1))
+    return miou, acc, kap, class_iou, class_acc, class_f1, float(np.mean(class_f1))
+
+
+def scene_evaluator(model, config, device, multi_scales=False, max_batch=32):
+    """The validation bank of a scene tree (<DATA.DATA_PATH>/val_images + /val_labels, uploaded here, labels stored as a `val` Dataset shifts them)
+    and the SceneEvaluator over it, from VAL.CROP_SIZE / STRIDE_SIZE / MEAN / STD and TRAIN.IGNORE_INDEX; VAL.SCALE_RATIOS when multi_scales."""
+    from .src.api.scene import SceneEvaluator
+    from .src.datasets import SceneBank
+    bank = SceneBank(config.DATA.DATA_PATH, device, label_shift=1 if config.DATA.DATASET == "LoveDA" else 0, sub=("val_images", "val_labels"),
+                     shift_on_upload=True)
+    return SceneEvaluator(model, bank, config.DATA.NUM_CLASSES, config.VAL.CROP_SIZE, config.VAL.STRIDE_SIZE, list(config.VAL.MEAN), list(config.VAL.STD),
+                          ignore_index=config.TRAIN.IGNORE_INDEX, max_batch=max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi_scales else None)
+
+
+def evaluate_scenes(evaluator, rank=0, nranks=1):
+    """evaluate() over a SceneEvaluator: this rank's scenes, one all-reduce of the areas when nranks > 1, the same tuple."""
+    t0 = time.time()
+    tot = evaluator.evaluate(rank, nranks)
+    if nranks > 1:
+        torch.distributed.all_reduce(tot)
+    return (time.time() - t0,) + metric_tuple(tot)
+
+
+def scene_lines(evaluator, nranks=1):
+    """One line per scene, "name  mIoU  Acc", from evaluator.per_scene in ONE device-to-host copy (the rows of the other ranks' scenes are summed in
+    first when nranks > 1: every row belongs to one rank, the others hold zeros there)."""
+    per = evaluator.per_scene
+    if nranks > 1:
+        per = per.clone()
+        torch.distributed.all_reduce(per)
+    per = per.cpu()
+    lines = []
+    for name, (H, W), a in zip(evaluator.bank.names, evaluator.bank.sizes, per):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            miou, acc = metrics.mean_iou(a[0], a[1], a[2])[1], metrics.accuracy(a[0], a[1], a[2])[0]
+        lines.append("[EVAL] Scene {} ({}x{}): mIoU: {:.4f}  Acc: {:.4f}".format(name, H, W, miou, acc))
+    return lines
 
 
 def main(argv=None):
@@ -117,7 +164,18 @@ def main(argv=None):
     if args.dtype == "fp16":
         model.compute_aux_in_eval = False      # the auxiliary head is computed and thrown away in eval (paddle_EMRT.py:300-302, infer.py:66)
     dev = torch.device("cuda", local_rank)
-    if args.data == "synthetic":
+    if list(config.VAL.STRIDE_SIZE) == [320, 320] and list(config.VAL.CROP_SIZE)[0] < 320:
+        config.VAL.STRIDE_SIZE = list(config.VAL.CROP_SIZE)   # default stride > crop leaves NaN stripes (SURVEY.md 3.4)
+    multi_scales = args.multi_scales or config.VAL.MULTI_SCALES_VAL
+    ev = None
+    if args.data == "scenes":           # whole validation scenes resident on the device, evaluated at their own resolution
+        if getattr(args, "data_path", None):
+            config.DATA.DATA_PATH = args.data_path
+        ev = scene_evaluator(model, config, dev, multi_scales)
+        images = ev.bank.names
+        if rank == 0:
+            print("[EVAL] data: %d validation scenes resident on the GPU (%.1f MB)" % (len(ev.bank), ev.bank.nbytes / 1e6), flush=True)
+    elif args.data == "synthetic":
         g = torch.Generator().manual_seed(0)
         h = w = config.VAL.IMAGE_BASE_SIZE or config.DATA.CROP_SIZE[0]
         images = [torch.randn(3, h, w, generator=g).to(dev) for _ in range(8)]
@@ -134,14 +192,19 @@ def main(argv=None):
         z = np.load(args.data)
         images = [torch.from_numpy(a).float().to(dev) for a in z["images"]]
         labels = [torch.from_numpy(a).long().to(dev) for a in z["labels"]]
-    if list(config.VAL.STRIDE_SIZE) == [320, 320] and list(config.VAL.CROP_SIZE)[0] < 320:
-        config.VAL.STRIDE_SIZE = list(config.VAL.CROP_SIZE)   # default stride > crop leaves NaN stripes (SURVEY.md 3.4)
-    cost, miou, acc, kap, ciou, cacc, cf1, mf1 = evaluate(model, images, labels, config, rank, nranks, multi_scales=args.multi_scales or config.VAL.MULTI_SCALES_VAL)
+    if ev is not None:
+        cost, miou, acc, kap, ciou, cacc, cf1, mf1 = evaluate_scenes(ev, rank, nranks)
+        lines = scene_lines(ev, nranks)
+    else:
+        cost, miou, acc, kap, ciou, cacc, cf1, mf1 = evaluate(model, images, labels, config, rank, nranks, multi_scales=multi_scales)
+        lines = []
     if rank == 0:
         print("[EVAL] Images: {}  mIoU: {:.4f}  Acc: {:.4f}  Kappa: {:.4f}  mF1: {:.4f}".format(len(images), miou, acc, kap, mf1))
         print("[EVAL] Class IoU: " + str(np.round(ciou, 4)))
         print("[EVAL] Class Acc: " + str(np.round(cacc, 4)))
         print("[EVAL] Class F1-score: " + str(np.round(cf1, 4)))
+        for line in lines:
+            print(line)
     return miou
 
 

@@ -447,7 +447,9 @@ int emrt_sgd_momentum_step_sched(float* params, const float* grads, float* veloc
 int emrt_adamw_step(float* params, const float* grads, float* moment1, float* moment2, long long n, const float* clip_state, const long long* step, const EmrtLrSchedule* sched, float beta1, float beta2, float eps, float weight_decay, int decoupled, const long long* ranges, int nranges, float range_mult, float* lr_out, void* mirror, int mirror_dtype, void* stream);
 /* ---- evaluation metric counts (src/utils/metrics.py:20-59 calculate_area; val.py:197-209): out[3][num_classes] (int64, ACCUMULATED into: the caller zeroes it
  * once per evaluation) += per-class pixel counts of (pred == label), pred, label over the pixels whose label != ignore_index; predictions / labels outside
- * [0, num_classes) are counted nowhere.  pred int32 (the argmax map of emrt_argmax / the sliding-window engine), label int64 (label_is_int64) or int32. */
+ * [0, num_classes) are counted nowhere.  pred int32 (the argmax map of emrt_argmax / the sliding-window engine).  label_is_int64 selects the label type:
+ * 0 = int32, 1 = int64, 2 = uint8 (a label map of a scene bank: no alignment is asked of the pointer, and an ignore_index outside 0..255 drops nothing);
+ * any other value is refused before any launch. */
 int emrt_segmentation_areas(const int* pred, const void* label, int label_is_int64, long long n, int num_classes, int ignore_index, long long* out, void* stream);
 int emrt_counter_add(long long* counter, long long delta, void* stream);
 /* fp32 master weights -> compute-dtype forward copy [OC][taps][C] and transposed dgrad copy [C][taps][OC];
