@@ -1,6 +1,7 @@
 """Seeded random case lists for the shape sweeps of csrc/norm.hip, csrc/spatial.hip and the inference glue
 (tests/test_gpu_norm_fuzz.py, tests/test_gpu_spatial_fuzz.py, tests/test_gpu_infer_glue.py) and of csrc/attn.hip
-(tests/test_gpu_mha_fuzz.py; its float64 reference and bounds are tests/mha_reference.py), and the dispatchers' shape predicates
+(tests/test_gpu_mha_fuzz.py; its float64 reference and bounds are tests/mha_reference.py), the written-out case list of the sweep of
+csrc/msda.hip by plan, build and layout (tests/test_gpu_msda_fuzz.py; tests/msda_reference.py), and the dispatchers' shape predicates
 restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
 entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
 seed or a range cannot silently empty one.
@@ -93,11 +94,106 @@ Regime -> case ids (regime_table() renders this text; the CPU test compares):
   mha               dropout, layout: fused                             mha1909-{54,59,60,65,66}
   mha               dropout, layout: split                             mha1909-{55,56,61,62,67,68}
   mha               dropout, layout: offset8                           mha1909-{57,58,63,64,69}
+  msda              FWD_GLOBAL, build (3, 6)                           msda2010-{37,38,39,40,41,42}
+  msda              FWD_GLOBAL, build (4, 4)                           msda2010-{43,44,50,53}
+  msda              FWD_GLOBAL, build (3, 4)                           msda2010-{45,46,51,52}
+  msda              FWD_GLOBAL, build (1, 4)                           msda2010-{47,48,49}
+  msda              FWD_LDS, build (3, 6)                              msda2010-{17,18,19,20,21,22,23,24,25,34,54,55,56,57,64,65}
+  msda              FWD_LDS, build (4, 4)                              msda2010-{26,27,28,36,58,59,66,67}
+  msda              FWD_LDS, build (3, 4)                              msda2010-{29,30,60,61,68,69}
+  msda              FWD_LDS, build (1, 4)                              msda2010-{31,32,33,35,62,63,70,71}
+  msda              FWD_BAND, build (3, 6)                             msda2010-{0,1,2,3,4,5,6,7,14}
+  msda              FWD_BAND, build (4, 4)                             msda2010-{8,9,10,15}
+  msda              FWD_BAND, build (3, 4)                             msda2010-{11,12,13,16}
+  msda              GRAD_GLOBAL, build (3, 6)                          msda2010-{7,20,37,38,39,40,41,42}
+  msda              GRAD_GLOBAL, build (4, 4)                          msda2010-{28,43,44,50}
+  msda              GRAD_GLOBAL, build (3, 4)                          msda2010-{45,46,51}
+  msda              GRAD_GLOBAL, build (1, 4)                          msda2010-{47,48,49}
+  msda              GRAD_LDS, build (3, 6)                             msda2010-{17,18,19,21,22,23,24,25,54,55,56,57,64,65}
+  msda              GRAD_LDS, build (4, 4)                             msda2010-{26,27,58,59,66,67}
+  msda              GRAD_LDS, build (3, 4)                             msda2010-{29,30,60,61,68,69}
+  msda              GRAD_LDS, build (1, 4)                             msda2010-{31,32,33,62,63,70,71}
+  msda              GRAD_BAND, build (3, 6)                            msda2010-{0,1,2,3,4,5,6}
+  msda              GRAD_BAND, build (4, 4)                            msda2010-{8,9,10}
+  msda              GRAD_BAND, build (3, 4)                            msda2010-{11,12,13}
+  msda              ABSMAX, build (3, 6)                               msda2010-{7,38,39,40}
+  msda              ABSMAX, build (4, 4)                               msda2010-{44,50}
+  msda              ABSMAX, build (3, 4)                               msda2010-{45,51}
+  msda              ABSMAX, build (1, 4)                               msda2010-{47,49}
+  msda              SCATTER_MF, build (3, 6)                           msda2010-{17,18,19,20,21,22,23,24,25,40,41,42,64,65}
+  msda              SCATTER_MF, build (4, 4)                           msda2010-{26,27,28,44,66,67}
+  msda              SCATTER_MF, build (3, 4)                           msda2010-{29,30,46,51,68,69}
+  msda              SCATTER_MF, build (1, 4)                           msda2010-{31,32,33,48,70,71}
+  msda              SCATTER_LDS, build (3, 6)                          msda2010-{0,1,2,3,4,5,6,7,37,38,39,54,55,56,57}
+  msda              SCATTER_LDS, build (4, 4)                          msda2010-{8,9,10,43,50,58,59}
+  msda              SCATTER_LDS, build (3, 4)                          msda2010-{11,12,13,45,60,61}
+  msda              SCATTER_LDS, build (1, 4)                          msda2010-{47,49,62,63}
+  msda              FINALIZE, build (3, 6)                             msda2010-{0,1,2,3,4,5,6,7,54,55}
+  msda              FINALIZE, build (4, 4)                             msda2010-{8,9,10,58,59}
+  msda              FINALIZE, build (3, 4)                             msda2010-{11,12,13,60,61}
+  msda              band plan: NB = 4                                  msda2010-{0,1,2,6,7,11,14}
+  msda              band plan: NB = 2                                  msda2010-{3,4,5,8,9,10,12,13,15,16}
+  msda              band plan: msda_band_halo = 3 (misses)             msda2010-{1,2,9,13,15}
+  msda              Lq = 1                                             msda2010-{17,26,31}
+  msda              Lq % 16 = 1, Lq > 1                                msda2010-{18,21,23,25,29,30,33,38,40,43,44,45,47,50,51,62,63,67,69,71}
+  msda              Lq >= 1024 behind GRAD_GLOBAL (ABSMAX)             msda2010-{7,38,39,40,44,45,47,49,50,51}
+  msda              Lq >= 1024, no max |dout| scan (M = 3, 16)         msda2010-{41,42}
+  msda              fp32, Lq >= 1024                                   msda2010-{38,39,45,47,49,50}
+  msda              fp32, a level cut into several scatter ranges      msda2010-{39,49}
+  msda              scatter ranges: msda_scatter_qsplit = 2            msda2010-{55,59,61,63}
+  msda              scatter ranges: msda_scatter_qsplit = -1 or msda_scatter_cuts = 3 msda2010-{56,57}
+  msda              matrix-product scatter: msda_mf_bands = 16         msda2010-{65,67,69,71}
+  msda              M = 1                                              msda2010-{23,45}
+  msda              M = 2                                              msda2010-{24,29,43,51,68}
+  msda              M = 3                                              msda2010-{18,33,42}
+  msda              M = 4                                              msda2010-{6,25,35,40,48,50,53,67}
+  msda              M = 8                                              msda2010-{0,1,2,3,4,5,7,8,9,10,11,12,13,14,15,16,17,19,20,21,26,27,28,30,31,32,34,36,37,38,39,44,46,47,49,52,54,55,56,57,58,59,60,61,62,63,64,65,66,69,70,71}
+  msda              M = 16                                             msda2010-{22,41}
+  msda              B = 1                                              msda2010-{0,1,2,3,4,5,7,8,9,10,11,12,13,14,15,16,17,24,25,26,28,31,35,38,39,41,44,46,47,49,50,52,54,55,56,57,58,59,60,61,62,63,66,68,71}
+  msda              B = 2                                              msda2010-{6,19,20,21,22,27,32,33,34,36,37,40,42,43,45,51,53,64,65,69,70}
+  msda              B = 3                                              msda2010-{18,23,29,30,48,67}
+  msda              dtype: f32                                         msda2010-{37,38,39,43,45,47,49,50}
+  msda              dtype: bf16                                        msda2010-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,17,18,19,20,21,22,23,24,25,26,27,28,29,30,31,32,33,40,41,42,44,46,48,51,54,55,56,57,58,59,60,61,62,63,64,65,66,67,68,69,70,71}
+  msda              dtype: f16                                         msda2010-{14,15,16,34,35,36,52,53}
+  msda              inputs: ordinary                                   msda2010-{0,6,7,8,14,17,20,22,29,34,37,41,49,53,54,57,60,64,69}
+  msda              inputs: far                                        msda2010-{1,11,23,26,30,39,42,48,50,52,56,61,68}
+  msda              inputs: border                                     msda2010-{5,15,24,28,31,35,43,46,58,66,70}
+  msda              inputs: bandedge                                   msda2010-{2,4,9,12,16}
+  msda              inputs: centres                                    msda2010-{19,27,32,36,47}
+  msda              inputs: spike                                      msda2010-{10,25,40,44,45,55,59,62,65,71}
+  msda              inputs: lastquery                                  msda2010-{3,13,18,21,33,38,51,63,67}
+  msda              strided, FWD_GLOBAL                                msda2010-{38,42,43,48,49,50,53}
+  msda              strided, FWD_LDS                                   msda2010-{18,21,23,26,27,29,33,34,55,57,59,61,63,65,67,69,70}
+  msda              strided, FWD_BAND                                  msda2010-{2,5,6,9,12,14}
+  msda              strided, GRAD_GLOBAL                               msda2010-{38,42,43,48,49,50}
+  msda              strided, GRAD_LDS                                  msda2010-{18,21,23,26,27,29,33,55,57,59,61,63,65,67,69,70}
+  msda              strided, GRAD_BAND                                 msda2010-{2,5,6,9,12}
+  msda              strided, SCATTER_MF                                msda2010-{18,21,23,26,27,29,33,42,48,65,67,69,70}
+  msda              strided, SCATTER_LDS                               msda2010-{2,5,6,9,12,38,43,49,50,55,57,59,61,63}
+  msda              strided, band miss path                            msda2010-{2,9,12}
+  msda              refmode shared-1, GRAD_GLOBAL                      msda2010-{20,38,39,42,45,47,49}
+  msda              refmode batch-1, GRAD_GLOBAL                       msda2010-{28,40,43,48,51}
+  msda              refmode shared-L, GRAD_GLOBAL                      msda2010-{41,46}
+  msda              refmode batch-L, GRAD_GLOBAL                       msda2010-{7,37,44,50}
+  msda              refmode shared-1, GRAD_LDS                         msda2010-{17,22,25,26,31,33,54,55,58,59,60,61,62,63,64,66,68,70,71}
+  msda              refmode batch-1, GRAD_LDS                          msda2010-{18,24,32,57,65}
+  msda              refmode shared-L, GRAD_LDS                         msda2010-{21,23,27,56,67}
+  msda              refmode batch-L, GRAD_LDS                          msda2010-{19,29,30,69}
+  msda              refmode shared-1, GRAD_BAND                        msda2010-{0,2,4,10,11}
+  msda              refmode batch-1, GRAD_BAND                         msda2010-{3,6,12}
+  msda              refmode shared-L, GRAD_BAND                        msda2010-{1,9,13}
+  msda              refmode batch-L, GRAD_BAND                         msda2010-{5,8}
+  msda              dref, GRAD_GLOBAL                                  msda2010-{7,37,38,44,46,47}
+  msda              dref, GRAD_LDS (msda_bwd_dref_lds = 1)             msda2010-{19,21,27,30,32}
+  msda              dref, msda_bwd_dref_lds = 0 (GRAD_GLOBAL)          msda2010-{20,28}
+  msda              dref on a band pyramid (GRAD_GLOBAL)               msda2010-{7}
 
 Not reachable through the wrappers, on purpose:
   * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
     draws no align_corners=False case; the per-scale resize kernels see both conventions in the resize sweep.
   * the 64-bit index branch of unravel3 / unravel4 (csrc/common.hpp) needs more than 2^32 elements and stays unexercised.
+  * msda: the refusals (rows too long for a scatter slab, L = 2, dref with M != 8) are pinned by tests/test_msda_plan_cpu.py and stay out
+    of the sweep; FINALIZE and the band kinds do not exist for the (1, 4) build (see MSDA_REGIMES).
 """
 import random
 
@@ -676,24 +772,238 @@ MHA_REGIMES = [
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# deformable attention: emrt_msda_fwd / emrt_msda_bwd (tests/test_gpu_msda_fuzz.py; the float64 reference and the bounds are
+# tests/msda_reference.py).  Unlike the lists above this one is written out: a case is there to reach named kernels, and `expect` says
+# which -- data, confirmed against the planner (emrt_msda_plan, no GPU needed) by tests/test_msda_reference_cpu.py.
+# ---------------------------------------------------------------------------------------------------------------------------------
+MSDA_MAX_ELEMS = 1500000          # per tensor; apart from MAX_ELEMS: the smallest pyramid the row-band kernels take has Lv ~ 2500
+MSDA_BUILDS = ((3, 6), (4, 4), (3, 4), (1, 4))          # (levels, points) of with_levels_points (csrc/msda.hip)
+MSDA_KINDS = ("FWD_GLOBAL", "FWD_LDS", "FWD_BAND", "GRAD_GLOBAL", "GRAD_LDS", "GRAD_BAND", "ABSMAX", "SCATTER_MF", "SCATTER_LDS", "FINALIZE")
+MSDA_INPUTS = ("ordinary", "far", "border", "bandedge", "centres", "spike", "lastquery")          # tests/msda_reference.make_inputs
+# dense: through functional.msda.  strided: the C entry points; value is a channel slice of a wider buffer (ldv = 32 M + 64, v_bs padded by
+# a further 8 ldv), ldo = 3 M L P + 2, every output in a pre-filled buffer
+MSDA_LAYOUTS = ("dense", "strided")
+# reference points shared by the batch or one set per batch element, one point per query or one per level; "+dref": their gradient is asked for
+MSDA_REFMODES = ("shared-1", "batch-1", "shared-L", "batch-L")
+MSDA_LDS_MAX = 159 * 1024
+MSDA_KNOBS = ("msda_fwd_global", "msda_bwd_global", "msda_bwd_dref_lds", "msda_scatter_mfma", "msda_scatter_qsplit", "msda_scatter_cuts",
+              "msda_band_halo", "msda_mf_bands", "msda_lds_min_pairs")
+
+
+def msda_band_geometry(shapes, B, M, halo_knob=0):
+    """(NB, halo, slab bytes) of the row-band plan of a self-attention call over `shapes`, (0, 0, 0) when the whole (batch, head) slab fits
+    in LDS or no band plan exists.  Mirrors msda_band_plan and the slab test of msda_plan (csrc/msda.hip)."""
+    L = len(shapes)
+    guard = max(w for _, w in shapes) + 2
+    if L < 2 or (sum(h * w for h, w in shapes) + 2 * guard) * 64 <= MSDA_LDS_MAX:
+        return 0, 0, 0
+    NB = 2
+    while NB <= 64:
+        if any(h % NB for h, _ in shapes):
+            break
+        if NB * B * M < 192 and NB * 2 <= 64 and not any(h % (NB * 2) for h, _ in shapes):
+            NB *= 2
+            continue
+        for halo in range(halo_knob if halo_knob > 0 else 7, 2, -1):
+            npx = guard
+            for h, w in shapes:
+                npx = ((npx + 15) & ~15) + min(h // NB + 2 * halo, h) * w
+            slab = ((npx + guard + 15) >> 4 << 4) * 64
+            if slab <= MSDA_LDS_MAX:
+                return NB, halo, slab
+        NB *= 2
+    return 0, 0, 0
+
+
+def msda_scatter_max_npix(shapes):
+    """most pixels of one range of the integer scatter's LDS slab.  Mirrors msda_max_npix (csrc/msda.hip)."""
+    return ((160 * 1024 - 20480) // (33 * 4) - 2 * (max(w for _, w in shapes) + 2)) & ~3
+
+
+def msda_lq(case):
+    return case[4] or sum(h * w for h, w in case[3])
+
+
+def msda_in_domain(case):
+    _, B, M, shapes, Lq, P, regime, layout, refmode, knobs, expect, _ = case
+    dtype, fwd, bwd = expect
+    base, _, dref = refmode.partition("+")
+    Lv = sum(h * w for h, w in shapes)
+    pow2 = all(h & (h - 1) == 0 and w & (w - 1) == 0 for h, w in shapes)
+    return ((len(shapes), P) in MSDA_BUILDS and B >= 1 and M >= 1 and B * max(Lv, Lq or Lv) * M * 32 <= MSDA_MAX_ELEMS
+            and regime in MSDA_INPUTS and layout in MSDA_LAYOUTS and base in MSDA_REFMODES and dref in ("", "dref")
+            and (not dref or (M == 8 and dtype != "f16")) and set(knobs) <= set(MSDA_KNOBS)
+            and dtype in ("f32", "bf16", "f16") and (bwd is None) == (dtype == "f16") and set(fwd) | set(bwd or ()) <= set(MSDA_KINDS)
+            and (regime != "bandedge" or (Lq is None and msda_band_geometry(shapes, B, M, knobs.get("msda_band_halo", 0))[0] > 0))
+            and (regime != "centres" or pow2)
+            and all(h * w <= msda_scatter_max_npix(shapes) * h for h, w in shapes))          # (a row fits a scatter slab: else a refusal)
+
+
+MSDA_BAND4 = ((48, 40), (24, 20), (12, 10))          # NB = 4, halo = 7
+MSDA_BAND4_4 = MSDA_BAND4 + ((6, 5),)
+MSDA_BAND2A = ((44, 45), (22, 23), (10, 11))         # NB = 2, odd widths, segments that are no multiples of 16
+MSDA_BAND2A_4 = MSDA_BAND2A + ((4, 5),)
+MSDA_BAND2B = ((50, 40), (26, 20), (14, 10))         # NB = 2
+MSDA_T3 = ((3, 5), (2, 3), (1, 1))
+MSDA_T4 = MSDA_T3 + ((1, 2),)
+MSDA_T1 = ((3, 5),)
+MSDA_ODD3 = ((13, 17), (7, 9), (4, 5))
+MSDA_ODD4 = MSDA_ODD3 + ((2, 3),)
+MSDA_P2_3 = ((16, 16), (8, 8), (4, 4))
+MSDA_P2_4 = MSDA_P2_3 + ((2, 2),)
+MSDA_MID3 = ((20, 18), (10, 9), (5, 5))
+MSDA_MF3 = ((7, 10), (4, 5), (2, 3))
+MSDA_MF4 = MSDA_MF3 + ((1, 2),)
+MSDA_FIN3 = ((32, 28), (16, 14), (8, 7))             # the smallest pyramid whose small levels' scatter blocks are split by queries (FINALIZE)
+MSDA_FIN4 = MSDA_FIN3 + ((4, 4),)
+
+# (B, M, shapes, Lq or None (= Lv: self-attention over the pyramid), P, input regime, layout, refmode, knobs, (dtype, forward kinds, backward kinds))
+_MSDA_ROWS = (
+    (1, 8, MSDA_BAND4, None, 6, "ordinary", "dense", "shared-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4, None, 6, "far", "dense", "shared-L", {"msda_band_halo": 3}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4, None, 6, "bandedge", "strided", "shared-1", {"msda_band_halo": 3}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND2A, None, 6, "lastquery", "dense", "batch-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND2B, None, 6, "bandedge", "dense", "shared-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND2A, None, 6, "border", "strided", "batch-L", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (2, 4, MSDA_BAND4, None, 6, "ordinary", "strided", "batch-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4, None, 6, "ordinary", "dense", "batch-L+dref", {}, ("bf16", ("FWD_BAND",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4_4, None, 4, "ordinary", "dense", "batch-L", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4_4, None, 4, "bandedge", "strided", "shared-L", {"msda_band_halo": 3}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND2A_4, None, 4, "spike", "dense", "shared-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4, None, 4, "far", "dense", "shared-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND2B, None, 4, "bandedge", "strided", "batch-1", {}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND2A, None, 4, "lastquery", "dense", "shared-L", {"msda_band_halo": 3}, ("bf16", ("FWD_BAND",), ("GRAD_BAND", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_BAND4, None, 6, "ordinary", "strided", "shared-1", {}, ("f16", ("FWD_BAND",), None)),
+    (1, 8, MSDA_BAND2A_4, None, 4, "border", "dense", "shared-L", {"msda_band_halo": 3}, ("f16", ("FWD_BAND",), None)),
+    (1, 8, MSDA_BAND2B, None, 4, "bandedge", "dense", "shared-1", {}, ("f16", ("FWD_BAND",), None)),
+    (1, 8, MSDA_T3, 1, 6, "ordinary", "dense", "shared-1", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (3, 3, MSDA_T3, 129, 6, "lastquery", "strided", "batch-1", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, MSDA_P2_3, None, 6, "centres", "dense", "batch-L+dref", {}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, MSDA_P2_3, 110, 6, "ordinary", "dense", "shared-1+dref", {"msda_bwd_dref_lds": 0, "msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_GLOBAL", "SCATTER_MF"))),
+    (2, 8, MSDA_P2_3, 113, 6, "lastquery", "strided", "shared-L+dref", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 16, MSDA_ODD3, None, 6, "ordinary", "dense", "shared-1", {}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (3, 1, MSDA_ODD3, 129, 6, "far", "strided", "shared-L", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 2, MSDA_ODD3, 200, 6, "border", "dense", "batch-1", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 4, MSDA_MID3, 1041, 6, "spike", "dense", "shared-1", {}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 8, MSDA_T4, 1, 4, "far", "strided", "shared-1", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, MSDA_P2_4, None, 4, "centres", "strided", "shared-L+dref", {}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 8, MSDA_ODD4, None, 4, "border", "dense", "batch-1+dref", {"msda_bwd_dref_lds": 0, "msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_GLOBAL", "SCATTER_MF"))),
+    (3, 2, MSDA_T3, 129, 4, "ordinary", "strided", "batch-L", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (3, 8, ((16, 12), (8, 6), (4, 3)), 145, 4, "far", "dense", "batch-L+dref", {}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 8, MSDA_T1, 1, 4, "border", "dense", "shared-1", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, ((16, 16),), None, 4, "centres", "dense", "batch-1+dref", {}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 3, ((13, 17),), 129, 4, "lastquery", "strided", "shared-1", {"msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, MSDA_ODD3, None, 6, "ordinary", "strided", "batch-1", {"msda_lds_min_pairs": 0}, ("f16", ("FWD_LDS",), None)),
+    (1, 4, ((9, 11),), 77, 4, "border", "dense", "shared-1", {"msda_lds_min_pairs": 0}, ("f16", ("FWD_LDS",), None)),
+    (2, 8, MSDA_P2_4, None, 4, "centres", "dense", "shared-L", {}, ("f16", ("FWD_LDS",), None)),
+    (2, 8, MSDA_T3, 37, 6, "ordinary", "dense", "batch-L+dref", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "SCATTER_LDS"))),
+    (1, 8, MSDA_MID3, 1041, 6, "lastquery", "strided", "shared-1+dref", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS"))),
+    (1, 8, MSDA_BAND4, None, 6, "far", "dense", "shared-1", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS"))),
+    (2, 4, ((12, 10), (6, 5), (3, 3)), 1025, 6, "spike", "dense", "batch-1", {"msda_fwd_global": 1, "msda_bwd_global": 1}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_MF"))),
+    (1, 16, MSDA_ODD3, 1040, 6, "ordinary", "dense", "shared-L", {"msda_fwd_global": 1, "msda_bwd_global": 1}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "SCATTER_MF"))),
+    (2, 3, MSDA_ODD3, 1030, 6, "far", "strided", "shared-1", {"msda_fwd_global": 1, "msda_bwd_global": 1}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "SCATTER_MF"))),
+    (2, 2, MSDA_T4, 129, 4, "border", "strided", "batch-1", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "SCATTER_LDS"))),
+    (1, 8, MSDA_ODD4, 1041, 4, "spike", "dense", "batch-L+dref", {"msda_fwd_global": 1, "msda_bwd_global": 1}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_MF"))),
+    (2, 1, MSDA_ODD3, 1041, 4, "spike", "dense", "shared-1", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS"))),
+    (1, 8, ((2, 2), (2, 2), (1, 2)), 10, 4, "border", "dense", "shared-L+dref", {}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "SCATTER_MF"))),
+    (1, 8, ((16, 16),), 1041, 4, "centres", "dense", "shared-1+dref", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS"))),
+    (3, 4, ((7, 10),), 70, 4, "far", "strided", "batch-1", {"msda_fwd_global": 1, "msda_bwd_global": 1}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "SCATTER_MF"))),
+    (1, 8, ((40, 30),), None, 4, "ordinary", "strided", "shared-1", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS"))),
+    (1, 4, MSDA_ODD4, 1041, 4, "far", "strided", "batch-L", {}, ("f32", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_LDS"))),
+    (2, 2, MSDA_MID3, 1041, 4, "lastquery", "dense", "batch-1", {"msda_fwd_global": 1, "msda_bwd_global": 1}, ("bf16", ("FWD_GLOBAL",), ("GRAD_GLOBAL", "ABSMAX", "SCATTER_MF"))),
+    (1, 8, MSDA_ODD3, None, 4, "far", "dense", "shared-1", {"msda_fwd_global": 1}, ("f16", ("FWD_GLOBAL",), None)),
+    (2, 4, MSDA_T4, 5, 4, "ordinary", "strided", "batch-L", {}, ("f16", ("FWD_GLOBAL",), None)),
+    (1, 8, MSDA_FIN3, None, 6, "ordinary", "dense", "shared-1", {"msda_scatter_mfma": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_FIN3, None, 6, "spike", "strided", "shared-1", {"msda_scatter_mfma": 0, "msda_scatter_qsplit": 2}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_FIN3, None, 6, "far", "dense", "shared-L", {"msda_scatter_mfma": 0, "msda_scatter_qsplit": -1}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS"))),
+    (1, 8, MSDA_FIN3, None, 6, "ordinary", "strided", "batch-1", {"msda_scatter_mfma": 0, "msda_scatter_cuts": 3}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS"))),
+    (1, 8, MSDA_FIN4, None, 4, "border", "dense", "shared-1", {"msda_scatter_mfma": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_FIN4, None, 4, "spike", "strided", "shared-1", {"msda_scatter_mfma": 0, "msda_scatter_qsplit": 2}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_FIN3, None, 4, "ordinary", "dense", "shared-1", {"msda_scatter_mfma": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, MSDA_FIN3, None, 4, "far", "strided", "shared-1", {"msda_scatter_mfma": 0, "msda_scatter_qsplit": 2}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS", "FINALIZE"))),
+    (1, 8, ((32, 28),), 1041, 4, "spike", "dense", "shared-1", {"msda_scatter_mfma": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS"))),
+    (1, 8, ((32, 28),), 1041, 4, "lastquery", "strided", "shared-1", {"msda_scatter_mfma": 0, "msda_scatter_qsplit": 2}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_LDS"))),
+    (2, 8, MSDA_MF3, None, 6, "ordinary", "dense", "shared-1", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, MSDA_MF3, None, 6, "spike", "strided", "batch-1", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0, "msda_mf_bands": 16}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 8, MSDA_MF4, None, 4, "border", "dense", "shared-1", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (3, 4, MSDA_MF4, 113, 4, "lastquery", "strided", "shared-L", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0, "msda_mf_bands": 16}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 2, MSDA_MF3, None, 4, "far", "dense", "shared-1", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, MSDA_MF3, 129, 4, "ordinary", "strided", "batch-L", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0, "msda_mf_bands": 16}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (2, 8, ((7, 10),), None, 4, "border", "strided", "shared-1", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+    (1, 8, ((7, 10),), 129, 4, "spike", "dense", "shared-1", {"msda_scatter_mfma": 2, "msda_lds_min_pairs": 0, "msda_mf_bands": 16}, ("bf16", ("FWD_LDS",), ("GRAD_LDS", "SCATTER_MF"))),
+)
+
+
+def msda_cases(seed=2010):
+    """(id, B, M, shapes, Lq or None, P, regime, layout, refmode, knobs, expect, seed); expect = (dtype, the kernel kinds the forward launches,
+    those the backward launches or None for the forward-only float16) under the case's knobs, every other knob at its default"""
+    return [("msda%d-%d" % (seed, i),) + row + (seed + i,) for i, row in enumerate(_MSDA_ROWS)]
+
+
+def _msda_kinds(c):
+    return set(c[10][1]) | set(c[10][2] or ())
+
+
+def _msda_has(kind, build):
+    return lambda c: kind in _msda_kinds(c) and (len(c[3]), c[5]) == build
+
+
+def _msda_first_stage(c):
+    return {k for k in _msda_kinds(c) if k.startswith(("FWD_", "GRAD_"))}
+
+
+# FWD_BAND / GRAD_BAND need two levels; FINALIZE needs two levels cut differently (msda_ranges: a query split goes to the levels with fewer
+# cuts than the most-cut one): none of the three exists for the (1, 4) build
+MSDA_REGIMES = [("%s, build (%d, %d)" % (k, b[0], b[1]), _msda_has(k, b)) for k in MSDA_KINDS for b in MSDA_BUILDS
+                if not (b[0] == 1 and k in ("FWD_BAND", "GRAD_BAND", "FINALIZE"))] + [
+    ("band plan: NB = 4", lambda c: "FWD_BAND" in _msda_kinds(c) and msda_band_geometry(c[3], c[1], c[2], c[9].get("msda_band_halo", 0))[0] == 4),
+    ("band plan: NB = 2", lambda c: "FWD_BAND" in _msda_kinds(c) and msda_band_geometry(c[3], c[1], c[2], c[9].get("msda_band_halo", 0))[0] == 2),
+    ("band plan: msda_band_halo = 3 (misses)", lambda c: "FWD_BAND" in _msda_kinds(c) and c[9].get("msda_band_halo") == 3),
+    ("Lq = 1", lambda c: c[4] == 1),
+    ("Lq % 16 = 1, Lq > 1", lambda c: msda_lq(c) % 16 == 1 and msda_lq(c) > 1),
+    ("Lq >= 1024 behind GRAD_GLOBAL (ABSMAX)", lambda c: msda_lq(c) >= 1024 and "ABSMAX" in _msda_kinds(c)),
+    ("Lq >= 1024, no max |dout| scan (M = 3, 16)", lambda c: msda_lq(c) >= 1024 and "GRAD_GLOBAL" in _msda_kinds(c) and "ABSMAX" not in _msda_kinds(c)),
+    ("fp32, Lq >= 1024", lambda c: c[10][0] == "f32" and msda_lq(c) >= 1024),
+    ("fp32, a level cut into several scatter ranges", lambda c: c[10][0] == "f32" and any(h * w > msda_scatter_max_npix(c[3]) for h, w in c[3])),
+    ("scatter ranges: msda_scatter_qsplit = 2", lambda c: c[9].get("msda_scatter_qsplit") == 2),
+    ("scatter ranges: msda_scatter_qsplit = -1 or msda_scatter_cuts = 3", lambda c: c[9].get("msda_scatter_qsplit") == -1 or c[9].get("msda_scatter_cuts") == 3),
+    ("matrix-product scatter: msda_mf_bands = 16", lambda c: c[9].get("msda_mf_bands") == 16 and "SCATTER_MF" in _msda_kinds(c)),
+] + [("M = %d" % m, (lambda m_: lambda c: c[2] == m_)(m)) for m in (1, 2, 3, 4, 8, 16)] + [
+    ("B = %d" % b, (lambda b_: lambda c: c[1] == b_)(b)) for b in (1, 2, 3)] + [
+    ("dtype: %s" % d, (lambda d_: lambda c: c[10][0] == d_)(d)) for d in ("f32", "bf16", "f16")] + [
+    ("inputs: %s" % r, (lambda r_: lambda c: c[6] == r_)(r)) for r in MSDA_INPUTS] + [
+    ("strided, %s" % k, (lambda k_: lambda c: c[7] == "strided" and k_ in _msda_kinds(c))(k))
+    for k in ("FWD_GLOBAL", "FWD_LDS", "FWD_BAND", "GRAD_GLOBAL", "GRAD_LDS", "GRAD_BAND", "SCATTER_MF", "SCATTER_LDS")] + [
+    ("strided, band miss path", lambda c: c[7] == "strided" and "GRAD_BAND" in _msda_kinds(c) and (c[9].get("msda_band_halo") == 3 or c[6] in ("bandedge", "far"))),
+] + [("refmode %s, %s" % (r, k), (lambda r_, k_: lambda c: c[8].partition("+")[0] == r_ and k_ in _msda_kinds(c))(r, k))
+     for k in ("GRAD_GLOBAL", "GRAD_LDS", "GRAD_BAND") for r in MSDA_REFMODES] + [
+    ("dref, GRAD_GLOBAL", lambda c: c[8].endswith("+dref") and "GRAD_GLOBAL" in _msda_kinds(c) and not c[9].get("msda_bwd_dref_lds", 1) == 0),
+    ("dref, GRAD_LDS (msda_bwd_dref_lds = 1)", lambda c: c[8].endswith("+dref") and "GRAD_LDS" in _msda_kinds(c)),
+    ("dref, msda_bwd_dref_lds = 0 (GRAD_GLOBAL)", lambda c: c[8].endswith("+dref") and c[9].get("msda_bwd_dref_lds", 1) == 0 and "GRAD_GLOBAL" in _msda_kinds(c)),
+    ("dref on a band pyramid (GRAD_GLOBAL)", lambda c: c[8].endswith("+dref") and "FWD_BAND" in _msda_kinds(c) and "GRAD_GLOBAL" in _msda_kinds(c)),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 CASES = {
     "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
     "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
-    "mha": mha_cases(),
+    "mha": mha_cases(), "msda": msda_cases(),
 }
 REGIMES = {
     "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
     "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
-    "mha": MHA_REGIMES,
+    "mha": MHA_REGIMES, "msda": MSDA_REGIMES,
 }
 IN_DOMAIN = {
     "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
     "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
-    "mha": mha_in_domain,
+    "mha": mha_in_domain, "msda": msda_in_domain,
 }
 
 
-REGIME_MIN = {("maxpool", "k = 7"): 1}          # cases a regime must keep: two, except where the sweep asks for exactly one
+# cases a regime must keep: two, except where the sweep asks for exactly one
+REGIME_MIN = {("maxpool", "k = 7"): 1, ("msda", "dref on a band pyramid (GRAD_GLOBAL)"): 1}
 
 
 def regime_hits(op):

@@ -48,6 +48,8 @@ def test_case_sizes_stay_small():
         assert c[1] * c[4] * c[5] * c[2] * (len(c[3]) + 1) <= fc.MAX_ELEMS
     for c in fc.CASES["mha"]:
         assert c[1] * c[2] * c[3] * c[3] <= fc.MAX_ELEMS and 1 <= c[1] <= 4 and c[2] in fc.MHA_MS and c[3] in fc.MHA_LS
+    for c in fc.CASES["msda"]:          # its own cap: the smallest pyramid the row-band kernels take has Lv ~ 2500
+        assert c[1] * max(fc.msda_lq(c), sum(h * w for h, w in c[3])) * c[2] * 32 <= fc.MSDA_MAX_ELEMS
 
 
 def test_mha_sweep_covers_what_it_was_written_for():
@@ -59,6 +61,27 @@ def test_mha_sweep_covers_what_it_was_written_for():
     assert {17, 33, 110, 111, 128} <= {c[3] for c in drop} and {c[5] for c in drop} == {0.1, 0.5}
     assert all(c[4] == "ordinary" for c in drop)
     assert fc.mha_cases() == cases
+
+
+def test_msda_sweep_covers_what_it_was_written_for():
+    """every kernel kind under every build that has it, twice (the regime list says which exist); every head count, batch size, dtype, input
+    regime, layout and refmode; the written-out list is what msda_cases() returns"""
+    cases = fc.CASES["msda"]
+    assert fc.msda_cases() == cases and 55 <= len(cases) <= 80
+    hits = dict(fc.regime_hits("msda"))
+    for k in fc.MSDA_KINDS:
+        for b in fc.MSDA_BUILDS:
+            name = "%s, build (%d, %d)" % (k, b[0], b[1])
+            if b[0] == 1 and k in ("FWD_BAND", "GRAD_BAND", "FINALIZE"):
+                assert name not in hits and not any(fc._msda_has(k, b)(c) for c in cases)
+            else:
+                assert len(hits[name]) >= 2, name
+    assert {c[2] for c in cases} == {1, 2, 3, 4, 8, 16} and {c[1] for c in cases} == {1, 2, 3}
+    assert {c[8].partition("+")[0] for c in cases} == set(fc.MSDA_REFMODES) and {c[7] for c in cases} == set(fc.MSDA_LAYOUTS)
+    assert all(c[2] == 8 for c in cases if c[8].endswith("+dref"))
+    assert fc.msda_band_geometry(fc.MSDA_BAND4, 1, 8)[:2] == (4, 7) and fc.msda_band_geometry(fc.MSDA_BAND4, 1, 8, 3)[:2] == (4, 3)
+    assert fc.msda_band_geometry(fc.MSDA_BAND2A, 1, 8)[0] == 2 and fc.msda_band_geometry(fc.MSDA_BAND2B, 1, 8)[0] == 2
+    assert fc.msda_band_geometry(fc.MSDA_FIN3, 1, 8) == (0, 0, 0) and fc.msda_band_geometry(((64, 64),), 2, 8) == (0, 0, 0)
 
 
 def test_mirrored_predicates_at_known_points():

@@ -412,57 +412,7 @@ def test_mha_fwd_rounds_to_nearest():
     rounding_is_nearest("mha valu", out, want_v)
 
 
-def _msda_ref64(value, offw, ref, shapes, M, Pn, round_weights):
-    """Multi-scale deformable attention in float64 with explicit corners (grid_sample, align_corners = False, zero padding):
-    out[b, q, m] = sum over (level, point, corner) of w * value[b, pixel, m], w = softmax weight * bilinear corner weight.
-    round_weights: the kernels' contract for 16-bit value types (csrc/msda.hip: the four corner weights are packed to the value type so that
-    one v_dot2_f32_f16 does two multiply-adds; products and sums stay fp32) -- w -> round16(w).  Returns (out, slack).
-    slack, derived: the kernel computes pixel coordinates (ref + off / size) * size - 0.5 and the softmax in fp32, so a weight carries
-    dw = aw * 2 * 4 * 2^-24 * (extent + |offset| + 1) (coordinate error times the unit slope of a bilinear weight, x and y) + 16 * 2^-24 w
-    (__expf, sum, divide, two products).  Unrounded weights: sum dw |v|.  Rounded weights: the rounding absorbs dw unless w lies within dw of
-    a float16 rounding boundary, where the kernel may round the other way: such a corner contributes ulp16(w) |v|.  Plus the fp32
-    accumulation of the 4 L P products (gemm_slack)."""
-    B, Lv, CC = value.shape
-    L = len(shapes)
-    Lq = offw.shape[1]
-    tp = M * L * Pn
-    off = offw[..., :2 * tp].reshape(B, Lq, M, L, Pn, 2)
-    aw = torch.softmax(offw[..., 2 * tp:3 * tp].reshape(B, Lq, M, L * Pn), -1).reshape(B, Lq, M, L, Pn)
-    val = value.reshape(B, Lv, M, 32).permute(0, 2, 1, 3)                     # [B, M, Lv, 32]
-    out = torch.zeros(B, M, Lq, 32, dtype=torch.float64)
-    sq = torch.zeros_like(out)
-    extra = torch.zeros_like(out)
-    start = 0
-    for l, (h, w) in enumerate(shapes):
-        rl = ref[:, :, l if ref.shape[2] == L else 0].reshape(ref.shape[0], Lq, 1, 1, 2)
-        loc = rl + off[:, :, :, l] / torch.tensor([w, h], dtype=torch.float64)              # normalised (x, y)
-        px, py = loc[..., 0] * w - 0.5, loc[..., 1] * h - 0.5                            # [B, Lq, M, P]
-        x0, y0 = px.floor(), py.floor()
-        lx, ly = px - x0, py - y0
-        dcoord = 4 * EPS32 * (max(h, w) + off[:, :, :, l].abs().amax(-1) + 1)
-        for dy_, dx_, cw in ((0, 0, (1 - ly) * (1 - lx)), (0, 1, (1 - ly) * lx), (1, 0, ly * (1 - lx)), (1, 1, ly * lx)):
-            xi, yi = x0 + dx_, y0 + dy_
-            ok = ((xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)).double()
-            wgt = aw[:, :, :, l] * cw * ok                                                # [B, Lq, M, P]
-            dw = (aw[:, :, :, l] * 2 * dcoord + 16 * EPS32 * wgt) * ok
-            idx = (start + yi.clamp(0, h - 1) * w + xi.clamp(0, w - 1)).long()
-            idx = idx.permute(0, 2, 1, 3).reshape(B, M, Lq * Pn, 1).expand(B, M, Lq * Pn, 32)
-            v = torch.gather(val, 2, idx).reshape(B, M, Lq, Pn, 32)
-            wq = wgt.permute(0, 2, 1, 3).unsqueeze(-1)                                    # [B, M, Lq, P, 1]
-            dwq = dw.permute(0, 2, 1, 3).unsqueeze(-1)
-            if round_weights:
-                wr = round16(wq)
-                up, dn = ulp16(wr), ulp16(wr * (1 - 2.0 ** -12))
-                dist = torch.minimum((wq - (wr + up / 2)).abs(), (wq - (wr - dn / 2)).abs())
-                extra += (((dist <= dwq) & (dwq > 0)).double() * ulp16(wq) * v.abs()).sum(3)
-                wq = wr
-            else:
-                extra += (dwq * v.abs()).sum(3)
-            out += (wq * v).sum(3)
-            sq += (wq * wq * v * v).sum(3)
-        start += h * w
-    back = lambda t: t.permute(0, 2, 1, 3).reshape(B, Lq, CC)
-    return back(out), back(gemm_slack(4 * L * Pn, sq) + extra)
+from tests.msda_reference import forward_with_slack as _msda_ref64          # noqa: E402  (this project's float64 forward, kept beside the backward)
 
 
 def test_msda_fwd_small():
