@@ -14,6 +14,11 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip.h")
 # EMRT_HIP_LIB: a differently built copy of the same library (developer experiments: tools/exp builds one with -DEMRT_8P_PROBES)
 LIB_PATH = os.environ.get("EMRT_HIP_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip.so")
 
+# The second library (include/emrt_hip_augment.h: vertical flip and colour distortion).  The ABI of emrt_hip.h is frozen, so its entry points
+# and its descriptor stay out of parse_header() / parse_structs() / struct() above and get a binding of their own: augment_lib(), augment_struct().
+AUG_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_augment.h")
+AUG_LIB_PATH = os.environ.get("EMRT_HIP_AUGMENT_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_augment.so")
+
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
 _CTYPES = {
@@ -257,3 +262,70 @@ def lib():
     if _LIB is None:
         _LIB = _Lib()
     return _LIB
+
+
+# ---- libemrt_hip_augment.so -------------------------------------------------------------------------------------------------------------------
+
+_AUG_STRUCTS = {}
+
+
+def augment_struct(name):
+    """The ctypes.Structure subclass of a descriptor struct of include/emrt_hip_augment.h, generated once (as struct() does for emrt_hip.h)."""
+    if not _AUG_STRUCTS:
+        for sname, members in parse_structs(AUG_HEADER).items():
+            fields = [(member_name(sname, m), _ctype_of(t) * n if n else _ctype_of(t)) for t, m, n in members]
+            _AUG_STRUCTS[sname] = type(sname, (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s of include/emrt_hip_augment.h" % sname})
+    if name not in _AUG_STRUCTS:
+        raise EmrtHipError("emrt_hip_augment.h declares no struct %s" % name)
+    return _AUG_STRUCTS[name]
+
+
+class _AugLib:
+    """libemrt_hip_augment.so bound from its header: call / query / last_error as _Lib, with the library's own error string.  No fallback: a
+    missing library or symbol raises."""
+
+    def __init__(self):
+        if not os.path.exists(AUG_LIB_PATH):
+            raise EmrtHipError(
+                "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(there is no CPU/PyTorch fallback for the device augmentation)" % AUG_LIB_PATH)
+        import torch  # noqa: F401      (torch first, for the reason given in _Lib.__init__)
+        self._dll = ctypes.CDLL(AUG_LIB_PATH)
+        self.protos = parse_header(AUG_HEADER)
+        for name, (ret, args) in self.protos.items():
+            try:
+                fn = getattr(self._dll, name)
+            except AttributeError:
+                raise EmrtHipError("libemrt_hip_augment.so does not export %s declared in emrt_hip_augment.h" % name)
+            fn.argtypes = [_ctype_of(t) for t, _ in args]
+            fn.restype = ctypes.c_char_p if ret == "const char*" else (ctypes.c_size_t if ret == "size_t" else ctypes.c_int)
+            setattr(self, "_raw_" + name, fn)
+        if self._raw_emrt_aug_version() != 1:
+            raise EmrtHipError("libemrt_hip_augment.so has version %d, this binding expects 1" % self._raw_emrt_aug_version())
+
+    def last_error(self):
+        return self._raw_emrt_aug_last_error().decode("utf-8", "replace")
+
+    def call(self, name, *args):
+        """Invoke an int-returning entry point; raise EmrtHipError on a non-zero return (EMRT_TRACE=1 as _Lib.call)."""
+        if _TRACE:
+            print("[emrt] %s%r" % (name, tuple(a.value if hasattr(a, "value") else a for a in args)), flush=True)
+        rc = getattr(self, "_raw_" + name)(*args)
+        if rc != 0:
+            raise EmrtHipError("%s failed (%d): %s" % (name, rc, self.last_error()))
+        if _TRACE:
+            import torch
+            torch.cuda.synchronize()
+
+    def query(self, name, *args):
+        return getattr(self, "_raw_" + name)(*args)
+
+
+_AUG_LIB = None
+
+
+def augment_lib():
+    global _AUG_LIB
+    if _AUG_LIB is None:
+        _AUG_LIB = _AugLib()
+    return _AUG_LIB

@@ -1,4 +1,5 @@
-"""Builds emrt_amd/csrc/libemrt_hip.so with hipcc for gfx950 (in-tree; the .so travels with gpurun snapshots).
+"""Builds emrt_amd/csrc/libemrt_hip.so and, beside it, emrt_amd/csrc/libemrt_hip_augment.so (csrc/augment_ext/*.hip: the entry points of
+include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) with hipcc for gfx950, in-tree.
 
 What is rebuilt is decided by CONTENT: every object and the library carry a `<file>.inputs` stamp with the sha256 of the sources, headers,
 compiler path and flags they were built from; "reused" therefore means "built from exactly these inputs", on whatever machine.
@@ -14,6 +15,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libemrt_hip.so")
 SOURCES = ["conv.hip", "norm.hip", "msda.hip", "attn.hip", "spatial.hip", "loss.hip", "optim.hip", "elementwise.hip", "gconv.hip", "augment.hip", "scene.hip"]
 HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip.h")      # the public C-ABI: csrc/common.hpp includes it, so it is an input of every object
+AUG_DIR = os.path.join(CSRC, "augment_ext")
+AUG_LIB = os.path.join(CSRC, "libemrt_hip_augment.so")
+AUG_SOURCES = ["augment_ext.hip"]
+AUG_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_augment.h")      # includes emrt_hip.h; the sources include csrc/augment_map.hpp
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
@@ -53,26 +58,34 @@ def _fresh(target, digest):
         return False
 
 
+def _headers():
+    """csrc/*.hpp and both public headers: inputs of every object of both libraries."""
+    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [HEADER, AUG_HEADER]
+
+
 def source_digest():
-    """Content hash of everything libemrt_hip.so is built from: csrc/*.hip, csrc/*.hpp, include/emrt_hip.h, the compiler path and the flags."""
-    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [HEADER]
-    return _digest([os.path.join(CSRC, s) for s in SOURCES] + hdrs, [_hipcc()] + FLAGS)
+    """Content hash of everything the two libraries are built from: csrc/*.hip, csrc/augment_ext/*.hip, csrc/*.hpp, include/*.h, the compiler
+    path and the flags."""
+    return _digest([os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(AUG_DIR, s) for s in AUG_SOURCES] + _headers(), [_hipcc()] + FLAGS)
 
 
 LAST_BUILD = {"mode": None, "digest": None, "compiled": []}      # what the last build() call did: "compiled" | "linked" | "reused"
 
 
 def build(force=False, verbose=True):
+    """Builds both libraries; -> the path of libemrt_hip.so (libemrt_hip_augment.so is AUG_LIB)."""
     hipcc = _hipcc()
-    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [HEADER]      # common.hpp (includes the public header), igemm8p.hpp (included by conv.hip)
-    objs, jobs = [], []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(CSRC, src.replace(".hip", ".o"))
-        objs.append(o)
-        d = _digest([s] + hdrs, [hipcc] + FLAGS)
-        if force or not _fresh(o, d):
-            jobs.append(([hipcc] + FLAGS + ["-c", s, "-o", o], o, d))
+    hdrs = _headers()
+    groups = [(LIB, CSRC, SOURCES), (AUG_LIB, AUG_DIR, AUG_SOURCES)]
+    objs, jobs = {LIB: [], AUG_LIB: []}, []
+    for lib, d, sources in groups:
+        for src in sources:
+            s = os.path.join(d, src)
+            o = os.path.join(d, src.replace(".hip", ".o"))
+            objs[lib].append(o)
+            dg = _digest([s] + hdrs, [hipcc] + FLAGS)
+            if force or not _fresh(o, dg):
+                jobs.append(([hipcc] + FLAGS + ["-c", s, "-o", o], o, dg, lib))
 
     def run(cmd):
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
@@ -80,7 +93,7 @@ def build(force=False, verbose=True):
             raise RuntimeError("hipcc failed: %s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
 
     def compile_one(job):
-        cmd, o, d = job
+        cmd, o, d, _ = job
         if os.path.exists(_stamp(o)):
             os.remove(_stamp(o))
         run(cmd)
@@ -96,17 +109,18 @@ def build(force=False, verbose=True):
                 if verbose:
                     print("[emrt_amd.build] compiled", os.path.basename(done), flush=True)
     total = source_digest()
-    if force or jobs or not _fresh(LIB, total):
-        if os.path.exists(_stamp(LIB)):
-            os.remove(_stamp(LIB))
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB])
-        with open(_stamp(LIB), "w") as f:
-            f.write(total + "\n")
-        LAST_BUILD["mode"] = "compiled" if jobs else "linked"
-        if verbose:
-            print("[emrt_amd.build] linked", LIB, flush=True)
-    else:
-        LAST_BUILD["mode"] = "reused"
+    linked = False
+    for lib, _, _ in groups:
+        if force or any(j[3] == lib for j in jobs) or not _fresh(lib, total):
+            if os.path.exists(_stamp(lib)):
+                os.remove(_stamp(lib))
+            run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs[lib] + ["-o", lib])
+            with open(_stamp(lib), "w") as f:
+                f.write(total + "\n")
+            linked = True
+            if verbose:
+                print("[emrt_amd.build] linked", lib, flush=True)
+    LAST_BUILD["mode"] = ("compiled" if jobs else "linked") if linked else "reused"
     LAST_BUILD["digest"] = total
     return LIB
 

@@ -95,7 +95,12 @@ _DEFAULTS = {
     "BASE": [""],
     "DATA": {"BATCH_SIZE": 4, "BATCH_SIZE_VAL": 1, "DATASET": "PascalContext",
              "DATA_PATH": "/home/ssd3/wutianyi/datasets/pascal_context", "CROP_SIZE": (480, 480), "NUM_CLASSES": 60,
-             "NUM_WORKERS": 0},
+             "NUM_WORKERS": 0,
+             # not in the reference's tree: RandomVerticalFlip and RandomDistort (hue off) after the Potsdam / Vaihingen chain's horizontal flip
+             # (transforms.get_transforms); the ranges are the reference's ADE20K values.  The defaults leave every chain as it was.
+             "AUGMENT": {"VFLIP_PROB": 0.0,
+                         "DISTORT": {"ENABLE": False, "BRIGHTNESS_RANGE": 0.4, "CONTRAST_RANGE": 0.4, "SATURATION_RANGE": 0.4,
+                                     "BRIGHTNESS_PROB": 0.5, "CONTRAST_PROB": 0.5, "SATURATION_PROB": 0.5}}},
     "MODEL": {
         "NAME": "SETR_MLA",
         "ENCODER": {"TYPE": "ViT_MLA", "OUT_INDICES": [5, 11, 17, 23], "MULTI_GRID": False, "MULTI_DILATION": None},

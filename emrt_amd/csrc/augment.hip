@@ -4,15 +4,13 @@
 // emrt_scene_sample (second half of the file): the decisions are drawn on the device and the sources are windows of whole scenes.  One map serves both.
 //
 // One thread = one output pixel of one sample: the 3 normalised fp32 channels of out[b][c][oy][ox] and the int64 label.  The arithmetic is
-// the numpy chain's, operation for operation, so the result is bit-identical to the CPU transforms:
-//   coordinates (float64): sy = max((y + 0.5) * (H / h) - 0.5, 0); y0 = min((long)sy, H - 1); y1 = min(y0 + 1, H - 1); wy = (float)(sy - y0)
-//   blend (float32):       top = a00 * (1 - wx) + a01 * wx; bot = a10 * (1 - wx) + a11 * wx; v = top * (1 - wy) + bot * wy
-//   label (nearest):       ly = min((long)(y * (H / h)), H - 1)
+// the numpy chain's, operation for operation, so the result is bit-identical to the CPU transforms: the geometry (coordinates, bilinear blend,
+// nearest label, padding) is augment_map.hpp, the text libemrt_hip_augment.so compiles too, and then
 //   normalise (float64):   (float)(((double)v - mean) * stdinv)
-// A size-equal resize needs no shortcut: H / h == 1 gives sy == y, wy == 0 and v == a00 exactly.
 // FMA contraction is off for the whole file: a fused multiply-add rounds once where numpy rounds twice.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "augment_map.hpp"
 
 namespace emrt {
 namespace {
@@ -46,49 +44,14 @@ struct AugArgs {
   AugSample s[AUG_CHUNK];
 };
 
-// One sample's source and decisions as the per-pixel map reads them: img / lab point at the sample's first pixel, `pitch` is the distance
-// between two rows in PIXELS (the sample's own W for a packed tile, the scene's W for a window of a scene).
-struct AugView {
-  const unsigned char* img;
-  const unsigned char* lab;
-  long long pitch;
-  double ry, rx;
-  int H, W, h, w, off_y, off_x, flip;
-};
-
-// Output pixel p of sample b: the map described at the top of this file.  Both kernels below are this function under two ways of finding `s`.
+// Output pixel p of sample b: the shared map (augment_map.hpp), then the normalisation and the stores.  Both kernels below are this function
+// under two ways of finding `s`.
 __device__ __forceinline__ void augment_pixel(const AugCommon& a, const AugView& s, long long b, int p) {
   const int npix = a.OH * a.OW;
   const int oy = p / a.OW, ox = p - oy * a.OW;
-  const int y = oy + s.off_y;                                  // row / column in the padded, resized image
-  const int x = (s.flip ? a.OW - 1 - ox : ox) + s.off_x;       // the flip follows the crop
   float v[3];
-  int lab = a.label_pad;
-  if (y < s.h && x < s.w) {
-    double sy = ((double)y + 0.5) * s.ry - 0.5;
-    double sx = ((double)x + 0.5) * s.rx - 0.5;
-    sy = sy < 0.0 ? 0.0 : sy;
-    sx = sx < 0.0 ? 0.0 : sx;
-    const long long y0 = min((long long)sy, (long long)s.H - 1), y1 = min(y0 + 1, (long long)s.H - 1);
-    const long long x0 = min((long long)sx, (long long)s.W - 1), x1 = min(x0 + 1, (long long)s.W - 1);
-    const float wy = (float)(sy - (double)y0), wx = (float)(sx - (double)x0);
-    const unsigned char* r0 = s.img + y0 * s.pitch * 3;
-    const unsigned char* r1 = s.img + y1 * s.pitch * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float top = (float)r0[x0 * 3 + c] * (1.0f - wx) + (float)r0[x1 * 3 + c] * wx;
-      const float bot = (float)r1[x0 * 3 + c] * (1.0f - wx) + (float)r1[x1 * 3 + c] * wx;
-      v[c] = top * (1.0f - wy) + bot * wy;
-    }
-    if (a.labels) {
-      const long long ly = min((long long)((double)y * s.ry), (long long)s.H - 1);
-      const long long lx = min((long long)((double)x * s.rx), (long long)s.W - 1);
-      lab = s.lab[ly * s.pitch + lx];
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = a.pad[c];
-  }
+  int lab;
+  augment_map(s, a.OH, a.OW, a.pad, a.label_pad, a.labels != nullptr, oy, ox, v, lab);
   float* o = a.out + b * a.out_bs + p;
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[(long long)c * npix] = (float)(((double)v[c] - a.mean[c]) * a.stdinv[c]);

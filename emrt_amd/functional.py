@@ -1922,3 +1922,33 @@ def augment_tiles(src, samples, out_size, mean, stdinv, img_pad, label_pad, labe
               (ctypes.c_double * 3)(*[float(v) for v in stdinv]), (ctypes.c_float * 3)(*[float(v) for v in img_pad]), int(label_pad), lut,
               P(out), 3 * OH * OW, P(lab), c.stream)
     return out, lab
+
+
+_AUG_OP_CODES = {"brightness": 0, "contrast": 1, "saturation": 2}      # EMRT_AUG_OP_* of include/emrt_hip_augment.h
+
+
+def aug_tiles(src, samples, out_size, mean, stdinv, img_pad, label_pad, label_lut=None, labels=True, distort=True):
+    """augment_tiles for a chain with RandomVerticalFlip / RandomDistort, on the second library (csrc/augment_ext: emrt_aug_tiles): per chunk of
+    16 samples a statistics launch (only if one of them applies contrast) and the apply launch.  samples: (img_off, lab_off, AugSamplePlan);
+    distort: the chain holds RandomDistort (pixels are truncated to uint8 even where no op was drawn).  Otherwise as augment_tiles."""
+    c = ctx()
+    A = _lib.augment_lib()
+    Desc = _lib.augment_struct("EmrtAugOpsDesc")
+    OH, OW = out_size
+    B = len(samples)
+    assert src.dtype == torch.uint8 and src.dim() == 1 and B > 0
+    descs = (Desc * B)()
+    for d, (io, lo, p) in zip(descs, samples):
+        d.img_off, d.lab_off, d.H, d.W, d.h, d.w, d.off_y, d.off_x = io, lo, p.H, p.W, p.h, p.w, p.off_y, p.off_x
+        d.flip, d.n_ops = int(bool(p.flip)) | (int(bool(p.vflip)) << 1), len(p.ops)
+        for k in range(3):
+            d.op[k], d.factor[k] = (_AUG_OP_CODES[p.ops[k][0]], p.ops[k][1]) if k < len(p.ops) else (0, 1.0)
+    out = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=src.device)
+    lab = torch.empty((B, OH, OW), dtype=torch.int64, device=src.device) if labels else None
+    nws = A.query("emrt_aug_workspace_bytes", B)
+    ws = torch.empty(nws // 8, dtype=torch.int64, device=src.device)
+    lut = None if label_lut is None else (ctypes.c_ubyte * 256)(*[int(v) for v in label_lut])
+    A.call("emrt_aug_tiles", P(src), src.numel(), descs, B, OH, OW, int(bool(distort)), (ctypes.c_double * 3)(*[float(v) for v in mean]),
+           (ctypes.c_double * 3)(*[float(v) for v in stdinv]), (ctypes.c_float * 3)(*[float(v) for v in img_pad]), int(label_pad), lut,
+           P(out), 3 * OH * OW, P(lab), P(ws), nws, c.stream)
+    return out, lab

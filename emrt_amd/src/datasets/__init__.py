@@ -218,8 +218,8 @@ class DeviceTileLoader(TileLoader):
     A worker, while it holds its batch's turn, reads each tile's size from the file header (no decode) and draws the sample's random
     decisions (DevicePlan.plan), so decisions are drawn in batch and sample order whatever the number of workers; it then decodes the tiles
     to uint8 with read_image's / read_label's PIL calls outside the turn and packs them into one pinned host buffer.  The consumer thread
-    issues one host->device copy of that buffer and one emrt_augment_tiles launch (resize, pad, crop, flip, normalise), both on the
-    training stream, into outputs from torch's caching allocator on that stream.  Never inside a graph capture: train.py calls it between
+    issues one host->device copy of that buffer and one emrt_augment_tiles launch (resize, pad, crop, flip, normalise; emrt_aug_tiles of the
+    second library when the chain holds RandomVerticalFlip / RandomDistort), both on the training stream, into outputs from torch's caching allocator on that stream.  Never inside a graph capture: train.py calls it between
     steps."""
 
     def __init__(self, dataset, sampler, device, workers=4, prefetch=4):
@@ -266,6 +266,8 @@ class DeviceTileLoader(TileLoader):
         dev = torch.device(self.device)
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
             src = buf.to(dev, non_blocking=True)
+            if dp.extended:      # RandomVerticalFlip / RandomDistort in the chain: the second library's entry point
+                return F.aug_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut, distort=dp.distort is not None)
             return F.augment_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut)
 
 
@@ -276,6 +278,7 @@ _SceneEntry = _lib.struct("EmrtSceneEntry")      # generated from include/emrt_h
 
 MAX_SCALES = 16           # csrc/augment.hip SCENE_MAX_SCALES: scale entries of one emrt_scene_draw launch
 DRAW_COLS = 10            # a row of the draw table: scene, y0, x0, scale_index, h, w, off_y, off_x, flip, 0
+AUG_DRAW_COLS = 18        # ... of emrt_aug_scene_draw (include/emrt_hip_augment.h: EMRT_AUG_DRAW_COLS), an extended chain's table
 
 
 def _free_device_bytes(device):
@@ -398,7 +401,9 @@ class SceneSampler:
     the current stream -- emrt_scene_draw (every random decision of the batch, from the device step counter) and emrt_scene_sample (the transform
     chain on the drawn windows) -- and touches nothing else, so it can run inside a captured training step.
 
-    `transforms` is one of the two chains DevicePlan accepts.  Potsdam / Vaihingen: the source tile is the crop size, the scale table is
+    `transforms` is one of the chains DevicePlan accepts.  With RandomVerticalFlip / RandomDistort in it (DATA.AUGMENT) the two calls are the second
+    library's emrt_aug_scene_draw and emrt_aug_scene_sample (draw, memset of the luminance sums, statistics, apply; include/emrt_hip_augment.h), just as
+    capturable; the other chains never touch that library.  Potsdam / Vaihingen: the source tile is the crop size, the scale table is
     ResizeStepScaling.resized(factor, th, tw) over its np.linspace factors (Python's round stays on the host).  [Normalize] alone (LoveDA): pass
     `tile` = (h, w); one scale entry of the tile's own size, no flip.  The bank's label_shift goes down as label_lut.
     The draws are a pure function of (seed, step counter, rank, sample): restoring the step counter continues the same data stream."""
@@ -438,7 +443,7 @@ class SceneSampler:
         self.key = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.total_origins = sum(bank.origins(*self.tile))
         self.lut = label_lut(bank.label_shift)
-        self.draws = torch.zeros((self.batch_size, DRAW_COLS), dtype=torch.int32, device=bank.device)
+        self.draws = torch.zeros((self.batch_size, AUG_DRAW_COLS if dp.extended else DRAW_COLS), dtype=torch.int32, device=bank.device)
         self._tables = bank.tables(*self.tile)       # uploaded here: fill() may run under stream capture, where no host -> device copy can
         # the HOST arguments of the two launches, built once: constants of the run, safe to bake into a captured graph
         self._scale_hw = (ctypes.c_int * (2 * len(self.scales)))(*[int(v) for hw in self.scales for v in hw])
@@ -446,6 +451,16 @@ class SceneSampler:
         self._stdinv = (ctypes.c_double * 3)(*[float(v) for v in dp.stdinv])
         self._pad = (ctypes.c_float * 3)(*[float(v) for v in dp.img_pad])
         self._lut = None if self.lut is None else (ctypes.c_ubyte * 256)(*[int(v) for v in self.lut])
+        if dp.extended:          # the second library's draws and launches (include/emrt_hip_augment.h); its workspace is allocated here, once
+            self.vflip_prob = float(dp.vflip.prob) if dp.vflip is not None else 0.0
+            if not 0.0 <= self.vflip_prob <= 1.0:
+                raise ValueError("scenes: vertical flip probability %r is outside [0, 1]" % self.vflip_prob)
+            names = ("brightness", "contrast", "saturation")
+            d = dp.distort
+            self._ranges = (ctypes.c_double * 3)(*[float(getattr(d, n + "_range")) if d is not None else 0.0 for n in names])
+            self._probs = (ctypes.c_double * 3)(*[float(getattr(d, n + "_prob")) if d is not None else 0.0 for n in names])
+            self._ws_bytes = 8 * self.batch_size          # = emrt_aug_workspace_bytes(B); the entry point checks it
+            self._ws = torch.zeros(self.batch_size, dtype=torch.int64, device=bank.device)
 
     @property
     def batch_shape(self):
@@ -465,6 +480,19 @@ class SceneSampler:
         scenes_dev, cum_dev, scenes_host, cum_host = self._tables
         n = len(self.bank)
         key = self.key - (1 << 64) if self.key >= (1 << 63) else self.key         # the same 64 bits as a C long long
+        if self.plan.extended:
+            A = _lib.augment_lib()
+            distort = int(self.plan.distort is not None)
+            A.call("emrt_aug_scene_draw", Fn.P(c.step_counter), Fn.P(scenes_dev), Fn.P(cum_dev), ctypes.cast(scenes_host, ctypes.c_void_p),
+                   ctypes.cast(cum_host, ctypes.c_void_p), n, self.bank.nbytes, key, self.rank, B, th, tw, OH, OW, self.flip_prob, self.vflip_prob,
+                   distort, ctypes.cast(self._ranges, ctypes.c_void_p), ctypes.cast(self._probs, ctypes.c_void_p),
+                   ctypes.cast(self._scale_hw, ctypes.c_void_p), len(self.scales), Fn.P(self.draws), c.stream)
+            A.call("emrt_aug_scene_sample", Fn.P(self.bank.buffer), self.bank.nbytes, Fn.P(scenes_dev), ctypes.cast(scenes_host, ctypes.c_void_p), n,
+                   Fn.P(self.draws), B, th, tw, OH, OW, distort, ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._stdinv, ctypes.c_void_p),
+                   ctypes.cast(self._pad, ctypes.c_void_p), int(self.plan.label_pad),
+                   None if self._lut is None else ctypes.cast(self._lut, ctypes.c_void_p), Fn.P(images), 3 * OH * OW, Fn.P(labels),
+                   Fn.P(self._ws), self._ws_bytes, c.stream)
+            return
         L = Fn._L()
         L.call("emrt_scene_draw", Fn.P(c.step_counter), Fn.P(scenes_dev), Fn.P(cum_dev), ctypes.cast(scenes_host, ctypes.c_void_p),
                ctypes.cast(cum_host, ctypes.c_void_p), n, self.bank.nbytes, key, self.rank, B, th, tw, OH, OW, self.flip_prob,

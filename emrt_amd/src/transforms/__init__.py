@@ -1,6 +1,6 @@
 """Image / label transforms of the EMRT data pipeline, cv2-free (reference: src/transforms/transforms.py:24-88 Compose,
-:91-110 RandomHorizontalFlip, :136-206 Resize, :209-270 ResizeStepScaling, :273-318 Normalize, :391-478
-RandomPaddingCrop; src/transforms/__init__.py:4-57 get_transforms).
+:91-110 RandomHorizontalFlip, :113-132 RandomVerticalFlip, :136-206 Resize, :209-270 ResizeStepScaling, :273-318 Normalize, :391-478
+RandomPaddingCrop, :588-681 RandomDistort; src/transforms/__init__.py:4-57 get_transforms).
 
 Arrays are HWC float32 RGB (the reference reads BGR with cv2 and converts to RGB; here PIL reads RGB directly), labels
 HW uint8.  Bilinear / nearest resizing are restated in numpy with cv2's conventions (INTER_LINEAR: half-pixel centres,
@@ -11,7 +11,7 @@ import random
 from collections import namedtuple
 
 import numpy as np
-from PIL import Image
+from PIL import Image, ImageEnhance
 
 
 def read_image(path):
@@ -89,6 +89,71 @@ class RandomHorizontalFlip:
             img = img[:, ::-1, :]
             if label is not None:
                 label = label[:, ::-1]
+        return (img,) if label is None else (img, label)
+
+
+class RandomVerticalFlip:
+    """transforms.py:113-132: rows mirrored with probability `prob`, image and label alike."""
+
+    def __init__(self, prob=0.1):
+        self.prob = prob
+
+    def draw(self):
+        """The flip decision: one Python `random.random()` (the CPU chain and DevicePlan.plan both draw it here)."""
+        return random.random() < self.prob
+
+    def __call__(self, img, label=None):
+        if self.draw():
+            img = img[::-1, :, :]
+            if label is not None:
+                label = label[::-1, :]
+        return (img,) if label is None else (img, label)
+
+
+class RandomDistort:
+    """transforms.py:588-681 with functional.py:76-96: brightness, contrast and saturation through PIL's ImageEnhance on the image truncated to
+    uint8, in a shuffled order, each with its own probability and a factor drawn from [1 - range, 1 + range].  The label is untouched.
+
+    Hue is refused: functional.hue adds a float to a uint8 HSV plane, a cast that is undefined for negative values (numpy warns), so there is
+    nothing exact to reproduce; the HSV round trip alone changes pixels, so hue_prob > 0 is refused whatever hue_range is.  Pass
+    hue_prob=0.  Hue keeps its place in the shuffle and its probability draw is still consumed, so a seeded run leaves `random` / `np.random`
+    where the reference leaves them with hue_prob=0."""
+
+    OPS = ("brightness", "contrast", "saturation", "hue")
+    _ENHANCE = {"brightness": ImageEnhance.Brightness, "contrast": ImageEnhance.Contrast, "saturation": ImageEnhance.Color}
+
+    def __init__(self, brightness_range=0.5, brightness_prob=0.5, contrast_range=0.5, contrast_prob=0.5, saturation_range=0.5,
+                 saturation_prob=0.5, hue_range=18, hue_prob=0.5):
+        if hue_prob > 0:
+            raise ValueError("RandomDistort: hue is not supported (hue_prob=%r, hue_range=%r): the reference's hue shift casts a negative float "
+                             "to uint8, which has no defined result; pass hue_prob=0" % (hue_prob, hue_range))
+        self.brightness_range, self.brightness_prob = brightness_range, brightness_prob
+        self.contrast_range, self.contrast_prob = contrast_range, contrast_prob
+        self.saturation_range, self.saturation_prob = saturation_range, saturation_prob
+        self.hue_range, self.hue_prob = hue_range, hue_prob
+
+    def draw(self):
+        """The decisions, with the reference's draws: random.shuffle of the four ops, then per op in shuffled order np.random.uniform(0, 1) < prob
+        and, only if that passes, np.random.uniform(lower, upper).  -> [(op name, factor)] of the applied ops, in application order."""
+        ops = list(self.OPS)
+        random.shuffle(ops)
+        applied = []
+        for name in ops:
+            if np.random.uniform(0, 1) < getattr(self, name + "_prob"):
+                r = getattr(self, name + "_range")
+                applied.append((name, np.random.uniform(1 - r, 1 + r)))       # (hue never gets here: its probability is 0)
+        return applied
+
+    @classmethod
+    def apply(cls, img, ops):
+        """img HWC float -> uint8 (truncation) -> PIL -> the ops of draw() in order -> float32."""
+        im = Image.fromarray(img.astype("uint8"))
+        for name, factor in ops:
+            im = cls._ENHANCE[name](im).enhance(factor)
+        return np.asarray(im).astype("float32")
+
+    def __call__(self, img, label=None):
+        img = self.apply(img, self.draw())
         return (img,) if label is None else (img, label)
 
 
@@ -212,18 +277,25 @@ _MEAN, _STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
 # One sample's decisions for the device kernel (emrt_augment_tiles): source H x W, resized h x w, crop offsets into the resized image padded
 # bottom / right to the crop size, horizontal flip after the crop.
 SamplePlan = namedtuple("SamplePlan", "H W h w off_y off_x flip")
+# ... of a chain with RandomVerticalFlip / RandomDistort (emrt_aug_tiles of the second library): SamplePlan's fields, the vertical flip, and the
+# applied colour ops [(op name, factor)] in application order.
+AugSamplePlan = namedtuple("AugSamplePlan", "H W h w off_y off_x flip vflip ops")
 
 
 class DevicePlan:
     """A training transform list compiled for the fused device kernel (emrt_amd.functional.augment_tiles).  Two chains are supported, the
     ones get_transforms ships: [ResizeStepScaling, RandomPaddingCrop, RandomHorizontalFlip, Normalize] (Potsdam, Vaihingen) and
     [Normalize] (LoveDA: output size = source size).  Any other op or order raises, naming the op: nothing is skipped or left to the CPU.
+    The first chain may carry RandomVerticalFlip and / or RandomDistort, in that order, between RandomHorizontalFlip and Normalize
+    (DATA.AUGMENT): `extended` is then True, plan() returns an AugSamplePlan and the loaders call the second library (functional.aug_tiles).
 
     plan(H, W) draws one sample's random decisions with the draw helpers the CPU transforms themselves call (ResizeStepScaling.draw,
-    RandomPaddingCrop.draw, RandomHorizontalFlip.draw), in the chain's order and under its conditions, so a seeded run makes the same
-    decisions on either path and leaves np.random / random in the same state."""
+    RandomPaddingCrop.draw, RandomHorizontalFlip.draw, RandomVerticalFlip.draw, RandomDistort.draw), in the chain's order and under its
+    conditions, so a seeded run makes the same decisions on either path and leaves np.random / random in the same state."""
 
-    CHAINS = ((ResizeStepScaling, RandomPaddingCrop, RandomHorizontalFlip, Normalize), (Normalize,))
+    _HEAD = (ResizeStepScaling, RandomPaddingCrop, RandomHorizontalFlip)
+    CHAINS = (_HEAD + (Normalize,), (Normalize,), _HEAD + (RandomVerticalFlip, Normalize), _HEAD + (RandomDistort, Normalize),
+              _HEAD + (RandomVerticalFlip, RandomDistort, Normalize))
 
     def __init__(self, transforms):
         transforms = list(transforms)
@@ -232,7 +304,8 @@ class DevicePlan:
             best = max(self.CHAINS, key=lambda c: sum(1 for a, b in zip(c, kinds) if a is b))
             i = next((i for i, (a, b) in enumerate(zip(best, kinds)) if a is not b), min(len(best), len(kinds)))
             what = ("%s at position %d" % (type(transforms[i]).__name__, i)) if i < len(transforms) else "the chain ends early"
-            raise ValueError("device transforms: %s is not supported; the device path runs [%s] or [%s] exactly, got [%s]" % (
+            raise ValueError("device transforms: %s is not supported; the device path runs [%s] or [%s] exactly, got [%s] (RandomVerticalFlip and "
+                             "RandomDistort may follow RandomHorizontalFlip, in that order)" % (
                 what, ", ".join(c.__name__ for c in self.CHAINS[0]), ", ".join(c.__name__ for c in self.CHAINS[1]),
                 ", ".join(type(t).__name__ for t in transforms)))
         norm = transforms[-1]
@@ -240,10 +313,15 @@ class DevicePlan:
             raise ValueError("device transforms: Normalize needs 3 channels, got mean %r std %r" % (norm.mean, norm.std))
         self.mean = np.asarray(norm.mean, dtype=np.float64)
         self.stdinv = 1.0 / np.asarray(norm.std, dtype=np.float64)          # as Normalize computes it
-        self.scaling = self.crop = self.flip = None
+        self.scaling = self.crop = self.flip = self.vflip = self.distort = None
         self.img_pad, self.label_pad = np.zeros(3, np.float32), 255
-        if len(transforms) == 4:
+        if len(transforms) >= 4:
             self.scaling, self.crop, self.flip = transforms[:3]
+            for t in transforms[3:-1]:
+                if isinstance(t, RandomVerticalFlip):
+                    self.vflip = t
+                else:
+                    self.distort = t
             chh, cw = self.crop.size()
             if chh <= 0 or cw <= 0:
                 raise ValueError("device transforms: RandomPaddingCrop size must be positive, got %r" % (self.crop.crop_size,))
@@ -254,31 +332,71 @@ class DevicePlan:
             self.label_pad = int(self.crop.label_padding_value)
             if not 0 <= self.label_pad <= 255:
                 raise ValueError("device transforms: label_padding_value must be 0..255, got %r" % (self.crop.label_padding_value,))
+            if self.distort is not None:
+                if not all(0 <= float(v) < 256 for v in pad):
+                    raise ValueError("device transforms: RandomDistort truncates to uint8; img_padding_value must lie in [0, 256), got %r" % (
+                        self.crop.img_padding_value,))
+                for name in RandomDistort.OPS[:3]:
+                    r, p = getattr(self.distort, name + "_range"), getattr(self.distort, name + "_prob")
+                    if not (0 <= r <= 1 and 0 <= p <= 1):
+                        raise ValueError("device transforms: RandomDistort %s_range and %s_prob must lie in [0, 1], got %r and %r" % (name, name, r, p))
+
+    @property
+    def extended(self):
+        """The chain holds RandomVerticalFlip or RandomDistort: it runs on the second library's entry points."""
+        return self.vflip is not None or self.distort is not None
 
     def out_size(self, H, W):
         """-> (OH, OW) of a sample whose source is H x W."""
         return (H, W) if self.crop is None else self.crop.size()
 
     def plan(self, H, W):
-        """Draw one H x W sample's decisions -> SamplePlan."""
+        """Draw one H x W sample's decisions -> SamplePlan (AugSamplePlan for an extended chain)."""
         if self.scaling is None:
             return SamplePlan(H, W, H, W, 0, 0, 0)
         h, w = ResizeStepScaling.resized(self.scaling.draw(), H, W)
         off = self.crop.draw(h, w) or (0, 0)
         flip = self.flip.draw()
-        return SamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip))
+        if not self.extended:
+            return SamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip))
+        vflip = self.vflip.draw() if self.vflip is not None else False
+        ops = self.distort.draw() if self.distort is not None else []
+        return AugSamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip), int(vflip), tuple((n, float(f)) for n, f in ops))
+
+
+def _augment(config, name, chain):
+    """DATA.AUGMENT on a dataset's chain: RandomVerticalFlip and RandomDistort (hue off) go after the flip and before Normalize, the order of
+    the reference's ADE20K chain.  A chain without RandomHorizontalFlip (LoveDA's) has no place for them: the key is refused by name."""
+    aug = config.DATA.AUGMENT
+    wanted = [k for k, on in (("DATA.AUGMENT.VFLIP_PROB", aug.VFLIP_PROB > 0), ("DATA.AUGMENT.DISTORT.ENABLE", bool(aug.DISTORT.ENABLE))) if on]
+    if not wanted:
+        return chain
+    at = next((i for i, t in enumerate(chain) if isinstance(t, RandomHorizontalFlip)), None)
+    if at is None:
+        raise ValueError("%s is set, but the %s chain is [%s]: the extra augmentations follow RandomHorizontalFlip, which it does not have" % (
+            wanted[0], name, ", ".join(type(t).__name__ for t in chain)))
+    extra = []
+    if aug.VFLIP_PROB > 0:
+        extra.append(RandomVerticalFlip(prob=aug.VFLIP_PROB))
+    if aug.DISTORT.ENABLE:
+        d = aug.DISTORT
+        extra.append(RandomDistort(brightness_range=d.BRIGHTNESS_RANGE, brightness_prob=d.BRIGHTNESS_PROB, contrast_range=d.CONTRAST_RANGE,
+                                   contrast_prob=d.CONTRAST_PROB, saturation_range=d.SATURATION_RANGE, saturation_prob=d.SATURATION_PROB,
+                                   hue_prob=0))
+    return chain[:at + 1] + extra + chain[at + 1:]
 
 
 def get_transforms(config):
     """Training transforms per dataset (src/transforms/__init__.py:4-57; only the datasets the EMRT yamls use)."""
     name = config.DATA.DATASET
     if name in ("Potsdam", "Vaihingen"):
-        return [ResizeStepScaling(0.5, 2.0, 0.25),
-                RandomPaddingCrop(crop_size=tuple(config.DATA.CROP_SIZE), img_padding_value=(0, 0, 0), label_padding_value=255),
-                RandomHorizontalFlip(prob=0.5),
-                Normalize(mean=_MEAN, std=_STD)]
+        return _augment(config, name, [
+            ResizeStepScaling(0.5, 2.0, 0.25),
+            RandomPaddingCrop(crop_size=tuple(config.DATA.CROP_SIZE), img_padding_value=(0, 0, 0), label_padding_value=255),
+            RandomHorizontalFlip(prob=0.5),
+            Normalize(mean=_MEAN, std=_STD)])
     if name == "LoveDA":
-        return [Normalize(mean=_MEAN, std=_STD)]
+        return _augment(config, name, [Normalize(mean=_MEAN, std=_STD)])
     raise NotImplementedError("{} dataset is not supported".format(name))
 
 
