@@ -19,6 +19,10 @@ LIB_PATH = os.environ.get("EMRT_HIP_LIB") or os.path.join(_HERE, "csrc", "libemr
 AUG_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_augment.h")
 AUG_LIB_PATH = os.environ.get("EMRT_HIP_AUGMENT_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_augment.so")
 
+# The third library (include/emrt_hip_sampler.h: the label index and the class-aware redraw of the scene sampler), for the same reason: sampler_lib().
+SMP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_sampler.h")
+SMP_LIB_PATH = os.environ.get("EMRT_HIP_SAMPLER_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_sampler.so")
+
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
 _CTYPES = {
@@ -280,31 +284,34 @@ def augment_struct(name):
     return _AUG_STRUCTS[name]
 
 
-class _AugLib:
-    """libemrt_hip_augment.so bound from its header: call / query / last_error as _Lib, with the library's own error string.  No fallback: a
-    missing library or symbol raises."""
+class _ExtLib:
+    """A library beside libemrt_hip.so (augment_lib(), sampler_lib()), bound from its own header: call / query / last_error as _Lib, with the
+    library's own `<prefix>_last_error` string and its `<prefix>_version` checked to be 1.  No fallback: a missing library or symbol raises."""
 
-    def __init__(self):
-        if not os.path.exists(AUG_LIB_PATH):
+    def __init__(self, path, header, prefix, what):
+        so, h = os.path.basename(path), os.path.basename(header)
+        if not os.path.exists(path):
             raise EmrtHipError(
                 "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(there is no CPU/PyTorch fallback for the device augmentation)" % AUG_LIB_PATH)
+                "(there is no CPU/PyTorch fallback for %s)" % (path, what))
         import torch  # noqa: F401      (torch first, for the reason given in _Lib.__init__)
-        self._dll = ctypes.CDLL(AUG_LIB_PATH)
-        self.protos = parse_header(AUG_HEADER)
+        self._dll = ctypes.CDLL(path)
+        self.protos = parse_header(header)
         for name, (ret, args) in self.protos.items():
             try:
                 fn = getattr(self._dll, name)
             except AttributeError:
-                raise EmrtHipError("libemrt_hip_augment.so does not export %s declared in emrt_hip_augment.h" % name)
+                raise EmrtHipError("%s does not export %s declared in %s" % (so, name, h))
             fn.argtypes = [_ctype_of(t) for t, _ in args]
             fn.restype = ctypes.c_char_p if ret == "const char*" else (ctypes.c_size_t if ret == "size_t" else ctypes.c_int)
             setattr(self, "_raw_" + name, fn)
-        if self._raw_emrt_aug_version() != 1:
-            raise EmrtHipError("libemrt_hip_augment.so has version %d, this binding expects 1" % self._raw_emrt_aug_version())
+        self._last_error = getattr(self, "_raw_%s_last_error" % prefix)
+        version = getattr(self, "_raw_%s_version" % prefix)()
+        if version != 1:
+            raise EmrtHipError("%s has version %d, this binding expects 1" % (so, version))
 
     def last_error(self):
-        return self._raw_emrt_aug_last_error().decode("utf-8", "replace")
+        return self._last_error().decode("utf-8", "replace")
 
     def call(self, name, *args):
         """Invoke an int-returning entry point; raise EmrtHipError on a non-zero return (EMRT_TRACE=1 as _Lib.call)."""
@@ -327,5 +334,17 @@ _AUG_LIB = None
 def augment_lib():
     global _AUG_LIB
     if _AUG_LIB is None:
-        _AUG_LIB = _AugLib()
+        _AUG_LIB = _ExtLib(AUG_LIB_PATH, AUG_HEADER, "emrt_aug", "the device augmentation")
     return _AUG_LIB
+
+
+# ---- libemrt_hip_sampler.so (include/emrt_hip_sampler.h: class-aware tile origins; loaded only when DATA.SCENE_SAMPLING.MODE is "class") -------
+
+_SMP_LIB = None
+
+
+def sampler_lib():
+    global _SMP_LIB
+    if _SMP_LIB is None:
+        _SMP_LIB = _ExtLib(SMP_LIB_PATH, SMP_HEADER, "emrt_smp", "the class-aware scene sampler")
+    return _SMP_LIB

@@ -1,5 +1,6 @@
 """Builds emrt_amd/csrc/libemrt_hip.so and, beside it, emrt_amd/csrc/libemrt_hip_augment.so (csrc/augment_ext/*.hip: the entry points of
-include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) with hipcc for gfx950, in-tree.
+include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) and emrt_amd/csrc/libemrt_hip_sampler.so
+(csrc/sampler_ext/*.hip: include/emrt_hip_sampler.h, for the same reason) with hipcc for gfx950, in-tree.  GROUPS is the table of the three.
 
 What is rebuilt is decided by CONTENT: every object and the library carry a `<file>.inputs` stamp with the sha256 of the sources, headers,
 compiler path and flags they were built from; "reused" therefore means "built from exactly these inputs", on whatever machine.
@@ -19,6 +20,12 @@ AUG_DIR = os.path.join(CSRC, "augment_ext")
 AUG_LIB = os.path.join(CSRC, "libemrt_hip_augment.so")
 AUG_SOURCES = ["augment_ext.hip"]
 AUG_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_augment.h")      # includes emrt_hip.h; the sources include csrc/augment_map.hpp
+SMP_DIR = os.path.join(CSRC, "sampler_ext")
+SMP_LIB = os.path.join(CSRC, "libemrt_hip_sampler.so")
+SMP_SOURCES = ["sampler_ext.hip"]
+SMP_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_sampler.h")      # includes emrt_hip.h; the sources include csrc/philox.hpp
+# one row per library: (library, the directory of its sources and objects, sources, public header)
+GROUPS = [(LIB, CSRC, SOURCES, HEADER), (AUG_LIB, AUG_DIR, AUG_SOURCES, AUG_HEADER), (SMP_LIB, SMP_DIR, SMP_SOURCES, SMP_HEADER)]
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
@@ -59,26 +66,26 @@ def _fresh(target, digest):
 
 
 def _headers():
-    """csrc/*.hpp and both public headers: inputs of every object of both libraries."""
-    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [HEADER, AUG_HEADER]
+    """csrc/*.hpp and the public headers: inputs of every object of every library."""
+    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [g[3] for g in GROUPS]
 
 
 def source_digest():
-    """Content hash of everything the two libraries are built from: csrc/*.hip, csrc/augment_ext/*.hip, csrc/*.hpp, include/*.h, the compiler
+    """Content hash of everything the libraries are built from: the sources of every row of GROUPS, csrc/*.hpp, include/*.h, the compiler
     path and the flags."""
-    return _digest([os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(AUG_DIR, s) for s in AUG_SOURCES] + _headers(), [_hipcc()] + FLAGS)
+    return _digest([os.path.join(d, s) for _, d, sources, _ in GROUPS for s in sources] + _headers(), [_hipcc()] + FLAGS)
 
 
-LAST_BUILD = {"mode": None, "digest": None, "compiled": []}      # what the last build() call did: "compiled" | "linked" | "reused"
+LAST_BUILD = {"mode": None, "digest": None, "compiled": [], "linked": []}      # what the last build() call did: "compiled" | "linked" | "reused"
 
 
 def build(force=False, verbose=True):
-    """Builds both libraries; -> the path of libemrt_hip.so (libemrt_hip_augment.so is AUG_LIB)."""
+    """Builds every library of GROUPS; -> the path of libemrt_hip.so (the others are AUG_LIB and SMP_LIB).  Only the objects whose inputs
+    changed are compiled, and only the libraries that hold one of them are linked again."""
     hipcc = _hipcc()
     hdrs = _headers()
-    groups = [(LIB, CSRC, SOURCES), (AUG_LIB, AUG_DIR, AUG_SOURCES)]
-    objs, jobs = {LIB: [], AUG_LIB: []}, []
-    for lib, d, sources in groups:
+    objs, jobs = {g[0]: [] for g in GROUPS}, []
+    for lib, d, sources, _ in GROUPS:
         for src in sources:
             s = os.path.join(d, src)
             o = os.path.join(d, src.replace(".hip", ".o"))
@@ -102,6 +109,9 @@ def build(force=False, verbose=True):
         return cmd[-3]
 
     LAST_BUILD["compiled"] = []
+    for lib in {j[3] for j in jobs}:      # a library whose objects are about to change loses its stamp first: a stamp beside a library
+        if os.path.exists(_stamp(lib)):   # therefore says "linked after the last compile of any of its objects", even after an interrupted build
+            os.remove(_stamp(lib))
     if jobs:
         with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
             for done in ex.map(compile_one, jobs):
@@ -109,17 +119,20 @@ def build(force=False, verbose=True):
                 if verbose:
                     print("[emrt_amd.build] compiled", os.path.basename(done), flush=True)
     total = source_digest()
-    linked = False
-    for lib, _, _ in groups:
-        if force or any(j[3] == lib for j in jobs) or not _fresh(lib, total):
+    linked = LAST_BUILD["linked"] = []
+    for lib, _, _, _ in GROUPS:
+        if force or any(j[3] == lib for j in jobs) or not (os.path.exists(lib) and os.path.exists(_stamp(lib))):
             if os.path.exists(_stamp(lib)):
                 os.remove(_stamp(lib))
             run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs[lib] + ["-o", lib])
             with open(_stamp(lib), "w") as f:
                 f.write(total + "\n")
-            linked = True
+            linked.append(os.path.basename(lib))
             if verbose:
                 print("[emrt_amd.build] linked", lib, flush=True)
+        elif not _fresh(lib, total):      # its own objects are all as they were (another library's source changed): the same library, the new digest
+            with open(_stamp(lib), "w") as f:
+                f.write(total + "\n")
     LAST_BUILD["mode"] = ("compiled" if jobs else "linked") if linked else "reused"
     LAST_BUILD["digest"] = total
     return LIB

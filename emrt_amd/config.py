@@ -100,7 +100,12 @@ _DEFAULTS = {
              # (transforms.get_transforms); the ranges are the reference's ADE20K values.  The defaults leave every chain as it was.
              "AUGMENT": {"VFLIP_PROB": 0.0,
                          "DISTORT": {"ENABLE": False, "BRIGHTNESS_RANGE": 0.4, "CONTRAST_RANGE": 0.4, "SATURATION_RANGE": 0.4,
-                                     "BRIGHTNESS_PROB": 0.5, "CONTRAST_PROB": 0.5, "SATURATION_PROB": 0.5}}},
+                                     "BRIGHTNESS_PROB": 0.5, "CONTRAST_PROB": 0.5, "SATURATION_PROB": 0.5}},
+             # not in the reference's tree, --data scenes only (datasets.SceneSampler): where the tiles are cut.  "uniform": every origin equally
+             # likely.  "class": a share PROB of the samples first draws a class with P(c) proportional to exp((1 - f_c) / TEMPERATURE), f_c = the
+             # class's share of the bank's non-ignored pixels (or to CLASS_PROBS[c], DATA.NUM_CLASSES non-negative weights), then a pixel of that
+             # class, and cuts a window around it (rare class sampling).  The default leaves every launch as it was.
+             "SCENE_SAMPLING": {"MODE": "uniform", "PROB": 0.5, "TEMPERATURE": 0.1, "CLASS_PROBS": None}},
     "MODEL": {
         "NAME": "SETR_MLA",
         "ENCODER": {"TYPE": "ViT_MLA", "OUT_INDICES": [5, 11, 17, 23], "MULTI_GRID": False, "MULTI_DILATION": None},

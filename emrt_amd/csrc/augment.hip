@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 #include "common.hpp"
 #include "augment_map.hpp"
+#include "philox.hpp"
 
 namespace emrt {
 namespace {
@@ -74,9 +75,7 @@ __global__ __launch_bounds__(AUG_THREADS) void emrt_augment_kernel(AugArgs a) {
 
 // ---- tiles cut out of whole scenes that live in device memory (emrt_scene_draw, emrt_scene_sample) ---------------------------------------------
 // The random decisions are drawn ON THE DEVICE from the step counter, so a replayed hipGraph cuts a new batch every time and the host does
-// nothing per step.  Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's constants):
-//   key = (key64 low word, key64 high word);  counter = (step low word, step high word, rank * B + b, j),  j = the sample's j-th 128-bit block
-// A 64-bit value is two output words, (w[2k + 1] << 32) | w[2k]; a uniform integer below n is the high half of value * n (bias < n * 2^-64).
+// nothing per step.  Philox4x32-10, its key and counter and the integer draw `below` are philox.hpp, shared with the other two libraries:
 //   block 0, words 0-1: tile origin among all origins of all scenes -> scene by binary search in the cumulative table, y0 = rem / nx, x0 = rem % nx
 //   block 0, words 2-3: scale index
 //   block 1, words 0-1: off_y below max(h, OH) - OH + 1;  words 2-3: off_x below max(w, OW) - OW + 1
@@ -84,26 +83,6 @@ __global__ __launch_bounds__(AUG_THREADS) void emrt_augment_kernel(AugArgs a) {
 constexpr int SCENE_MAX_SCALES = 16;
 constexpr int DRAW_COLS = 10;          // scene, y0, x0, scale_index, h, w, off_y, off_x, flip, 0
 constexpr int DRAW_THREADS = 64;
-
-struct Philox {
-  unsigned v[4];
-};
-
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox{{c0, c1, c2, c3}};
-}
-
-__device__ __forceinline__ unsigned long long below(unsigned lo, unsigned hi, unsigned long long n) {
-  return __umul64hi(((unsigned long long)hi << 32) | lo, n);
-}
 
 struct DrawArgs {
   const long long* step;               // device: the step counter

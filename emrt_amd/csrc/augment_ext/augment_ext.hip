@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include "../../../include/emrt_hip_augment.h"
 #include "../augment_map.hpp"
+#include "../philox.hpp"
 
 namespace emrt {
 namespace {
@@ -234,29 +235,7 @@ struct SceneSrc {
   }
 };
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's constants), as in ../augment.hip.
-struct Philox {
-  unsigned v[4];
-};
-
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox{{c0, c1, c2, c3}};
-}
-
-__device__ __forceinline__ unsigned long long below(unsigned lo, unsigned hi, unsigned long long n) {
-  return __umul64hi(((unsigned long long)hi << 32) | lo, n);
-}
-
-__device__ __forceinline__ double unit(unsigned w) { return (double)w * (1.0 / 4294967296.0); }
-
+// Philox4x32-10, `below` and `unit`: ../philox.hpp, the text ../augment.hip compiles too.
 struct DrawArgs {
   const long long* step;               // device: the step counter
   const EmrtSceneEntry* scenes;        // device

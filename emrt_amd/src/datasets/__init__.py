@@ -10,6 +10,7 @@ Directory layouts are the reference's:
 Whole scenes (train.py --data scenes; no counterpart in the reference): <root>/images/<name>.* + <root>/labels/<name>.* (uint8 class indices),
 optionally <root>/val_images + <root>/val_labels: SceneBank keeps them in device memory, SceneSampler cuts the training tiles there.
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -318,6 +319,48 @@ def scene_files(img_dir, label_dir):
     return out
 
 
+ClassIndex = collections.namedtuple("ClassIndex", "counts totals cum cum_dev row_start row_start_host row_start_dev build_ms")
+ClassIndex.__doc__ = """SceneBank.class_index(): the label index of include/emrt_hip_sampler.h.  counts int32 [R][n_classes] and totals int64
+[n_classes] (numpy); cum int64 [n_classes][R + 1] (numpy) and cum_dev its device copy; row_start int64 [n_scenes + 1] as numpy, as the ctypes
+host mirror the entry points check, and on the device; build_ms the counting launch between device events (None off the GPU)."""
+
+
+def class_probabilities(totals, temperature=0.1, class_probs=None):
+    """The class distribution of DATA.SCENE_SAMPLING, float64 [n_classes].  totals: pixels per class in the bank.  P(c) is proportional to
+    exp((1 - f_c) / temperature) with f_c = totals[c] / sum(totals), or to class_probs[c] when that list is given; a class without a pixel gets
+    0 either way.  A bank without a countable pixel, and weights that leave nothing to draw, are refused."""
+    n = np.asarray(totals, dtype=np.int64)
+    if n.ndim != 1 or n.size < 1 or (n < 0).any():
+        raise ValueError("scenes: class totals must be a non-empty list of non-negative counts, got %r" % (totals,))
+    if int(n.sum()) == 0:
+        raise ValueError("scenes: the bank holds no pixel of any of the %d classes (every label is ignored): class-aware sampling has "
+                         "nothing to draw" % n.size)
+    if class_probs is not None:
+        w = np.asarray(class_probs, dtype=np.float64)
+        if w.shape != n.shape or not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("scenes: SCENE_SAMPLING.CLASS_PROBS must be %d finite non-negative weights (DATA.NUM_CLASSES), got %r"
+                             % (n.size, class_probs))
+    else:
+        t = float(temperature)
+        if not (np.isfinite(t) and t >= 1.0 / 700.0):
+            raise ValueError("scenes: SCENE_SAMPLING.TEMPERATURE must be finite and at least 1/700 (exp(1 / T) must stay finite), got %r" % (temperature,))
+        f = n.astype(np.float64) / float(n.sum())
+        w = np.exp((1.0 - f) / t)
+    w = np.where(n > 0, w, 0.0)
+    if not float(w.sum()) > 0.0:
+        raise ValueError("scenes: SCENE_SAMPLING.CLASS_PROBS gives no weight to a class that has pixels in the bank")
+    return w / w.sum()
+
+
+def class_thresholds(probs):
+    """uint64 [n_classes]: thr[c] = floor(2^32 * sum of probs[:c + 1]) in float64, and exactly 2^32 from the last class with a non-zero
+    probability on.  A 32-bit word w picks the class `number of c with w >= thr[c]` (include/emrt_hip_sampler.h)."""
+    p = np.asarray(probs, dtype=np.float64)
+    thr = np.minimum(np.floor(np.cumsum(p) * 4294967296.0), 4294967296.0).astype(np.uint64)
+    thr[int(np.flatnonzero(p > 0)[-1]):] = np.uint64(1 << 32)
+    return thr
+
+
 class SceneBank:
     """Whole training scenes in ONE uint8 device buffer: <root>/images/* (RGB) with the same-named uint8 class-index maps of <root>/labels/* (the
     format of the *_convert_labels trees).  Scene i is its HWC image at img_off[i] followed by its HW label map at lab_off[i].
@@ -366,7 +409,7 @@ class SceneBank:
                     lab = lab - np.uint8(self.label_shift)          # uint8 wrap: class 0 (ignore) -> 255
                 self.buffer[io:lo].copy_(torch.from_numpy(img.reshape(-1)))
                 self.buffer[lo:lo + H * W].copy_(torch.from_numpy(lab.reshape(-1)))
-        self._tables = {}
+        self._tables, self._index = {}, {}
 
     def __len__(self):
         return len(self.sizes)
@@ -396,6 +439,39 @@ class SceneBank:
         return self._tables[(th, tw)]
 
 
+    def class_index(self, n_classes, lut=None):
+        """-> ClassIndex: pixels per class and row, counted once on the device (emrt_smp_row_counts of the third library, after the 256-byte
+        `lut` when given; values >= n_classes are not counted), read back once, and its class-major prefix over the rows of the whole bank.
+        Synchronises and uploads: call it before any capture (SceneSampler does, in its constructor)."""
+        key = (int(n_classes), None if lut is None else bytes(bytearray(int(v) for v in lut)))
+        if key not in self._index:
+            from ... import functional as Fn
+            from ...runtime import ctx
+            n, ncls = len(self), int(n_classes)
+            row_start = np.concatenate([[0], np.cumsum([H for H, _ in self.sizes], dtype=np.int64)]).astype(np.int64)
+            R = int(row_start[-1])
+            row_start_host = (ctypes.c_longlong * (n + 1))(*row_start.tolist())
+            row_start_dev = torch.from_numpy(row_start).to(self.device)
+            scenes_dev, _, scenes_host, _ = self.tables(1, 1)
+            counts = torch.zeros((R, ncls), dtype=torch.int32, device=self.device)
+            lut_host = None if lut is None else (ctypes.c_ubyte * 256)(*[int(v) for v in lut])
+            on_gpu = self.device.type == "cuda"
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if on_gpu else None
+            if on_gpu:
+                ev[0].record()
+            _lib.sampler_lib().call("emrt_smp_row_counts", Fn.P(self.buffer), self.nbytes, Fn.P(scenes_dev), ctypes.cast(scenes_host, ctypes.c_void_p),
+                                    Fn.P(row_start_dev), ctypes.cast(row_start_host, ctypes.c_void_p), n,
+                                    None if lut_host is None else ctypes.cast(lut_host, ctypes.c_void_p), ncls, Fn.P(counts), R, ctx().stream)
+            if on_gpu:
+                ev[1].record()
+            host = counts.cpu().numpy()          # (the copy waits for the launch)
+            cum = np.zeros((ncls, R + 1), dtype=np.int64)
+            np.cumsum(host.T.astype(np.int64), axis=1, out=cum[:, 1:])
+            self._index[key] = ClassIndex(host, cum[:, -1].copy(), cum, torch.from_numpy(cum).to(self.device), row_start, row_start_host,
+                                          row_start_dev, ev[0].elapsed_time(ev[1]) if on_gpu else None)
+        return self._index[key]
+
+
 class SceneSampler:
     """The training batches of `--data scenes`: SceneSampler(bank, transforms, batch_size, seed, rank).fill(images, labels) enqueues two launches on
     the current stream -- emrt_scene_draw (every random decision of the batch, from the device step counter) and emrt_scene_sample (the transform
@@ -406,9 +482,15 @@ class SceneSampler:
     capturable; the other chains never touch that library.  Potsdam / Vaihingen: the source tile is the crop size, the scale table is
     ResizeStepScaling.resized(factor, th, tw) over its np.linspace factors (Python's round stays on the host).  [Normalize] alone (LoveDA): pass
     `tile` = (h, w); one scale entry of the tile's own size, no flip.  The bank's label_shift goes down as label_lut.
-    The draws are a pure function of (seed, step counter, rank, sample): restoring the step counter continues the same data stream."""
+    The draws are a pure function of (seed, step counter, rank, sample): restoring the step counter continues the same data stream.
 
-    def __init__(self, bank, transforms, batch_size, seed, rank=0, tile=None):
+    `sampling` is the DATA.SCENE_SAMPLING config node (MODE, PROB, TEMPERATURE, CLASS_PROBS).  None or MODE "uniform": the launches above and
+    nothing else.  MODE "class" (needs num_classes): the constructor builds the bank's label index (SceneBank.class_index) and the class
+    thresholds and uploads them, and fill() puts ONE launch of the third library, emrt_smp_class_redraw (include/emrt_hip_sampler.h), between the
+    draw and the sample launch: it moves a share PROB of the windows onto a pixel of a drawn class and leaves every other decision alone.
+    sampler.class_table then holds (class, pixel share, sampling probability) per class; class_names, when given, name the log lines."""
+
+    def __init__(self, bank, transforms, batch_size, seed, rank=0, tile=None, sampling=None, num_classes=None, class_names=None):
         self.bank, self.plan = bank, DevicePlan(list(transforms))
         dp = self.plan
         if dp.crop is not None:
@@ -461,6 +543,47 @@ class SceneSampler:
             self._probs = (ctypes.c_double * 3)(*[float(getattr(d, n + "_prob")) if d is not None else 0.0 for n in names])
             self._ws_bytes = 8 * self.batch_size          # = emrt_aug_workspace_bytes(B); the entry point checks it
             self._ws = torch.zeros(self.batch_size, dtype=torch.int64, device=bank.device)
+        mode = "uniform" if sampling is None else sampling["MODE"]
+        if mode not in ("uniform", "class"):
+            raise ValueError("scenes: SCENE_SAMPLING.MODE must be 'uniform' or 'class', got %r" % (mode,))
+        self.class_mode, self.class_table = mode == "class", None
+        if self.class_mode:
+            self._init_class_mode(sampling, num_classes, class_names)
+
+    def _init_class_mode(self, sampling, num_classes, class_names):
+        """Everything the redraw launch needs, once: fill() may run under stream capture, where nothing can be counted, read back or uploaded."""
+        if num_classes is None or not 1 <= int(num_classes) <= 256:
+            raise ValueError("scenes: SCENE_SAMPLING.MODE 'class' needs num_classes in 1..256 (DATA.NUM_CLASSES), got %r" % (num_classes,))
+        self.class_prob = float(sampling["PROB"])
+        if not 0.0 <= self.class_prob <= 1.0:
+            raise ValueError("scenes: SCENE_SAMPLING.PROB %r is outside [0, 1]" % (sampling["PROB"],))
+        ncls, bank = int(num_classes), self.bank
+        self.index = idx = bank.class_index(ncls, self.lut)
+        self.class_probs = class_probabilities(idx.totals, sampling["TEMPERATURE"], sampling["CLASS_PROBS"])
+        self.thresholds = class_thresholds(self.class_probs)
+        share = idx.totals / float(idx.totals.sum())
+        name = (lambda c: str(class_names[c])) if class_names is not None else (lambda c: "class %d" % c)
+        self.class_table = [(name(c), float(share[c]), float(self.class_probs[c])) for c in range(ncls)]
+        for c in range(ncls):
+            if idx.totals[c] == 0:
+                print("[scenes] %s has no pixel in the bank: its sampling probability is 0" % name(c), flush=True)
+        self._thr_host = (ctypes.c_ulonglong * ncls)(*[int(v) for v in self.thresholds])
+        self._thr_dev = torch.from_numpy(self.thresholds.view(np.int64).copy()).to(bank.device)          # (the same 64 bits)
+        scenes_host = self._tables[2]
+        # the HOST arguments of the redraw launch: the same objects in every call
+        self._smp_host = (ctypes.cast(scenes_host, ctypes.c_void_p), ctypes.cast(idx.row_start_host, ctypes.c_void_p),
+                          ctypes.cast(self._thr_host, ctypes.c_void_p), None if self._lut is None else ctypes.cast(self._lut, ctypes.c_void_p))
+        self._num_classes = ncls
+
+    def _redraw(self, Fn, c, key):
+        """emrt_smp_class_redraw on self.draws: after the draw launch, before the sample launch, on the same stream."""
+        scenes_dev = self._tables[0]
+        scenes_host, rows_host, thr_host, lut = self._smp_host
+        idx, (th, tw) = self.index, self.tile
+        _lib.sampler_lib().call("emrt_smp_class_redraw", Fn.P(c.step_counter), Fn.P(self.bank.buffer), self.bank.nbytes, Fn.P(scenes_dev), scenes_host,
+                                Fn.P(idx.row_start_dev), rows_host, len(self.bank), Fn.P(idx.cum_dev), Fn.P(self._thr_dev), thr_host,
+                                self._num_classes, lut, key, self.rank, self.batch_size, th, tw, self.class_prob, Fn.P(self.draws),
+                                int(self.draws.shape[1]), c.stream)
 
     @property
     def batch_shape(self):
@@ -487,6 +610,8 @@ class SceneSampler:
                    ctypes.cast(cum_host, ctypes.c_void_p), n, self.bank.nbytes, key, self.rank, B, th, tw, OH, OW, self.flip_prob, self.vflip_prob,
                    distort, ctypes.cast(self._ranges, ctypes.c_void_p), ctypes.cast(self._probs, ctypes.c_void_p),
                    ctypes.cast(self._scale_hw, ctypes.c_void_p), len(self.scales), Fn.P(self.draws), c.stream)
+            if self.class_mode:
+                self._redraw(Fn, c, key)
             A.call("emrt_aug_scene_sample", Fn.P(self.bank.buffer), self.bank.nbytes, Fn.P(scenes_dev), ctypes.cast(scenes_host, ctypes.c_void_p), n,
                    Fn.P(self.draws), B, th, tw, OH, OW, distort, ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._stdinv, ctypes.c_void_p),
                    ctypes.cast(self._pad, ctypes.c_void_p), int(self.plan.label_pad),
@@ -497,6 +622,8 @@ class SceneSampler:
         L.call("emrt_scene_draw", Fn.P(c.step_counter), Fn.P(scenes_dev), Fn.P(cum_dev), ctypes.cast(scenes_host, ctypes.c_void_p),
                ctypes.cast(cum_host, ctypes.c_void_p), n, self.bank.nbytes, key, self.rank, B, th, tw, OH, OW, self.flip_prob,
                ctypes.cast(self._scale_hw, ctypes.c_void_p), len(self.scales), Fn.P(self.draws), c.stream)
+        if self.class_mode:
+            self._redraw(Fn, c, key)
         L.call("emrt_scene_sample", Fn.P(self.bank.buffer), self.bank.nbytes, Fn.P(scenes_dev), ctypes.cast(scenes_host, ctypes.c_void_p), n,
                Fn.P(self.draws), B, th, tw, OH, OW, ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._stdinv, ctypes.c_void_p),
                ctypes.cast(self._pad, ctypes.c_void_p), int(self.plan.label_pad),

@@ -151,6 +151,11 @@ def main(argv=None):
     if os.environ.get("EMRT_ALL_RANKS_ON_GPU0"):      # test aid (with EMRT_DIST_BACKEND=gloo): every rank on device 0
         os.environ["LOCAL_RANK"] = "0"
     config = update_config(get_config(), args)
+    if config.DATA.SCENE_SAMPLING.MODE not in ("uniform", "class"):
+        raise SystemExit("[train] DATA.SCENE_SAMPLING.MODE must be 'uniform' or 'class', got %r" % (config.DATA.SCENE_SAMPLING.MODE,))
+    if config.DATA.SCENE_SAMPLING.MODE == "class" and args.data != "scenes":
+        raise SystemExit("[train] DATA.SCENE_SAMPLING.MODE 'class' needs --data scenes (the classes are drawn from the label maps of the resident "
+                         "scenes; --data %s has none)" % args.data)
     rank, local_rank, nranks = init_process_group()
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -193,11 +198,17 @@ def main(argv=None):
         root = config.DATA.DATA_PATH
         tile = (config.DATA.CROP_SIZE[1], config.DATA.CROP_SIZE[0])        # CROP_SIZE is (w, h)
         bank = SceneBank(root, dev, label_shift=1 if config.DATA.DATASET == "LoveDA" else 0)
-        source = SceneSampler(bank, get_transforms(config), bs, args.seed, rank, tile=tile)
+        source = SceneSampler(bank, get_transforms(config), bs, args.seed, rank, tile=tile, sampling=config.DATA.SCENE_SAMPLING,
+                              num_classes=config.DATA.NUM_CLASSES)
         n_tiles = None
         if rank == 0:
             print("[train] data: %d scenes resident on the GPU (%.1f MB), %d tile origins, %d scale steps; tiles are drawn and cut on the device" % (
                 len(bank), bank.nbytes / 1e6, source.total_origins, len(source.scales)), flush=True)
+            if source.class_mode:
+                print("[train] data: class-aware sampling, %.0f %% of the tiles are cut around a pixel of a drawn class (label index built in %.2f ms)" % (
+                    100.0 * source.class_prob, source.index.build_ms), flush=True)
+                for name, share, prob in source.class_table:
+                    print("[train] data:   %-12s pixel share %8.4f %%   sampling probability %8.4f %%" % (name, 100.0 * share, 100.0 * prob), flush=True)
     elif args.data == "synthetic":
         images, labels = synthetic_tiles(max(4 * bs * nranks, 64), config.DATA.CROP_SIZE, config.DATA.NUM_CLASSES, args.seed, dev)
         n_tiles = images.shape[0]
