@@ -23,6 +23,10 @@ AUG_LIB_PATH = os.environ.get("EMRT_HIP_AUGMENT_LIB") or os.path.join(_HERE, "cs
 SMP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_sampler.h")
 SMP_LIB_PATH = os.environ.get("EMRT_HIP_SAMPLER_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_sampler.so")
 
+# The fourth library (include/emrt_hip_loss.h: cross entropy + Dice in one pass), for the same reason: loss_lib().
+LOSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_loss.h")
+LOSS_LIB_PATH = os.environ.get("EMRT_HIP_LOSS_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_loss.so")
+
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
 _CTYPES = {
@@ -285,7 +289,7 @@ def augment_struct(name):
 
 
 class _ExtLib:
-    """A library beside libemrt_hip.so (augment_lib(), sampler_lib()), bound from its own header: call / query / last_error as _Lib, with the
+    """A library beside libemrt_hip.so (augment_lib(), sampler_lib(), loss_lib()), bound from its own header: call / query / last_error as _Lib, with the
     library's own `<prefix>_last_error` string and its `<prefix>_version` checked to be 1.  No fallback: a missing library or symbol raises."""
 
     def __init__(self, path, header, prefix, what):
@@ -348,3 +352,15 @@ def sampler_lib():
     if _SMP_LIB is None:
         _SMP_LIB = _ExtLib(SMP_LIB_PATH, SMP_HEADER, "emrt_smp", "the class-aware scene sampler")
     return _SMP_LIB
+
+
+# ---- libemrt_hip_loss.so (include/emrt_hip_loss.h: cross entropy + Dice; loaded only when TRAIN.LOSS is "DiceCrossEntropyLoss") ----------------
+
+_LOSS_LIB = None
+
+
+def loss_lib():
+    global _LOSS_LIB
+    if _LOSS_LIB is None:
+        _LOSS_LIB = _ExtLib(LOSS_LIB_PATH, LOSS_HEADER, "emrt_lx", "the Dice + cross-entropy loss")
+    return _LOSS_LIB

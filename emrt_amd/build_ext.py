@@ -1,6 +1,7 @@
 """Builds emrt_amd/csrc/libemrt_hip.so and, beside it, emrt_amd/csrc/libemrt_hip_augment.so (csrc/augment_ext/*.hip: the entry points of
 include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) and emrt_amd/csrc/libemrt_hip_sampler.so
-(csrc/sampler_ext/*.hip: include/emrt_hip_sampler.h, for the same reason) with hipcc for gfx950, in-tree.  GROUPS is the table of the three.
+(csrc/sampler_ext/*.hip: include/emrt_hip_sampler.h, for the same reason) with hipcc for gfx950, in-tree.  GROUPS is the table of the three;
+EXTRA_GROUPS holds the libraries added since: emrt_amd/csrc/libemrt_hip_loss.so (csrc/loss_ext/*.hip: include/emrt_hip_loss.h).
 
 What is rebuilt is decided by CONTENT: every object and the library carry a `<file>.inputs` stamp with the sha256 of the sources, headers,
 compiler path and flags they were built from; "reused" therefore means "built from exactly these inputs", on whatever machine.
@@ -26,6 +27,12 @@ SMP_SOURCES = ["sampler_ext.hip"]
 SMP_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_sampler.h")      # includes emrt_hip.h; the sources include csrc/philox.hpp
 # one row per library: (library, the directory of its sources and objects, sources, public header)
 GROUPS = [(LIB, CSRC, SOURCES, HEADER), (AUG_LIB, AUG_DIR, AUG_SOURCES, AUG_HEADER), (SMP_LIB, SMP_DIR, SMP_SOURCES, SMP_HEADER)]
+LOSS_DIR = os.path.join(CSRC, "loss_ext")
+LOSS_LIB = os.path.join(CSRC, "libemrt_hip_loss.so")
+LOSS_SOURCES = ["loss_ext.hip"]
+LOSS_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_loss.h")      # the sources include csrc/common.hpp and csrc/loss_pixel.hpp
+# the rows behind the first three, same form and same rules (GROUPS itself stays the table of the three libraries the sampler's tests pin)
+EXTRA_GROUPS = [(LOSS_LIB, LOSS_DIR, LOSS_SOURCES, LOSS_HEADER)]
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
@@ -65,27 +72,32 @@ def _fresh(target, digest):
         return False
 
 
+def all_groups():
+    """Every library's row: GROUPS, then EXTRA_GROUPS."""
+    return GROUPS + EXTRA_GROUPS
+
+
 def _headers():
     """csrc/*.hpp and the public headers: inputs of every object of every library."""
-    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [g[3] for g in GROUPS]
+    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [g[3] for g in all_groups()]
 
 
 def source_digest():
-    """Content hash of everything the libraries are built from: the sources of every row of GROUPS, csrc/*.hpp, include/*.h, the compiler
+    """Content hash of everything the libraries are built from: the sources of every row of all_groups(), csrc/*.hpp, include/*.h, the compiler
     path and the flags."""
-    return _digest([os.path.join(d, s) for _, d, sources, _ in GROUPS for s in sources] + _headers(), [_hipcc()] + FLAGS)
+    return _digest([os.path.join(d, s) for _, d, sources, _ in all_groups() for s in sources] + _headers(), [_hipcc()] + FLAGS)
 
 
 LAST_BUILD = {"mode": None, "digest": None, "compiled": [], "linked": []}      # what the last build() call did: "compiled" | "linked" | "reused"
 
 
 def build(force=False, verbose=True):
-    """Builds every library of GROUPS; -> the path of libemrt_hip.so (the others are AUG_LIB and SMP_LIB).  Only the objects whose inputs
+    """Builds every library of all_groups(); -> the path of libemrt_hip.so (the others are AUG_LIB, SMP_LIB and LOSS_LIB).  Only the objects whose inputs
     changed are compiled, and only the libraries that hold one of them are linked again."""
     hipcc = _hipcc()
     hdrs = _headers()
-    objs, jobs = {g[0]: [] for g in GROUPS}, []
-    for lib, d, sources, _ in GROUPS:
+    objs, jobs = {g[0]: [] for g in all_groups()}, []
+    for lib, d, sources, _ in all_groups():
         for src in sources:
             s = os.path.join(d, src)
             o = os.path.join(d, src.replace(".hip", ".o"))
@@ -120,7 +132,7 @@ def build(force=False, verbose=True):
                     print("[emrt_amd.build] compiled", os.path.basename(done), flush=True)
     total = source_digest()
     linked = LAST_BUILD["linked"] = []
-    for lib, _, _, _ in GROUPS:
+    for lib, _, _, _ in all_groups():
         if force or any(j[3] == lib for j in jobs) or not (os.path.exists(lib) and os.path.exists(_stamp(lib))):
             if os.path.exists(_stamp(lib)):
                 os.remove(_stamp(lib))

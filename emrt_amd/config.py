@@ -138,6 +138,8 @@ _DEFAULTS = {
         # not in the reference's tree: OhemCrossEntropyLoss's constructor arguments (losses/ohem_cross_entropy_loss.py:18) and the class-weight
         # option of its cross entropy (losses/cross_entropy_loss.py:30-35; empty = off), which the reference leaves to code
         "OHEM": {"THRESH": 0.7, "MIN_KEPT": 10000}, "CLASS_WEIGHTS": [],
+        # not in the reference's tree either: DiceCrossEntropyLoss, L = CE_WEIGHT * CE + WEIGHT * Dice per head (SMOOTH: PaddleSeg DiceLoss's default)
+        "DICE": {"WEIGHT": 1.0, "CE_WEIGHT": 1.0, "SMOOTH": 1.0},
         "LR_SCHEDULER": {"NAME": "PolynomialDecay", "WARM_UP_STEPS": 0, "WARM_UP_LR_INIT": 0.0, "MILESTONES": [30, 60, 90],
                          "POWER": 0.9, "GAMMA": 0.1},
         "OPTIMIZER": {"NAME": "SGD", "EPS": 1e-8, "BETAS": (0.9, 0.999), "MOMENTUM": 0.9, "NESTEROV": False, "WEIGHT_DECAY": 0.0,

@@ -13,6 +13,7 @@
 //    on): loss = sum w[y] CE / sum w[y] over the non-ignored pixels, one head or the two heads of the Mix loss in one pass.
 #include <cfloat>
 #include "common.hpp"
+#include "loss_pixel.hpp"
 
 using namespace emrt;
 
@@ -54,42 +55,7 @@ inline OhemWs ohem_ws(void* workspace, int heads) {
   return w;
 }
 
-// ---- the pixel core: every loss kernel's index split and softmax arithmetic, written once ------------------------------------------
-__device__ __forceinline__ void pixel_of(long long idx, long long total, long long HW, long long& n, long long& p) {
-  n = total <= 0xffffffffll ? (long long)((unsigned)idx / (unsigned)HW) : idx / HW;      // (32-bit division when it can be)
-  p = idx - n * HW;
-}
-
-struct PixelStats {
-  float mx, den;      // max logit over the classes, sum of exp(logit - max)
-};
-__device__ __forceinline__ PixelStats pixel_stats(const float* __restrict__ lp, int C, long long HW) {
-  PixelStats s;
-  s.mx = -3.0e38f;
-  for (int c = 0; c < C; ++c) s.mx = fmaxf(s.mx, lp[c * HW]);
-  s.den = 0.f;
-  for (int c = 0; c < C; ++c) s.den += __expf(lp[c * HW] - s.mx);
-  return s;
-}
-// the pixel's CE; pr = softmax probability of its own class (a label outside [0, C) that is not ignore_index picks logit 0, as it always did)
-__device__ __forceinline__ float pixel_ce(const float* __restrict__ lp, int C, long long HW, long long lab, const PixelStats& s, float& pr) {
-  const float picked = (lab >= 0 && lab < C) ? lp[lab * HW] : 0.f;
-  pr = __expf(picked - s.mx) / s.den;
-  return logf(s.den) + s.mx - picked;
-}
-__device__ __forceinline__ float pixel_ce(const float* __restrict__ lp, int C, long long HW, long long lab) {
-  float pr;
-  return pixel_ce(lp, C, HW, lab, pixel_stats(lp, C, HW), pr);
-}
-// dp[c] = g * (softmax_c - onehot_c)
-__device__ __forceinline__ void pixel_grad_store(const float* __restrict__ lp, float* __restrict__ dp, int C, long long HW, long long lab, float g) {
-  const PixelStats s = pixel_stats(lp, C, HW);
-  const float inv = 1.f / s.den;
-  for (int c = 0; c < C; ++c) dp[c * HW] = g * (__expf(lp[c * HW] - s.mx) * inv - (c == lab ? 1.f : 0.f));
-}
-__device__ __forceinline__ void pixel_zero_store(float* __restrict__ dp, int C, long long HW) {
-  for (int c = 0; c < C; ++c) dp[c * HW] = 0.f;
-}
+// (the pixel core -- pixel_of, pixel_stats, pixel_ce, pixel_grad_store, pixel_zero_store, class_weight_of -- is loss_pixel.hpp)
 
 // the block's LDS histogram -> the global bins: one integer atomic per non-empty bin
 __device__ __forceinline__ void flush_bins(const unsigned* lh, unsigned* __restrict__ gh, int nbins) {
@@ -284,11 +250,6 @@ __global__ __launch_bounds__(256) void ohem_bwd_kernel(OhemHeads<NH> hd, const l
 // ------------------------------------------------------------------------------------------------
 // The kernels take the heads as plain __restrict__ pointer and scalar arguments (head b unused when NH = 1), as the plain CE kernels always
 // did: handed over as a by-value record the plain forward measured 0.6 us slower at 8 x 6 x 256 x 256.
-template <bool CW>
-__device__ __forceinline__ float class_weight_of(const float* __restrict__ cw, long long lab, int C) {
-  return CW ? ((lab >= 0 && lab < C) ? cw[lab] : 0.f) : 1.f;
-}
-
 // partial[block] = {sum w[y] CE of head a, (of head b,) sum w[y]}
 template <int NH, bool CW>
 __global__ __launch_bounds__(256) void wce_fwd_kernel(const float* __restrict__ la, const float* __restrict__ lb, const long long* __restrict__ labels,
@@ -372,14 +333,6 @@ __global__ __launch_bounds__(256) void wce_bwd_kernel(const float* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 // host side.  Grids: one thread per pixel, capped (1024 blocks forward -- the partials' workspace --, 4096 backward, 128 for the digit histograms).
 // ------------------------------------------------------------------------------------------------
-inline int stream_grid(long long npix, int cap) {
-  long long g = (npix + 255) / 256;
-  return (int)(g > cap ? cap : g < 1 ? 1 : g);
-}
-
-inline bool shape_ok(int N, int C, int H, int W) { return N >= 1 && C >= 1 && H >= 1 && W >= 1 && (long long)N * H * W < (1ll << 31); }
-#define SHAPE_MSG "N, C, H, W >= 1 and N * H * W < 2^31"
-
 // the one filler of the OHEM head record: every array is per head, in head order
 template <int NH>
 OhemHeads<NH> ohem_heads(const float* const (&logits)[NH], const float* const (&prob)[NH], const float* const (&result)[NH], float* const (&dlogits)[NH],

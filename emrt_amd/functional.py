@@ -1905,6 +1905,63 @@ def ohem_ce_pair(logits_a, logits_b, labels, ignore_index, thresh, min_kept, wa,
     return res_a, res_b, total, prob_a, prob_b
 
 
+def _dice_args(labels, class_weight, C, *logits):
+    for z in logits:
+        assert z.dtype == torch.float32 and z.is_contiguous() and tuple(z.shape) == tuple(logits[0].shape)
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    assert class_weight is None or (class_weight.dtype == torch.float32 and class_weight.is_contiguous() and class_weight.numel() == C)
+
+
+def dice_ce(logits, labels, ignore_index, weight=1.0, class_weight=None, ce_weight=1.0, dice_weight=1.0, smooth=1.0):
+    """ce_weight * CE + dice_weight * Dice of one head (fp32 NCHW logits) on the fourth library (include/emrt_hip_loss.h): CE as softmax_ce
+    (class_weight likewise), Dice = 1 - mean over all C classes of (2 I_c + smooth) / (P_c + T_c + smooth) with the sums over the whole batch.
+    Returns a device float[8] = {L, CE, Dice, sum w[y], non-ignored count, ...}.  One streaming launch and a finalize forward, one launch backward:
+    weight * upstream * dL/dlogits, exact zeros at the ignored pixels."""
+    c = ctx()
+    X = _lib.loss_lib()
+    N, C, H, W = logits.shape
+    _dice_args(labels, class_weight, C, logits)
+    res, coef = c.empty((8,), torch.float32), c.empty((2 * C,), torch.float32)
+    ws = c.workspace(X.query("emrt_lx_dice_ce_workspace_bytes", C, 1))
+    X.call("emrt_lx_dice_ce_fwd", P(logits), P(labels), P(class_weight), N, C, H, W, ignore_index, float(ce_weight), float(dice_weight), float(smooth),
+           P(res), P(coef), P(ws), c.stream)
+    tape = c.tape
+    if tape is not None:
+        def bwd():
+            up = tape.pop_grad(res)   # device scalar or None (== 1)
+            dl = c.empty((N, C, H, W), torch.float32)
+            X.call("emrt_lx_dice_ce_bwd", P(logits), P(labels), P(class_weight), P(res), P(coef), P(up), float(weight), float(ce_weight), N, C, H, W,
+                   ignore_index, P(dl), c.stream)
+            tape.add_grad(logits, dl, owned=True)
+        tape.record(bwd)
+    return res
+
+
+def dice_ce_pair(logits_a, logits_b, labels, ignore_index, wa, wb, class_weight=None, ce_weight=1.0, dice_weight=1.0, smooth=1.0):
+    """dice_ce of two heads on the same labels (main + aux) through the launches of one: the head is a grid dimension of the streaming kernels,
+    so each head's result and gradient are the single form's bits.  Returns (res_a, res_b, total); total = wa * L_a + wb * L_b."""
+    c = ctx()
+    X = _lib.loss_lib()
+    N, C, H, W = logits_a.shape
+    _dice_args(labels, class_weight, C, logits_a, logits_b)
+    res_a, res_b, total = c.empty((8,), torch.float32), c.empty((8,), torch.float32), c.empty((1,), torch.float32)
+    coef_a, coef_b = c.empty((2 * C,), torch.float32), c.empty((2 * C,), torch.float32)
+    ws = c.workspace(X.query("emrt_lx_dice_ce_workspace_bytes", C, 2))
+    X.call("emrt_lx_dice_ce_pair_fwd", P(logits_a), P(logits_b), P(labels), P(class_weight), N, C, H, W, ignore_index, float(wa), float(wb),
+           float(ce_weight), float(dice_weight), float(smooth), P(res_a), P(res_b), P(coef_a), P(coef_b), P(total), P(ws), c.stream)
+    tape = c.tape
+    if tape is not None:
+        def bwd():
+            up_a, up_b = tape.pop_grad(res_a), tape.pop_grad(res_b)      # device scalars or None (== 1)
+            da, db = c.empty((N, C, H, W), torch.float32), c.empty((N, C, H, W), torch.float32)
+            X.call("emrt_lx_dice_ce_pair_bwd", P(logits_a), P(logits_b), P(labels), P(class_weight), P(res_a), P(res_b), P(coef_a), P(coef_b), P(up_a),
+                   P(up_b), float(wa), float(wb), float(ce_weight), N, C, H, W, ignore_index, P(da), P(db), c.stream)
+            tape.add_grad(logits_a, da, owned=True)
+            tape.add_grad(logits_b, db, owned=True)
+        tape.record(bwd)
+    return res_a, res_b, total
+
+
 def augment_tiles(src, samples, out_size, mean, stdinv, img_pad, label_pad, label_lut=None, labels=True):
     """Training augmentation of a packed batch of decoded tiles, one launch (csrc/augment.hip: resize, pad, crop, flip, normalise).
     src: uint8 [n] on the device; samples: per sample (img_off, lab_off, SamplePlan) with byte offsets into src; out_size (OH, OW);

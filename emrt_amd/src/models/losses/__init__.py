@@ -164,7 +164,61 @@ class OhemCrossEntropyLoss:
         return _combine_heads(parts, weights, tape)
 
 
-SUPPORTED_LOSSES = ("MixSoftmaxCrossEntropyLoss", "OhemCrossEntropyLoss")
+class DiceCrossEntropyLoss:
+    """CE_WEIGHT * CE + DICE_WEIGHT * Dice per head, in one pass over the logits on the device (functional.dice_ce; include/emrt_hip_loss.h).
+    CE is MixSoftmaxCrossEntropyLoss's term (class_weights likewise); Dice = 1 - the mean over ALL classes of (2 I_c + s) / (P_c + T_c + s),
+    I_c / P_c / T_c = intersection, probability mass and pixel count of class c over the non-ignored pixels of the whole batch, s = smooth:
+    PaddleSeg's DiceLoss(ignore_index, smooth) in its softmax form.  The per-class sums are formed on the device between forward and backward, so
+    the loss is part of a captured step.  Under data parallelism each rank forms Dice over its own shard and the gradients are averaged: that is
+    not the Dice of the global batch.
+
+    The heads are combined as MixSoftmaxCrossEntropyLoss combines them, main + AUX_WEIGHT * aux (MODEL.AUX.LOSS off: weight 1; a None head is
+    skipped).  parts[i] is head i's device float[8] = {L, CE, Dice, sum w[y], non-ignored count, ...}."""
+
+    def __init__(self, config=None, ce_weight=1.0, dice_weight=1.0, smooth=1.0, ignore_index=255, aux=True, aux_weight=0.4, class_weights=None):
+        num_classes = None
+        if config is not None:
+            ignore_index, aux, aux_weight = config.TRAIN.IGNORE_INDEX, config.MODEL.AUX.LOSS, config.MODEL.AUX.AUX_WEIGHT
+            class_weights, num_classes = config.TRAIN.CLASS_WEIGHTS, config.DATA.NUM_CLASSES
+            ce_weight, dice_weight, smooth = config.TRAIN.DICE.CE_WEIGHT, config.TRAIN.DICE.WEIGHT, config.TRAIN.DICE.SMOOTH
+        ce_weight, dice_weight, smooth = float(ce_weight), float(dice_weight), float(smooth)
+        for key, v in (("CE_WEIGHT", ce_weight), ("WEIGHT", dice_weight), ("SMOOTH", smooth)):
+            if v != v:
+                raise ValueError("TRAIN.DICE.%s is NaN" % key)
+            if v < 0:
+                raise ValueError("TRAIN.DICE.%s must be >= 0, got %r" % (key, v))
+        if ce_weight == 0 and dice_weight == 0:
+            raise ValueError("TRAIN.DICE.WEIGHT and TRAIN.DICE.CE_WEIGHT are both 0: nothing to minimise")
+        self.ce_weight, self.dice_weight, self.smooth = ce_weight, dice_weight, smooth
+        self.ignore_index, self.aux, self.aux_weight = ignore_index, aux, aux_weight
+        self.class_weights = _class_weights(class_weights, num_classes)
+        self._cw = None      # uploaded here when the model is already placed, as MixSoftmaxCrossEntropyLoss does: no copy inside a captured step
+        if self.class_weights is not None and ctx().device is not None:
+            self._upload(ctx().device)
+
+    _upload = MixSoftmaxCrossEntropyLoss._upload
+    _device_class_weights = MixSoftmaxCrossEntropyLoss._device_class_weights
+
+    def __call__(self, preds, target):
+        c = ctx()
+        tape = getattr(preds, "tape", None)
+        c.tape = tape
+        try:
+            target = target.contiguous()
+            weights = [1.0] + [self.aux_weight if self.aux else 1.0] * (len(preds) - 1)
+            live = [(p, w) for p, w in zip(preds, weights) if p is not None]
+            kw = dict(class_weight=self._device_class_weights(live[0][0]), ce_weight=self.ce_weight, dice_weight=self.dice_weight, smooth=self.smooth)
+            if len(live) == 2 and tuple(live[0][0].shape) == tuple(live[1][0].shape):
+                # main + aux head at the input size: both heads through the launches of one, the weighted total formed by the finalize launch
+                ra, rb, total = Fn.dice_ce_pair(live[0][0], live[1][0], target, self.ignore_index, live[0][1], live[1][1], **kw)
+                return LossValue(total, [ra, rb], tape)
+            parts = [Fn.dice_ce(p, target, self.ignore_index, w, **kw) for p, w in live]
+        finally:
+            c.tape = None
+        return _combine_heads(parts, weights, tape)
+
+
+SUPPORTED_LOSSES = ("MixSoftmaxCrossEntropyLoss", "OhemCrossEntropyLoss", "DiceCrossEntropyLoss")
 
 
 def get_loss_function(config):
@@ -172,4 +226,6 @@ def get_loss_function(config):
         return MixSoftmaxCrossEntropyLoss(config)
     if config.TRAIN.LOSS == "OhemCrossEntropyLoss":
         return OhemCrossEntropyLoss(config)
-    raise NotImplementedError("TRAIN.LOSS %r is not on the EMRT path: supported are %s" % (config.TRAIN.LOSS, " and ".join(SUPPORTED_LOSSES)))
+    if config.TRAIN.LOSS == "DiceCrossEntropyLoss":
+        return DiceCrossEntropyLoss(config)
+    raise NotImplementedError("TRAIN.LOSS %r is not on the EMRT path: supported are %s" % (config.TRAIN.LOSS, ", ".join(SUPPORTED_LOSSES)))

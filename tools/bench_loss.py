@@ -1,6 +1,6 @@
 """Loss-pass timing: forward + backward of MixSoftmaxCrossEntropyLoss (emrt_softmax_ce_pair_*), its class-weighted form (emrt_wce_pair_*) and
-OhemCrossEntropyLoss on two heads (emrt_ohem_ce_pair_fwd / _bwd) at the two training shapes,
-8 x 6 x 256 x 256 and 4 x 7 x 512 x 512.
+OhemCrossEntropyLoss on two heads (emrt_ohem_ce_pair_fwd / _bwd) and DiceCrossEntropyLoss (emrt_lx_dice_ce_pair_*, the fourth library) at the
+two training shapes, 8 x 6 x 256 x 256 and 4 x 7 x 512 x 512.
 
     python tools/bench_loss.py [--reps 30] [--inner 20] [--json profiles/loss_bench.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/bench_loss.py --reps 3 ; python tools/bench_loss.py --stats-csv OUT/.../*_kernel_stats.csv
@@ -21,8 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = [(8, 6, 256, 256), (4, 7, 512, 512)]
-# GPU launches of one forward + backward pass (csrc/loss.hip)
-LAUNCHES = {"mix": 2 + 1, "weighted_mix": 2 + 1, "ohem": 9 + 1}
+# GPU launches of one forward + backward pass (csrc/loss.hip; dice: csrc/loss_ext/loss_ext.hip)
+LAUNCHES = {"mix": 2 + 1, "weighted_mix": 2 + 1, "ohem": 9 + 1, "dice": 2 + 1}
 
 
 def selection_share(path):
@@ -57,7 +57,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_loss needs a GPU")
     from emrt_amd.runtime import ctx, F32, Tape
-    from emrt_amd.src.models.losses import MixSoftmaxCrossEntropyLoss, OhemCrossEntropyLoss
+    from emrt_amd.src.models.losses import DiceCrossEntropyLoss, MixSoftmaxCrossEntropyLoss, OhemCrossEntropyLoss
     c = ctx()
     c.init_device("cuda:0", F32, 0)
     c.training = True
@@ -79,7 +79,8 @@ def main():
         c.workspace(64 << 20)
         fns = {"mix": MixSoftmaxCrossEntropyLoss(ignore_index=255, aux=True, aux_weight=0.4),
                "weighted_mix": MixSoftmaxCrossEntropyLoss(ignore_index=255, aux=True, aux_weight=0.4, class_weights=[1.0 + 0.25 * i for i in range(C)]),
-               "ohem": OhemCrossEntropyLoss(thresh=0.7, min_kept=npix // 8, ignore_index=255, aux=True, aux_weight=0.4)}
+               "ohem": OhemCrossEntropyLoss(thresh=0.7, min_kept=npix // 8, ignore_index=255, aux=True, aux_weight=0.4),
+               "dice": DiceCrossEntropyLoss(ce_weight=1.0, dice_weight=1.0, smooth=1.0, ignore_index=255, aux=True, aux_weight=0.4)}
 
         def one_pass(fn):
             out = Out((la, lb))
@@ -94,6 +95,9 @@ def main():
                 loss = one_pass(fn)
             torch.cuda.synchronize()
             info[k] = {"loss": round(loss.item(), 6)}
+            if k == "dice":
+                info[k]["ce"] = [round(p[1].item(), 6) for p in loss.parts]
+                info[k]["dice"] = [round(p[2].item(), 6) for p in loss.parts]
             if k == "ohem":
                 info[k]["kept"] = [int(p[1].item()) for p in loss.parts]
                 info[k]["threshold"] = [round(p[2].item(), 6) for p in loss.parts]
@@ -120,6 +124,8 @@ def main():
         row["weighted_over_mix"] = round(row["weighted_mix"]["median_us"] / row["mix"]["median_us"], 3)
         row["ohem_over_mix"] = round(row["ohem"]["median_us"] / row["mix"]["median_us"], 3)
         row["ohem_minus_mix_us"] = round(row["ohem"]["median_us"] - row["mix"]["median_us"], 2)
+        row["dice_over_mix"] = round(row["dice"]["median_us"] / row["mix"]["median_us"], 3)
+        row["dice_minus_mix_us"] = round(row["dice"]["median_us"] - row["mix"]["median_us"], 2)
         res["shapes"]["%dx%dx%dx%d" % (N, C, H, W)] = row
     print(json.dumps(res), flush=True)
     if a.json:
