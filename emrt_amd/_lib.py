@@ -27,6 +27,10 @@ SMP_LIB_PATH = os.environ.get("EMRT_HIP_SAMPLER_LIB") or os.path.join(_HERE, "cs
 LOSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_loss.h")
 LOSS_LIB_PATH = os.environ.get("EMRT_HIP_LOSS_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_loss.so")
 
+# The fifth library (include/emrt_hip_tta.h: flip and rotation test-time augmentation of whole-scene inference), for the same reason: tta_lib().
+TTA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_tta.h")
+TTA_LIB_PATH = os.environ.get("EMRT_HIP_TTA_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_tta.so")
+
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
 _CTYPES = {
@@ -289,7 +293,7 @@ def augment_struct(name):
 
 
 class _ExtLib:
-    """A library beside libemrt_hip.so (augment_lib(), sampler_lib(), loss_lib()), bound from its own header: call / query / last_error as _Lib, with the
+    """A library beside libemrt_hip.so (augment_lib(), sampler_lib(), loss_lib(), tta_lib()), bound from its own header: call / query / last_error as _Lib, with the
     library's own `<prefix>_last_error` string and its `<prefix>_version` checked to be 1.  No fallback: a missing library or symbol raises."""
 
     def __init__(self, path, header, prefix, what):
@@ -364,3 +368,15 @@ def loss_lib():
     if _LOSS_LIB is None:
         _LOSS_LIB = _ExtLib(LOSS_LIB_PATH, LOSS_HEADER, "emrt_lx", "the Dice + cross-entropy loss")
     return _LOSS_LIB
+
+
+# ---- libemrt_hip_tta.so (include/emrt_hip_tta.h: window-level flips and rotations; loaded only when a scene is predicted with tta other than "none") ----
+
+_TTA_LIB = None
+
+
+def tta_lib():
+    global _TTA_LIB
+    if _TTA_LIB is None:
+        _TTA_LIB = _ExtLib(TTA_LIB_PATH, TTA_HEADER, "emrt_tta", "the test-time augmentation of whole-scene inference")
+    return _TTA_LIB

@@ -1,7 +1,8 @@
 """Builds emrt_amd/csrc/libemrt_hip.so and, beside it, emrt_amd/csrc/libemrt_hip_augment.so (csrc/augment_ext/*.hip: the entry points of
 include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) and emrt_amd/csrc/libemrt_hip_sampler.so
 (csrc/sampler_ext/*.hip: include/emrt_hip_sampler.h, for the same reason) with hipcc for gfx950, in-tree.  GROUPS is the table of the three;
-EXTRA_GROUPS holds the libraries added since: emrt_amd/csrc/libemrt_hip_loss.so (csrc/loss_ext/*.hip: include/emrt_hip_loss.h).
+EXTRA_GROUPS holds the library added next, emrt_amd/csrc/libemrt_hip_loss.so (csrc/loss_ext/*.hip: include/emrt_hip_loss.h), and MORE_GROUPS the
+ones after it: emrt_amd/csrc/libemrt_hip_tta.so (csrc/tta_ext/*.hip: include/emrt_hip_tta.h).  all_groups() is every row.
 
 What is rebuilt is decided by CONTENT: every object and the library carry a `<file>.inputs` stamp with the sha256 of the sources, headers,
 compiler path and flags they were built from; "reused" therefore means "built from exactly these inputs", on whatever machine.
@@ -33,6 +34,12 @@ LOSS_SOURCES = ["loss_ext.hip"]
 LOSS_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_loss.h")      # the sources include csrc/common.hpp and csrc/loss_pixel.hpp
 # the rows behind the first three, same form and same rules (GROUPS itself stays the table of the three libraries the sampler's tests pin)
 EXTRA_GROUPS = [(LOSS_LIB, LOSS_DIR, LOSS_SOURCES, LOSS_HEADER)]
+TTA_DIR = os.path.join(CSRC, "tta_ext")
+TTA_LIB = os.path.join(CSRC, "libemrt_hip_tta.so")
+TTA_SOURCES = ["tta_ext.hip"]
+TTA_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_tta.h")      # the sources include csrc/common.hpp and csrc/scene_norm.hpp
+# the rows behind those (EXTRA_GROUPS is pinned at one row by the loss library's tests, as GROUPS is at three)
+MORE_GROUPS = [(TTA_LIB, TTA_DIR, TTA_SOURCES, TTA_HEADER)]
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
@@ -73,8 +80,8 @@ def _fresh(target, digest):
 
 
 def all_groups():
-    """Every library's row: GROUPS, then EXTRA_GROUPS."""
-    return GROUPS + EXTRA_GROUPS
+    """Every library's row: GROUPS, then EXTRA_GROUPS, then MORE_GROUPS."""
+    return GROUPS + EXTRA_GROUPS + MORE_GROUPS
 
 
 def _headers():
@@ -92,7 +99,7 @@ LAST_BUILD = {"mode": None, "digest": None, "compiled": [], "linked": []}      #
 
 
 def build(force=False, verbose=True):
-    """Builds every library of all_groups(); -> the path of libemrt_hip.so (the others are AUG_LIB, SMP_LIB and LOSS_LIB).  Only the objects whose inputs
+    """Builds every library of all_groups(); -> the path of libemrt_hip.so (the others are AUG_LIB, SMP_LIB, LOSS_LIB and TTA_LIB).  Only the objects whose inputs
     changed are compiled, and only the libraries that hold one of them are linked again."""
     hipcc = _hipcc()
     hdrs = _headers()

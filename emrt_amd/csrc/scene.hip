@@ -9,6 +9,7 @@
 // Both are pure streaming: four consecutive pixels of a row per lane (16-byte loads from the fp32 planes, the byte outputs packed into whole
 // dwords), a grid-stride loop over a capped grid; a one-pixel-per-thread form covers ragged widths and unaligned pointers.
 #include "common.hpp"
+#include "scene_norm.hpp"      // SceneNorm, normalise_u8
 
 using namespace emrt;
 
@@ -21,12 +22,6 @@ inline int scene_grid(long long items) {
   long long g = (items + 255) / 256;
   return (int)(g < 1 ? 1 : (g > SC_MAX_BLOCKS ? SC_MAX_BLOCKS : g));
 }
-
-struct SceneNorm {
-  double mean[3], stdinv[3];
-};
-
-__device__ __forceinline__ float normalise_u8(unsigned v, double mean, double stdinv) { return (float)(((double)v - mean) * stdinv); }
 
 // VEC = 4: one thread makes four consecutive x of one window row for the three channels (cw % 4 == 0, batch 16-byte aligned); VEC = 1: one x.
 // The scene bytes of a window row start anywhere, so they are read as bytes (a wave reads one contiguous run of 768 of them).

@@ -17,7 +17,7 @@ from PIL import Image
 
 from .config import get_config, update_config
 from .runtime import BF16, F16, F32
-from .src.api.scene import ScenePredictor
+from .src.api.scene import TTA_MODES, ScenePredictor
 from .src.models import get_model
 from .src.utils import vis
 
@@ -35,12 +35,19 @@ def parse_args(argv=None):
     p.add_argument("--save_dir", default=None, help="default: <SAVE_DIR>/predict")
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     p.add_argument("--max_batch", default=32, type=int, help="windows per model call (1..64)")
+    p.add_argument("--tta", default="none", choices=list(TTA_MODES),
+                   help="test-time augmentation of every window at scale 1: hflip = 2 variants, flips = both flips and their product (4), "
+                        "d4 = the 8 flips and quarter turns (square crop); the class probabilities of all variants are averaged. "
+                        "A model call then carries max_batch // variants windows. Not with --multi_scales, which keeps its own flip")
     p.add_argument("--overlay", default=None, type=float, metavar="ALPHA",
                    help="also write <stem>_overlay.png = ALPHA * colour + (1 - ALPHA) * image, ALPHA in [0, 1]")
     p.add_argument("--save_index", action="store_true",
                    help="also write <stem>_index.png, an 8-bit palette PNG whose pixel values are the class indices. "
                         "Outputs are named after the source file's stem (<stem>.png is the colour mask), not after a running counter as in the reference")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.tta != "none" and args.multi_scales:
+        p.error("--tta %s cannot be combined with --multi_scales: multi-scale inference keeps its own horizontal flip" % args.tta)
+    return args
 
 
 def input_files(paths):
@@ -99,7 +106,7 @@ def main(argv=None):
         stride = crop          # the default stride left in place over a smaller crop, as emrt_amd.val treats it
     multi = args.multi_scales or config.VAL.MULTI_SCALES_VAL
     predictor = ScenePredictor(model, ncls, crop, stride, palette, list(config.VAL.MEAN), list(config.VAL.STD), overlay=args.overlay,
-                               max_batch=args.max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi else None)
+                               max_batch=args.max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi else None, tta=args.tta)
     written, jobs = [], []
     with ThreadPoolExecutor(max_workers=max(1, min(WRITERS, len(files)))) as pool:
         for f, stem in zip(files, stems):

@@ -11,6 +11,10 @@ infer.ms_accumulate (multi-scale + horizontal flip) are finished instead.
 
 SceneEvaluator runs the same windows over the scenes of a resident validation bank (datasets.SceneBank) and counts the metric areas
 against the bank's uint8 label maps where they lie: emrt_window_normalise, emrt_argmax_nchw and emrt_segmentation_areas stand where the finish stands.
+
+Both take `tta`: "hflip", "flips" or "d4" puts every window through the model in 2, 4 or 8 flipped / turned variants and averages
+the class probabilities of all variants of all covering windows -- two launches of libemrt_hip_tta.so around the model call stand where the crop
+and the accumulation stand; "none" (the default) issues what it always issued and never loads that library.
 """
 import ctypes
 from collections import namedtuple
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 
 from . import infer
+from ... import _lib
 from ... import functional as Fn
 from ...runtime import ctx
 
@@ -61,13 +66,56 @@ def crop_windows(scene, H, W, org, ch, cw, mean, stdinv):
     return batch, ptr, arr
 
 
-def accumulate_windows(model, scene, H, W, crop, stride, ncls, max_batch, mean, stdinv, final, count):
+# Test-time augmentation of a window: mode -> variant codes, t * 4 + fv * 2 + fh (include/emrt_hip_tta.h): the window with its rows
+# reversed if fv and its columns reversed if fh, then transposed if t.  "d4" is the eight flips and quarter turns of a square window.
+TTA_MODES = {"none": (0,), "hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def check_tta(tta, crop, max_batch, scales):
+    """-> the variant codes of mode `tta` for windows of `crop` (w, h); what cannot run is refused here, before anything is loaded"""
+    if tta not in TTA_MODES:
+        raise ValueError("tta must be one of %s, got %r" % (", ".join(TTA_MODES), tta))
+    codes = TTA_MODES[tta]
+    if len(codes) > 1:
+        if scales is not None:
+            raise ValueError("tta=%r cannot be combined with scales: multi-scale inference keeps its own horizontal flip" % tta)
+        if any(k & 4 for k in codes) and crop[0] != crop[1]:
+            raise ValueError("tta=%r turns windows by 90 degrees and needs a square crop, got %dx%d (w x h)" % (tta, crop[0], crop[1]))
+        if max_batch < len(codes):
+            raise ValueError("tta=%r makes %d variants of a window and needs max_batch >= %d, got %d" % (tta, len(codes), len(codes), max_batch))
+    return codes
+
+
+def accumulate_windows_tta(model, scene, H, W, org, crop, ncls, max_batch, mean, stdinv, final, count, codes):
+    """The windows at `org` in that order, max_batch // G per model call, each with its G = len(codes) variants (variant g of window j is image
+    j * G + g of the call): emrt_tta_crop_windows_u8 makes them from the uint8 scene, emrt_tta_window_accumulate adds the softmax of every
+    variant's logits, turned back, to `final` [1, ncls, H, W] and G per covering window to `count` [1, 1, H, W]."""
+    T, c = _lib.tta_lib(), ctx()
+    w_crop, h_crop = crop
+    G = len(codes)
+    karr = (ctypes.c_int * G)(*codes)
+    kptr = ctypes.cast(karr, ctypes.c_void_p)
+    per = max_batch // G
+    for i in range(0, len(org), per):
+        chunk = org[i:i + per]
+        _keep, ptr = _origins(chunk)
+        batch = c.empty((len(chunk) * G, 3, h_crop, w_crop), torch.float32)
+        T.call("emrt_tta_crop_windows_u8", Fn.P(scene), Fn.P(batch), ptr, len(chunk), kptr, G, H, W, h_crop, w_crop, *mean, *stdinv, c.stream)
+        logits = model(batch)[0]
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and tuple(logits.shape) == (len(chunk) * G, ncls, h_crop, w_crop)
+        T.call("emrt_tta_window_accumulate", Fn.P(logits), Fn.P(final), Fn.P(count), ptr, len(chunk), kptr, G, ncls, H, W, h_crop, w_crop, c.stream)
+
+
+def accumulate_windows(model, scene, H, W, crop, stride, ncls, max_batch, mean, stdinv, final, count, codes=(0,)):
     """The single-scale pass both classes share: the windows of infer.window_grid(H, W, crop, stride) in that order, max_batch per model call
     (chunked exactly as infer.slide_inference: the same logits, bit for bit), cropped and normalised from the uint8 scene, their logits added to
-    `final` [1, ncls, H, W] and their hits to `count` [1, 1, H, W]; both fp32 and zeroed by the caller."""
+    `final` [1, ncls, H, W] and their hits to `count` [1, 1, H, W]; both fp32 and zeroed by the caller.  With more than one variant code
+    (check_tta) the sums are those of accumulate_windows_tta instead: class probabilities, not logits."""
     L, c = Fn._L(), ctx()
     w_crop, h_crop = crop
     wins = infer.window_grid(H, W, crop, stride)
+    if len(codes) > 1:
+        return accumulate_windows_tta(model, scene, H, W, [(a, b) for (a, b, _, _) in wins], crop, ncls, max_batch, mean, stdinv, final, count, codes)
     for i in range(0, len(wins), max_batch):
         chunk = wins[i:i + max_batch]
         batch, ptr, _keep = crop_windows(scene, H, W, [(a, b) for (a, b, _, _) in chunk], h_crop, w_crop, mean, stdinv)
@@ -77,15 +125,16 @@ def accumulate_windows(model, scene, H, W, crop, stride, ncls, max_batch, mean, 
 
 
 class ScenePredictor:
-    """p = ScenePredictor(model, num_classes, crop_size, stride_size, palette, mean, std, overlay=None, max_batch=32, scales=None)
+    """p = ScenePredictor(model, num_classes, crop_size, stride_size, palette, mean, std, overlay=None, max_batch=32, scales=None, tta="none")
     p(scene_u8)            torch.uint8 [H, W, 3] RGB on the device -> SceneResult
     p.predict_tiles(t_u8)  torch.uint8 [n, h, w, 3] with h x w == crop: one model call per max_batch tiles -> SceneResult with [n, ...] maps
 
     crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); palette uint8 [num_classes, 3] RGB; mean / std as
-    transforms.Normalize takes them; overlay = alpha in [0, 1] (the colour's weight over the scene) or None."""
+    transforms.Normalize takes them; overlay = alpha in [0, 1] (the colour's weight over the scene) or None; tta = a key of TTA_MODES: with
+    G > 1 variants a model call carries max_batch // G windows."""
 
     def __init__(self, model, num_classes, crop_size, stride_size, palette, mean, std, overlay=None, max_batch=32, scales=None,
-                 flip_horizontal=True):
+                 flip_horizontal=True, tta="none"):
         self.model, self.ncls = model, int(num_classes)
         self.crop, self.stride = check_windows(crop_size, stride_size)
         pal = np.ascontiguousarray(np.asarray(palette))
@@ -103,18 +152,21 @@ class ScenePredictor:
         self.max_batch = int(max_batch)
         self.scales = None if scales is None else tuple(scales)
         self.flip_horizontal = flip_horizontal
+        self.tta, self.codes = tta, check_tta(tta, self.crop, self.max_batch, self.scales)
 
     # ---- kernels ---------------------------------------------------------------------------------------------------
     def _crop(self, scene, H, W, org, ch, cw):
         """windows at `org` of the uint8 [H, W, 3] scene -> normalised fp32 [n, 3, ch, cw]"""
         return crop_windows(scene, H, W, org, ch, cw, self.mean, self.stdinv)
 
-    def _finish(self, values, count, scene, out, j0, N, H, W):
-        """values [N, ncls, H, W] (+ count) -> maps j0 .. j0 + N of `out`; the areas are added to out.areas"""
+    def _finish(self, values, count, scene, out, j0, N, H, W, tall=False):
+        """values [N, ncls, H, W] (+ count) -> maps j0 .. j0 + N of `out`; the areas are added to out.areas.  tall: the N maps are one scene of
+        N * H rows (values [1, ncls, N * H, W])"""
         overlay = None if out.overlay is None else out.overlay[j0:j0 + N]
+        shape = (1, self.ncls, N * H, W) if tall else (N, self.ncls, H, W)
         Fn._L().call("emrt_scene_finish", Fn.P(values), Fn.P(count), ctypes.cast(self._pal, ctypes.c_void_p),
                      None if overlay is None else Fn.P(scene), 0.0 if self.alpha is None else self.alpha, Fn.P(out.index[j0:j0 + N]),
-                     Fn.P(out.color[j0:j0 + N]), Fn.P(overlay), Fn.P(out.areas), N, self.ncls, H, W, ctx().stream)
+                     Fn.P(out.color[j0:j0 + N]), Fn.P(overlay), Fn.P(out.areas), *shape, ctx().stream)
 
     def _outputs(self, n, H, W):
         c = ctx()
@@ -144,19 +196,31 @@ class ScenePredictor:
         else:
             final = c.zeros((1, self.ncls, H, W), torch.float32)
             count = c.zeros((1, 1, H, W), torch.float32)
-            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count)
+            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count,
+                               self.codes)
             self._finish(final, count, scene, out, 0, 1, H, W)
         return SceneResult(out.index[0], out.color[0], None if out.overlay is None else out.overlay[0], out.areas)
 
     # ---- a stack of crop-sized tiles -----------------------------------------------------------------------------
     def predict_tiles(self, tiles_u8):
         """The stack is one tall scene [n * h][w][3] whose windows are the tiles; the model's logits are finished directly (a batch
-        dimension, no count), max_batch tiles per model call, results in tile order."""
+        dimension, no count), max_batch tiles per model call, results in tile order.  With tta, max_batch // G tiles per model call are one tall
+        scene of their own: its sums and counts (accumulate_windows_tta) are finished."""
         tiles = self._check_u8(tiles_u8, 4, "tiles")
         n, h, w = (int(v) for v in tiles.shape[:3])
         if (w, h) != self.crop:
             raise ValueError("tiles are %dx%d (h x w), the crop is %dx%d: predict_tiles takes crop-sized tiles" % (h, w, self.crop[1], self.crop[0]))
         out = self._outputs(n, h, w)
+        if len(self.codes) > 1:
+            c, per = ctx(), self.max_batch // len(self.codes)
+            for j0 in range(0, n, per):
+                m = min(per, n - j0)
+                final = c.zeros((1, self.ncls, m * h, w), torch.float32)
+                count = c.zeros((1, 1, m * h, w), torch.float32)
+                accumulate_windows_tta(self.model, tiles[j0:j0 + m], m * h, w, [(j * h, 0) for j in range(m)], self.crop, self.ncls, self.max_batch,
+                                       self.mean, self.stdinv, final, count, self.codes)
+                self._finish(final, count, tiles[j0:j0 + m], out, j0, m, h, w, tall=True)
+            return out
         for j0 in range(0, n, self.max_batch):
             m = min(self.max_batch, n - j0)
             batch, _, _keep = self._crop(tiles, n * h, w, [(j * h, 0) for j in range(j0, j0 + m)], h, w)
@@ -167,7 +231,7 @@ class ScenePredictor:
 
 
 class SceneEvaluator:
-    """ev = SceneEvaluator(model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None)
+    """ev = SceneEvaluator(model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None, tta="none")
     tot = ev.evaluate(rank=0, nranks=1)     int64 [3, ncls] on the device: intersect, prediction and label areas of this rank's scenes
     ev.per_scene                            int64 [n_scenes, 3, ncls] on the device: the same per scene, rows of other ranks' scenes zero
 
@@ -177,10 +241,11 @@ class SceneEvaluator:
     normalised scene and the argmax, infer.ms_inference's) -- and emrt_segmentation_areas counts it against the uint8 label view into the scene's
     row.  Everything is enqueued on the current stream: no host copy of a pixel, no synchronisation.  Sums, counts, normalised logits and the
     prediction are allocated once per distinct scene shape and reused by every scene of that shape and by every later evaluation.
-    crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); mean / std as transforms.Normalize takes them."""
+    crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); mean / std as transforms.Normalize takes them; tta as
+    ScenePredictor takes it (the argmax is then that of the mean class probability)."""
 
     def __init__(self, model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None,
-                 flip_horizontal=True):
+                 flip_horizontal=True, tta="none"):
         self.model, self.bank, self.ncls = model, bank, int(num_classes)
         self.crop, self.stride = check_windows(crop_size, stride_size)
         for i, (H, W) in enumerate(bank.sizes):
@@ -196,6 +261,7 @@ class SceneEvaluator:
         self.ignore_index = int(ignore_index)
         self.scales = None if scales is None else tuple(scales)
         self.flip_horizontal = flip_horizontal
+        self.tta, self.codes = tta, check_tta(tta, self.crop, self.max_batch, self.scales)
         self.per_scene = torch.empty((len(bank), 3, self.ncls), dtype=torch.int64, device=bank.device)
         self._scratch = {}          # (H, W) -> (sums, counts, normalised logits, prediction)
 
@@ -221,7 +287,8 @@ class SceneEvaluator:
         else:
             L.call("emrt_memset", Fn.P(final), 0, final.numel() * 4, c.stream)
             L.call("emrt_memset", Fn.P(count), 0, count.numel() * 4, c.stream)
-            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count)
+            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count,
+                               self.codes)
             L.call("emrt_window_normalise", Fn.P(final), Fn.P(count), Fn.P(logits), self.ncls, H, W, c.stream)
         L.call("emrt_argmax_nchw", Fn.P(logits), Fn.P(pred), 1, self.ncls, H, W, c.stream)
         return pred

@@ -21,6 +21,7 @@ from .config import get_config, update_config
 from .distributed import init_process_group
 from .runtime import BF16, F16, F32
 from .src.api import infer
+from .src.api.scene import TTA_MODES
 from .src.models import get_model
 from .src.utils import metrics
 
@@ -35,7 +36,16 @@ def parse_args(argv=None):
                    "DATA.DATA_PATH/val_images + /val_labels, resident on the GPU and evaluated at their own resolution) or a .npz")
     p.add_argument("--data_path", default=None, help="override DATA.DATA_PATH of the yaml")
     p.add_argument("--dtype", default="fp32", choices=["bf16", "fp16", "fp32"])
-    return p.parse_args(argv)
+    p.add_argument("--tta", default="none", choices=list(TTA_MODES),
+                   help="with --data scenes: test-time augmentation of every window at scale 1 (hflip: 2 variants, flips: 4, d4: the 8 flips and "
+                        "quarter turns of a square crop); the class probabilities of all variants are averaged. Not with --multi_scales")
+    args = p.parse_args(argv)
+    if args.tta != "none" and args.data != "scenes":
+        p.error("--tta %s needs --data scenes: only whole scenes resident on the GPU are evaluated with test-time augmentation, --data %s is not"
+                % (args.tta, args.data))
+    if args.tta != "none" and args.multi_scales:
+        p.error("--tta %s cannot be combined with --multi_scales: multi-scale inference keeps its own horizontal flip" % args.tta)
+    return args
 
 
 class _OnDevice:
@@ -116,15 +126,16 @@ def metric_tuple(tot):
     return miou, acc, kap, class_iou, class_acc, class_f1, float(np.mean(class_f1))
 
 
-def scene_evaluator(model, config, device, multi_scales=False, max_batch=32):
+def scene_evaluator(model, config, device, multi_scales=False, max_batch=32, tta="none"):
     """The validation bank of a scene tree (<DATA.DATA_PATH>/val_images + /val_labels, uploaded here, labels stored as a `val` Dataset shifts them)
-    and the SceneEvaluator over it, from VAL.CROP_SIZE / STRIDE_SIZE / MEAN / STD and TRAIN.IGNORE_INDEX; VAL.SCALE_RATIOS when multi_scales."""
+    and the SceneEvaluator over it, from VAL.CROP_SIZE / STRIDE_SIZE / MEAN / STD and TRAIN.IGNORE_INDEX; VAL.SCALE_RATIOS when multi_scales; tta as
+    SceneEvaluator takes it."""
     from .src.api.scene import SceneEvaluator
     from .src.datasets import SceneBank
     bank = SceneBank(config.DATA.DATA_PATH, device, label_shift=1 if config.DATA.DATASET == "LoveDA" else 0, sub=("val_images", "val_labels"),
                      shift_on_upload=True)
     return SceneEvaluator(model, bank, config.DATA.NUM_CLASSES, config.VAL.CROP_SIZE, config.VAL.STRIDE_SIZE, list(config.VAL.MEAN), list(config.VAL.STD),
-                          ignore_index=config.TRAIN.IGNORE_INDEX, max_batch=max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi_scales else None)
+                          ignore_index=config.TRAIN.IGNORE_INDEX, max_batch=max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi_scales else None, tta=tta)
 
 
 def evaluate_scenes(evaluator, rank=0, nranks=1):
@@ -171,7 +182,7 @@ def main(argv=None):
     if args.data == "scenes":           # whole validation scenes resident on the device, evaluated at their own resolution
         if getattr(args, "data_path", None):
             config.DATA.DATA_PATH = args.data_path
-        ev = scene_evaluator(model, config, dev, multi_scales)
+        ev = scene_evaluator(model, config, dev, multi_scales, tta=args.tta)
         images = ev.bank.names
         if rank == 0:
             print("[EVAL] data: %d validation scenes resident on the GPU (%.1f MB)" % (len(ev.bank), ev.bank.nbytes / 1e6), flush=True)
