@@ -368,6 +368,7 @@ extern "C" int emrt_gconv2d(const void* in, const void* w, void* out, const floa
                             const float* out_scale, int dtype, void* stream) {
   EMRT_REQUIRE(in && w && out, "null pointer");
   EMRT_REQUIRE_FWD_DTYPE(dtype);
+  EMRT_REQUIRE(dtype != EMRT_F16 || !bn_stats, "fp16 (dtype 2) is inference-only: no BatchNorm statistics");
   if (int r = check_common(__func__, N, H, W, C, OH, OW, OC, stride, groups)) return r;
   EMRT_REQUIRE(ldin >= C && ldout >= OC && in_bs >= (long long)H * W * ldin && out_bs >= (long long)OH * OW * ldout, "strides smaller than the map");
   EMRT_REQUIRE(ldin % 8 == 0 && in_bs % 8 == 0 && ldout % 4 == 0 && out_bs % 4 == 0, "ldin / in_bs must be multiples of 8, ldout / out_bs of 4");

@@ -141,7 +141,7 @@ int emrt_conv2d_bwd(const void* x, const void* dy, const void* w_bwd_packed, voi
 /* ---- grouped 3x3 convolution, pad 1 (csrc/gconv.hip) --------------------------------------------------------------------------------------------
  * replaces the grouped nn.Conv2D of ResNeXt's bottleneck (backbones/resnext.py, BottleneckBlock.conv1: groups = 64).  C / groups (Cg) must be
  * 4, 8, 16 or 32 and OC / groups a multiple of 4; stride 1 or 2.  w = [OC][3][3][Cg] (the forward operand: the compute-dtype mirror of the
- * parameter, no transposed copy).  Forward: out = conv(in, w) * out_scale [+ bias] [relu]; bn_stats (nullable) as emrt_conv2d's; fp32 / bf16 / fp16.
+ * parameter, no transposed copy).  Forward: out = conv(in, w) * out_scale [+ bias] [relu]; bn_stats (nullable, fp32 / bf16 only) as emrt_conv2d's; fp32 / bf16 / fp16.
  * ldin / in_bs multiples of 8, ldout / out_bs of 4, operands 16-byte aligned.  Output written without atomics (bit-reproducible).
  * Backward (fp32 / bf16): dx (nullable) = dgrad [+ dx if accumulate], no atomics; dw (nullable) += wgrad and dbias (nullable) += sum dy, fp32 atomics
  * (the pixel reduction is cut into slices over blocks).  x is the forward input, dy the gradient of out. */

@@ -1,7 +1,8 @@
 """Seeded random case lists for the shape sweeps of csrc/norm.hip, csrc/spatial.hip and the inference glue
 (tests/test_gpu_norm_fuzz.py, tests/test_gpu_spatial_fuzz.py, tests/test_gpu_infer_glue.py) and of csrc/attn.hip
 (tests/test_gpu_mha_fuzz.py; its float64 reference and bounds are tests/mha_reference.py), the written-out case list of the sweep of
-csrc/msda.hip by plan, build and layout (tests/test_gpu_msda_fuzz.py; tests/msda_reference.py), and the dispatchers' shape predicates
+csrc/msda.hip by plan, build and layout (tests/test_gpu_msda_fuzz.py; tests/msda_reference.py), the written-out case list of the sweep of
+csrc/gconv.hip by group shape, launch plan and view (tests/test_gpu_gconv_fuzz.py), and the dispatchers' shape predicates
 restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
 entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
 seed or a range cannot silently empty one.
@@ -187,6 +188,83 @@ Regime -> case ids (regime_table() renders this text; the CPU test compares):
   msda              dref, GRAD_LDS (msda_bwd_dref_lds = 1)             msda2010-{19,21,27,30,32}
   msda              dref, msda_bwd_dref_lds = 0 (GRAD_GLOBAL)          msda2010-{20,28}
   msda              dref on a band pyramid (GRAD_GLOBAL)               msda2010-{7}
+  gconv             Cg = 4, f32                                        gconv2111-{0,3,22,26,30,40}
+  gconv             Cg = 4, bf16                                       gconv2111-{1,2,16,18,21,23,38}
+  gconv             Cg = 8, f32                                        gconv2111-{4,7,17,19}
+  gconv             Cg = 8, bf16                                       gconv2111-{5,6,28,29}
+  gconv             Cg = 16, f32                                       gconv2111-{8,11,24}
+  gconv             Cg = 16, bf16                                      gconv2111-{9,10,20,27}
+  gconv             Cg = 32, f32                                       gconv2111-{12,15,31}
+  gconv             Cg = 32, bf16                                      gconv2111-{13,14,25,39}
+  gconv             Og == Cg                                           gconv2111-{0,2,5,8,12,13,21,23,24,27,29,30,32,35,36}
+  gconv             Og < Cg                                            gconv2111-{4,7,9,11,14,15,19,20,25,31,34,39}
+  gconv             Og > Cg                                            gconv2111-{1,3,6,10,16,17,18,22,26,28,33,37,38,40}
+  gconv             Og = 4                                             gconv2111-{0,2,4,7,9,19,20,21,23,25,30,32,39}
+  gconv             Og not a power of two (12, 20)                     gconv2111-{1,3,6,10,15,16,28,31,33}
+  gconv             forward: QB < 64 dividing 256                      gconv2111-{4,5,8,9,12,19,21,22,23,24,25,26,27,29,32,34,36,39}
+  gconv             forward: QB not dividing 256 (idle threads)        gconv2111-{0,1,2,3,6,7,10,11,14,15,20,28,30,31,33,35,37}
+  gconv             forward: exactly one full slice                    gconv2111-{13,18,38}
+  gconv             forward: several slices, ragged last               gconv2111-{16,17}
+  gconv             dgrad: QB < 64 dividing 256                        gconv2111-{4,5,8,9,12,16,18,22,23,25,26,27,29,38,40}
+  gconv             dgrad: QB not dividing 256 (idle threads)          gconv2111-{0,1,2,7,11,15,17,28,30}
+  gconv             dgrad: exactly one full slice                      gconv2111-{13,19,39}
+  gconv             dgrad: several slices, ragged last                 gconv2111-{14,20}
+  gconv             forward: M below one tile                          gconv2111-{0,2,3,4,6,7,8,9,10,11,12,14,15,19,20,21,24,25,26,27,28,29,30,31,33,34,35,36,37}
+  gconv             forward: M % (4 PS) != 0                           gconv2111-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,19,20,21,22,23,24,25,26,27,28,29,30,31,32,33,34,35,36,37,38,39,40}
+  gconv             forward: M % 4 != 0                                gconv2111-{0,1,2,3,4,6,9,11,15,16,19,21,22,23,24,27,28,31,35,37,38,39,40}
+  gconv             forward: OW % 4 != 0 (pixels cross a row end)      gconv2111-{0,1,2,3,4,6,8,9,10,11,12,13,14,15,16,19,20,21,22,23,24,25,26,27,28,29,30,31,32,33,34,35,36,37,38,39,40}
+  gconv             forward: N > 1, OH OW % 4 != 0 (pixels cross an image end) gconv2111-{0,1,3,4,6,10,13,21,22,24,26,28,29,31,32}
+  gconv             dgrad: W % 4 != 0 (pixels cross a row end)         gconv2111-{0,1,2,4,8,9,11,12,13,14,15,16,19,20,22,23,25,26,27,28,29,30,38,39,40}
+  gconv             dgrad: N > 1, H W % 4 != 0 (pixels cross an image end) gconv2111-{0,1,4,13,22,26,28,29}
+  gconv             grid-stride: forward, no statistics                gconv2111-{38}
+  gconv             grid-stride: forward with statistics               gconv2111-{40}
+  gconv             grid-stride: dgrad                                 gconv2111-{39}
+  gconv             stride 1                                           gconv2111-{0,1,4,5,6,8,9,11,12,13,15,16,17,18,19,20,21,22,23,26,28,29,31,32,34,35,37,38,39,40}
+  gconv             stride 2                                           gconv2111-{2,3,7,10,14,24,25,27,30,33,36}
+  gconv             H or W = 1                                         gconv2111-{11,15}
+  gconv             H or W = 2                                         gconv2111-{13,14,20}
+  gconv             stride 2 on an even size                           gconv2111-{3,7,14,24,25,30,36}
+  gconv             stride 2 on an odd size                            gconv2111-{2,10,14,24,27,30,33,36}
+  gconv             non-square                                         gconv2111-{0,1,2,3,4,6,8,9,10,11,13,14,15,17,19,22,23,24,25,26,27,28,29,30,32,33,35,36,37}
+  gconv             input view: ld                                     gconv2111-{0,2,7,10,17,20,24,26,30,32,36}
+  gconv             input view: bs                                     gconv2111-{6,8,14,22,27,33}
+  gconv             input view: ld+bs                                  gconv2111-{1,3,12,25,29,35}
+  gconv             output view: ld                                    gconv2111-{1,4,10,12,16,19,24,26,32,36}
+  gconv             output view: bs                                    gconv2111-{2,7,14,17,21,27,33,37}
+  gconv             output view: ld+bs                                 gconv2111-{6,9,15,22,28,34}
+  gconv             dy view: ld                                        gconv2111-{2,8,11,14,19,21,22,26,29}
+  gconv             dy view: bs                                        gconv2111-{3,9,15,20,24,27,31}
+  gconv             dy view: ld+bs                                     gconv2111-{6,12,17,23,28}
+  gconv             dx view: ld                                        gconv2111-{8,14,16,22,26}
+  gconv             dx view: bs                                        gconv2111-{1,7,11,17,19,23,27,29}
+  gconv             dx view: ld+bs                                     gconv2111-{4,9,12,20,25,28}
+  gconv             all dense                                          gconv2111-{5,13,18,38,39,40}
+  gconv             epilogue: none                                     gconv2111-{0,2,9,12,14,19,26,28,29,30,31,32,35,38}
+  gconv             epilogue: bias                                     gconv2111-{1,8,13,17,27,33,36,39}
+  gconv             epilogue: fold                                     gconv2111-{3,10,22}
+  gconv             epilogue: fold+relu                                gconv2111-{7,18,25,34,37}
+  gconv             epilogue: stats                                    gconv2111-{4,5,16,20,40}
+  gconv             epilogue: stats+relu                               gconv2111-{11,21,24}
+  gconv             epilogue: stats+bias                               gconv2111-{6,15,23}
+  gconv             f16 epilogue: none                                 gconv2111-{32,35}
+  gconv             f16 epilogue: bias                                 gconv2111-{33,36}
+  gconv             f16 epilogue: fold+relu                            gconv2111-{34,37}
+  gconv             f16 at Cg = 4                                      gconv2111-{32,37}
+  gconv             f16 at Cg = 8                                      gconv2111-{33,35}
+  gconv             f16 at Cg = 32                                     gconv2111-{34,36}
+  gconv             backward arm: all                                  gconv2111-{0,1,4,8,11,13,14,15,16,17,20,22,23,26,27,29,30,38,39,40}
+  gconv             backward arm: dx                                   gconv2111-{2,7,12,18,25,28}
+  gconv             backward arm: dw                                   gconv2111-{3,10,24}
+  gconv             backward arm: dbias                                gconv2111-{6,21,31}
+  gconv             backward arm: dx-acc+dw                            gconv2111-{5,9,19}
+  gconv             backward arm: none                                 gconv2111-{32,33,34,35,36,37}
+  gconv             wgrad: S = 1                                       gconv2111-{3,8,9,10,11,13,14,15,17,19,20,21,24,27,30}
+  gconv             wgrad: S > 1, rows_per_slice % 4 != 0              gconv2111-{0,1,4,6,16,22,23,26,29,31,38,39}
+  gconv             wgrad: S bounded by the thread count               gconv2111-{38,39,40}
+  gconv             wgrad: threads % 256 != 0                          gconv2111-{0,1,3,4,5,6,8,9,10,11,14,15,16,17,19,20,21,22,23,24,26,27,29,30,31,39}
+  gconv             inputs: ordinary                                   gconv2111-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,32,33,34,35,36,37,38,39,40}
+  gconv             inputs: corner                                     gconv2111-{26,27,28}
+  gconv             inputs: lastpixel                                  gconv2111-{29,30,31}
 
 Not reachable through the wrappers, on purpose:
   * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
@@ -194,6 +272,8 @@ Not reachable through the wrappers, on purpose:
   * the 64-bit index branch of unravel3 / unravel4 (csrc/common.hpp) needs more than 2^32 elements and stays unexercised.
   * msda: the refusals (rows too long for a scatter slab, L = 2, dref with M != 8) are pinned by tests/test_msda_plan_cpu.py and stay out
     of the sweep; FINALIZE and the band kinds do not exist for the (1, 4) build (see MSDA_REGIMES).
+  * gconv: emrt_gconv2d has no dilation and no kernel size but 3; maps of 2^31 pixels and more are refused (check_common).  The refusals
+    are one separate test without a launch (tests/test_gpu_gconv_fuzz.py).
 """
 import random
 
@@ -985,25 +1065,235 @@ MSDA_REGIMES = [("%s, build (%d, %d)" % (k, b[0], b[1]), _msda_has(k, b)) for k 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# grouped 3x3 convolution: emrt_gconv2d / emrt_gconv2d_bwd (csrc/gconv.hip; tests/test_gpu_gconv_fuzz.py).  Written out like the msda list:
+# every row ends with what it is there for, and the regimes are computed from the mirrored launch arithmetic below, not from that text.
+# ---------------------------------------------------------------------------------------------------------------------------------
+GCONV_LONG_MAX_ELEMS = 257 * 257 * 256          # per tensor, for the three grid-stride cases alone: the smallest maps that send a block round its tile loop twice
+GCONV_DTYPES = ("f32", "bf16", "f16")
+GCONV_EPILOGUES = ("none", "bias", "fold", "fold+relu", "stats", "stats+relu", "stats+bias")          # fold = scale + shift (eval-mode BatchNorm)
+GCONV_VIEWS = ("dense", "ld", "bs", "ld+bs")          # ld: a channel slice of a wider buffer; bs: rows of padding behind every image
+GCONV_ARMS = ("all", "dx", "dw", "dbias", "dx-acc+dw", "none")          # all = dx + dw + dbias in one call; none: the forward-only float16
+GCONV_INPUTS = ("ordinary", "corner", "lastpixel")
+GCONV_THREADS, GCONV_PPT = 256, 4          # GC_THREADS, GC_PPT
+
+
+def gconv_block(quads):
+    """(QB, PS): channel quads and pixel slots of a block.  Mirrors pick_block (csrc/gconv.hip)."""
+    QB = quads if quads < 64 else 64
+    return QB, GCONV_THREADS // QB
+
+
+def gconv_grid(M, chans, stats):
+    """(ntiles, gx, nslices, loops) of the forward over chans = OC output channels, or of the data gradient over chans = C input channels
+    and M input pixels (stats False); loops: a block walks more than one pixel tile.  Mirrors launch_fwd / launch_dgrad (csrc/gconv.hip)."""
+    quads = chans // 4
+    QB, PS = gconv_block(quads)
+    nslices = _ceil_div(quads, QB)
+    ntiles = _ceil_div(M, PS * GCONV_PPT)
+    cap = _ceil_div(2048, nslices) if stats else 4096
+    gx = min(ntiles, cap)
+    return ntiles, gx, nslices, ntiles > gx
+
+
+def gconv_wgrad_plan(M, OC, Cg):
+    """(threads, rows_per_slice, S): one thread per (oc, tap, 8- or 4-channel chunk), S slices of the pixel reduction over gridDim.y.
+    Mirrors launch_wgrad (csrc/gconv.hip)."""
+    CH = 8 if Cg >= 8 else 4
+    threads = OC * 9 * (Cg // CH)
+    S = max(1, min(1048576 // threads, M // 32))
+    rows = _ceil_div(M, S)
+    return threads, rows, _ceil_div(M, rows)
+
+
+def gconv_view(kind, C, HW):
+    """(ld, bs) of a tensor of C channels and HW pixels per image under a view kind of GCONV_VIEWS: ld = C rounded up to 8, plus 8; three
+    pixel rows of padding behind each image"""
+    ld = C if "ld" not in kind else (C + 7) // 8 * 8 + 8
+    return ld, HW * ld + (3 * ld if "bs" in kind else 0)
+
+
+def gconv_dims(case):
+    """(C, OC, OH, OW, M forward = output pixels, M data gradient = input pixels)"""
+    _, N, H, W, groups, Cg, Og, stride = case[:8]
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return groups * Cg, groups * Og, OH, OW, N * OH * OW, N * H * W
+
+
+def gconv_in_domain(case):
+    """check_common plus the EMRT_REQUIRE lines of emrt_gconv2d and emrt_gconv2d_bwd (csrc/gconv.hip), under the strides gconv_view gives.  The
+    input's ldin / in_bs (ldx / x_bs) must be multiples of 8, so an input with C % 8 != 0 (3 groups of 4) is legal only as a slice of a wider
+    buffer (view `ld` or `ld+bs`); every other stride is a multiple of 4.  No statistics and no backward in float16."""
+    _, N, H, W, groups, Cg, Og, stride, dtype, epilogue, views, arm, inputs, _, _ = case
+    if not (N > 0 and H > 0 and W > 0 and groups > 0 and stride in (1, 2) and Cg in (4, 8, 16, 32) and Og > 0 and Og % 4 == 0):
+        return False
+    if dtype not in GCONV_DTYPES or epilogue not in GCONV_EPILOGUES or arm not in GCONV_ARMS or inputs not in GCONV_INPUTS:
+        return False
+    if len(views) != 4 or any(v not in GCONV_VIEWS for v in views) or N * H * W + 512 >= 2 ** 31:
+        return False
+    if dtype == "f16" and (arm != "none" or epilogue.startswith("stats")):
+        return False
+    if dtype != "f16" and arm == "none":
+        return False
+    C, OC, OH, OW, _, _ = gconv_dims(case)
+    (ldin, in_bs), (ldout, out_bs) = gconv_view(views[0], C, H * W), gconv_view(views[1], OC, OH * OW)
+    (lddy, dy_bs), (lddx, dx_bs) = gconv_view(views[2], OC, OH * OW), gconv_view(views[3], C, H * W)
+    return (ldin >= C and in_bs >= H * W * ldin and ldin % 8 == 0 and in_bs % 8 == 0
+            and ldout >= OC and out_bs >= OH * OW * ldout and ldout % 4 == 0 and out_bs % 4 == 0
+            and lddy >= OC and dy_bs >= OH * OW * lddy and lddy % 4 == 0 and dy_bs % 4 == 0
+            and lddx >= C and dx_bs >= H * W * lddx and lddx % 4 == 0 and dx_bs % 4 == 0)
+
+
+_D = "dense"
+_DENSE = (_D, _D, _D, _D)
+# (N, H, W, groups, Cg, Og, stride, dtype, epilogue, views of (input, output, dy, dx), backward arm, input recipe, what the row is there for)
+_GCONV_ROWS = (
+    (2, 9, 7, 3, 4, 4, 1, "f32", "none", ("ld", _D, _D, _D), "all", "ordinary", "3 groups of 4: C = 12 only as a slice, QB = 3 both ways (85 slots, one idle thread), M below a tile"),
+    (2, 9, 7, 3, 4, 12, 1, "bf16", "bias", ("ld+bs", "ld", _D, "bs"), "all", "ordinary", "Og 12 > Cg 4: 9 output quads (QB = 9, 28 slots, 4 idle threads)"),
+    (1, 17, 13, 5, 4, 4, 2, "bf16", "none", ("ld", "bs", "ld", _D), "dx", "ordinary", "5 groups, stride 2 on odd sizes, dx alone"),
+    (2, 6, 10, 6, 4, 20, 2, "f32", "fold", ("ld+bs", _D, "bs", "ld"), "dw", "ordinary", "Og 20, stride 2 on even sizes, M = 30 (S = 1), dw alone, a ragged last wgrad block"),
+    (2, 5, 11, 4, 8, 4, 1, "f32", "stats", (_D, "ld", _D, "ld+bs"), "all", "ordinary", "Og 4 < Cg 8; QB = 4: 64 pixel slots in the statistics' column sum"),
+    (1, 12, 12, 8, 8, 8, 1, "bf16", "stats", _DENSE, "dx-acc+dw", "ordinary", "all dense, dx accumulates onto what is there"),
+    (3, 7, 5, 2, 8, 12, 1, "bf16", "stats+bias", ("bs", "ld+bs", "ld+bs", _D), "dbias", "ordinary", "Og 12 > Cg 8, dbias alone, 35 pixels per image: a thread's pixels cross image ends"),
+    (1, 8, 8, 6, 8, 4, 2, "f32", "fold+relu", ("ld", "bs", _D, "bs"), "dx", "ordinary", "Og 4, 12 input quads and 6 output quads (neither divides 256), stride 2 on even sizes"),
+    (2, 4, 6, 4, 16, 16, 1, "f32", "bias", ("bs", _D, "ld", "ld"), "all", "ordinary", "Cg 16 fp32: two 8-channel passes per tap"),
+    (1, 10, 3, 2, 16, 4, 1, "bf16", "none", (_D, "ld+bs", "bs", "ld+bs"), "dx-acc+dw", "ordinary", "Og 4 < Cg 16: 2 output quads, 128 pixel slots; M = 30 far below the 512-pixel tile"),
+    (2, 3, 9, 5, 16, 20, 2, "bf16", "fold", ("ld", "ld", _D, _D), "dw", "ordinary", "Og 20 > Cg 16, 20 input and 25 output quads, stride 2 (odd sizes), dw alone"),
+    (1, 1, 13, 3, 16, 8, 1, "f32", "stats+relu", (_D, _D, "ld", "bs"), "all", "ordinary", "H = 1: only the middle kernel row is ever inside"),
+    (1, 6, 6, 2, 32, 32, 1, "f32", "none", ("ld+bs", "ld", "ld+bs", "ld+bs"), "dx", "ordinary", "Cg 32 fp32: four passes per tap, every tensor a padded view"),
+    (2, 2, 5, 8, 32, 32, 1, "bf16", "bias", _DENSE, "all", "ordinary", "C = OC = 256: exactly one full slice both ways; H = 2"),
+    (1, 7, 2, 10, 32, 8, 2, "bf16", "none", ("bs", "bs", "ld", "ld"), "all", "ordinary", "C = 320: 80 input quads, the data gradient's second slice is ragged; W = 2 under stride 2"),
+    (1, 5, 1, 3, 32, 12, 1, "f32", "stats+bias", (_D, "ld+bs", "bs", _D), "all", "ordinary", "W = 1; Og 12 < Cg 32"),
+    (1, 9, 9, 16, 4, 20, 1, "bf16", "stats", (_D, "ld", _D, "ld"), "all", "ordinary", "OC = 320: the forward's second slice is ragged, with statistics (oc < OC in the column sum)"),
+    (2, 5, 4, 10, 8, 32, 1, "f32", "bias", ("ld", "bs", "ld+bs", "bs"), "all", "ordinary", "OC = 320 again in fp32, 20 input quads"),
+    (1, 4, 4, 16, 4, 16, 1, "bf16", "fold+relu", (_D, _D, _D, _D), "dx", "ordinary", "OC = 256: one full forward slice from 16 input quads"),
+    (1, 3, 5, 32, 8, 4, 1, "f32", "none", (_D, "ld", "ld", "bs"), "dx-acc+dw", "ordinary", "C = 256: one full data-gradient slice; 32 output quads"),
+    (2, 2, 2, 20, 16, 4, 1, "bf16", "stats", ("ld", _D, "bs", "ld+bs"), "all", "ordinary", "C = 320 from 20 groups of 16; a 2 x 2 map: every tap position is a border"),
+    (2, 3, 3, 4, 4, 4, 1, "bf16", "stats+relu", (_D, "bs", "ld", _D), "dbias", "ordinary", "ReLU together with statistics in bf16, dbias alone"),
+    (2, 13, 17, 2, 4, 8, 1, "f32", "fold", ("bs", "ld+bs", "ld", "ld"), "all", "ordinary", "M = 442: two 256-pixel tiles, the second ragged; 13 wgrad slices of 34 rows"),
+    (1, 13, 17, 8, 4, 4, 1, "bf16", "stats+bias", (_D, _D, "ld+bs", "bs"), "all", "ordinary", "OC = 32: 288 wgrad threads (a ragged second block), 6 slices of 37 rows"),
+    (3, 11, 6, 2, 16, 16, 2, "f32", "stats+relu", ("ld", "ld", "bs", "ld"), "dw", "ordinary", "stride 2 on an odd and an even size at once, 18 pixels per image"),
+    (2, 16, 10, 4, 32, 4, 2, "bf16", "fold+relu", ("ld+bs", _D, _D, "ld+bs"), "dx", "ordinary", "Og 4 < Cg 32, stride 2 on even sizes"),
+    (2, 6, 7, 4, 4, 8, 1, "f32", "none", ("ld", "ld", "ld", "ld"), "all", "corner", "corner pixels only: a halo or bounds slip changes an exact, small set"),
+    (1, 9, 5, 2, 16, 16, 2, "bf16", "bias", ("bs", "bs", "bs", "bs"), "all", "corner", "corner pixels under stride 2"),
+    (2, 5, 3, 3, 8, 12, 1, "bf16", "none", (_D, "ld+bs", "ld+bs", "ld+bs"), "dx", "corner", "corner pixels, Og 12, dx alone"),
+    (2, 7, 6, 4, 8, 8, 1, "bf16", "none", ("ld+bs", _D, "ld", "bs"), "all", "lastpixel", "dy at the last output pixel alone"),
+    (1, 8, 11, 3, 4, 4, 2, "f32", "none", ("ld", _D, _D, _D), "all", "lastpixel", "dy at the last output pixel under stride 2, C = 12"),
+    (3, 5, 5, 2, 32, 20, 1, "f32", "none", (_D, _D, "bs", "ld"), "dbias", "lastpixel", "dbias of one pixel: every other channel sum is an exact zero"),
+    (2, 9, 14, 8, 4, 4, 1, "f16", "none", ("ld", "ld", _D, _D), "none", "ordinary", "fp16 forward at Cg 4"),
+    (1, 7, 5, 4, 8, 12, 2, "f16", "bias", ("bs", "bs", _D, _D), "none", "ordinary", "fp16 forward at Cg 8 with bias, stride 2"),
+    (2, 6, 6, 2, 32, 8, 1, "f16", "fold+relu", (_D, "ld+bs", _D, _D), "none", "ordinary", "fp16 forward at Cg 32, folded BatchNorm + ReLU"),
+    (1, 5, 9, 3, 8, 8, 1, "f16", "none", ("ld+bs", _D, _D, _D), "none", "ordinary", "fp16 forward at Cg 8, 6 quads"),
+    (2, 4, 3, 2, 32, 32, 2, "f16", "bias", ("ld", "ld", _D, _D), "none", "ordinary", "fp16 forward at Cg 32 with bias"),
+    (1, 11, 6, 6, 4, 8, 1, "f16", "fold+relu", (_D, "bs", _D, _D), "none", "ordinary", "fp16 forward at Cg 4, folded BatchNorm + ReLU"),
+    (1, 257, 257, 8, 4, 32, 1, "bf16", "none", _DENSE, "all", "ordinary", "4129 forward tiles on 4096 blocks: the forward's grid-stride loop"),
+    (1, 257, 257, 8, 32, 4, 1, "bf16", "bias", _DENSE, "all", "ordinary", "4129 data-gradient tiles on 4096 blocks: the data gradient's grid-stride loop"),
+    (1, 65, 65, 16, 4, 128, 1, "f32", "stats", _DENSE, "all", "ordinary", "265 tiles on 256 blocks x 8 slices: statistics summed over two tiles per thread; S = 56 bounded by the thread count"),
+)
+
+
+def gconv_cases(seed=2111):
+    """(id, N, H, W, groups, Cg, Og, stride, dtype, epilogue, views, arm, inputs, why, seed)"""
+    return [("gconv%d-%d" % (seed, i),) + row + (seed + i,) for i, row in enumerate(_GCONV_ROWS)]
+
+
+def _gc_has_dx(c):
+    return c[11] in ("all", "dx", "dx-acc+dw")
+
+
+def _gc_has_wgrad(c):
+    return c[11] in ("all", "dw", "dbias", "dx-acc+dw")
+
+
+def _gc_fwd_quads(c):
+    return gconv_dims(c)[1] // 4
+
+
+def _gc_dgrad_quads(c):
+    return gconv_dims(c)[0] // 4 if _gc_has_dx(c) else None
+
+
+def _gc_block_regimes(side, quads_of):
+    return [
+        ("%s: QB < 64 dividing 256" % side, lambda c: quads_of(c) is not None and quads_of(c) < 64 and 256 % quads_of(c) == 0),
+        ("%s: QB not dividing 256 (idle threads)" % side, lambda c: quads_of(c) is not None and quads_of(c) < 64 and 256 % quads_of(c) != 0),
+        ("%s: exactly one full slice" % side, lambda c: quads_of(c) == 64),
+        ("%s: several slices, ragged last" % side, lambda c: quads_of(c) is not None and quads_of(c) > 64 and quads_of(c) % 64 != 0),
+    ]
+
+
+def _gc_fwd_tile(c):
+    return GCONV_PPT * gconv_block(_gc_fwd_quads(c))[1]
+
+
+def _gc_fwd_grid(c):
+    return gconv_grid(gconv_dims(c)[4], gconv_dims(c)[1], c[9].startswith("stats"))
+
+
+def _gc_plan(c):
+    return gconv_wgrad_plan(gconv_dims(c)[4], gconv_dims(c)[1], c[5]) if _gc_has_wgrad(c) else None
+
+
+GCONV_REGIMES = [("Cg = %d, %s" % (cg, d), (lambda cg_, d_: lambda c: c[5] == cg_ and c[8] == d_)(cg, d)) for cg in (4, 8, 16, 32) for d in ("f32", "bf16")] + [
+    ("Og == Cg", lambda c: c[6] == c[5]),
+    ("Og < Cg", lambda c: c[6] < c[5]),
+    ("Og > Cg", lambda c: c[6] > c[5]),
+    ("Og = 4", lambda c: c[6] == 4),
+    ("Og not a power of two (12, 20)", lambda c: c[6] in (12, 20)),
+] + _gc_block_regimes("forward", _gc_fwd_quads) + _gc_block_regimes("dgrad", _gc_dgrad_quads) + [
+    ("forward: M below one tile", lambda c: gconv_dims(c)[4] < _gc_fwd_tile(c)),
+    ("forward: M % (4 PS) != 0", lambda c: gconv_dims(c)[4] % _gc_fwd_tile(c) != 0),
+    ("forward: M % 4 != 0", lambda c: gconv_dims(c)[4] % 4 != 0),
+    ("forward: OW % 4 != 0 (pixels cross a row end)", lambda c: gconv_dims(c)[3] % 4 != 0),
+    ("forward: N > 1, OH OW % 4 != 0 (pixels cross an image end)", lambda c: c[1] > 1 and (gconv_dims(c)[2] * gconv_dims(c)[3]) % 4 != 0),
+    ("dgrad: W % 4 != 0 (pixels cross a row end)", lambda c: _gc_has_dx(c) and c[3] % 4 != 0),
+    ("dgrad: N > 1, H W % 4 != 0 (pixels cross an image end)", lambda c: _gc_has_dx(c) and c[1] > 1 and (c[2] * c[3]) % 4 != 0),
+    ("grid-stride: forward, no statistics", lambda c: not c[9].startswith("stats") and _gc_fwd_grid(c)[3]),
+    ("grid-stride: forward with statistics", lambda c: c[9].startswith("stats") and _gc_fwd_grid(c)[3]),
+    ("grid-stride: dgrad", lambda c: _gc_has_dx(c) and gconv_grid(gconv_dims(c)[5], gconv_dims(c)[0], False)[3]),
+    ("stride 1", lambda c: c[7] == 1),
+    ("stride 2", lambda c: c[7] == 2),
+    ("H or W = 1", lambda c: 1 in (c[2], c[3])),
+    ("H or W = 2", lambda c: 2 in (c[2], c[3])),
+    ("stride 2 on an even size", lambda c: c[7] == 2 and (c[2] % 2 == 0 or c[3] % 2 == 0)),
+    ("stride 2 on an odd size", lambda c: c[7] == 2 and (c[2] % 2 == 1 or c[3] % 2 == 1)),
+    ("non-square", lambda c: c[2] != c[3]),
+] + [("%s view: %s" % (t, v), (lambda i_, v_, need_: lambda c: c[10][i_] == v_ and need_(c))(i, v, need))
+     for i, (t, need) in enumerate((("input", lambda c: True), ("output", lambda c: True), ("dy", lambda c: c[11] != "none"), ("dx", _gc_has_dx)))
+     for v in ("ld", "bs", "ld+bs")] + [
+    ("all dense", lambda c: c[10] == _DENSE),
+] + [("epilogue: %s" % e, (lambda e_: lambda c: c[9] == e_)(e)) for e in GCONV_EPILOGUES] + [
+    ("f16 epilogue: %s" % e, (lambda e_: lambda c: c[8] == "f16" and c[9] == e_)(e)) for e in ("none", "bias", "fold+relu")] + [
+    ("f16 at Cg = %d" % cg, (lambda cg_: lambda c: c[8] == "f16" and c[5] == cg_)(cg)) for cg in (4, 8, 32)] + [
+    ("backward arm: %s" % a, (lambda a_: lambda c: c[11] == a_)(a)) for a in GCONV_ARMS] + [
+    ("wgrad: S = 1", lambda c: _gc_plan(c) is not None and _gc_plan(c)[2] == 1),
+    ("wgrad: S > 1, rows_per_slice % 4 != 0", lambda c: _gc_plan(c) is not None and _gc_plan(c)[2] > 1 and _gc_plan(c)[1] % 4 != 0),
+    ("wgrad: S bounded by the thread count", lambda c: _gc_plan(c) is not None and 1048576 // _gc_plan(c)[0] < gconv_dims(c)[4] // 32),
+    ("wgrad: threads % 256 != 0", lambda c: _gc_plan(c) is not None and _gc_plan(c)[0] % 256 != 0),
+] + [("inputs: %s" % r, (lambda r_: lambda c: c[12] == r_)(r)) for r in GCONV_INPUTS]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 CASES = {
     "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
     "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
-    "mha": mha_cases(), "msda": msda_cases(),
+    "mha": mha_cases(), "msda": msda_cases(), "gconv": gconv_cases(),
 }
 REGIMES = {
     "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
     "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
-    "mha": MHA_REGIMES, "msda": MSDA_REGIMES,
+    "mha": MHA_REGIMES, "msda": MSDA_REGIMES, "gconv": GCONV_REGIMES,
 }
 IN_DOMAIN = {
     "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
     "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
-    "mha": mha_in_domain, "msda": msda_in_domain,
+    "mha": mha_in_domain, "msda": msda_in_domain, "gconv": gconv_in_domain,
 }
 
 
-# cases a regime must keep: two, except where the sweep asks for exactly one
-REGIME_MIN = {("maxpool", "k = 7"): 1, ("msda", "dref on a band pyramid (GRAD_GLOBAL)"): 1}
+# cases a regime must keep: two, except where the sweep asks for exactly one.  gconv: a block goes round its tile loop twice only from
+# 4097 tiles (257 x 257 pixels) or, with statistics, from 2049 / nslices: one case each, under GCONV_LONG_MAX_ELEMS
+REGIME_MIN = {("maxpool", "k = 7"): 1, ("msda", "dref on a band pyramid (GRAD_GLOBAL)"): 1,
+              ("gconv", "grid-stride: forward, no statistics"): 1, ("gconv", "grid-stride: forward with statistics"): 1, ("gconv", "grid-stride: dgrad"): 1}
 
 
 def regime_hits(op):

@@ -50,6 +50,14 @@ def test_case_sizes_stay_small():
         assert c[1] * c[2] * c[3] * c[3] <= fc.MAX_ELEMS and 1 <= c[1] <= 4 and c[2] in fc.MHA_MS and c[3] in fc.MHA_LS
     for c in fc.CASES["msda"]:          # its own cap: the smallest pyramid the row-band kernels take has Lv ~ 2500
         assert c[1] * max(fc.msda_lq(c), sum(h * w for h, w in c[3])) * c[2] * 32 <= fc.MSDA_MAX_ELEMS
+    long_cases = []
+    for c in fc.CASES["gconv"]:         # the three grid-stride cases have their own cap, the largest of their own tensors
+        C, OC, _, _, M, Mi = fc.gconv_dims(c)
+        hits = [name for name, pred in fc.GCONV_REGIMES if name.startswith("grid-stride") and pred(c)]
+        assert max(Mi * C, M * OC) <= (fc.GCONV_LONG_MAX_ELEMS if hits else fc.MAX_ELEMS), c[0]
+        if hits:
+            long_cases.append(max(Mi * C, M * OC))
+    assert len(long_cases) == 3 and max(long_cases) == fc.GCONV_LONG_MAX_ELEMS <= 17000000
 
 
 def test_mha_sweep_covers_what_it_was_written_for():
@@ -84,6 +92,44 @@ def test_msda_sweep_covers_what_it_was_written_for():
     assert fc.msda_band_geometry(fc.MSDA_FIN3, 1, 8) == (0, 0, 0) and fc.msda_band_geometry(((64, 64),), 2, 8) == (0, 0, 0)
 
 
+def test_gconv_sweep_covers_what_it_was_written_for():
+    """one assertion per gap the sweep was written to close in csrc/gconv.hip, against the mirrored launch arithmetic"""
+    cases = fc.CASES["gconv"]
+    assert fc.gconv_cases() == cases and 40 <= len(cases) <= 50
+    bwd = [c for c in cases if c[11] != "none"]
+    dims = {c[0]: fc.gconv_dims(c) for c in cases}
+    # output channels per group different from input channels per group, on both sides, Og = 4 and Og no power of two, forward and data gradient
+    assert {4, 12, 20} <= {c[6] for c in bwd if c[6] != c[5] and fc._gc_has_dx(c)} and any(c[6] < c[5] for c in bwd) and any(c[6] > c[5] for c in bwd)
+    # a second trip of each grid-stride loop: forward (cap 4096), data gradient (cap 4096), forward with statistics (cap ceil(2048 / nslices))
+    loops = [c for c in cases if fc._gc_fwd_grid(c)[3]]
+    assert any(not c[9].startswith("stats") and fc._gc_fwd_grid(c)[1] == 4096 for c in loops)
+    assert any(fc._gc_has_dx(c) and fc.gconv_grid(dims[c[0]][5], dims[c[0]][0], False)[1:] == (4096, 1, True) for c in cases)
+    assert any(c[9].startswith("stats") and fc._gc_fwd_grid(c)[1] == fc._ceil_div(2048, fc._gc_fwd_grid(c)[2]) and fc._gc_fwd_grid(c)[2] > 1 for c in loops)
+    # dbias: in the full call and alone
+    assert sum(c[11] == "all" for c in cases) >= 2 and sum(c[11] == "dbias" for c in cases) >= 2
+    # block shapes that are no powers of two: idle threads at quads 3, 5, 6, 12 on either side; a ragged last channel slice on either side
+    assert {3, 5, 6, 12} <= {fc._gc_fwd_quads(c) for c in cases} | {fc._gc_dgrad_quads(c) for c in cases}
+    assert any(fc._gc_fwd_quads(c) > 64 and fc._gc_fwd_quads(c) % 64 for c in cases) and any((fc._gc_dgrad_quads(c) or 0) > 64 and fc._gc_dgrad_quads(c) % 64 for c in cases)
+    # tiny and awkward maps: H or W of 1 and of 2, M below a tile, M % 4 != 0, even sizes under stride 2
+    assert {1, 2} <= {v for c in cases for v in (c[2], c[3])}
+    assert any(dims[c[0]][4] < fc._gc_fwd_tile(c) for c in cases) and any(dims[c[0]][4] % 4 for c in cases)
+    assert any(c[7] == 2 and c[2] % 2 == 0 and c[3] % 2 == 0 for c in cases)
+    # batch strides larger than the map, for each of in_bs, out_bs, dy_bs and dx_bs
+    for i, need in enumerate((lambda c: True, lambda c: True, lambda c: c[11] != "none", fc._gc_has_dx)):
+        assert sum("bs" in c[10][i] and need(c) for c in cases) >= 4, i
+    # the weight gradient's slice plan: S = 1, slices no multiple of the unroll, S limited by the thread count, a ragged last thread block
+    plans = [fc._gc_plan(c) for c in cases if fc._gc_plan(c) is not None]
+    assert any(p[2] == 1 for p in plans) and any(p[2] > 1 and p[1] % 4 for p in plans) and any(p[0] % 256 for p in plans)
+    assert any(fc._gc_plan(c) is not None and 1048576 // fc._gc_plan(c)[0] < dims[c[0]][4] // 32 for c in cases)
+    # call forms: dw alone, dbias alone, dx alone; bias without scale; ReLU together with statistics; float16 at Cg other than 4
+    assert {"dw", "dbias", "dx", "dx-acc+dw"} <= {c[11] for c in cases} and {"bias", "stats+bias", "stats+relu"} <= {c[9] for c in cases}
+    assert {4, 8, 32} <= {c[5] for c in cases if c[8] == "f16"} and {"none", "bias", "fold+relu"} == {c[9] for c in cases if c[8] == "f16"}
+    # C % 8 != 0 is inside the domain only as a slice of a wider buffer
+    odd = [c for c in cases if dims[c[0]][0] % 8]
+    assert odd and all("ld" in c[10][0] for c in odd)
+    assert not fc.gconv_in_domain(odd[0][:10] + (("dense",) + odd[0][10][1:],) + odd[0][11:])
+
+
 def test_mirrored_predicates_at_known_points():
     """the shapes the fixed tests and the model use, whose path is known from the dispatchers' comments"""
     assert fc.bn_rowgeom(64) == (256, 16) and fc.bn_rowgeom(1024) == (256, 1) and fc.bn_rowgeom(2048) == (512, 1) and fc.bn_rowgeom(1028) == (257, 1)
@@ -102,6 +148,10 @@ def test_mirrored_predicates_at_known_points():
     assert fc.mha_path(True, 110, 1, True) == 0 and fc.mha_path(True, 110, 0, False) == 0 and fc.mha_path(True, 2, 0, True) == 1
     assert [fc.mha_tiles(L) for L in (1, 16, 17, 110, 113, 128)] == [1, 1, 2, 7, 8, 8]
     assert [fc.mha_fwd_chunks(L) for L in (1, 32, 33, 110, 128)] == [1, 1, 2, 4, 4]
+    assert [fc.gconv_block(q) for q in (3, 8, 64, 80)] == [(3, 85), (8, 32), (64, 4), (64, 4)] and fc.gconv_grid(64, 320, False)[2] == 2
+    assert fc.gconv_wgrad_plan(221, 32, 4) == (288, 37, 6) and fc.gconv_wgrad_plan(20, 32, 4)[2] == 1 and fc.gconv_wgrad_plan(4225, 2048, 4) == (18432, 76, 56)
+    assert fc.gconv_grid(4225, 2048, True) == (265, 256, 8, True) and fc.gconv_grid(8 * 64 * 64, 256, True) == (2048, 2048, 1, False)
+    assert fc.gconv_grid(257 * 257, 256, False) == (4129, 4096, 1, True) and fc.gconv_grid(257 * 257, 32, False) == (517, 517, 1, False)
 
 
 def test_window_cases():

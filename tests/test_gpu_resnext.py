@@ -22,33 +22,45 @@ def _P(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _padded(t_nhwc, ld, dtype):
-    """device NHWC map whose pixel stride is ld >= C (a channel slice of a wider buffer)"""
+def _padded(t_nhwc, ld, dtype, bs=None, fill=0.0):
+    """device NHWC map whose pixel stride is ld >= C (a channel slice of a wider buffer) and whose batch stride is bs >= H * W * ld (padding
+    behind every image); everything the view does not address holds `fill`"""
     N, H, W, C = t_nhwc.shape
-    buf = torch.zeros(N, H, W, ld, dtype=_TD[dtype], device="cuda")
-    buf[..., :C] = t_nhwc.to(device="cuda", dtype=_TD[dtype])
-    return buf[..., :C]
+    bs = bs or H * W * ld
+    buf = torch.full((N * bs,), fill, dtype=_TD[dtype], device="cuda")
+    view = buf.as_strided((N, H, W, C), (bs, W * ld, ld, 1))
+    view.copy_(t_nhwc.to(device="cuda", dtype=_TD[dtype]))
+    return view
 
 
-def _run_fwd(x, w, groups, stride, dtype, relu=False, bias=None, scale=None, stats=None, ld_in=None, ld_out=None):
+def _whole(view):
+    """the flat buffer behind a _padded view"""
+    return view.as_strided((view.shape[0] * view.stride(0),), (1,), 0)
+
+
+def _run_fwd(x, w, groups, stride, dtype, relu=False, bias=None, scale=None, stats=None, ld_in=None, ld_out=None, bs_in=None, bs_out=None, fill=0.0,
+             xd=None, wd=None):
+    """x, w on the host (or xd, wd as a former call returned them); the output starts as `fill` everywhere"""
     N, H, W, C = x.shape
     OC = w.shape[0]
     OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-    xd = _padded(x, ld_in or C, dtype)
-    wd = w.permute(0, 2, 3, 1).contiguous().to(device="cuda", dtype=_TD[dtype])       # [OC][3][3][Cg]
-    y = _padded(torch.zeros(N, OH, OW, OC), ld_out or OC, dtype)
+    if xd is None:
+        xd = _padded(x, ld_in or C, dtype, bs_in, fill)
+    if wd is None:
+        wd = w.permute(0, 2, 3, 1).contiguous().to(device="cuda", dtype=_TD[dtype])       # [OC][3][3][Cg]
+    y = _padded(torch.full((N, OH, OW, OC), fill), ld_out or OC, dtype, bs_out, fill)
     L = _lib.lib()
     L.call("emrt_gconv2d", _P(xd), _P(wd), _P(y), _P(bias), N, H, W, C, xd.stride(2), xd.stride(0), OH, OW, OC, y.stride(2), y.stride(0), stride, groups,
            int(relu), _P(stats), _P(scale), dtype, ctx().stream)
     return y, xd, wd
 
 
-def _run_bwd(xd, wd, dy, groups, stride, dtype, dx=None, accumulate=False, dw=None):
+def _run_bwd(xd, wd, dy, groups, stride, dtype, dx=None, accumulate=False, dw=None, dbias=None):
     N, H, W, C = xd.shape
     _, OH, OW, OC = dy.shape
     L = _lib.lib()
     L.call("emrt_gconv2d_bwd", _P(xd), _P(dy), _P(wd), _P(dx), dx.stride(2) if dx is not None else 0, dx.stride(0) if dx is not None else 0, int(accumulate),
-           _P(dw), None, N, H, W, C, xd.stride(2), xd.stride(0), OH, OW, OC, dy.stride(2), dy.stride(0), stride, groups, dtype, ctx().stream)
+           _P(dw), _P(dbias), N, H, W, C, xd.stride(2), xd.stride(0), OH, OW, OC, dy.stride(2), dy.stride(0), stride, groups, dtype, ctx().stream)
 
 
 def _ref(x, w, groups, stride, dy=None):
