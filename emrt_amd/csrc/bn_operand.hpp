@@ -59,13 +59,17 @@ struct BnOperand {
 
 // All threads of the block: lds[0..C) = scale, lds[C..2C) = shift; block `first` also saves mean / invstd and updates the running
 // statistics (Paddle convention: running = momentum * running + (1 - momentum) * batch, biased variance).  Ends with a barrier.
-__device__ __forceinline__ void bn_operand_preamble(const BnOperand& b, int C, float* lds, bool first) {
-  for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
+// c0, cs: a block that only touches the channel slice [c0, c0 + cs) builds (and, when `first`, saves) that slice alone:
+// lds[0..cs) = scale, lds[cs..2cs) = shift of channels c0.. (the default is the whole layer)
+__device__ __forceinline__ void bn_operand_preamble(const BnOperand& b, int C, float* lds, bool first, int c0 = 0, int cs = -1) {
+  if (cs < 0) cs = C;
+  for (int l = threadIdx.x; l < cs; l += blockDim.x) {
+    const int ch = c0 + l;
     const BnChan k = bn_chan(b.sums, nullptr, nullptr, C, ch, b.inv_count, b.eps);
     float sc, sh;
     bn_scale_shift(k.mean, k.invstd, b.gamma[ch], b.beta[ch], sc, sh);
-    lds[ch] = sc;
-    lds[C + ch] = sh;
+    lds[l] = sc;
+    lds[cs + l] = sh;
     if (first) {
       b.mean[ch] = k.mean;
       b.invstd[ch] = k.invstd;

@@ -56,7 +56,9 @@ struct Tuning {
   int msda_fwd_threads; // ... threads per block (1024)
   int msda_fwd_probe;   // timing experiments only (results are WRONG): forward 1 = no gather, 2 = no staging, 4 = no preparation;
                         // value-gradient scatter 16 = no |g| scan, 32 = no sample loop (tools/exp/probe_msda_*.sh)
-  int bn_block_kb;      // BatchNorm streaming kernels: KB of input per block (8)
+  int bn_block_kb;      // BatchNorm streaming kernels: KB of input per block (0 = automatic: 1024 blocks of 2 to 8 KB)
+  int bn_slice_c;       // ... channels per block (a block owns a channel slice x a run of rows): 0 = automatic, n = slices of n channels
+                        // where the shape allows, n >= C = whole rows (tests compare the two bit for bit; A/B knob)
   int bn_operand_blocks; // kernels that apply BatchNorm to their input operand (bn_operand.hpp): most blocks per launch (0 = 1024; the classifier kernel 512)
   int ln_bwd_rows;      // LayerNorm backward: rows per block (0 = 32) and most blocks (0 = 512): every block ends with 2C fp32 atomics
   int ln_bwd_max_blocks;

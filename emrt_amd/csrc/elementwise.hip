@@ -19,7 +19,8 @@ const TuneEntry kTune[] = {
     {"thin_cblk", &emrt::Tuning::thin_cblk, 64},        {"thin_blocks", &emrt::Tuning::thin_blocks, 128},
     {"thin_ch", &emrt::Tuning::thin_ch, 8},             {"no_thin_bwd", &emrt::Tuning::no_thin_bwd, 0},
     {"pair_max", &emrt::Tuning::pair_max, 768},         {"msda_fwd_global", &emrt::Tuning::msda_fwd_global, 0},
-    {"bn_block_kb", &emrt::Tuning::bn_block_kb, 8},     {"ln_atomic", &emrt::Tuning::ln_atomic, 1},
+    {"bn_block_kb", &emrt::Tuning::bn_block_kb, 0},     {"ln_atomic", &emrt::Tuning::ln_atomic, 1},
+    {"bn_slice_c", &emrt::Tuning::bn_slice_c, 0},
     {"msda_fwd_chunks", &emrt::Tuning::msda_fwd_chunks, 0}, {"msda_fwd_threads", &emrt::Tuning::msda_fwd_threads, 1024},
     {"msda_fwd_probe", &emrt::Tuning::msda_fwd_probe, 0}, {"wgrad_nst", &emrt::Tuning::wgrad_nst, 2},
     {"igemm64_nst", &emrt::Tuning::igemm64_nst, 3}, {"msda_bwd_global", &emrt::Tuning::msda_bwd_global, 0},

@@ -173,6 +173,9 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ sums, int C, fl
 // sums; block 0 also saves them for backward and updates the running statistics (Paddle convention: momentum 0.9 =>
 // running = 0.9*running + 0.1*batch, biased variance).  Threads own a fixed channel quad, so the per-channel constants
 // are computed once per thread and the row loop is a pure streaming fma.
+// A block owns the channel slice [blockIdx.x * cs, + cs) x a run of rows (grid = slices x row blocks; cs == C: whole rows, one slice), so its
+// preamble derives the constants of cs channels only (cs * 128 B of fp64 sums instead of C * 128 B); the first row block of every slice saves
+// mean / invstd and updates the running statistics of its own channels -- every channel exactly once per launch.
 template <class T, bool JOIN = false>
 __global__ __launch_bounds__(512) void bn_apply_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ res, int ldres,
                                                        T* __restrict__ y, int ldy, const double* __restrict__ sums, double inv_count,
@@ -180,32 +183,36 @@ __global__ __launch_bounds__(512) void bn_apply_kernel(const T* __restrict__ x, 
                                                        float* __restrict__ invstd_out, float* __restrict__ run_mean,
                                                        float* __restrict__ run_var, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, long long M, int C, int relu, int rows_per_pass,
-                                                       BnOperand rbn) {
+                                                       int cs, BnOperand rbn) {
   // rbn.sums != null: `res` is the RAW output of the shortcut's conv and its own training-mode BatchNorm (no ReLU) is applied as it is
   // loaded -- out = relu(BN(x) + BN_shortcut(res)), the first block of a ResNet stage (paddle_vision_resnet.py:132-147, 226-233) -- instead
   // of a separate launch that writes the normalised shortcut for this one to read back
-  const int quads = C / 4;
-  const int c = (threadIdx.x % quads) * 4;
+  const int quads = cs / 4;
+  const int c0 = blockIdx.x * cs;                  // first channel of the block's slice
+  const int lc = (threadIdx.x % quads) * 4;        // the thread's quad within the slice
+  const int c = c0 + lc;
   const int lane_row = threadIdx.x / quads;
-  // A block only streams ~8 KB, so its time is latency: the first row's loads go out BEFORE the per-channel preamble
+  const bool first = blockIdx.y == 0;              // the slice's first row block: the once-per-layer duties for the slice's channels
+  // A block only streams a few KB, so its time is latency: the first row's loads go out BEFORE the per-channel preamble
   // (fp64 replica sums -> scale/shift -> LDS -> barrier) and every later row is fetched one iteration ahead.
-  const long long rstep = (long long)gridDim.x * rows_per_pass;
-  long long r = (long long)blockIdx.x * rows_per_pass + lane_row;
+  const long long rstep = (long long)gridDim.y * rows_per_pass;
+  long long r = (long long)blockIdx.y * rows_per_pass + lane_row;
   float v[4], w[4];
   if (r < M) {
     Vec4<T>::load(x + r * ldx + c, v);
     if (res) Vec4<T>::load(res + r * ldres + c, w);
   }
   // per-channel scale/shift computed cooperatively (one channel per thread) and shared through LDS
-  extern __shared__ float bn_lds[];          // [2][C] (+ [2][C] for the shortcut's BatchNorm)
-  if constexpr (JOIN) bn_operand_preamble(rbn, C, bn_lds + 2 * C, blockIdx.x == 0);      // (its barrier is harmless here)
-  for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
+  extern __shared__ float bn_lds[];          // [2][cs] (+ [2][cs] for the shortcut's BatchNorm)
+  if constexpr (JOIN) bn_operand_preamble(rbn, C, bn_lds + 2 * cs, first, c0, cs);      // (its barrier is harmless here)
+  for (int l = threadIdx.x; l < cs; l += blockDim.x) {
+    const int ch = c0 + l;
     const BnChan k = bn_chan(sums, run_mean, run_var, C, ch, inv_count, eps);
     float scale, shift;
     bn_scale_shift(k.mean, k.invstd, gamma[ch], beta[ch], scale, shift);
-    bn_lds[ch] = scale;
-    bn_lds[C + ch] = shift;
-    if (sums && blockIdx.x == 0) {
+    bn_lds[l] = scale;
+    bn_lds[cs + l] = shift;
+    if (sums && first) {
       mean_out[ch] = k.mean;
       invstd_out[ch] = k.invstd;
       if (run_mean) {
@@ -221,8 +228,8 @@ __global__ __launch_bounds__(512) void bn_apply_kernel(const T* __restrict__ x, 
   float sc[4], sh[4], rsc[JOIN ? 4 : 1], rsh[JOIN ? 4 : 1];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    sc[e] = bn_lds[c + e]; sh[e] = bn_lds[C + c + e];
-    if constexpr (JOIN) { rsc[e] = bn_lds[2 * C + c + e]; rsh[e] = bn_lds[3 * C + c + e]; }
+    sc[e] = bn_lds[lc + e]; sh[e] = bn_lds[cs + lc + e];
+    if constexpr (JOIN) { rsc[e] = bn_lds[2 * cs + lc + e]; rsh[e] = bn_lds[3 * cs + lc + e]; }
   }
   while (r < M) {
     const long long rn = r + rstep;
@@ -255,7 +262,8 @@ __global__ __launch_bounds__(512) void bn_apply_kernel(const T* __restrict__ x, 
 }
 
 // dx = gamma*invstd*(dy' - sum_dy/count - xhat*sum_dyxhat/count); optional dres = dy' (gradient of the fused residual);
-// block 0 accumulates dgamma += sum dy'*xhat, dbeta += sum dy' (from this rank's `lsums` when given: SyncBN).
+// the first row block of every channel slice (geometry as bn_apply_kernel) accumulates dgamma += sum dy'*xhat, dbeta += sum dy' for the slice's
+// channels (from this rank's `lsums` when given: SyncBN).
 // MX: the ReLU mask is re-derived from x (mbeta; bn_operand.hpp) -- a separate instantiation: with the mask parameters in the common
 // kernel it went from 64 to 68 registers (8 -> 7 waves per SIMD) and from 8.3 to 9.8 us per launch x 75 launches
 template <class T, bool MX = false>
@@ -265,22 +273,25 @@ __global__ __launch_bounds__(512) void bn_bwd_dx_kernel(const T* __restrict__ x,
                                                         const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                         const double* __restrict__ sums, const double* __restrict__ lsums,
                                                         double inv_count, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                        long long M, int C, int rows_per_pass, const float* __restrict__ beta_y, int sums_vs_x,
+                                                        long long M, int C, int rows_per_pass, int cs, const float* __restrict__ beta_y, int sums_vs_x,
                                                         const float* __restrict__ mbeta) {
-  const int quads = C / 4;
-  const int c = (threadIdx.x % quads) * 4;
+  const int quads = cs / 4;
+  const int c0 = blockIdx.x * cs;
+  const int lc = (threadIdx.x % quads) * 4;
+  const int c = c0 + lc;
   const int lane_row = threadIdx.x / quads;
   // as in bn_apply_kernel: first row fetched before the preamble, later rows one iteration ahead
-  const long long rstep = (long long)gridDim.x * rows_per_pass;
-  long long r = (long long)blockIdx.x * rows_per_pass + lane_row;
+  const long long rstep = (long long)gridDim.y * rows_per_pass;
+  long long r = (long long)blockIdx.y * rows_per_pass + lane_row;
   float v[4], g[4], yy[4];
   if (r < M) {
     Vec4<T>::load(x + r * ldx + c, v);
     Vec4<T>::load(dy + r * lddy + c, g);
     if (y) Vec4<T>::load(y + r * ldy + c, yy);
   }
-  extern __shared__ float bn_lds[];          // [2][C]: sum_dy/count, sum_dyxhat/count
-  for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
+  extern __shared__ float bn_lds[];          // [2][cs]: sum_dy/count, sum_dyxhat/count of the slice's channels
+  for (int l = threadIdx.x; l < cs; l += blockDim.x) {
+    const int ch = c0 + l;
     const double t0 = rep_sum(sums, C, ch);
     double t1 = rep_sum(sums, C, C + ch);
     if (beta_y) {      // the sums are (sum dy', sum dy' * y) from the consumer's dgrad epilogue: xhat = (y - beta) / gamma where y > 0
@@ -288,9 +299,9 @@ __global__ __launch_bounds__(512) void bn_bwd_dx_kernel(const T* __restrict__ x,
       t1 = gm != 0.0 ? (t1 - (double)beta_y[ch] * t0) / gm : 0.0;
     }
     if (sums_vs_x) t1 = (t1 - (double)mean[ch] * t0) * (double)invstd[ch];      // (sum dy', sum dy' * x): xhat = (x - mean) * invstd
-    bn_lds[ch] = (float)(t0 * inv_count);
-    bn_lds[C + ch] = (float)(t1 * inv_count);
-    if (blockIdx.x == 0) {
+    bn_lds[l] = (float)(t0 * inv_count);
+    bn_lds[cs + l] = (float)(t1 * inv_count);
+    if (blockIdx.y == 0) {
       if (dbeta) dbeta[ch] += (float)(lsums ? rep_sum(lsums, C, ch) : t0);
       if (dgamma) dgamma[ch] += (float)(lsums ? rep_sum(lsums, C, C + ch) : t1);
     }
@@ -302,8 +313,8 @@ __global__ __launch_bounds__(512) void bn_bwd_dx_kernel(const T* __restrict__ x,
     mu[e] = mean[c + e];
     is[e] = invstd[c + e];
     gi[e] = gamma[c + e] * is[e];
-    k0[e] = bn_lds[c + e];
-    k1[e] = bn_lds[C + c + e];
+    k0[e] = bn_lds[lc + e];
+    k1[e] = bn_lds[cs + lc + e];
     if constexpr (MX) bn_scale_shift(mu[e], is[e], gamma[c + e], mbeta[c + e], msc[e], msh[e]);      // ReLU mask re-derived from x (bn_operand.hpp)
   }
   while (r < M) {
@@ -1234,21 +1245,44 @@ extern "C" size_t emrt_colreduce_workspace_bytes(long long M, int C) {
 }
 
 // threads / rows-per-pass / grid for the hoisted (fixed channel quad per thread) BN kernels
-static inline bool bn_rowgeom(long long M, int C, int& threads, int& rows_per_pass, int& grid) {
+// bn_slice_c = 0: the slice width the in-step measurements chose (profiles/bn_slice_kernels.txt): 64 channels for every (C, M) of the
+// step -- 128 was level with it on the small maps and behind on the large ones, 256 and 512 behind everywhere
+static inline int bn_slice_auto(long long M, int C) {
+  (void)M; (void)C;
+  return 64;
+}
+// bn_block_kb = 0: bytes of (bf16) input per block.  With the preamble cut to a slice a block is cheap to start: aim at 1024 blocks of 2 to 8 KB --
+// maps of up to 2 / 4 MB gain from 2 / 4 KB blocks (5-6 us per launch instead of 6-7), the 8-32 MB maps lose 1-2 us there and keep 8 KB
+static inline long long bn_block_bytes_auto(long long M, int C) {
+  const long long b = M * C * 2 / 1024;
+  return b < 2048 ? 2048 : b > 8192 ? 8192 : b;
+}
+
+// A block owns a channel slice of cs channels x a run of rows; grid = (C / cs slices, row blocks).  cs == C is the whole-row geometry.
+static inline bool bn_rowgeom(long long M, int C, int& threads, int& rows_per_pass, int& cs, dim3& grid) {
   const int quads = C / 4;
   if (quads <= 256) { if (256 % quads) return false; threads = 256; rows_per_pass = 256 / quads; }
   else if (quads <= 512) { threads = quads; rows_per_pass = 1; }          // C = 2048 -> 512 threads
   else return false;
-  // every block first derives the per-channel constants (C x 16 fp64 loads + fp64 math, ~2 us of latency), so it should
-  // then stream a decent amount of data: ~32 KB of input per block, between 64 and 1024 blocks
-  const long long per_block = (long long)(g_tune.bn_block_kb > 0 ? g_tune.bn_block_kb : 8) * 1024;
+  // Every block first derives the per-channel constants of its channels (16 fp64 loads + fp64 math each, then LDS and a barrier): over whole rows
+  // that is C * 128 B of sums per block (262 KB at C = 2048) in front of a few KB of payload, so wide layers are cut into channel slices: a slice
+  // is 256 threads = cs / 4 channel quads x 256 / (cs / 4) rows per pass, a row of a slice a contiguous run of >= 128 B.  bn_slice_c: 0 = the
+  // rule below, n = slices of n channels where n divides C, n / 4 divides 256 and 64 <= n < C -- any other n (n >= C: the knob's "off") and any C
+  // the rule does not cut keep whole rows.
+  cs = g_tune.bn_slice_c > 0 ? g_tune.bn_slice_c : bn_slice_auto(M, C);
+  if (cs < 64 || cs >= C || cs % 4 || C % cs || 256 % (cs / 4)) cs = C;
+  if (cs < C) { threads = 256; rows_per_pass = 256 / (cs / 4); }
+  const int slices = C / cs;
+  // the payload target and the bounds are for the launch as a whole: row blocks x slices blocks of bn_block_kb KB of input each, 64 to 4096 of them
+  const long long per_block = g_tune.bn_block_kb > 0 ? (long long)g_tune.bn_block_kb * 1024 : bn_block_bytes_auto(M, C);
   long long g = (M * C * 2 + per_block - 1) / per_block;
   const long long gmax = (M + rows_per_pass - 1) / rows_per_pass;
   if (g < 64) g = 64;
   if (g > 4096) g = 4096;
+  g = (g + slices - 1) / slices;      // row blocks
   if (g > gmax) g = gmax;
   if (g < 1) g = 1;
-  grid = (int)g;
+  grid = dim3(slices, (unsigned)g);
   return true;
 }
 
@@ -1276,15 +1310,16 @@ extern "C" int emrt_bn_apply(const void* x, int ldx, const void* res, int ldres,
   EMRT_REQUIRE(x && y && gamma && beta, "null pointer");
   EMRT_REQUIRE(sums ? (mean && invstd) : (run_mean && run_var), "training needs mean/invstd outputs, eval needs running statistics");
   EMRT_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (!res || ldres % 4 == 0), "C and ld must be multiples of 4");
-  int threads, rpp, grid;
-  EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
+  int threads, rpp, cs;
+  dim3 grid;
+  EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, cs, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
   hipStream_t st = (hipStream_t)stream;
   const double inv_count = sums ? 1.0 / count : 0.0;
   BnOperand none;
   memset(&none, 0, sizeof(none));
   return with_fwd_dtype("emrt_bn_apply", dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const T*)x, ldx, (const T*)res, ldres, (T*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, none);
+    hipLaunchKernelGGL((bn_apply_kernel<T>), grid, dim3(threads), (size_t)2 * cs * sizeof(float), st, (const T*)x, ldx, (const T*)res, ldres, (T*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, cs, none);
     return check_launch("emrt_bn_apply");
   });
 }
@@ -1303,17 +1338,18 @@ extern "C" int emrt_bn_apply_join(const void* x, int ldx, const void* res_raw, i
   EMRT_REQUIRE(r_sums && r_mean && r_invstd && r_gamma && r_beta && r_count > 0.0 && count > 0.0 && (r_run_mean != nullptr) == (r_run_var != nullptr),
                "the shortcut's BatchNorm needs sums, mean, invstd, gamma, beta and a positive count");
   EMRT_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldres % 4 == 0, "C and ld must be multiples of 4");
-  int threads, rpp, grid;
-  EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
+  int threads, rpp, cs;
+  dim3 grid;
+  EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, cs, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
   BnOperand r;
   r.sums = r_sums; r.inv_count = 1.0 / r_count; r.eps = r_eps; r.momentum = r_momentum; r.mean = r_mean; r.invstd = r_invstd;
   r.run_mean = r_run_mean; r.run_var = r_run_var; r.gamma = r_gamma; r.beta = r_beta; r.relu = 0;
   hipStream_t st = (hipStream_t)stream;
   const double inv_count = 1.0 / count;
-  const size_t lds = (size_t)4 * C * sizeof(float);
+  const size_t lds = (size_t)4 * cs * sizeof(float);
   return with_train_dtype("emrt_bn_apply_join", dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL((bn_apply_kernel<T, true>), dim3(grid), dim3(threads), lds, st, (const T*)x, ldx, (const T*)res_raw, ldres, (T*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, r);
+    hipLaunchKernelGGL((bn_apply_kernel<T, true>), grid, dim3(threads), lds, st, (const T*)x, ldx, (const T*)res_raw, ldres, (T*)y, ldy, sums, inv_count, eps, momentum, mean, invstd, run_mean, run_var, gamma, beta, M, C, relu, rpp, cs, r);
     return check_launch("emrt_bn_apply_join");
   });
 }
@@ -1382,16 +1418,17 @@ extern "C" int emrt_bn_bwd_dx(const void* x, int ldx, const void* dy, int lddy, 
   EMRT_REQUIRE(x && dy && dx && mean && invstd && gamma && sums, "null pointer");
   EMRT_REQUIRE(!(mask_beta && (y || beta_y_moments || sums_vs_x)), "mask_beta (ReLU mask re-derived from x) excludes y and the fused-sum forms");
   EMRT_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0, "C and ld must be multiples of 4");
-  int threads, rpp, grid;
-  EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
+  int threads, rpp, cs;
+  dim3 grid;
+  EMRT_REQUIRE(bn_rowgeom(M, C, threads, rpp, cs, grid), "unsupported channel count (C/4 must divide 256, or C <= 2048)");
   hipStream_t st = (hipStream_t)stream;
   return with_train_dtype("emrt_bn_bwd_dx", dtype, [&](auto t) {
     using T = decltype(t);
     if (mask_beta) {
-      hipLaunchKernelGGL((bn_bwd_dx_kernel<T, true>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)nullptr, 0, (T*)dx, lddx, (T*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, nullptr, 0, mask_beta);
+      hipLaunchKernelGGL((bn_bwd_dx_kernel<T, true>), grid, dim3(threads), (size_t)2 * cs * sizeof(float), st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)nullptr, 0, (T*)dx, lddx, (T*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, cs, nullptr, 0, mask_beta);
       return check_launch("emrt_bn_bwd_dx");
     }
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<T>), dim3(grid), dim3(threads), (size_t)2 * C * sizeof(float), st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)y, ldy, (T*)dx, lddx, (T*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, beta_y_moments, sums_vs_x, mask_beta);
+    hipLaunchKernelGGL((bn_bwd_dx_kernel<T>), grid, dim3(threads), (size_t)2 * cs * sizeof(float), st, (const T*)x, ldx, (const T*)dy, lddy, (const T*)y, ldy, (T*)dx, lddx, (T*)dres, lddres, mean, invstd, gamma, sums, local_sums, 1.0 / count, dgamma, dbeta, M, C, rpp, cs, beta_y_moments, sums_vs_x, mask_beta);
     return check_launch("emrt_bn_bwd_dx");
   });
 }
