@@ -31,6 +31,10 @@ LOSS_LIB_PATH = os.environ.get("EMRT_HIP_LOSS_LIB") or os.path.join(_HERE, "csrc
 TTA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_tta.h")
 TTA_LIB_PATH = os.environ.get("EMRT_HIP_TTA_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_tta.so")
 
+# The sixth library (include/emrt_hip_mstta.h: scale as one more axis of that window-level augmentation), for the same reason: mst_lib().
+MST_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_mstta.h")
+MST_LIB_PATH = os.environ.get("EMRT_HIP_MSTTA_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_mstta.so")
+
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
 _CTYPES = {
@@ -293,7 +297,7 @@ def augment_struct(name):
 
 
 class _ExtLib:
-    """A library beside libemrt_hip.so (augment_lib(), sampler_lib(), loss_lib(), tta_lib()), bound from its own header: call / query / last_error as _Lib, with the
+    """A library beside libemrt_hip.so (augment_lib(), sampler_lib(), loss_lib(), tta_lib(), mst_lib()), bound from its own header: call / query / last_error as _Lib, with the
     library's own `<prefix>_last_error` string and its `<prefix>_version` checked to be 1.  No fallback: a missing library or symbol raises."""
 
     def __init__(self, path, header, prefix, what):
@@ -380,3 +384,15 @@ def tta_lib():
     if _TTA_LIB is None:
         _TTA_LIB = _ExtLib(TTA_LIB_PATH, TTA_HEADER, "emrt_tta", "the test-time augmentation of whole-scene inference")
     return _TTA_LIB
+
+
+# ---- libemrt_hip_mstta.so (include/emrt_hip_mstta.h: window-level scales, with or without flips and rotations; loaded only when a scene is predicted with tta_scales) ----
+
+_MST_LIB = None
+
+
+def mst_lib():
+    global _MST_LIB
+    if _MST_LIB is None:
+        _MST_LIB = _ExtLib(MST_LIB_PATH, MST_HEADER, "emrt_mst", "the multi-scale test-time augmentation of whole-scene inference")
+    return _MST_LIB

@@ -2,7 +2,9 @@
 include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) and emrt_amd/csrc/libemrt_hip_sampler.so
 (csrc/sampler_ext/*.hip: include/emrt_hip_sampler.h, for the same reason) with hipcc for gfx950, in-tree.  GROUPS is the table of the three;
 EXTRA_GROUPS holds the library added next, emrt_amd/csrc/libemrt_hip_loss.so (csrc/loss_ext/*.hip: include/emrt_hip_loss.h), and MORE_GROUPS the
-ones after it: emrt_amd/csrc/libemrt_hip_tta.so (csrc/tta_ext/*.hip: include/emrt_hip_tta.h).  all_groups() is every row.
+ones after it: emrt_amd/csrc/libemrt_hip_tta.so (csrc/tta_ext/*.hip: include/emrt_hip_tta.h).  all_groups() is those five rows, pinned by the tests
+of the fifth library; LATER_GROUPS holds what came after them, emrt_amd/csrc/libemrt_hip_mstta.so (csrc/mstta_ext/*.hip:
+include/emrt_hip_mstta.h), and every_group() is every row: what build(), _headers() and source_digest() walk.
 
 What is rebuilt is decided by CONTENT: every object and the library carry a `<file>.inputs` stamp with the sha256 of the sources, headers,
 compiler path and flags they were built from; "reused" therefore means "built from exactly these inputs", on whatever machine.
@@ -40,6 +42,12 @@ TTA_SOURCES = ["tta_ext.hip"]
 TTA_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_tta.h")      # the sources include csrc/common.hpp and csrc/scene_norm.hpp
 # the rows behind those (EXTRA_GROUPS is pinned at one row by the loss library's tests, as GROUPS is at three)
 MORE_GROUPS = [(TTA_LIB, TTA_DIR, TTA_SOURCES, TTA_HEADER)]
+MST_DIR = os.path.join(CSRC, "mstta_ext")
+MST_LIB = os.path.join(CSRC, "libemrt_hip_mstta.so")
+MST_SOURCES = ["mstta_ext.hip"]
+MST_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_mstta.h")      # the sources include csrc/common.hpp and csrc/scene_norm.hpp
+# the rows behind all_groups() (MORE_GROUPS is pinned at one row and all_groups() at the three tables above by the tta library's tests)
+LATER_GROUPS = [(MST_LIB, MST_DIR, MST_SOURCES, MST_HEADER)]
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
@@ -84,27 +92,32 @@ def all_groups():
     return GROUPS + EXTRA_GROUPS + MORE_GROUPS
 
 
+def every_group():
+    """Every library's row: all_groups(), then LATER_GROUPS."""
+    return all_groups() + LATER_GROUPS
+
+
 def _headers():
     """csrc/*.hpp and the public headers: inputs of every object of every library."""
-    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [g[3] for g in all_groups()]
+    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [g[3] for g in every_group()]
 
 
 def source_digest():
-    """Content hash of everything the libraries are built from: the sources of every row of all_groups(), csrc/*.hpp, include/*.h, the compiler
+    """Content hash of everything the libraries are built from: the sources of every row of every_group(), csrc/*.hpp, include/*.h, the compiler
     path and the flags."""
-    return _digest([os.path.join(d, s) for _, d, sources, _ in all_groups() for s in sources] + _headers(), [_hipcc()] + FLAGS)
+    return _digest([os.path.join(d, s) for _, d, sources, _ in every_group() for s in sources] + _headers(), [_hipcc()] + FLAGS)
 
 
 LAST_BUILD = {"mode": None, "digest": None, "compiled": [], "linked": []}      # what the last build() call did: "compiled" | "linked" | "reused"
 
 
 def build(force=False, verbose=True):
-    """Builds every library of all_groups(); -> the path of libemrt_hip.so (the others are AUG_LIB, SMP_LIB, LOSS_LIB and TTA_LIB).  Only the objects whose inputs
+    """Builds every library of every_group(); -> the path of libemrt_hip.so (the others are AUG_LIB, SMP_LIB, LOSS_LIB, TTA_LIB and MST_LIB).  Only the objects whose inputs
     changed are compiled, and only the libraries that hold one of them are linked again."""
     hipcc = _hipcc()
     hdrs = _headers()
-    objs, jobs = {g[0]: [] for g in all_groups()}, []
-    for lib, d, sources, _ in all_groups():
+    objs, jobs = {g[0]: [] for g in every_group()}, []
+    for lib, d, sources, _ in every_group():
         for src in sources:
             s = os.path.join(d, src)
             o = os.path.join(d, src.replace(".hip", ".o"))
@@ -139,7 +152,7 @@ def build(force=False, verbose=True):
                     print("[emrt_amd.build] compiled", os.path.basename(done), flush=True)
     total = source_digest()
     linked = LAST_BUILD["linked"] = []
-    for lib, _, _, _ in all_groups():
+    for lib, _, _, _ in every_group():
         if force or any(j[3] == lib for j in jobs) or not (os.path.exists(lib) and os.path.exists(_stamp(lib))):
             if os.path.exists(_stamp(lib)):
                 os.remove(_stamp(lib))

@@ -12,4 +12,7 @@ struct SceneNorm {
 // float64 math, one rounding
 __device__ __forceinline__ float normalise_u8(unsigned v, double mean, double stdinv) { return (float)(((double)v - mean) * stdinv); }
 
+// the same arithmetic on a sample that has been resampled in fp32 (mstta_ext/mstta_ext.hip): on a whole number, normalise_u8's bits
+__device__ __forceinline__ float normalise_f32(float v, double mean, double stdinv) { return (float)(((double)v - mean) * stdinv); }
+
 }  // namespace emrt

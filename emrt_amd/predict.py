@@ -17,7 +17,7 @@ from PIL import Image
 
 from .config import get_config, update_config
 from .runtime import BF16, F16, F32
-from .src.api.scene import TTA_MODES, ScenePredictor
+from .src.api.scene import TTA_MODES, ScenePredictor, check_tta_scales, refuse_scales_with_config
 from .src.models import get_model
 from .src.utils import vis
 
@@ -39,6 +39,10 @@ def parse_args(argv=None):
                    help="test-time augmentation of every window at scale 1: hflip = 2 variants, flips = both flips and their product (4), "
                         "d4 = the 8 flips and quarter turns (square crop); the class probabilities of all variants are averaged. "
                         "A model call then carries max_batch // variants windows. Not with --multi_scales, which keeps its own flip")
+    p.add_argument("--tta_scales", default=None, type=float, nargs="+", metavar="S",
+                   help="window-level scales in [0.25, 4], e.g. 0.75 1.0 1.25, with any --tta: at scale S a window is resampled from CROP / S scene "
+                        "pixels and its logits are resampled back; the class probabilities of all scales and variants are averaged. "
+                        "Not with --multi_scales / VAL.MULTI_SCALES_VAL, the reference's whole-scene multi-scale pass")
     p.add_argument("--overlay", default=None, type=float, metavar="ALPHA",
                    help="also write <stem>_overlay.png = ALPHA * colour + (1 - ALPHA) * image, ALPHA in [0, 1]")
     p.add_argument("--save_index", action="store_true",
@@ -47,6 +51,13 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.tta != "none" and args.multi_scales:
         p.error("--tta %s cannot be combined with --multi_scales: multi-scale inference keeps its own horizontal flip" % args.tta)
+    if args.tta_scales is not None:
+        if args.multi_scales:
+            p.error("--tta_scales cannot be combined with --multi_scales: choose the window-level scales or the reference's whole-scene pass")
+        try:
+            check_tta_scales(args.tta_scales, None)
+        except ValueError as e:
+            p.error("--tta_scales: %s" % e)
     return args
 
 
@@ -79,6 +90,7 @@ def _write(save_dir, stem, palette, index, color, overlay):
 def main(argv=None):
     args = parse_args(argv)
     config = update_config(get_config(), args)
+    refuse_scales_with_config(args, config)
     palette = vis.get_palette(config.DATA.DATASET)
     ncls = config.DATA.NUM_CLASSES
     if args.input:
@@ -106,7 +118,8 @@ def main(argv=None):
         stride = crop          # the default stride left in place over a smaller crop, as emrt_amd.val treats it
     multi = args.multi_scales or config.VAL.MULTI_SCALES_VAL
     predictor = ScenePredictor(model, ncls, crop, stride, palette, list(config.VAL.MEAN), list(config.VAL.STD), overlay=args.overlay,
-                               max_batch=args.max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi else None, tta=args.tta)
+                               max_batch=args.max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi else None, tta=args.tta,
+                               tta_scales=args.tta_scales)
     written, jobs = [], []
     with ThreadPoolExecutor(max_workers=max(1, min(WRITERS, len(files)))) as pool:
         for f, stem in zip(files, stems):

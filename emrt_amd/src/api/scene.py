@@ -15,6 +15,11 @@ against the bank's uint8 label maps where they lie: emrt_window_normalise, emrt_
 Both take `tta`: "hflip", "flips" or "d4" puts every window through the model in 2, 4 or 8 flipped / turned variants and averages
 the class probabilities of all variants of all covering windows -- two launches of libemrt_hip_tta.so around the model call stand where the crop
 and the accumulation stand; "none" (the default) issues what it always issued and never loads that library.
+
+Both take `tta_scales`, with any `tta`: a sequence of scales in [0.25, 4].  At scale s a window is resampled from a footprint of
+crop / s native pixels where it is cropped from the uint8 scene, and its logits are resampled back where they are accumulated -- two launches of
+libemrt_hip_mstta.so per model call, no scaled scene and no fp32 scene; the result is the mean class probability over every scale, covering
+footprint and variant.  None (the default) takes the paths above untouched and never loads that library.
 """
 import ctypes
 from collections import namedtuple
@@ -106,6 +111,92 @@ def accumulate_windows_tta(model, scene, H, W, org, crop, ncls, max_batch, mean,
         T.call("emrt_tta_window_accumulate", Fn.P(logits), Fn.P(final), Fn.P(count), ptr, len(chunk), kptr, G, ncls, H, W, h_crop, w_crop, c.stream)
 
 
+# Scale as one more axis of that augmentation: at scale s a window of the crop is resampled from a FOOTPRINT of crop / s native
+# pixels where it is cropped, and its logits are resampled back where they are accumulated (include/emrt_hip_mstta.h).
+TTA_SCALE_RANGE = (0.25, 4.0)
+MAX_EDGE = 2048           # include/emrt_hip_mstta.h EMRT_MST_MAX_EDGE: footprint and window edges of one launch
+
+
+def footprint(crop, stride, s):
+    """-> ((fw, fh), (sw, sh)): the native pixels a crop-sized window covers at scale s, f = int(c / s + 0.5) per axis, and the stride its
+    footprints are laid out with, min(f, max(1, int(t / s + 0.5))): size and stride scale together.  At s = 1 these are crop and stride."""
+    s = float(s)
+    size = tuple(int(c / s + 0.5) for c in crop)
+    for c, f in zip(crop, size):
+        if not (1 <= f <= MAX_EDGE and 1 <= c <= MAX_EDGE and f <= 4 * c and c <= 4 * f):
+            raise ValueError("scale %g turns a crop edge of %d into a footprint of %d pixels: both must be 1..%d and within 4 times of each other"
+                             % (s, c, f, MAX_EDGE))
+    return size, tuple(min(f, max(1, int(t / s + 0.5))) for f, t in zip(size, stride))
+
+
+def check_tta_scales(tta_scales, scales):
+    """-> None, or the scales as a tuple of floats in the order given; an empty or non-sequence value, a scale outside [0.25, 4], a repeated
+    scale and the combination with `scales` (the reference's multi-scale pass) are refused"""
+    if tta_scales is None:
+        return None
+    if isinstance(tta_scales, (str, bytes)) or not hasattr(tta_scales, "__len__") or not hasattr(tta_scales, "__iter__") or len(tta_scales) == 0:
+        raise ValueError("tta_scales must be a non-empty sequence of scales, got %r" % (tta_scales,))
+    try:
+        out = tuple(float(s) for s in tta_scales)
+    except (TypeError, ValueError):
+        raise ValueError("tta_scales must be a non-empty sequence of scales, got %r" % (tta_scales,))
+    for s in out:
+        if not TTA_SCALE_RANGE[0] <= s <= TTA_SCALE_RANGE[1]:          # (a NaN fails this too)
+            raise ValueError("tta_scales must lie in [%g, %g], got %r" % (TTA_SCALE_RANGE + (s,)))
+    if len(set(out)) != len(out):
+        raise ValueError("tta_scales repeats a scale: %r" % (out,))
+    if scales is not None:
+        raise ValueError("tta_scales cannot be combined with scales: the reference's multi-scale pass resizes the whole scene itself")
+    return out
+
+
+def refuse_scales_with_config(args, config):
+    """For the command lines: VAL.MULTI_SCALES_VAL is known only once the yaml is read, and --tta_scales is refused with it as with
+    --multi_scales: a message on stderr and exit status 2, as argparse refuses."""
+    if getattr(args, "tta_scales", None) is not None and config.VAL.MULTI_SCALES_VAL:
+        import sys
+        sys.stderr.write("error: --tta_scales cannot be combined with VAL.MULTI_SCALES_VAL of the config: choose the window-level scales or the "
+                         "reference's whole-scene pass\n")
+        raise SystemExit(2)
+
+
+def footprint_grids(H, W, crop, stride, tta_scales, what="scene"):
+    """-> [(s, fh, fw, [(y, x)])] in the order of tta_scales: per scale the footprint and the origins of infer.window_grid over footprints, in
+    its order.  A scene smaller than a footprint is refused (nothing is padded), before anything is launched for any scale."""
+    grids = []
+    for s in tta_scales:
+        (fw, fh), fstride = footprint(crop, stride, s)
+        if H < fh or W < fw:
+            raise ValueError("%s %dx%d (h x w) is smaller than the %dx%d footprint of the %dx%d crop at scale %g: nothing is resized or padded"
+                             % (what, H, W, fh, fw, crop[1], crop[0], s))
+        grids.append((s, fh, fw, [(a, b) for (a, b, _, _) in infer.window_grid(H, W, (fw, fh), fstride)]))
+    return grids
+
+
+def accumulate_windows_ms(model, scene, H, W, crop, stride, ncls, max_batch, mean, stdinv, final, count, codes, tta_scales, what="scene"):
+    """accumulate_windows_tta with scale as one more axis: the scales in the order given, per scale the footprints of footprint_grids in grid
+    order, max_batch // G per model call, each with its G = len(codes) variants.  emrt_mst_crop_windows_u8 resamples the windows from the uint8
+    scene, emrt_mst_window_accumulate resamples every variant's logits back to the footprint, turned back, and adds their softmax to `final`
+    [1, ncls, H, W] and G per covering footprint to `count` [1, 1, H, W]: the mean class probability over scales, footprints and variants."""
+    grids = footprint_grids(H, W, crop, stride, tta_scales, what)
+    M, c = _lib.mst_lib(), ctx()
+    w_crop, h_crop = crop
+    G = len(codes)
+    karr = (ctypes.c_int * G)(*codes)
+    kptr = ctypes.cast(karr, ctypes.c_void_p)
+    per = max_batch // G
+    for _s, fh, fw, org in grids:
+        for i in range(0, len(org), per):
+            chunk = org[i:i + per]
+            _keep, ptr = _origins(chunk)
+            batch = c.empty((len(chunk) * G, 3, h_crop, w_crop), torch.float32)
+            M.call("emrt_mst_crop_windows_u8", Fn.P(scene), Fn.P(batch), ptr, len(chunk), kptr, G, H, W, fh, fw, h_crop, w_crop, *mean, *stdinv, c.stream)
+            logits = model(batch)[0]
+            assert logits.dtype == torch.float32 and logits.is_contiguous() and tuple(logits.shape) == (len(chunk) * G, ncls, h_crop, w_crop)
+            M.call("emrt_mst_window_accumulate", Fn.P(logits), Fn.P(final), Fn.P(count), ptr, len(chunk), kptr, G, ncls, H, W, fh, fw, h_crop, w_crop,
+                   c.stream)
+
+
 def accumulate_windows(model, scene, H, W, crop, stride, ncls, max_batch, mean, stdinv, final, count, codes=(0,)):
     """The single-scale pass both classes share: the windows of infer.window_grid(H, W, crop, stride) in that order, max_batch per model call
     (chunked exactly as infer.slide_inference: the same logits, bit for bit), cropped and normalised from the uint8 scene, their logits added to
@@ -131,10 +222,11 @@ class ScenePredictor:
 
     crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); palette uint8 [num_classes, 3] RGB; mean / std as
     transforms.Normalize takes them; overlay = alpha in [0, 1] (the colour's weight over the scene) or None; tta = a key of TTA_MODES: with
-    G > 1 variants a model call carries max_batch // G windows."""
+    G > 1 variants a model call carries max_batch // G windows; tta_scales = None or a sequence of scales in [0.25, 4] (check_tta_scales), with
+    any tta, not with `scales` and not for predict_tiles."""
 
     def __init__(self, model, num_classes, crop_size, stride_size, palette, mean, std, overlay=None, max_batch=32, scales=None,
-                 flip_horizontal=True, tta="none"):
+                 flip_horizontal=True, tta="none", tta_scales=None):
         self.model, self.ncls = model, int(num_classes)
         self.crop, self.stride = check_windows(crop_size, stride_size)
         pal = np.ascontiguousarray(np.asarray(palette))
@@ -152,6 +244,7 @@ class ScenePredictor:
         self.max_batch = int(max_batch)
         self.scales = None if scales is None else tuple(scales)
         self.flip_horizontal = flip_horizontal
+        self.tta_scales = check_tta_scales(tta_scales, self.scales)
         self.tta, self.codes = tta, check_tta(tta, self.crop, self.max_batch, self.scales)
 
     # ---- kernels ---------------------------------------------------------------------------------------------------
@@ -184,11 +277,19 @@ class ScenePredictor:
         scene = self._check_u8(scene_u8, 3, "scene")
         H, W = int(scene.shape[0]), int(scene.shape[1])
         w_crop, h_crop = self.crop
-        if H < h_crop or W < w_crop:
+        if self.tta_scales is not None:
+            footprint_grids(H, W, self.crop, self.stride, self.tta_scales)          # a scene smaller than a footprint is refused before anything is allocated
+        elif H < h_crop or W < w_crop:
             raise ValueError("scene %dx%d (h x w) is smaller than the crop %dx%d: nothing is resized or padded" % (H, W, h_crop, w_crop))
         c = ctx()
         out = self._outputs(1, H, W)
-        if self.scales is not None:
+        if self.tta_scales is not None:
+            final = c.zeros((1, self.ncls, H, W), torch.float32)
+            count = c.zeros((1, 1, H, W), torch.float32)
+            accumulate_windows_ms(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count,
+                                  self.codes, self.tta_scales)
+            self._finish(final, count, scene, out, 0, 1, H, W)
+        elif self.scales is not None:
             img, _, _ = self._crop(scene, H, W, [(0, 0)], H, W)          # the whole scene as normalised fp32 CHW: one window
             final = infer.ms_accumulate(self.model, img[0], (H, W), True, None, self.stride, self.crop, self.ncls, scales=list(self.scales),
                                         flip_horizontal=self.flip_horizontal)
@@ -206,6 +307,8 @@ class ScenePredictor:
         """The stack is one tall scene [n * h][w][3] whose windows are the tiles; the model's logits are finished directly (a batch
         dimension, no count), max_batch tiles per model call, results in tile order.  With tta, max_batch // G tiles per model call are one tall
         scene of their own: its sums and counts (accumulate_windows_tta) are finished."""
+        if self.tta_scales is not None:
+            raise ValueError("predict_tiles does not take tta_scales: tiles are crop-sized, and the footprint of a scale below 1 does not fit in one")
         tiles = self._check_u8(tiles_u8, 4, "tiles")
         n, h, w = (int(v) for v in tiles.shape[:3])
         if (w, h) != self.crop:
@@ -242,14 +345,18 @@ class SceneEvaluator:
     row.  Everything is enqueued on the current stream: no host copy of a pixel, no synchronisation.  Sums, counts, normalised logits and the
     prediction are allocated once per distinct scene shape and reused by every scene of that shape and by every later evaluation.
     crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); mean / std as transforms.Normalize takes them; tta as
-    ScenePredictor takes it (the argmax is then that of the mean class probability)."""
+    ScenePredictor takes it (the argmax is then that of the mean class probability), and tta_scales likewise."""
 
     def __init__(self, model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None,
-                 flip_horizontal=True, tta="none"):
+                 flip_horizontal=True, tta="none", tta_scales=None):
         self.model, self.bank, self.ncls = model, bank, int(num_classes)
         self.crop, self.stride = check_windows(crop_size, stride_size)
+        self.scales = None if scales is None else tuple(scales)
+        self.tta_scales = check_tta_scales(tta_scales, self.scales)
         for i, (H, W) in enumerate(bank.sizes):
-            if H < self.crop[1] or W < self.crop[0]:
+            if self.tta_scales is not None:
+                footprint_grids(H, W, self.crop, self.stride, self.tta_scales, "scene %d (%s)" % (i, bank.names[i]))
+            elif H < self.crop[1] or W < self.crop[0]:
                 raise ValueError("scene %d (%s) is %dx%d (h x w), smaller than the crop %dx%d: nothing is resized or padded"
                                  % (i, bank.names[i], H, W, self.crop[1], self.crop[0]))
         if not 1 <= self.ncls <= 256:
@@ -259,7 +366,6 @@ class SceneEvaluator:
         self.max_batch = int(max_batch)
         self.mean, self.stdinv = check_normalise(mean, std)
         self.ignore_index = int(ignore_index)
-        self.scales = None if scales is None else tuple(scales)
         self.flip_horizontal = flip_horizontal
         self.tta, self.codes = tta, check_tta(tta, self.crop, self.max_batch, self.scales)
         self.per_scene = torch.empty((len(bank), 3, self.ncls), dtype=torch.int64, device=bank.device)
@@ -287,8 +393,12 @@ class SceneEvaluator:
         else:
             L.call("emrt_memset", Fn.P(final), 0, final.numel() * 4, c.stream)
             L.call("emrt_memset", Fn.P(count), 0, count.numel() * 4, c.stream)
-            accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count,
-                               self.codes)
+            if self.tta_scales is not None:
+                accumulate_windows_ms(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count,
+                                      self.codes, self.tta_scales, "scene %d (%s)" % (i, self.bank.names[i]))
+            else:
+                accumulate_windows(self.model, scene, H, W, self.crop, self.stride, self.ncls, self.max_batch, self.mean, self.stdinv, final, count,
+                                   self.codes)
             L.call("emrt_window_normalise", Fn.P(final), Fn.P(count), Fn.P(logits), self.ncls, H, W, c.stream)
         L.call("emrt_argmax_nchw", Fn.P(logits), Fn.P(pred), 1, self.ncls, H, W, c.stream)
         return pred

@@ -21,7 +21,7 @@ from .config import get_config, update_config
 from .distributed import init_process_group
 from .runtime import BF16, F16, F32
 from .src.api import infer
-from .src.api.scene import TTA_MODES
+from .src.api.scene import TTA_MODES, check_tta_scales, refuse_scales_with_config
 from .src.models import get_model
 from .src.utils import metrics
 
@@ -39,7 +39,20 @@ def parse_args(argv=None):
     p.add_argument("--tta", default="none", choices=list(TTA_MODES),
                    help="with --data scenes: test-time augmentation of every window at scale 1 (hflip: 2 variants, flips: 4, d4: the 8 flips and "
                         "quarter turns of a square crop); the class probabilities of all variants are averaged. Not with --multi_scales")
+    p.add_argument("--tta_scales", default=None, type=float, nargs="+", metavar="S",
+                   help="with --data scenes: window-level scales in [0.25, 4], e.g. 0.75 1.0 1.25, with any --tta (DESIGN.md 23); the class "
+                        "probabilities of all scales and variants are averaged. Not with --multi_scales / VAL.MULTI_SCALES_VAL")
     args = p.parse_args(argv)
+    if args.tta_scales is not None:
+        if args.data != "scenes":
+            p.error("--tta_scales needs --data scenes: only whole scenes resident on the GPU are evaluated with test-time augmentation, --data %s is not"
+                    % args.data)
+        if args.multi_scales:
+            p.error("--tta_scales cannot be combined with --multi_scales: choose the window-level scales or the reference's whole-scene pass")
+        try:
+            check_tta_scales(args.tta_scales, None)
+        except ValueError as e:
+            p.error("--tta_scales: %s" % e)
     if args.tta != "none" and args.data != "scenes":
         p.error("--tta %s needs --data scenes: only whole scenes resident on the GPU are evaluated with test-time augmentation, --data %s is not"
                 % (args.tta, args.data))
@@ -126,16 +139,17 @@ def metric_tuple(tot):
     return miou, acc, kap, class_iou, class_acc, class_f1, float(np.mean(class_f1))
 
 
-def scene_evaluator(model, config, device, multi_scales=False, max_batch=32, tta="none"):
+def scene_evaluator(model, config, device, multi_scales=False, max_batch=32, tta="none", tta_scales=None):
     """The validation bank of a scene tree (<DATA.DATA_PATH>/val_images + /val_labels, uploaded here, labels stored as a `val` Dataset shifts them)
     and the SceneEvaluator over it, from VAL.CROP_SIZE / STRIDE_SIZE / MEAN / STD and TRAIN.IGNORE_INDEX; VAL.SCALE_RATIOS when multi_scales; tta as
-    SceneEvaluator takes it."""
+    SceneEvaluator takes it, and tta_scales likewise."""
     from .src.api.scene import SceneEvaluator
     from .src.datasets import SceneBank
     bank = SceneBank(config.DATA.DATA_PATH, device, label_shift=1 if config.DATA.DATASET == "LoveDA" else 0, sub=("val_images", "val_labels"),
                      shift_on_upload=True)
     return SceneEvaluator(model, bank, config.DATA.NUM_CLASSES, config.VAL.CROP_SIZE, config.VAL.STRIDE_SIZE, list(config.VAL.MEAN), list(config.VAL.STD),
-                          ignore_index=config.TRAIN.IGNORE_INDEX, max_batch=max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi_scales else None, tta=tta)
+                          ignore_index=config.TRAIN.IGNORE_INDEX, max_batch=max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi_scales else None, tta=tta,
+                          tta_scales=tta_scales)
 
 
 def evaluate_scenes(evaluator, rank=0, nranks=1):
@@ -166,6 +180,7 @@ def scene_lines(evaluator, nranks=1):
 def main(argv=None):
     args = parse_args(argv)
     config = update_config(get_config(), args)
+    refuse_scales_with_config(args, config)
     rank, local_rank, nranks = init_process_group()
     model = get_model(config)
     if args.model_path:                 # a .pdparams written by the reference / by train.py, or a torch checkpoint
@@ -182,7 +197,7 @@ def main(argv=None):
     if args.data == "scenes":           # whole validation scenes resident on the device, evaluated at their own resolution
         if getattr(args, "data_path", None):
             config.DATA.DATA_PATH = args.data_path
-        ev = scene_evaluator(model, config, dev, multi_scales, tta=args.tta)
+        ev = scene_evaluator(model, config, dev, multi_scales, tta=args.tta, tta_scales=args.tta_scales)
         images = ev.bank.names
         if rank == 0:
             print("[EVAL] data: %d validation scenes resident on the GPU (%.1f MB)" % (len(ev.bank), ev.bank.nbytes / 1e6), flush=True)
