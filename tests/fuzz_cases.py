@@ -2,8 +2,9 @@
 (tests/test_gpu_norm_fuzz.py, tests/test_gpu_spatial_fuzz.py, tests/test_gpu_infer_glue.py) and of csrc/attn.hip
 (tests/test_gpu_mha_fuzz.py; its float64 reference and bounds are tests/mha_reference.py), the written-out case list of the sweep of
 csrc/msda.hip by plan, build and layout (tests/test_gpu_msda_fuzz.py; tests/msda_reference.py), the written-out case list of the sweep of
-csrc/gconv.hip by group shape, launch plan and view (tests/test_gpu_gconv_fuzz.py), and the dispatchers' shape predicates
-restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
+csrc/gconv.hip by group shape, launch plan and view (tests/test_gpu_gconv_fuzz.py), the written-out case list of the sweep of the dense
+convolution's fused epilogues through every tile and backward path of csrc/conv.hip and csrc/igemm8p.hpp (tests/test_gpu_conv_epilogue_fuzz.py),
+and the dispatchers' shape predicates restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
 entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
 seed or a range cannot silently empty one.
 
@@ -265,6 +266,231 @@ Regime -> case ids (regime_table() renders this text; the CPU test compares):
   gconv             inputs: ordinary                                   gconv2111-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,32,33,34,35,36,37,38,39,40}
   gconv             inputs: corner                                     gconv2111-{26,27,28}
   gconv             inputs: lastpixel                                  gconv2111-{29,30,31}
+  conv              64x64 G1, vec epilogue                             conv2212-{0,2,4,5,77,78,81,110,112,113}
+  conv              64x64 G1, scalar epilogue                          conv2212-{1,3,67,79,80,118,121}
+  conv              64x64 G2, vec epilogue                             conv2212-{6,8,82}
+  conv              64x64 G2, scalar epilogue                          conv2212-{7,9,83}
+  conv              64x64 G4, vec epilogue                             conv2212-{10,12,84,111}
+  conv              64x64 G4, scalar epilogue                          conv2212-{11,13,85}
+  conv              128x64, vec epilogue                               conv2212-{14,16,86,88,120}
+  conv              128x64, scalar epilogue                            conv2212-{15,17,87}
+  conv              128x128 G1, vec epilogue                           conv2212-{18,20,89,91,115,119}
+  conv              128x128 G1, scalar epilogue                        conv2212-{19,21,90,122}
+  conv              128x128 G2, vec epilogue                           conv2212-{22,24,92}
+  conv              128x128 G2, scalar epilogue                        conv2212-{23,25,93}
+  conv              256x32, vec epilogue                               conv2212-{26,29,31,33,94,97}
+  conv              256x32, scalar epilogue                            conv2212-{27,28,30,32,95,96,117}
+  conv              xk, vec epilogue                                   conv2212-{34,35,36,37,38,39,98,99,100,116}
+  conv              s2, vec epilogue                                   conv2212-{40,41,42,43,44,45,46,47}
+  conv              8p, 8p epilogue                                    conv2212-{54,55,56,57,58,59,60,61,62,63,64,65,66,101,102,103,104,105,106,107,108,109,114}
+  conv              pair, vec epilogue                                 conv2212-{48,49,50,51,52,53}
+  conv              thin, thin epilogue                                conv2212-{68,69,70,71,72,73,74,75,76,123,124}
+  conv              64x64 G1: backward with mask                       conv2212-{0,1,2,5,67,77,121}
+  conv              64x64 G1: backward with stats                      conv2212-{0,1,2,67,77}
+  conv              64x64 G1: backward with stat_x                     conv2212-{0,1,67}
+  conv              64x64 G1: backward with addend                     conv2212-{0,1,67}
+  conv              64x64 G1: backward with accumulate                 conv2212-{2,3,77}
+  conv              64x64 G2: backward with mask                       conv2212-{6,7,8}
+  conv              64x64 G2: backward with stats                      conv2212-{6,7,8}
+  conv              64x64 G2: backward with stat_x                     conv2212-{6,7}
+  conv              64x64 G2: backward with addend                     conv2212-{6,7}
+  conv              64x64 G2: backward with accumulate                 conv2212-{8,9}
+  conv              64x64 G4: backward with mask                       conv2212-{10,11,12}
+  conv              64x64 G4: backward with stats                      conv2212-{10,11,12,13}
+  conv              64x64 G4: backward with stat_x                     conv2212-{10,11}
+  conv              64x64 G4: backward with addend                     conv2212-{10,11}
+  conv              64x64 G4: backward with accumulate                 conv2212-{12,13}
+  conv              128x64: backward with mask                         conv2212-{14,15,16,120}
+  conv              128x64: backward with stats                        conv2212-{14,15,16}
+  conv              128x64: backward with stat_x                       conv2212-{14,15}
+  conv              128x64: backward with addend                       conv2212-{14,15}
+  conv              128x64: backward with accumulate                   conv2212-{16,17}
+  conv              128x128 G1: backward with mask                     conv2212-{18,19,20,122}
+  conv              128x128 G1: backward with stats                    conv2212-{18,19,20}
+  conv              128x128 G1: backward with stat_x                   conv2212-{18,19}
+  conv              128x128 G1: backward with addend                   conv2212-{18,19}
+  conv              128x128 G1: backward with accumulate               conv2212-{20,21}
+  conv              128x128 G2: backward with mask                     conv2212-{22,23,24}
+  conv              128x128 G2: backward with stats                    conv2212-{22,23,24,25}
+  conv              128x128 G2: backward with stat_x                   conv2212-{22,23}
+  conv              128x128 G2: backward with addend                   conv2212-{22,23}
+  conv              128x128 G2: backward with accumulate               conv2212-{24,25}
+  conv              256x32: backward with mask                         conv2212-{26,27,28,29,30,31,33}
+  conv              256x32: backward with stats                        conv2212-{26,27,28,29,30,31,33}
+  conv              256x32: backward with stat_x                       conv2212-{29,30,33}
+  conv              256x32: backward with addend                       conv2212-{29,30,33}
+  conv              256x32: backward with accumulate                   conv2212-{31,32}
+  conv              xk: backward with mask                             conv2212-{34,35,37,39}
+  conv              xk: backward with stats                            conv2212-{34,35,37,39}
+  conv              xk: backward with stat_x                           conv2212-{34,35,39}
+  conv              xk: backward with addend                           conv2212-{34,36,39}
+  conv              xk: backward with accumulate                       conv2212-{37,38}
+  conv              s2: backward with mask                             conv2212-{40,41,42,43,47}
+  conv              s2: backward with stats                            conv2212-{40,41,43,46,47}
+  conv              s2: backward with stat_x                           conv2212-{40,41,47}
+  conv              s2: backward with addend                           conv2212-{40,44,47}
+  conv              s2: backward with accumulate                       conv2212-{43,45}
+  conv              8p: backward with mask                             conv2212-{55,56,59,61,62,63,64,65,66}
+  conv              8p: backward with stats                            conv2212-{55,56,58,61,62,64,65,66}
+  conv              8p: backward with stat_x                           conv2212-{55,56,64,65}
+  conv              8p: backward with addend                           conv2212-{56,60,64}
+  conv              8p: backward with accumulate                       conv2212-{57,61,66}
+  conv              pair: backward with mask                           conv2212-{48,49,50,51,52}
+  conv              pair: backward with stats                          conv2212-{48,49,50,51,52}
+  conv              pair: backward with stat_x                         conv2212-{50,51}
+  conv              pair: backward with addend                         conv2212-{50,51}
+  conv              pair: backward with accumulate                     conv2212-{52,53}
+  conv              thin: backward with mask                           conv2212-{72,73,74,75,76,123,124}
+  conv              thin: backward with stats                          conv2212-{69,71,73,75,123}
+  conv              thin: backward with accumulate                     conv2212-{70,71}
+  conv              64x64 G1: forward                                  conv2212-{78,79,80,81,110,112,113,118}
+  conv              64x64 G2: forward                                  conv2212-{82,83}
+  conv              64x64 G4: forward                                  conv2212-{84,85,111}
+  conv              128x64: forward                                    conv2212-{86,87,88}
+  conv              128x128 G1: forward                                conv2212-{89,90,91,115,119}
+  conv              128x128 G2: forward                                conv2212-{92,93}
+  conv              256x32: forward                                    conv2212-{94,95,96,97,117}
+  conv              xk: forward                                        conv2212-{98,99,100,116}
+  conv              8p: forward                                        conv2212-{101,102,103,104,105,106,107,108,109,114}
+  conv              vec epilogue, forward with bias                    conv2212-{78,84,86,89,91,92,98,100,110,113,116}
+  conv              vec epilogue, forward with scale                   conv2212-{84,92,100,113}
+  conv              vec epilogue, forward with residual                conv2212-{78,89,98,112}
+  conv              vec epilogue, forward with relu                    conv2212-{78,82,84,88,89,94,97,98,99,100,115}
+  conv              vec epilogue, forward with stats                   conv2212-{82,94,99}
+  conv              vec epilogue, forward with out_f32                 conv2212-{86,119}
+  conv              scalar epilogue, forward with bias                 conv2212-{79,80,87,95,96,118}
+  conv              scalar epilogue, forward with scale                conv2212-{79,87}
+  conv              scalar epilogue, forward with residual             conv2212-{80,83}
+  conv              scalar epilogue, forward with relu                 conv2212-{79,80,90}
+  conv              scalar epilogue, forward with stats                conv2212-{85,90}
+  conv              scalar epilogue, forward with out_f32              conv2212-{93,96,117,118}
+  conv              8p epilogue, forward with bias                     conv2212-{102,103,105,106,114}
+  conv              8p epilogue, forward with scale                    conv2212-{103,106}
+  conv              8p epilogue, forward with residual                 conv2212-{102,107,114}
+  conv              8p epilogue, forward with relu                     conv2212-{102,103,104,109,114}
+  conv              8p epilogue, forward with stats                    conv2212-{104,108}
+  conv              8p epilogue, forward with out_f32                  conv2212-{101,105}
+  conv              vec epilogue, backward with mask                   conv2212-{0,2,5,6,8,10,12,14,16,18,20,22,24,26,29,31,33,34,35,37,39,40,41,42,43,47,48,49,50,51,52,77,120}
+  conv              vec epilogue, backward with stats                  conv2212-{0,2,6,8,10,12,14,16,18,20,22,24,26,29,31,33,34,35,37,39,40,41,43,46,47,48,49,50,51,52,77}
+  conv              vec epilogue, backward with stat_x                 conv2212-{0,6,10,14,18,22,29,33,34,35,39,40,41,47,50,51}
+  conv              vec epilogue, backward with addend                 conv2212-{0,6,10,14,18,22,29,33,34,36,39,40,44,47,50,51}
+  conv              vec epilogue, backward with accumulate             conv2212-{2,8,12,16,20,24,31,37,38,43,45,52,53,77}
+  conv              vec epilogue, backward with mask_scale             conv2212-{42,120}
+  conv              scalar epilogue, backward with mask                conv2212-{1,7,11,15,19,23,27,28,30,67,121,122}
+  conv              scalar epilogue, backward with stats               conv2212-{1,7,11,13,15,19,23,25,27,28,30,67}
+  conv              scalar epilogue, backward with stat_x              conv2212-{1,7,11,15,19,23,30,67}
+  conv              scalar epilogue, backward with addend              conv2212-{1,7,11,15,19,23,30,67}
+  conv              scalar epilogue, backward with accumulate          conv2212-{3,9,13,17,21,25,32}
+  conv              scalar epilogue, backward with mask_scale          conv2212-{121,122}
+  conv              64x64 G1: ragged last M tile                       conv2212-{0,1,2,3,4,5,67,77,78,79,80,81,110,112,113,118,121}
+  conv              64x64 G2: ragged last M tile                       conv2212-{6,7,8,9,82,83}
+  conv              64x64 G4: ragged last M tile                       conv2212-{10,11,12,13,84,85,111}
+  conv              128x64: ragged last M tile                         conv2212-{14,15,16,17,86,87,88,120}
+  conv              128x128 G1: ragged last M tile                     conv2212-{18,19,20,21,89,90,91,115,119,122}
+  conv              128x128 G2: ragged last M tile                     conv2212-{22,23,24,25,92,93}
+  conv              256x32: ragged last M tile                         conv2212-{26,27,28,29,30,31,32,33,94,95,96,97,117}
+  conv              xk: ragged last M tile                             conv2212-{34,35,36,37,38,39,98,99,100,116}
+  conv              8p: ragged last M tile                             conv2212-{54,55,56,57,58,59,60,61,62,63,64,65,66,101,102,103,104,105,106,107,108,109,114}
+  conv              pair: ragged last M tile                           conv2212-{48,49,50,51,52,53}
+  conv              64x64 G1: ragged last OC tile                      conv2212-{0,1,2,3,4,5,67,78,79,80,81,110,112,113,118,121}
+  conv              64x64 G2: ragged last OC tile                      conv2212-{6,7,8,9,82,83}
+  conv              64x64 G4: ragged last OC tile                      conv2212-{10,11,12,13,84,85,111}
+  conv              128x64: ragged last OC tile                        conv2212-{14,15,16,17,86,87,88,120}
+  conv              128x128 G1: ragged last OC tile                    conv2212-{18,19,20,21,89,90,91,115,119,122}
+  conv              128x128 G2: ragged last OC tile                    conv2212-{22,23,24,25,92,93}
+  conv              256x32: ragged last OC tile                        conv2212-{26,27,28,29,30,31,32,33,94,95,96,97,117}
+  conv              xk: ragged last OC tile                            conv2212-{34,35,36,37,38,39,98,99,100,116}
+  conv              s2: ragged last OC tile                            conv2212-{40,42,44,46}
+  conv              8p: ragged last OC tile                            conv2212-{54,55,56,57,58,59,60,61,62,63,64,65,66,101,102,103,104,105,106,107,108,109,114}
+  conv              pair: ragged last OC tile                          conv2212-{48,49,50,51,52,53}
+  conv              scalar epilogue by alignment alone, fwd            conv2212-{83,85,93}
+  conv              scalar epilogue by alignment alone, bwd            conv2212-{1,7,9,11,15,21,23,67}
+  conv              in view: ld                                        conv2212-{79,96}
+  conv              in view: bs                                        conv2212-{84,116}
+  conv              in view: ld+bs                                     conv2212-{81,88,103}
+  conv              out view: ld                                       conv2212-{82,85,86,93,94,98,105,113}
+  conv              out view: bs                                       conv2212-{78,92,100}
+  conv              out view: ld+bs                                    conv2212-{91,102,108}
+  conv              res view: ld                                       conv2212-{78,83,102,114}
+  conv              res view: bs                                       conv2212-{80,107}
+  conv              res view: ld+bs                                    conv2212-{89,98}
+  conv              x view: ld                                         conv2212-{1,20,69,124}
+  conv              x view: bs                                         conv2212-{8,15,72}
+  conv              x view: ld+bs                                      conv2212-{3,11}
+  conv              dy view: ld                                        conv2212-{2,11,20}
+  conv              dy view: bs                                        conv2212-{1,8}
+  conv              dy view: ld+bs                                     conv2212-{15,24}
+  conv              dx view: ld                                        conv2212-{1,9,14,36,43,53,57}
+  conv              dx view: bs                                        conv2212-{13,38,50}
+  conv              dx view: ld+bs                                     conv2212-{2,21,31,40,66,70}
+  conv              mask view: ld                                      conv2212-{0,1,16,23,26,34,40,48,55,62,67,74}
+  conv              mask view: bs                                      conv2212-{5,18,28,41,59,76,122}
+  conv              mask view: ld+bs                                   conv2212-{10,15,42,56,64,75}
+  conv              statx view: ld                                     conv2212-{6,11,41,64}
+  conv              statx view: bs                                     conv2212-{10,55}
+  conv              statx view: ld+bs                                  conv2212-{22,35,47,65}
+  conv              addend view: ld                                    conv2212-{7,18,29,44,56}
+  conv              addend view: bs                                    conv2212-{0,47,64}
+  conv              addend view: ld+bs                                 conv2212-{6,36,50,60}
+  conv              fwd, f32                                           conv2212-{79,83,88,90,91,96,97,111}
+  conv              fwd, bf16                                          conv2212-{78,80,81,82,84,85,86,87,89,92,93,94,95,98,99,100,101,102,103,104,105,106,107,108,109,110,112,119}
+  conv              fwd, f16                                           conv2212-{113,114,115,116,117,118}
+  conv              bwd, f32                                           conv2212-{1,8,9,12,13,15,20,21,28,29,32,43,45,46,49,51,53,69,73,74,122}
+  conv              bwd, bf16                                          conv2212-{0,2,3,4,5,6,7,10,11,14,16,17,18,19,22,23,24,25,26,27,30,31,33,34,35,36,37,38,39,40,41,42,44,47,48,50,52,54,55,56,57,58,59,60,61,62,63,64,65,66,67,68,70,71,72,75,76,77,120,121,123,124}
+  conv              forward epilogue: none                             conv2212-{81,111}
+  conv              forward epilogue: bias                             conv2212-{91,95,110,116}
+  conv              forward epilogue: fold                             conv2212-{87,92,106,113}
+  conv              forward epilogue: residual                         conv2212-{83,107,112}
+  conv              forward epilogue: relu                             conv2212-{88,97,109,115}
+  conv              forward epilogue: stats                            conv2212-{85,108}
+  conv              forward epilogue: out_f32                          conv2212-{93,101,117,119}
+  conv              forward epilogue: bias+residual+relu               conv2212-{78,80,89,98,102,114}
+  conv              forward epilogue: fold+relu                        conv2212-{79,84,100,103}
+  conv              forward epilogue: stats+relu                       conv2212-{82,90,94,99,104}
+  conv              forward epilogue: out_f32+bias                     conv2212-{86,96,105,118}
+  conv              backward epilogue: none                            conv2212-{4,54,68}
+  conv              backward epilogue: stats                           conv2212-{46,58,69}
+  conv              backward epilogue: mask                            conv2212-{5,59,74}
+  conv              backward epilogue: mask+stats                      conv2212-{26,27,28,48,49,62,75}
+  conv              backward epilogue: mask+stats+stat_x               conv2212-{35,41,55,65}
+  conv              backward epilogue: mask+scale                      conv2212-{42,63,76,120,121,122}
+  conv              backward epilogue: addend                          conv2212-{36,44,60}
+  conv              backward epilogue: addend+mask+stats+stat_x        conv2212-{0,1,6,7,10,11,14,15,18,19,22,23,29,30,33,34,39,40,47,50,51,56,64,67}
+  conv              backward epilogue: accumulate                      conv2212-{3,9,17,21,32,38,45,53,57,70}
+  conv              backward epilogue: accumulate+mask+stats           conv2212-{2,8,12,16,20,24,31,37,43,52,61,66,77}
+  conv              backward epilogue: accumulate+stats                conv2212-{13,25,71}
+  conv              backward epilogue: maskx                           conv2212-{72,124}
+  conv              backward epilogue: maskx+stats                     conv2212-{73,123}
+  conv              backward arm: dx                                   conv2212-{0,2,4,5,6,7,9,10,12,13,14,16,17,18,19,21,22,24,25,28,29,30,31,32,33,34,36,37,38,39,40,42,43,44,45,46,47,54,55,57,58,59,60,62,63,64,65,66,67,120,121,122}
+  conv              backward arm: dx+dw                                conv2212-{1,8,11,20,23,26,35,41,50,52,56,69,71,73,74,76,77,124}
+  conv              backward arm: dx+dw+dbias                          conv2212-{3,15,27,48,49,51,53,61,68,70,72,75,123}
+  conv              xk = 2 asked                                       conv2212-{34,38,98,116}
+  conv              xk = 3 asked                                       conv2212-{35,39,99}
+  conv              xk = 8 asked                                       conv2212-{36,37,100}
+  conv              xk: fewer k-tiles than the copies asked for        conv2212-{37,39,100}
+  conv              8p: k = 3, tap-major                               conv2212-{54,55,56,57,101,102,107,109,114}
+  conv              8p: k = 3, channel-block-major                     conv2212-{58,59,60,61,103}
+  conv              8p: k = 1, tap-major                               conv2212-{62,63,64,105,106,108}
+  conv              8p: k = 1, channel-block-major                     conv2212-{65,66,104}
+  conv              8p asked, refused by igemm8p_ok: the ladder's kernel conv2212-{67}
+  conv              s2: k = 3 pad 1                                    conv2212-{40,41,46,47}
+  conv              s2: k = 5 pad 2                                    conv2212-{42,43}
+  conv              s2: k = 2 pad 0                                    conv2212-{44,45}
+  conv              s2: 1 x 16 x 16                                    conv2212-{40,42,44,46}
+  conv              s2: 2 x 8 x 16                                     conv2212-{41,43,45,47}
+  conv              s2: generic twin, bit-identical dx                 conv2212-{40,41,42,43,44,45,46,47}
+  conv              thin: MASK 0                                       conv2212-{68,69,70,71}
+  conv              thin: MASK 1 (mask_y is x)                         conv2212-{72,73,123,124}
+  conv              thin: MASK 2                                       conv2212-{74,75,76}
+  conv              thin: 4 channels per thread                        conv2212-{68,74,123}
+  conv              thin: 8 channels per thread                        conv2212-{69,70,71,72,73,75,76,124}
+  conv              thin: generic twin                                 conv2212-{68,69,70,71,72,73,74,75,76,123,124}
+  conv              thin shape refused by thin_bwd_ok                  conv2212-{77}
+  conv              grouped launch: emrt_conv2d_dgrad_multi            conv2212-{125,126,127}
+  conv              grouped launch: emrt_conv2d_group                  conv2212-{128,129,130}
+  conv              inputs: ordinary                                   conv2212-{0,1,2,3,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,26,27,28,29,30,31,32,33,34,35,36,37,38,39,40,41,42,43,44,45,46,48,49,50,51,52,54,55,56,57,58,60,61,62,63,64,65,67,68,69,70,71,72,73,74,75,77,78,79,80,82,83,84,85,86,87,88,89,90,92,93,94,95,96,97,98,99,100,101,102,103,104,105,107,108,109,110,111,112,113,114,115,116,117,118,119,120,121,122,123,124}
+  conv              inputs: corner                                     conv2212-{4,53,59,81}
+  conv              inputs: lastpixel                                  conv2212-{5,47,66,76,91,106}
 
 Not reachable through the wrappers, on purpose:
   * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
@@ -274,6 +500,11 @@ Not reachable through the wrappers, on purpose:
     of the sweep; FINALIZE and the band kinds do not exist for the (1, 4) build (see MSDA_REGIMES).
   * gconv: emrt_gconv2d has no dilation and no kernel size but 3; maps of 2^31 pixels and more are refused (check_common).  The refusals
     are one separate test without a launch (tests/test_gpu_gconv_fuzz.py).
+  * conv: the dropout epilogue (emrt_conv2d_drop) and the BatchNorm operand transform (emrt_conv2d_bna) have their own tests and stay out of
+    the sweep (bna_plan is mirrored only to hold conv_plan to the recorded table); mode 1 of emrt_conv2d is not what the model runs.  The
+    parity-class kernel has no ragged M tile (M / 4 is a multiple of 64 by its own condition) and, like the cross-block split and the pair
+    kernel, no scalar epilogue (the host sends those problems elsewhere); the thin kernel takes neither stat_x nor an addend (thin_bwd_ok).
+    The weight-gradient kernels' own plan space belongs to tests/test_gpu_wgrad_group.py and the WG8 cases of tests/test_gpu_conv_fuzz.py.
 """
 import random
 
@@ -1273,27 +1504,784 @@ GCONV_REGIMES = [("Cg = %d, %s" % (cg, d), (lambda cg_, d_: lambda c: c[5] == cg
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# dense convolution, the fused epilogues: emrt_conv2d (mode 0) / emrt_conv2d_bwd / emrt_conv2d_dgrad_multi / emrt_conv2d_group (csrc/conv.hip,
+# csrc/igemm8p.hpp; tests/test_gpu_conv_epilogue_fuzz.py).  Written out like the gconv list; the host-side decisions of conv.hip are restated
+# below as pure functions of a case, and the regimes -- (kernel kind) x (epilogue copy) x (epilogue features) -- are computed from them.
+# ---------------------------------------------------------------------------------------------------------------------------------
+CONV_ESZ = {"f32": 4, "bf16": 2, "f16": 2}
+CONV_FWD_EPILOGUES = ("none", "bias", "fold", "residual", "relu", "stats", "out_f32", "bias+residual+relu", "fold+relu", "stats+relu", "out_f32+bias")
+# mask: zero where mask_y <= 0; maskx: mask_y is x itself (the thin kernel's MASK = 1); scale: mask_scale = 1 / (1 - 0.25)
+CONV_BWD_EPILOGUES = ("none", "stats", "mask", "mask+stats", "mask+stats+stat_x", "mask+scale", "addend", "addend+mask+stats+stat_x", "accumulate",
+                      "accumulate+mask+stats", "accumulate+stats", "maskx", "maskx+stats")
+CONV_ARMS = ("dx", "dx+dw", "dx+dw+dbias")
+CONV_ROLES = {"fwd": ("in", "out", "res"), "bwd": ("x", "dy", "dx", "mask", "statx", "addend")}
+CONV_VIEWS = ("ld", "bs", "ld+bs")
+CONV_INPUTS = ("ordinary", "corner", "lastpixel")
+# the tuning knobs a case may set, with the library's defaults (csrc/elementwise.hip)
+CONV_KNOBS = dict(conv_tile=0, xk=0, pair_max=768, no_s2_dgrad=0, no_thin_bwd=0, no_ksplit128=0, igemm8p_cmajor=0, igemm8p_min_blocks=160, no_bna=0,
+                  thin_cblk=64, thin_blocks=128, thin_ch=8, wgrad_split=0)
+CONV_KINDS = ("64x64 G1", "64x64 G2", "64x64 G4", "128x64", "128x128 G1", "128x128 G2", "256x32", "xk", "s2", "8p", "pair", "thin")
+CONV_TILE = {"64x64": (64, 64), "128x64": (128, 64), "128x128": (128, 128), "256x32": (256, 32), "xk": (64, 64), "s2": (64, 64), "8p": (256, 256),
+             "pair": (64, 64)}
+
+
+class _NS(object):
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def conv_case_fields(c):
+    """a case as a namespace: (id, N, H, W, C, OC, k, stride, pad, dil, dtype, side, epilogue, arm, views, knobs, twin, inputs, why, seed)"""
+    keys = ("id", "N", "H", "W", "C", "OC", "k", "stride", "pad", "dil", "dtype", "side", "epilogue", "arm", "views", "knobs", "twin", "inputs", "why", "seed")
+    return _NS(**dict(zip(keys, c)))
+
+
+def conv_out_size(S, k, stride, pad, dil):
+    return (S + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
+def conv_feats(c):
+    """the epilogue's features as a set: fold = scale + bias; mask+scale = mask + mask_scale; maskx = mask whose tensor is x"""
+    toks = set(c[12].split("+")) - {"none"}
+    if "fold" in toks:
+        toks = (toks - {"fold"}) | {"scale", "bias"}
+    if c[11] == "bwd" and "scale" in toks:
+        toks = (toks - {"scale"}) | {"mask_scale"}
+    if "maskx" in toks:
+        toks = (toks - {"maskx"}) | {"mask", "mask_is_x"}
+    return frozenset(toks)
+
+
+def conv_parse_views(spec, roles):
+    """'mask:ld8 dx:ld+bs' -> {role: (kind, channel offset)}; a role the string does not name is dense"""
+    out = dict((r, ("dense", 0)) for r in roles)
+    for tok in spec.split():
+        role, _, v = tok.partition(":")
+        kind = v.rstrip("0123456789")
+        if role not in out or kind not in CONV_VIEWS:
+            raise ValueError("bad view %r" % tok)
+        out[role] = (kind, int(v[len(kind):] or 0))
+    return out
+
+
+def conv_view(kind, off, ch, pix):
+    """(ld, bs) of a tensor of ch channels and pix pixels per image: `ld` makes it the channels [off, off + ch) of a buffer of ch + off rounded up
+    to 8, plus 8, channels (the offset decides the 16-byte alignment of the slice); `bs` puts three pixel rows of padding behind every image"""
+    ld = ch if "ld" not in kind else (ch + off + 7) // 8 * 8 + 8
+    return ld, pix * ld + (3 * ld if "bs" in kind else 0)
+
+
+def conv_tensors(c):
+    """{role: namespace(ch, pix, ld, bs, off, esz, al)} of the tensors the call takes (al: the slice starts on a 16-byte boundary)"""
+    f = conv_case_fields(c)
+    OH, OW = conv_out_size(f.H, f.k, f.stride, f.pad, f.dil), conv_out_size(f.W, f.k, f.stride, f.pad, f.dil)
+    feats, esz = conv_feats(c), CONV_ESZ[f.dtype]
+    views = conv_parse_views(f.views, CONV_ROLES[f.side])
+    if f.side == "fwd":
+        geo = {"in": (f.C, f.H * f.W, esz, True), "out": (f.OC, OH * OW, 4 if "out_f32" in feats else esz, True), "res": (f.OC, OH * OW, esz, "residual" in feats)}
+    else:
+        px = f.H * f.W
+        geo = {"x": (f.C, px, esz, True), "dy": (f.OC, OH * OW, esz, True), "dx": (f.C, px, esz, True),
+               "mask": (f.C, px, esz, "mask" in feats and "mask_is_x" not in feats), "statx": (f.C, px, esz, "stat_x" in feats), "addend": (f.C, px, esz, "addend" in feats)}
+    out = {}
+    for role, (ch, pix, e, present) in geo.items():
+        kind, off = views[role]
+        if not present:
+            if kind != "dense":
+                raise ValueError("%s: a view for %s, which the call does not take" % (f.id, role))
+            continue
+        ld, bs = conv_view(kind, off, ch, pix)
+        out[role] = _NS(ch=ch, pix=pix, ld=ld, bs=bs, off=off if "ld" in kind else 0, esz=e, al=((off if "ld" in kind else 0) * e) % 16 == 0, kind=kind)
+    if f.side == "bwd" and "mask_is_x" in feats:
+        out["mask"] = out["x"]
+    return out
+
+
+def conv_problem(c, knobs=None):
+    """(a, w): the ConvArgs the entry point builds (conv_fwd_args / conv_dgrad_args: the data gradient is the swapped convolution, in = dy, out = dx)
+    and the WgradArgs (None without dw).  Pointers appear as their 16-byte alignment; the packed weights are aligned."""
+    f = conv_case_fields(c)
+    kn = conv_knobs(c) if knobs is None else knobs
+    OH, OW = conv_out_size(f.H, f.k, f.stride, f.pad, f.dil), conv_out_size(f.W, f.k, f.stride, f.pad, f.dil)
+    feats, t, esz = conv_feats(c), conv_tensors(c), CONV_ESZ[f.dtype]
+    a = _NS(esz=esz, KH=f.k, KW=f.k, stride=f.stride, pad=f.pad, dil=f.dil, N=f.N, cmajor=kn["igemm8p_cmajor"], stats="stats" in feats,
+            res=False, ldres=0, res_bs=0, res_al=True, res_is_out=False, mask=False, ldy=0, y_bs=0, mask_al=True, mask_is_x=False,
+            statx=False, ldsx=0, sx_bs=0, sx_al=True, bias=False, scale=False, relu=False, out_f32=False)
+    if f.side == "fwd":
+        a.mode, a.H, a.W, a.C, a.OH, a.OW, a.OC = 0, f.H, f.W, f.C, OH, OW, f.OC
+        a.ldin, a.in_bs, a.in_al = t["in"].ld, t["in"].bs, t["in"].al
+        a.ldout, a.out_bs, a.out_al = t["out"].ld, t["out"].bs, t["out"].al
+        a.bias, a.scale, a.relu, a.out_f32 = "bias" in feats, "scale" in feats, "relu" in feats, "out_f32" in feats
+        if "residual" in feats:
+            a.res, a.ldres, a.res_bs, a.res_al = True, t["res"].ld, t["res"].bs, t["res"].al
+        return a, None
+    a.mode, a.H, a.W, a.C, a.OH, a.OW, a.OC = 1, OH, OW, f.OC, f.H, f.W, f.C
+    a.ldin, a.in_bs, a.in_al = t["dy"].ld, t["dy"].bs, t["dy"].al
+    a.ldout, a.out_bs, a.out_al = t["dx"].ld, t["dx"].bs, t["dx"].al
+    if "accumulate" in feats:
+        a.res, a.ldres, a.res_bs, a.res_al, a.res_is_out = True, a.ldout, a.out_bs, a.out_al, True
+    elif "addend" in feats:
+        a.res, a.ldres, a.res_bs, a.res_al = True, t["addend"].ld, t["addend"].bs, t["addend"].al
+    if "mask" in feats:
+        a.mask, a.ldy, a.y_bs, a.mask_al, a.mask_is_x = True, t["mask"].ld, t["mask"].bs, t["mask"].al, "mask_is_x" in feats
+    if "stat_x" in feats:
+        a.statx, a.ldsx, a.sx_bs, a.sx_al = True, t["statx"].ld, t["statx"].bs, t["statx"].al
+    w = None
+    if "dw" in f.arm:
+        w = _NS(esz=esz, N=f.N, H=f.H, W=f.W, C=f.C, ldx=t["x"].ld, x_bs=t["x"].bs, x_al=t["x"].al, OH=OH, OW=OW, OC=f.OC, lddy=t["dy"].ld, dy_bs=t["dy"].bs,
+                dy_al=t["dy"].al, KH=f.k, KW=f.k, stride=f.stride, pad=f.pad, dil=f.dil, dbias="dbias" in f.arm)
+    return a, w
+
+
+def conv_knobs(c, twin=False):
+    """the knob values a case's launch runs under: CONV_KNOBS overridden by the case's own (or its twin's) set"""
+    kn = dict(CONV_KNOBS)
+    kn.update(dict(c[16] if twin else c[15]))
+    return kn
+
+
+# ---- csrc/conv.hip, host side ----------------------------------------------------------------------------------------------------
+def conv_is_vec(a):
+    """Mirrors conv_is_vec: C in whole 16-byte chunks, rows and images of `in` 16-byte aligned (the packed weight always is)"""
+    epc = 16 // a.esz
+    return a.C % epc == 0 and a.ldin % epc == 0 and a.in_bs % epc == 0 and a.in_al
+
+
+def conv_blocks(a, bm, bn):
+    return _ceil_div(a.N * a.OH * a.OW, bm) * _ceil_div(a.OC, bn)
+
+
+def conv_k_tiles(a):
+    return _ceil_div(a.KH * a.KW * a.C, 8 * (16 // a.esz))
+
+
+def conv_takes_128(a):
+    return a.OC > 64 and conv_k_tiles(a) >= 16 and conv_blocks(a, 128, 128) >= 256
+
+
+def _conv_epi_aligned(a):
+    """what igemm_s2_ok, igemm_xk_copies and the row-vectorised epilogue all ask of the epilogue operands but for OC % 8 and the output's own rows"""
+    epc = 16 // a.esz
+    return (a.out_al and (not a.res or a.res_al) and (not a.mask or a.mask_al) and (not a.statx or a.sx_al)
+            and (not a.res or (a.ldres % epc == 0 and a.res_bs % epc == 0)) and (not a.mask or (a.ldy % epc == 0 and a.y_bs % epc == 0))
+            and (not a.statx or (a.ldsx % epc == 0 and a.sx_bs % epc == 0)))
+
+
+def conv_epilogue_vec_ok(a):
+    """Mirrors vec_ok of igemm_body's epilogue: true = the row-vectorised copy, false = the scalar one"""
+    eo = 4 if a.out_f32 else 16 // a.esz
+    return _conv_epi_aligned(a) and a.ldout % eo == 0 and a.out_bs % eo == 0 and a.OC % 8 == 0
+
+
+def igemm_s2_ok(a, kn):
+    """Mirrors igemm_s2_ok: the parity-class kernel for the data gradient of a stride-2 convolution"""
+    epc = 16 // a.esz
+    M = a.N * a.OH * a.OW
+    if a.KH * a.KW == 1 and kn["no_s2_dgrad"] != -1:
+        return False
+    if (kn["no_s2_dgrad"] == 1 or a.stride != 2 or a.dil != 1 or a.C % (8 * epc) != 0 or a.OH & 1 or a.OW & 1 or M % 4 or (M // 4) % 64 or a.OC <= 32
+            or a.OC % 8):
+        return False
+    if a.out_f32 or a.bias or a.scale:
+        return False
+    return _conv_epi_aligned(a) and a.ldout % epc == 0 and a.out_bs % epc == 0
+
+
+def igemm_xk_copies(a, kn, scratch):
+    """Mirrors igemm_xk_copies: copies of the 64x64 tile grid the K range is cut over, 0 = not applicable.  scratch: the partial-tile region is
+    registered on the launching stream (tests.hip_utils.init does that for the 2-byte dtypes); the 8 MiB / 16384-counter limits are mirrored"""
+    if a.esz != 2 or kn["xk"] < 0 or not scratch:
+        return 0
+    if a.OC <= 32 or a.OC % 8 or a.out_f32:
+        return 0
+    if not (_conv_epi_aligned(a) and a.ldout % 8 == 0 and a.out_bs % 8 == 0):
+        return 0
+    nb, nkt = conv_blocks(a, 64, 64), conv_k_tiles(a)
+    S = kn["xk"] if kn["xk"] > 0 else 0
+    if S <= 0:
+        if not ((nb <= 64 and nkt >= 36) or (nb <= 128 and nkt >= 128)):
+            return 0
+        S = 4
+    S = min(S, nkt)
+    if S >= 2:
+        per = _ceil_div(nkt, S)
+        S = _ceil_div(nkt, per)
+    if S < 2 or nb > 16384 or nb * S * 64 * 64 * 4 > (8 << 20):
+        return 0
+    return S
+
+
+def igemm8p_ok(a):
+    """Mirrors igemm8p_ok (csrc/igemm8p.hpp): the 256x256 LDS-DMA kernel's operand and epilogue conditions"""
+    if a.esz != 2 or a.C % 64 or a.OC % 8:
+        return False
+    if a.ldin % 8 or a.in_bs % 8 or not a.in_al:
+        return False
+    eo = 4 if a.out_f32 else 8
+    if not a.out_al or a.ldout % eo or a.out_bs % eo:
+        return False
+    if a.res and (not a.res_al or a.ldres % 8 or a.res_bs % 8):
+        return False
+    if a.mask and (not a.mask_al or a.ldy % 8 or a.y_bs % 8):
+        return False
+    return not (a.statx and (not a.sx_al or a.ldsx % 8 or a.sx_bs % 8))
+
+
+def conv_plan(a, kn, scratch):
+    """(kind, n, forced): mirrors conv_plan<T, MODE, VEC> without the dropout epilogue (emrt_conv2d_drop is not swept here).  kind: 64x64,
+    128x64, 128x128, 256x32, xk, s2, 8p; n: wave groups (64x64, 128x128) or copies (xk).  A forced tile the layer cannot take falls through the
+    ladder below it, minus the cross-block split."""
+    vec = conv_is_vec(a)
+    vec2 = vec and a.esz == 2
+    tile = kn["conv_tile"]
+    if a.mode == 1 and vec and not tile and igemm_s2_ok(a, kn):
+        return "s2", 1, False
+    if tile == 1:
+        return "64x64", 1, True
+    if tile == 2:
+        return "128x64", 1, True
+    if tile == 3:
+        return "128x128", 1, True
+    if tile == 4:
+        return "256x32", 1, True
+    if tile == 5 and vec:
+        return "64x64", 2, True
+    if tile == 6 and vec:
+        return "64x64", 4, True
+    if tile == 7 and vec2 and igemm8p_ok(a):
+        return "8p", 1, True
+    if tile == 8 and vec2:
+        return "128x128", 2, True
+    if a.OC <= 32:
+        return "256x32", 1, False
+    if vec2 and not tile:
+        S = igemm_xk_copies(a, kn, scratch)
+        if S >= 2:
+            return "xk", S, False
+    if vec2:
+        nb256, nkt64, minb = conv_blocks(a, 256, 256), a.KH * a.KW * a.C // 64, kn["igemm8p_min_blocks"]
+        if minb > 0 and nkt64 >= 16 and (nb256 >= minb or (nb256 >= (minb * 3) // 5 and nkt64 >= 144)) and igemm8p_ok(a):
+            return "8p", 1, False
+    nkt = conv_k_tiles(a)
+    if conv_takes_128(a):
+        ksplit = vec2 and nkt >= 32 and conv_blocks(a, 128, 128) == 256 and not kn["no_ksplit128"]
+        return "128x128", 2 if ksplit else 1, False
+    if vec:
+        nb = conv_blocks(a, 64, 64)
+        if nb <= 128 and nkt >= 32:
+            return "64x64", 4, False
+        if nb <= 256 and nkt >= 16:
+            return "64x64", 2, False
+    return "64x64", 1, False
+
+
+def bna_plan(a, kn, scratch):
+    """Mirrors bna_plan: the kind that runs the layer with the BatchNorm on its A operand, or "none" (a_out aligned)"""
+    bk = 8 * (16 // a.esz)
+    if not conv_is_vec(a) or a.C % bk or a.C > 1024 or a.OC <= 32:
+        return "none", 0, False
+    if a.stride != 1 or a.KH != a.KW or a.KH not in (1, 3) or a.pad != a.dil * (a.KH >> 1) or a.OH != a.H or a.OW != a.W:
+        return "none", 0, False
+    if a.KH == 3 and a.C > 128 and kn["no_bna"] != -1:
+        return "none", 0, False
+    p = conv_plan(a, kn, scratch)
+    if kn["conv_tile"] and not p[2]:
+        return "none", 0, False
+    return p if p[0] in ("64x64", "xk") else ("none", 0, False)
+
+
+def wgrad_is_vec(w):
+    epc = 16 // w.esz
+    return w.C % epc == 0 and w.OC % epc == 0 and w.ldx % epc == 0 and w.lddy % epc == 0 and w.x_bs % epc == 0 and w.dy_bs % epc == 0 and w.x_al and w.dy_al
+
+
+def wgrad_plan(w, kn):
+    """(tx, ty, S): mirrors wgrad_plan's cost model (the same double arithmetic)"""
+    bkm = 64 if w.esz == 2 else 32
+    K, M = w.KH * w.KW * w.C, w.N * w.OH * w.OW
+    tx, ty = _ceil_div(K, 128), _ceil_div(w.OC, 128)
+    mt = _ceil_div(M, bkm)
+    atom_us = float(tx) * 128.0 * float(ty) * 128.0 * 4.0 / 1.3e6
+    S, best = 1, 1e30
+    for sc in (1, 2, 4, 8, 16, 32, 64, 128):
+        if sc > mt or (sc > 1 and tx * ty >= 256):
+            break
+        per, nblk = float(_ceil_div(mt, sc)), float(tx) * ty * sc
+        t = per * (nblk / 1024.0 if nblk > 1024.0 else 1.0) + sc * atom_us
+        if t < best:
+            best, S = t, sc
+    if kn["wgrad_split"] > 0:
+        S = min(kn["wgrad_split"], mt)
+    per = _ceil_div(mt, S)
+    return tx, ty, _ceil_div(mt, per)
+
+
+def thin_bwd_ok(a, w):
+    """Mirrors thin_bwd_ok: the one-pass backward of a 1x1 layer with at most 8 output channels (the 2^31-element limits hold for every case here)"""
+    if w is None or w.KH != 1 or w.KW != 1 or w.stride != 1 or w.pad != 0 or w.OC > 8:
+        return False
+    if a.statx or (a.res and a.mask) or (a.res and not a.res_is_out):
+        return False
+    if w.C < 32 or w.C > 1024 or w.C & (w.C - 1):
+        return False
+    if not w.x_al or not a.out_al or (a.mask and not a.mask_al):
+        return False
+    if w.ldx % 4 or w.x_bs % 4 or a.ldout % 4 or a.out_bs % 4:
+        return False
+    return not (a.mask and (a.ldy % 4 or a.y_bs % 4))
+
+
+def thin_bwd_geometry(a, w, kn):
+    """(CH, pixel slots per block, pixels per block, MASK): mirrors thin_bwd_launch / thin_bwd_launch_ch"""
+    can8 = w.C >= 64 and w.ldx % 8 == 0 and w.x_bs % 8 == 0 and a.ldout % 8 == 0 and a.out_bs % 8 == 0 and (not a.mask or (a.ldy % 8 == 0 and a.y_bs % 8 == 0)) and 16 // w.esz <= 8
+    CH = 8 if kn["thin_ch"] == 8 and can8 else 4
+    cblk = min(max(kn["thin_cblk"], 8 * CH), w.C, 256 * CH)
+    sh = 0
+    while (CH << sh) < cblk:
+        sh += 1
+    ppb = 256 >> sh
+    M = w.N * w.H * w.W
+    per = _ceil_div(M, kn["thin_blocks"] if kn["thin_blocks"] > 0 else 128)
+    per = max(_ceil_div(per, 2 * ppb) * 2 * ppb, 8 * ppb)
+    return CH, ppb, per, 0 if not a.mask else (1 if a.mask_is_x else 2)
+
+
+def conv_bwd_pairs(a, w, kn):
+    """Mirrors the pair condition of conv_bwd_dispatch: data-gradient and weight-gradient tiles in one launch"""
+    if w is None or not (conv_is_vec(a) and wgrad_is_vec(w)):
+        return False
+    tx, ty, S = wgrad_plan(w, kn)
+    nd = conv_blocks(a, 64, 64)
+    return a.OC > 32 and not conv_takes_128(a) and nd <= kn["pair_max"] and nd + tx * ty * S <= 4096
+
+
+def _conv_route(c, twin):
+    kn = conv_knobs(c, twin)
+    a, w = conv_problem(c, kn)
+    scratch = a.esz == 2
+    if a.mode == 1 and w is not None:
+        if thin_bwd_ok(a, w) and not kn["no_thin_bwd"]:
+            return "thin", thin_bwd_geometry(a, w, kn)[0], "thin"
+        if conv_bwd_pairs(a, w, kn):
+            return "pair", 1, "vec" if conv_epilogue_vec_ok(a) else "scalar"
+    kind, n, _ = conv_plan(a, kn, scratch)
+    return kind, n, "8p" if kind == "8p" else ("vec" if conv_epilogue_vec_ok(a) else "scalar")
+
+
+_CONV_ROUTES = {}
+
+
+def conv_route(c, twin=False):
+    """(kind, n, epilogue copy) of the launch a single case makes: kind of CONV_TILE or "thin"; copy: vec (igemm_body's row-vectorised epilogue),
+    scalar (its fallback), 8p (igemm8p_kernel's per-wave copy), thin"""
+    key = (c[0], twin)
+    if key not in _CONV_ROUTES:
+        _CONV_ROUTES[key] = _conv_route(c, twin)
+    return _CONV_ROUTES[key]
+
+
+def conv_kind_name(route):
+    kind, n, _ = route
+    return "%s G%d" % (kind, n) if kind in ("64x64", "128x128") else kind
+
+
+def conv_stat_n(c, twin=False):
+    """fp32 additions in front of one fp64 atomic of the statistics, read from the kernels: igemm_body's row-vectorised epilogue adds BM / RP rows per
+    thread and then RP partials per column; its scalar copy 16 TM rows per lane and the other half-wave; igemm8p_kernel 16 rows per lane, 8 row
+    lanes by shuffles and the two wave rows: in each at most the tile's row count BM (64, 128 or 256).  thin_bwd_kernel: a thread's share of the
+    block's pixels, then the block's pixel slots: at most the block's pixel count."""
+    route = conv_route(c, twin)
+    if route[0] == "thin":
+        kn = conv_knobs(c, twin)
+        a, w = conv_problem(c, kn)
+        return min(thin_bwd_geometry(a, w, kn)[2], w.N * w.H * w.W)
+    return CONV_TILE[route[0]][0]
+
+
+def conv_gemm_dims(c):
+    """(M, N) of the implicit GEMM whose epilogue the case runs: output pixels x output channels forward, input pixels x input channels backward"""
+    f = conv_case_fields(c)
+    if f.side == "fwd":
+        return f.N * conv_out_size(f.H, f.k, f.stride, f.pad, f.dil) * conv_out_size(f.W, f.k, f.stride, f.pad, f.dil), f.OC
+    return f.N * f.H * f.W, f.C
+
+
+def conv_group_members(c):
+    """the member cases of a grouped case (side multi: emrt_conv2d_dgrad_multi; side group: emrt_conv2d_group)"""
+    return [conv_cases()[i] for i in c[14]]
+
+
+def conv_group_is_one_launch(c):
+    """Mirrors conv_group_launch: every problem on the vector path with OC > 32 and at most tile_cap 64x64 tiles, at most 4096 in all"""
+    cap = 2048 if c[11] == "multi" else 4096
+    ps = [conv_problem(m, dict(CONV_KNOBS))[0] for m in conv_group_members(c)]
+    return all(conv_is_vec(a) and a.OC > 32 and conv_blocks(a, 64, 64) <= cap for a in ps) and sum(conv_blocks(a, 64, 64) for a in ps) <= 4096
+
+
+def conv_in_domain(c):
+    """the checks of emrt_conv2d (mode 0), emrt_conv2d_bwd, emrt_conv2d_dgrad_multi and emrt_conv2d_group, plus what the case format itself asks"""
+    f = conv_case_fields(c)
+    if f.side in ("multi", "group"):
+        ms = conv_group_members(c)
+        want = "bwd" if f.side == "multi" else "fwd"
+        if len(ms) != 2 or any(m[11] != want or m[10] != f.dtype for m in ms) or ms[0][1:10] == ms[1][1:10]:
+            return False
+        if f.side == "group" and any(m[9] != 1 or "scale" in conv_feats(m) for m in ms):          # EmrtConvDesc: no dilation, no folded scale
+            return False
+        return (f.dtype != "f16" or f.side == "group") and all(conv_in_domain(m) for m in ms)
+    if f.side not in ("fwd", "bwd") or f.dtype not in CONV_ESZ or f.inputs not in CONV_INPUTS:
+        return False
+    if not (f.N > 0 and f.H > 0 and f.W > 0 and f.C > 0 and f.OC > 0 and f.k > 0 and f.stride > 0 and f.pad >= 0 and f.dil >= 1):
+        return False
+    OH, OW = conv_out_size(f.H, f.k, f.stride, f.pad, f.dil), conv_out_size(f.W, f.k, f.stride, f.pad, f.dil)
+    if OH <= 0 or OW <= 0:
+        return False
+    if f.side == "fwd" and (f.epilogue not in CONV_FWD_EPILOGUES or f.arm != "none"):
+        return False
+    if f.side == "bwd" and (f.epilogue not in CONV_BWD_EPILOGUES or f.arm not in CONV_ARMS or f.dtype == "f16"):
+        return False
+    if any(k not in CONV_KNOBS for k, _ in f.knobs + f.twin):
+        return False
+    try:
+        t = conv_tensors(c)
+    except (ValueError, KeyError):
+        return False
+    for v in t.values():          # strides at least the map; every view here keeps them multiples of 4 elements only by the tensor's own width
+        if v.ld < v.ch + v.off or v.bs < v.pix * v.ld:
+            return False
+    feats = conv_feats(c)
+    if "accumulate" in feats and "addend" in feats:
+        return False
+    if "stat_x" in feats and "mask" not in feats:
+        return False
+    if "mask" in feats and "out_f32" in feats:
+        return False
+    return max(v.bs * f.N for v in t.values()) <= MAX_ELEMS and f.OC * f.k * f.k * f.C <= MAX_ELEMS
+
+
+_cv_L72k3 = (2, 9, 11, 72, 64, 3, 1, 1, 1)          # backward: M = 198 (four 64-row tiles, the last of 6 rows), 72 channels (two 64-column tiles), 9 k-tiles in bf16
+_cv_L72k1 = (2, 9, 11, 72, 128, 1, 1, 0, 1)         # ... 2 k-tiles in bf16: fewer than the wave groups / copies asked for
+_cv_L136k3 = (3, 10, 11, 136, 128, 3, 1, 1, 1)      # backward: M = 330 (three 128-row tiles, two 256-row tiles), 136 channels (two 128-column tiles)
+_cv_L136k1 = (3, 10, 11, 136, 64, 1, 1, 0, 1)
+_cv_L264k3 = (3, 10, 11, 264, 64, 3, 1, 1, 1)       # backward on the 256x256 kernel: two ragged M tiles, two ragged OC tiles, C = 64
+_cv_L264k1 = (3, 10, 11, 264, 64, 1, 1, 0, 1)       # ... one k-tile: the loop's odd tail multiplies an all-zero tile
+_cv_L24 = (3, 10, 11, 24, 64, 3, 1, 1, 1)           # backward of a layer with C <= 32: the ladder's 256x32 rung, vector epilogue
+_cv_L6 = (3, 10, 11, 6, 64, 1, 1, 0, 1)             # ... scalar epilogue
+_cv_L7 = (3, 10, 11, 7, 64, 3, 1, 1, 1)
+_cv_L20 = (2, 9, 11, 20, 64, 3, 1, 1, 1)            # C % 8 != 0: the scalar epilogue by the channel count
+_cv_L100 = (3, 10, 11, 100, 128, 3, 1, 1, 1)
+_cv_F72k3 = (2, 9, 11, 64, 72, 3, 1, 1, 1)          # forward twins of the above
+_cv_F72k1 = (2, 9, 11, 128, 72, 1, 1, 0, 1)
+_cv_F136k3 = (3, 10, 11, 128, 136, 3, 1, 1, 1)
+_cv_F136k1 = (3, 10, 11, 64, 136, 1, 1, 0, 1)
+_cv_F264k3 = (3, 10, 11, 64, 264, 3, 1, 1, 1)
+_cv_F264k1 = (3, 10, 11, 64, 264, 1, 1, 0, 1)
+_cv_F24 = (3, 10, 11, 64, 24, 3, 1, 1, 1)
+_cv_F6 = (3, 10, 11, 64, 6, 1, 1, 0, 1)
+_cv_F7 = (3, 10, 11, 64, 7, 3, 1, 1, 1)
+_cv_F20 = (2, 9, 11, 64, 20, 3, 1, 1, 1)
+_cv_F100 = (3, 10, 11, 128, 100, 3, 1, 1, 1)
+_cv_S3a = (1, 16, 16, 72, 64, 3, 2, 1, 1)           # stride 2: 256 input pixels = 4 parity classes of one 64-row tile each; 72 channels: a ragged column tile
+_cv_S3b = (2, 8, 16, 64, 128, 3, 2, 1, 1)
+_cv_S5a = (1, 16, 16, 72, 128, 5, 2, 2, 1)
+_cv_S5b = (2, 8, 16, 64, 64, 5, 2, 2, 1)
+_cv_S2a = (1, 16, 16, 72, 64, 2, 2, 0, 1)
+_cv_S2b = (2, 8, 16, 64, 128, 2, 2, 0, 1)
+_cv_T32o6 = (3, 10, 11, 32, 6, 1, 1, 0, 1)          # thin backward: 330 pixels = two pixel blocks of 256, the second ragged; C = 32: 4 channels per thread
+_cv_T64o7 = (3, 10, 11, 64, 7, 1, 1, 0, 1)
+_cv_T256o6 = (3, 10, 11, 256, 6, 1, 1, 0, 1)        # four channel chunks
+_cv_T256o7 = (3, 10, 11, 256, 7, 1, 1, 0, 1)
+_T = lambda t: (("conv_tile", t),)
+_TP = lambda t: (("conv_tile", t), ("pair_max", 0))          # with dw the pair kernel would come first
+_XK = lambda s: (("xk", s),)
+_XKP = lambda s: (("xk", s), ("pair_max", 0))
+_8P = lambda cm: (("conv_tile", 7), ("igemm8p_cmajor", cm))
+_8PP = lambda cm: (("conv_tile", 7), ("igemm8p_cmajor", cm), ("pair_max", 0))
+_S2TWIN = (("no_s2_dgrad", 1), ("conv_tile", 1), ("pair_max", 0))          # the generic 64x64 tile without a K split: the parity-class kernel's k order
+_NOPAIR = (("pair_max", 0),)
+_PAIR = (("pair_max", 1 << 30),)
+_NOTHIN = (("no_thin_bwd", 1),)
+_AMSX = "addend+mask+stats+stat_x"
+_ACMS = "accumulate+mask+stats"
+# (layer (N, H, W, C, OC, k, stride, pad, dilation), dtype, side, epilogue, backward arm, views, knobs, twin knobs, input recipe, what the row is there for)
+_CONV_ROWS = (
+    # ---- backward, 64x64 tile, one wave group ----
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "mask:ld8 addend:bs", _T(1), (), "ordinary", "64x64: every backward feature at once, ragged M and OC tiles"),
+    (_cv_L72k3, "f32", "bwd", _AMSX, "dx+dw", "mask:ld2 dx:ld x:ld dy:bs", _TP(1), (), "ordinary", "64x64 fp32: a mask slice 8 bytes off the grid: the scalar epilogue by alignment alone"),
+    (_cv_L72k1, "bf16", "bwd", _ACMS, "dx", "dx:ld+bs8 dy:ld", _T(1), (), "ordinary", "64x64: accumulate into a padded slice of dx"),
+    (_cv_L20, "bf16", "bwd", "accumulate", "dx+dw+dbias", "x:ld+bs", _TP(1), (), "ordinary", "64x64: 20 channels, the scalar epilogue by the channel count"),
+    (_cv_L72k3, "bf16", "bwd", "none", "dx", "", _T(1), (), "corner", "64x64: corner pixels only, exact zeros elsewhere"),
+    (_cv_L72k3, "bf16", "bwd", "mask", "dx", "mask:bs", _T(1), (), "lastpixel", "64x64: dy at the last pixel, masked"),
+    # ---- two and four wave groups ----
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "statx:ld16 addend:ld+bs", _T(5), (), "ordinary", "64x64 G2: the summed accumulators under every feature"),
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "addend:ld4", _T(5), (), "ordinary", "64x64 G2: an addend slice 8 bytes off the grid: scalar epilogue"),
+    (_cv_L72k1, "f32", "bwd", _ACMS, "dx+dw", "dy:bs x:bs", _TP(5), (), "ordinary", "64x64 G2 fp32, 4 k-tiles on two groups"),
+    (_cv_L72k3, "f32", "bwd", "accumulate", "dx", "dx:ld2", _T(5), (), "ordinary", "64x64 G2: dx itself off the grid: scalar epilogue, accumulate"),
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "mask:ld+bs statx:bs", _T(6), (), "ordinary", "64x64 G4"),
+    (_cv_L72k1, "bf16", "bwd", _AMSX, "dx+dw", "statx:ld4 x:ld+bs dy:ld", _TP(6), (), "ordinary", "64x64 G4: 2 k-tiles on four groups (two walk nothing); stat_x off the grid: scalar"),
+    (_cv_L72k3, "f32", "bwd", _ACMS, "dx", "", _T(6), (), "ordinary", "64x64 G4 fp32"),
+    (_cv_L20, "f32", "bwd", "accumulate+stats", "dx", "dx:bs", _T(6), (), "ordinary", "64x64 G4: 20 channels, scalar epilogue with statistics"),
+    # ---- 128x64 ----
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "dx:ld8", _T(2), (), "ordinary", "128x64: 198 rows = two tiles, the second of 70 rows"),
+    (_cv_L72k3, "f32", "bwd", _AMSX, "dx+dw+dbias", "mask:ld+bs2 x:bs dy:ld+bs", _TP(2), (), "ordinary", "128x64 fp32, scalar epilogue by a mask slice off the grid"),
+    (_cv_L72k1, "bf16", "bwd", _ACMS, "dx", "mask:ld", _T(2), (), "ordinary", "128x64: accumulate"),
+    (_cv_L20, "bf16", "bwd", "accumulate", "dx", "", _T(2), (), "ordinary", "128x64: 20 channels, scalar epilogue"),
+    # ---- 128x128, one and two wave groups ----
+    (_cv_L136k3, "bf16", "bwd", _AMSX, "dx", "mask:bs addend:ld8", _T(3), (), "ordinary", "128x128: 330 rows = three tiles, 136 channels = two tiles"),
+    (_cv_L100, "bf16", "bwd", _AMSX, "dx", "", _T(3), (), "ordinary", "128x128: 100 channels, scalar epilogue"),
+    (_cv_L136k1, "f32", "bwd", _ACMS, "dx+dw", "x:ld8 dy:ld", _TP(3), (), "ordinary", "128x128 fp32, accumulate"),
+    (_cv_L136k3, "f32", "bwd", "accumulate", "dx", "dx:ld+bs2", _T(3), (), "ordinary", "128x128 fp32: dx off the grid, scalar epilogue"),
+    (_cv_L136k3, "bf16", "bwd", _AMSX, "dx", "statx:ld+bs8", _T(8), (), "ordinary", "128x128 G2: K split over two wave groups"),
+    (_cv_L136k1, "bf16", "bwd", _AMSX, "dx+dw", "mask:ld4", _TP(8), (), "ordinary", "128x128 G2: one k-tile on two groups; scalar epilogue by alignment"),
+    (_cv_L136k3, "bf16", "bwd", _ACMS, "dx", "dy:ld+bs", _T(8), (), "ordinary", "128x128 G2: accumulate"),
+    (_cv_L100, "bf16", "bwd", "accumulate+stats", "dx", "", _T(8), (), "ordinary", "128x128 G2: 100 channels, scalar epilogue, accumulate with statistics"),
+    # ---- 256x32: the ladder's rung for a layer with C <= 32, and forced ----
+    (_cv_L24, "bf16", "bwd", "mask+stats", "dx+dw", "mask:ld8", (), (), "ordinary", "256x32 by the ladder: 24 channels take the vector epilogue"),
+    (_cv_L6, "bf16", "bwd", "mask+stats", "dx+dw+dbias", "", (), (), "ordinary", "256x32: 6 channels, scalar epilogue, mask + statistics"),
+    (_cv_L7, "f32", "bwd", "mask+stats", "dx", "mask:bs", (), (), "ordinary", "256x32: 7 channels"),
+    (_cv_L24, "f32", "bwd", _AMSX, "dx", "addend:ld4", (), (), "ordinary", "256x32 fp32: vector epilogue with every feature"),
+    (_cv_L7, "bf16", "bwd", _AMSX, "dx", "", (), (), "ordinary", "256x32: 7 channels with every feature"),
+    (_cv_L24, "bf16", "bwd", _ACMS, "dx", "dx:ld+bs8", (), (), "ordinary", "256x32: accumulate into a slice"),
+    (_cv_L6, "f32", "bwd", "accumulate", "dx", "", (), (), "ordinary", "256x32: accumulate, scalar"),
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "", _T(4), (), "ordinary", "256x32 forced on 72 channels: three column tiles, the last of 8"),
+    # ---- cross-block K split ----
+    (_cv_L72k3, "bf16", "bwd", _AMSX, "dx", "mask:ld8", _XK(2), (), "ordinary", "xk = 2: 9 k-tiles as 5 + 4"),
+    (_cv_L72k3, "bf16", "bwd", "mask+stats+stat_x", "dx+dw", "statx:ld+bs", _XKP(3), (), "ordinary", "xk = 3: three copies of 3 k-tiles"),
+    (_cv_L72k3, "bf16", "bwd", "addend", "dx", "addend:ld+bs16 dx:ld", _XK(8), (), "ordinary", "xk = 8: cut down to 5 copies of 2 k-tiles, the last of one"),
+    (_cv_L72k1, "bf16", "bwd", _ACMS, "dx", "", _XK(8), (), "ordinary", "xk = 8 on 2 k-tiles: fewer k-tiles than copies asked for"),
+    (_cv_L72k3, "bf16", "bwd", "accumulate", "dx", "dx:bs", _XK(2), (), "ordinary", "xk = 2: accumulate"),
+    (_cv_L72k1, "bf16", "bwd", _AMSX, "dx", "", _XK(3), (), "ordinary", "xk = 3 on 2 k-tiles"),
+    # ---- parity-class kernel, each with its generic twin (bit-identical dx) ----
+    (_cv_S3a, "bf16", "bwd", _AMSX, "dx", "dx:ld+bs8 mask:ld8", (), _S2TWIN, "ordinary", "s2 3x3: the remapped row finds mask, stat_x and addend; strided dx"),
+    (_cv_S3b, "bf16", "bwd", "mask+stats+stat_x", "dx+dw", "mask:bs statx:ld", _NOPAIR, _S2TWIN, "ordinary", "s2 3x3 on 2 x 8 x 16: a class spans both images"),
+    (_cv_S5a, "bf16", "bwd", "mask+scale", "dx", "mask:ld+bs", (), _S2TWIN, "ordinary", "s2 5x5 pad 2: mask_scale on the parity-class path"),
+    (_cv_S5b, "f32", "bwd", _ACMS, "dx", "dx:ld4", (), _S2TWIN, "ordinary", "s2 5x5 fp32: accumulate into a strided dx"),
+    (_cv_S2a, "bf16", "bwd", "addend", "dx", "addend:ld8", (), _S2TWIN, "ordinary", "s2 2x2 pad 0: one tap per class"),
+    (_cv_S2b, "f32", "bwd", "accumulate", "dx", "", (), _S2TWIN, "ordinary", "s2 2x2 fp32"),
+    (_cv_S3a, "f32", "bwd", "stats", "dx", "", (), _S2TWIN, "ordinary", "s2 3x3 fp32: statistics alone"),
+    (_cv_S3b, "bf16", "bwd", _AMSX, "dx", "statx:ld+bs8 addend:bs", (), _S2TWIN, "lastpixel", "s2: dy at the last pixel, every feature"),
+    # ---- pair kernel ----
+    (_cv_L72k3, "bf16", "bwd", "mask+stats", "dx+dw+dbias", "mask:ld8", _PAIR, (), "ordinary", "pair: mask + statistics on the data-gradient half, dw from random contents"),
+    (_cv_L72k3, "f32", "bwd", "mask+stats", "dx+dw+dbias", "", _PAIR, (), "ordinary", "pair fp32"),
+    (_cv_L72k1, "bf16", "bwd", _AMSX, "dx+dw", "addend:ld+bs dx:bs", _PAIR, (), "ordinary", "pair: every feature"),
+    (_cv_L136k1, "f32", "bwd", _AMSX, "dx+dw+dbias", "", _PAIR, (), "ordinary", "pair fp32, 330 rows"),
+    (_cv_L72k3, "bf16", "bwd", _ACMS, "dx+dw", "", _PAIR, (), "ordinary", "pair: accumulate"),
+    (_cv_L72k3, "f32", "bwd", "accumulate", "dx+dw+dbias", "dx:ld4", _PAIR, (), "corner", "pair fp32: accumulate, corner pixels"),
+    # ---- 256x256 LDS-DMA kernel: k = 3 and k = 1, both k orders, every backward epilogue ----
+    (_cv_L264k3, "bf16", "bwd", "none", "dx", "", _8P(0), (), "ordinary", "8p 3x3 tap-major: plain"),
+    (_cv_L264k3, "bf16", "bwd", "mask+stats+stat_x", "dx", "mask:ld8 statx:bs", _8P(0), (), "ordinary", "8p: strided mask, stat_x"),
+    (_cv_L264k3, "bf16", "bwd", _AMSX, "dx+dw", "mask:ld+bs8 addend:ld16", _8PP(0), (), "ordinary", "8p: strided mask and addend that keep it eligible"),
+    (_cv_L264k3, "bf16", "bwd", "accumulate", "dx", "dx:ld8", _8P(0), (), "ordinary", "8p: accumulate into a slice"),
+    (_cv_L264k3, "bf16", "bwd", "stats", "dx", "", _8P(1), (), "ordinary", "8p 3x3 channel-block-major: statistics"),
+    (_cv_L264k3, "bf16", "bwd", "mask", "dx", "mask:bs", _8P(1), (), "corner", "8p cmajor: mask, corner pixels"),
+    (_cv_L264k3, "bf16", "bwd", "addend", "dx", "addend:ld+bs", _8P(1), (), "ordinary", "8p cmajor: addend"),
+    (_cv_L264k3, "bf16", "bwd", _ACMS, "dx+dw+dbias", "", _8PP(1), (), "ordinary", "8p cmajor: accumulate + mask + statistics"),
+    (_cv_L264k1, "bf16", "bwd", "mask+stats", "dx", "mask:ld", _8P(0), (), "ordinary", "8p 1x1: one k-tile"),
+    (_cv_L264k1, "bf16", "bwd", "mask+scale", "dx", "", _8P(0), (), "ordinary", "8p 1x1: mask_scale"),
+    (_cv_L264k1, "bf16", "bwd", _AMSX, "dx", "mask:ld+bs statx:ld8 addend:bs", _8P(0), (), "ordinary", "8p 1x1: every operand strided"),
+    (_cv_L264k1, "bf16", "bwd", "mask+stats+stat_x", "dx", "statx:ld+bs", _8P(1), (), "ordinary", "8p 1x1 cmajor"),
+    (_cv_L264k1, "bf16", "bwd", _ACMS, "dx", "dx:ld+bs", _8P(1), (), "lastpixel", "8p 1x1 cmajor: accumulate, dy at the last pixel"),
+    (_cv_L264k3, "bf16", "bwd", _AMSX, "dx", "mask:ld4", _8P(0), (), "ordinary", "8p refused: a mask slice off the grid sends conv_tile = 7 down the ladder to the 64x64 tile, scalar epilogue"),
+    # ---- thin backward, each with the generic kernels as twin ----
+    (_cv_T32o6, "bf16", "bwd", "none", "dx+dw+dbias", "", (), _NOTHIN, "ordinary", "thin MASK 0, C = 32: 4 channels per thread"),
+    (_cv_T64o7, "f32", "bwd", "stats", "dx+dw", "x:ld", (), _NOTHIN, "ordinary", "thin MASK 0 with statistics, 7 output channels"),
+    (_cv_T256o6, "bf16", "bwd", "accumulate", "dx+dw+dbias", "dx:ld+bs8", (), _NOTHIN, "ordinary", "thin ACC: four channel chunks"),
+    (_cv_T64o7, "bf16", "bwd", "accumulate+stats", "dx+dw", "", (), _NOTHIN, "ordinary", "thin ACC with statistics"),
+    (_cv_T64o7, "bf16", "bwd", "maskx", "dx+dw+dbias", "x:bs", (), _NOTHIN, "ordinary", "thin MASK 1: mask_y is x"),
+    (_cv_T256o7, "f32", "bwd", "maskx+stats", "dx+dw", "", (), _NOTHIN, "ordinary", "thin MASK 1 with statistics, fp32"),
+    (_cv_T32o6, "f32", "bwd", "mask", "dx+dw", "mask:ld4", (), _NOTHIN, "ordinary", "thin MASK 2, C = 32 fp32"),
+    (_cv_T256o6, "bf16", "bwd", "mask+stats", "dx+dw+dbias", "mask:ld+bs8", (), _NOTHIN, "ordinary", "thin MASK 2 with statistics"),
+    (_cv_T64o7, "bf16", "bwd", "mask+scale", "dx+dw", "mask:bs", (), _NOTHIN, "lastpixel", "thin MASK 2 with mask_scale, dy at the last pixel"),
+    (_cv_T256o6, "bf16", "bwd", _ACMS, "dx+dw", "", (), (), "ordinary", "accumulate + mask at a thin shape: refused by thin_bwd_ok, the generic kernels"),
+    # ---- forward ----
+    (_cv_F72k3, "bf16", "fwd", "bias+residual+relu", "none", "res:ld8 out:bs", _T(1), (), "ordinary", "64x64 forward: the bottleneck's join"),
+    (_cv_F20, "f32", "fwd", "fold+relu", "none", "in:ld", _T(1), (), "ordinary", "64x64: 20 output channels, scalar epilogue, folded BatchNorm with negative scales"),
+    (_cv_F100, "bf16", "fwd", "bias+residual+relu", "none", "res:bs", _T(1), (), "ordinary", "64x64: 100 output channels, scalar epilogue"),
+    (_cv_F72k3, "bf16", "fwd", "none", "none", "in:ld+bs8", _T(1), (), "corner", "64x64 forward, corner pixels"),
+    (_cv_F72k3, "bf16", "fwd", "stats+relu", "none", "out:ld8", _T(5), (), "ordinary", "64x64 G2 forward: statistics of the stored output"),
+    (_cv_F72k1, "f32", "fwd", "residual", "none", "res:ld2", _T(5), (), "ordinary", "64x64 G2 fp32: residual slice off the grid, scalar epilogue"),
+    (_cv_F72k1, "bf16", "fwd", "fold+relu", "none", "in:bs", _T(6), (), "ordinary", "64x64 G4 forward"),
+    (_cv_F72k3, "bf16", "fwd", "stats", "none", "out:ld4", _T(6), (), "ordinary", "64x64 G4: output slice off the grid, scalar epilogue with statistics"),
+    (_cv_F72k3, "bf16", "fwd", "out_f32+bias", "none", "out:ld4", _T(2), (), "ordinary", "128x64: fp32 output slice 16 bytes into its buffer: vector epilogue"),
+    (_cv_F20, "bf16", "fwd", "fold", "none", "", _T(2), (), "ordinary", "128x64: 20 output channels, scalar epilogue"),
+    (_cv_F72k3, "f32", "fwd", "relu", "none", "in:ld+bs", _T(2), (), "ordinary", "128x64 fp32"),
+    (_cv_F136k3, "bf16", "fwd", "bias+residual+relu", "none", "res:ld+bs8", _T(3), (), "ordinary", "128x128 forward"),
+    (_cv_F100, "f32", "fwd", "stats+relu", "none", "", _T(3), (), "ordinary", "128x128 fp32: 100 output channels, scalar epilogue with statistics"),
+    (_cv_F136k1, "f32", "fwd", "bias", "none", "out:ld+bs", _T(3), (), "lastpixel", "128x128 fp32 1x1, x at the last pixel"),
+    (_cv_F136k3, "bf16", "fwd", "fold", "none", "out:bs", _T(8), (), "ordinary", "128x128 G2 forward"),
+    (_cv_F136k1, "bf16", "fwd", "out_f32", "none", "out:ld2", _T(8), (), "ordinary", "128x128 G2: fp32 output 8 bytes off the grid, scalar epilogue"),
+    (_cv_F24, "bf16", "fwd", "stats+relu", "none", "out:ld8", (), (), "ordinary", "256x32 forward by the ladder, vector epilogue"),
+    (_cv_F6, "bf16", "fwd", "bias", "none", "", (), (), "ordinary", "256x32: 6 output channels"),
+    (_cv_F7, "f32", "fwd", "out_f32+bias", "none", "in:ld", (), (), "ordinary", "256x32 fp32: 7 output channels"),
+    (_cv_F24, "f32", "fwd", "relu", "none", "", (), (), "ordinary", "256x32 fp32"),
+    (_cv_F72k3, "bf16", "fwd", "bias+residual+relu", "none", "res:ld+bs out:ld", _XK(2), (), "ordinary", "xk = 2 forward"),
+    (_cv_F72k3, "bf16", "fwd", "stats+relu", "none", "", _XK(3), (), "ordinary", "xk = 3 forward with statistics"),
+    (_cv_F72k1, "bf16", "fwd", "fold+relu", "none", "out:bs", _XK(8), (), "ordinary", "xk = 8 on 4 k-tiles"),
+    (_cv_F264k3, "bf16", "fwd", "out_f32", "none", "", _8P(0), (), "ordinary", "8p forward: fp32 output"),
+    (_cv_F264k3, "bf16", "fwd", "bias+residual+relu", "none", "res:ld8 out:ld+bs", _8P(0), (), "ordinary", "8p forward: join"),
+    (_cv_F264k3, "bf16", "fwd", "fold+relu", "none", "in:ld+bs", _8P(1), (), "ordinary", "8p forward cmajor"),
+    (_cv_F264k1, "bf16", "fwd", "stats+relu", "none", "", _8P(1), (), "ordinary", "8p forward 1x1 with statistics"),
+    (_cv_F264k1, "bf16", "fwd", "out_f32+bias", "none", "out:ld4", _8P(0), (), "ordinary", "8p forward: fp32 output slice"),
+    (_cv_F264k1, "bf16", "fwd", "fold", "none", "", _8P(0), (), "lastpixel", "8p forward: folded BatchNorm, x at the last pixel"),
+    (_cv_F264k3, "bf16", "fwd", "residual", "none", "res:bs", _8P(0), (), "ordinary", "8p forward: residual"),
+    (_cv_F264k1, "bf16", "fwd", "stats", "none", "out:ld+bs8", _8P(0), (), "ordinary", "8p forward: statistics"),
+    (_cv_F264k3, "bf16", "fwd", "relu", "none", "", _8P(0), (), "ordinary", "8p forward: ReLU alone"),
+    (_cv_F72k3, "bf16", "fwd", "bias", "none", "", (), (), "ordinary", "the dispatcher's own choice, bias"),
+    (_cv_F136k3, "f32", "fwd", "none", "none", "", (), (), "ordinary", "the dispatcher's own choice, fp32"),
+    (_cv_F136k1, "bf16", "fwd", "residual", "none", "", (), (), "ordinary", "the dispatcher's own choice, residual"),
+    # ---- forward-only float16 ----
+    (_cv_F72k3, "f16", "fwd", "fold", "none", "out:ld8", _T(1), (), "ordinary", "fp16 64x64: folded BatchNorm"),
+    (_cv_F264k3, "f16", "fwd", "bias+residual+relu", "none", "res:ld", _8P(0), (), "ordinary", "fp16 on the 256x256 kernel"),
+    (_cv_F136k3, "f16", "fwd", "relu", "none", "", _T(3), (), "ordinary", "fp16 128x128"),
+    (_cv_F72k1, "f16", "fwd", "bias", "none", "in:bs", _XK(2), (), "ordinary", "fp16 cross-block split"),
+    (_cv_F6, "f16", "fwd", "out_f32", "none", "", (), (), "ordinary", "fp16 256x32, fp32 output, scalar epilogue"),
+    (_cv_F20, "f16", "fwd", "out_f32+bias", "none", "", _T(1), (), "ordinary", "fp16 64x64: fp32 output of 20 channels, scalar epilogue"),
+    # ---- what the lists above left with one case ----
+    (_cv_F136k1, "bf16", "fwd", "out_f32", "none", "", _T(3), (), "ordinary", "128x128: fp32 output through the vector epilogue"),
+    (_cv_L72k1, "bf16", "bwd", "mask+scale", "dx", "", _T(2), (), "ordinary", "128x64: mask_scale, vector epilogue"),
+    (_cv_L20, "bf16", "bwd", "mask+scale", "dx", "", _T(1), (), "ordinary", "64x64: mask_scale, scalar epilogue"),
+    (_cv_L100, "f32", "bwd", "mask+scale", "dx", "mask:bs", _T(3), (), "ordinary", "128x128 fp32: mask_scale, scalar epilogue"),
+    (_cv_T32o6, "bf16", "bwd", "maskx+stats", "dx+dw+dbias", "", (), _NOTHIN, "ordinary", "thin MASK 1 with statistics at C = 32"),
+    (_cv_T256o7, "bf16", "bwd", "maskx", "dx+dw", "x:ld8", (), _NOTHIN, "ordinary", "thin MASK 1 on a slice of a wider x"),
+)
+# two unequal problems of the list in one launch: (entry point, (row, row), dtype, what it is there for)
+_CONV_GROUP_ROWS = (
+    ("multi", (0, 2), "bf16", "dgrad_multi: every feature beside accumulate + mask + statistics"),
+    ("multi", (36, 39), "bf16", "dgrad_multi: two of the xk cases' problems side by side on the grouped 64x64 kernel"),
+    ("multi", (1, 8), "f32", "dgrad_multi fp32: a scalar-epilogue problem beside a vector one"),
+    ("group", (80, 82), "bf16", "conv2d_group: a scalar-epilogue join beside statistics"),
+    ("group", (83, 91), "f32", "conv2d_group fp32: a 1x1 residual off the grid beside a 330-pixel 1x1"),
+    ("group", (115, 116), "f16", "conv2d_group fp16"),
+)
+
+
+def conv_cases(seed=2212):
+    """(id, N, H, W, C, OC, k, stride, pad, dilation, dtype, side, epilogue, arm, views, knobs, twin, inputs, why, seed); a grouped case has side
+    multi / group, zeros for the layer and the indices of its two member cases in the views field"""
+    if seed not in _CONV_CASES:
+        out = [("conv%d-%d" % (seed, i),) + row[0] + row[1:] + (seed + i,) for i, row in enumerate(_CONV_ROWS)]
+        for side, members, dtype, why in _CONV_GROUP_ROWS:
+            out.append(("conv%d-%d" % (seed, len(out)),) + (0,) * 9 + (dtype, side, "none", "none", members, (), (), "ordinary", why, seed + len(out)))
+        _CONV_CASES[seed] = out
+    return _CONV_CASES[seed]
+
+
+_CONV_CASES = {}
+
+
+def _cv_single(c):
+    return c[11] in ("fwd", "bwd")
+
+
+def _cv_kind(c):
+    return conv_kind_name(conv_route(c)) if _cv_single(c) else None
+
+
+def _cv_copy(c):
+    return conv_route(c)[2] if _cv_single(c) else None
+
+
+def _cv_has(c, feat):
+    return _cv_single(c) and feat in conv_feats(c)
+
+
+def _cv_ragged(c, axis):
+    if not _cv_single(c) or conv_route(c)[0] == "thin":
+        return False
+    bm, bn = CONV_TILE[conv_route(c)[0]]
+    return conv_gemm_dims(c)[axis] % (bm, bn)[axis] != 0
+
+
+def _cv_view_kind(c, role):
+    if not _cv_single(c) or role not in CONV_ROLES[c[11]]:
+        return None
+    t = conv_tensors(c)
+    return t[role].kind if role in t and not (role == "mask" and "mask_is_x" in conv_feats(c)) else None
+
+
+def _cv_off_grid_only(c):
+    """the scalar epilogue for alignment alone: channel count a multiple of 8, some epilogue operand's slice off the 16-byte grid"""
+    return _cv_copy(c) == "scalar" and conv_gemm_dims(c)[1] % 8 == 0
+
+
+_CV_COPIES = {"64x64 G1": ("vec", "scalar"), "64x64 G2": ("vec", "scalar"), "64x64 G4": ("vec", "scalar"), "128x64": ("vec", "scalar"),
+              "128x128 G1": ("vec", "scalar"), "128x128 G2": ("vec", "scalar"), "256x32": ("vec", "scalar"), "xk": ("vec",), "s2": ("vec",), "8p": ("8p",),
+              "pair": ("vec",), "thin": ("thin",)}
+_CV_BWD_FEATS = ("mask", "stats", "stat_x", "addend", "accumulate")
+_CV_FWD_FEATS = ("bias", "scale", "residual", "relu", "stats", "out_f32")
+_CV_FWD_KINDS = ("64x64 G1", "64x64 G2", "64x64 G4", "128x64", "128x128 G1", "128x128 G2", "256x32", "xk", "8p")
+
+
+def _cv_l(fn, *args):
+    return lambda c: fn(c, *args)
+
+
+CONV_REGIMES = [("%s, %s epilogue" % (k, cp), _cv_l(lambda c, k_, cp_: _cv_kind(c) == k_ and _cv_copy(c) == cp_, k, cp)) for k in CONV_KINDS for cp in _CV_COPIES[k]] + [
+    ("%s: backward with %s" % (k, ft), _cv_l(lambda c, k_, ft_: c[11] == "bwd" and _cv_kind(c) == k_ and _cv_has(c, ft_), k, ft))
+    for k in CONV_KINDS for ft in _CV_BWD_FEATS if not (k == "thin" and ft in ("stat_x", "addend"))] + [
+    ("%s: forward" % k, _cv_l(lambda c, k_: c[11] == "fwd" and _cv_kind(c) == k_, k)) for k in _CV_FWD_KINDS] + [
+    ("%s epilogue, forward with %s" % (cp, ft), _cv_l(lambda c, cp_, ft_: c[11] == "fwd" and _cv_copy(c) == cp_ and _cv_has(c, ft_), cp, ft))
+    for cp in ("vec", "scalar", "8p") for ft in _CV_FWD_FEATS] + [
+    ("%s epilogue, backward with %s" % (cp, ft), _cv_l(lambda c, cp_, ft_: c[11] == "bwd" and _cv_copy(c) == cp_ and _cv_has(c, ft_), cp, ft))
+    for cp in ("vec", "scalar") for ft in _CV_BWD_FEATS + ("mask_scale",)] + [
+    ("%s: ragged last M tile" % k, _cv_l(lambda c, k_: _cv_kind(c) == k_ and _cv_ragged(c, 0), k)) for k in CONV_KINDS if k not in ("s2", "thin")] + [
+    ("%s: ragged last OC tile" % k, _cv_l(lambda c, k_: _cv_kind(c) == k_ and _cv_ragged(c, 1), k)) for k in CONV_KINDS if k != "thin"] + [
+    ("scalar epilogue by alignment alone, %s" % side, _cv_l(lambda c, s_: c[11] == s_ and _cv_off_grid_only(c), side)) for side in ("fwd", "bwd")] + [
+    ("%s view: %s" % (role, v), _cv_l(lambda c, r_, v_: _cv_view_kind(c, r_) == v_, role, v)) for side in ("fwd", "bwd") for role in CONV_ROLES[side] for v in CONV_VIEWS] + [
+    ("%s, %s" % (side, d), _cv_l(lambda c, s_, d_: c[11] == s_ and c[10] == d_, side, d)) for side, d in (("fwd", "f32"), ("fwd", "bf16"), ("fwd", "f16"), ("bwd", "f32"), ("bwd", "bf16"))] + [
+    ("forward epilogue: %s" % e, _cv_l(lambda c, e_: c[11] == "fwd" and c[12] == e_, e)) for e in CONV_FWD_EPILOGUES] + [
+    ("backward epilogue: %s" % e, _cv_l(lambda c, e_: c[11] == "bwd" and c[12] == e_, e)) for e in CONV_BWD_EPILOGUES] + [
+    ("backward arm: %s" % arm, _cv_l(lambda c, a_: c[11] == "bwd" and c[13] == a_, arm)) for arm in CONV_ARMS] + [
+    ("xk = %d asked" % s, _cv_l(lambda c, s_: _cv_kind(c) == "xk" and dict(c[15]).get("xk") == s_, s)) for s in (2, 3, 8)] + [
+    ("xk: fewer k-tiles than the copies asked for", lambda c: _cv_kind(c) == "xk" and conv_k_tiles(conv_problem(c)[0]) < dict(c[15]).get("xk", 0)),
+    ("8p: k = 3, tap-major", lambda c: _cv_kind(c) == "8p" and c[6] == 3 and not dict(c[15]).get("igemm8p_cmajor")),
+    ("8p: k = 3, channel-block-major", lambda c: _cv_kind(c) == "8p" and c[6] == 3 and dict(c[15]).get("igemm8p_cmajor") == 1),
+    ("8p: k = 1, tap-major", lambda c: _cv_kind(c) == "8p" and c[6] == 1 and not dict(c[15]).get("igemm8p_cmajor")),
+    ("8p: k = 1, channel-block-major", lambda c: _cv_kind(c) == "8p" and c[6] == 1 and dict(c[15]).get("igemm8p_cmajor") == 1),
+    ("8p asked, refused by igemm8p_ok: the ladder's kernel", lambda c: _cv_single(c) and dict(c[15]).get("conv_tile") == 7 and _cv_kind(c) != "8p"),
+    ("s2: k = 3 pad 1", lambda c: _cv_kind(c) == "s2" and (c[6], c[8]) == (3, 1)),
+    ("s2: k = 5 pad 2", lambda c: _cv_kind(c) == "s2" and (c[6], c[8]) == (5, 2)),
+    ("s2: k = 2 pad 0", lambda c: _cv_kind(c) == "s2" and (c[6], c[8]) == (2, 0)),
+    ("s2: 1 x 16 x 16", lambda c: _cv_kind(c) == "s2" and c[1:4] == (1, 16, 16)),
+    ("s2: 2 x 8 x 16", lambda c: _cv_kind(c) == "s2" and c[1:4] == (2, 8, 16)),
+    ("s2: generic twin, bit-identical dx", lambda c: _cv_kind(c) == "s2" and conv_route(c, True)[:2] == ("64x64", 1)),
+    ("thin: MASK 0", lambda c: _cv_kind(c) == "thin" and not _cv_has(c, "mask")),
+    ("thin: MASK 1 (mask_y is x)", lambda c: _cv_kind(c) == "thin" and _cv_has(c, "mask_is_x")),
+    ("thin: MASK 2", lambda c: _cv_kind(c) == "thin" and _cv_has(c, "mask") and not _cv_has(c, "mask_is_x")),
+    ("thin: 4 channels per thread", lambda c: _cv_kind(c) == "thin" and conv_route(c)[1] == 4),
+    ("thin: 8 channels per thread", lambda c: _cv_kind(c) == "thin" and conv_route(c)[1] == 8),
+    ("thin: generic twin", lambda c: _cv_kind(c) == "thin" and conv_route(c, True)[0] != "thin"),
+    ("thin shape refused by thin_bwd_ok", lambda c: _cv_single(c) and c[11] == "bwd" and c[6] == 1 and c[5] <= 8 and "dw" in c[13] and _cv_kind(c) != "thin"),
+    ("grouped launch: emrt_conv2d_dgrad_multi", lambda c: c[11] == "multi" and conv_group_is_one_launch(c)),
+    ("grouped launch: emrt_conv2d_group", lambda c: c[11] == "group" and conv_group_is_one_launch(c)),
+] + [("inputs: %s" % r, _cv_l(lambda c, r_: _cv_single(c) and c[17] == r_, r)) for r in CONV_INPUTS]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 CASES = {
     "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
     "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
-    "mha": mha_cases(), "msda": msda_cases(), "gconv": gconv_cases(),
+    "mha": mha_cases(), "msda": msda_cases(), "gconv": gconv_cases(), "conv": conv_cases(),
 }
 REGIMES = {
     "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
     "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
-    "mha": MHA_REGIMES, "msda": MSDA_REGIMES, "gconv": GCONV_REGIMES,
+    "mha": MHA_REGIMES, "msda": MSDA_REGIMES, "gconv": GCONV_REGIMES, "conv": CONV_REGIMES,
 }
 IN_DOMAIN = {
     "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
     "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
-    "mha": mha_in_domain, "msda": msda_in_domain, "gconv": gconv_in_domain,
+    "mha": mha_in_domain, "msda": msda_in_domain, "gconv": gconv_in_domain, "conv": conv_in_domain,
 }
 
 
 # cases a regime must keep: two, except where the sweep asks for exactly one.  gconv: a block goes round its tile loop twice only from
 # 4097 tiles (257 x 257 pixels) or, with statistics, from 2049 / nslices: one case each, under GCONV_LONG_MAX_ELEMS
 REGIME_MIN = {("maxpool", "k = 7"): 1, ("msda", "dref on a band pyramid (GRAD_GLOBAL)"): 1,
-              ("gconv", "grid-stride: forward, no statistics"): 1, ("gconv", "grid-stride: forward with statistics"): 1, ("gconv", "grid-stride: dgrad"): 1}
+              ("gconv", "grid-stride: forward, no statistics"): 1, ("gconv", "grid-stride: forward with statistics"): 1, ("gconv", "grid-stride: dgrad"): 1,
+              # conv: one case each shows that a refused kernel's problem reaches the ladder's own kernel (the issue asks for exactly one)
+              ("conv", "8p asked, refused by igemm8p_ok: the ladder's kernel"): 1, ("conv", "thin shape refused by thin_bwd_ok"): 1,
+              ("conv", "xk: fewer k-tiles than the copies asked for"): 1}
 
 
 def regime_hits(op):

@@ -58,6 +58,10 @@ def test_case_sizes_stay_small():
         if hits:
             long_cases.append(max(Mi * C, M * OC))
     assert len(long_cases) == 3 and max(long_cases) == fc.GCONV_LONG_MAX_ELEMS <= 17000000
+    for c in fc.CASES["conv"]:          # every tensor with its padding, and the weight
+        if c[11] in ("fwd", "bwd"):
+            assert max(v.bs * c[1] for v in fc.conv_tensors(c).values()) <= fc.MAX_ELEMS and c[4] * c[5] * c[6] * c[6] <= fc.MAX_ELEMS, c[0]
+            assert fc.conv_gemm_dims(c)[0] * fc.conv_gemm_dims(c)[1] * (c[6] * c[6] * (c[4] if c[11] == "fwd" else c[5])) <= 60000000, c[0]      # multiply-adds of the float64 reference
 
 
 def test_mha_sweep_covers_what_it_was_written_for():
@@ -130,6 +134,105 @@ def test_gconv_sweep_covers_what_it_was_written_for():
     assert not fc.gconv_in_domain(odd[0][:10] + (("dense",) + odd[0][10][1:],) + odd[0][11:])
 
 
+def _conv_point(N, H, W, C, OC, k, stride, pad, dtype, side, epilogue="none", arm=None, views="", knobs=()):
+    """a case tuple for a dense layer, for the mirrored predicates alone"""
+    return ("point", N, H, W, C, OC, k, stride, pad, 1, dtype, side, epilogue, arm or ("none" if side == "fwd" else "dx"), views, tuple(knobs), (), "ordinary", "", 0)
+
+
+def test_conv_sweep_covers_what_it_was_written_for():
+    """one assertion per gap the sweep was written to close in csrc/conv.hip / csrc/igemm8p.hpp, against the mirrored host-side decisions"""
+    cases = fc.CASES["conv"]
+    assert fc.conv_cases() == cases and 100 <= len(cases) <= 140
+    single = [c for c in cases if c[11] in ("fwd", "bwd")]
+    bwd = [c for c in single if c[11] == "bwd"]
+    kind, copy, feats = fc._cv_kind, fc._cv_copy, fc.conv_feats
+    assert {kind(c) for c in single} == set(fc.CONV_KINDS)
+    # every kernel kind runs the masked / statistics epilogue and an addend (the thin kernel, which takes no addend: accumulate)
+    for k in fc.CONV_KINDS:
+        mine = [c for c in bwd if kind(c) == k]
+        assert any({"mask", "stats"} <= feats(c) for c in mine), k
+        assert any(("accumulate" if k == "thin" else "addend") in feats(c) for c in mine), k
+    # the 256x256 LDS-DMA kernel and the parity-class kernel: stat_x and a strided mask; the 256x256 kernel with a strided addend too
+    for k in ("8p", "s2"):
+        mine = [c for c in bwd if kind(c) == k]
+        assert any("stat_x" in feats(c) for c in mine) and any(fc._cv_view_kind(c, "mask") in fc.CONV_VIEWS for c in mine), k
+        assert any(fc._cv_view_kind(c, "dx") in fc.CONV_VIEWS for c in mine), k
+    assert any(kind(c) == "8p" and fc._cv_view_kind(c, "addend") in fc.CONV_VIEWS for c in bwd)
+    # both epilogue copies of igemm_body with every feature of either side; the 8-phase copy with every feature
+    for cp in ("vec", "scalar", "8p"):
+        mine = [c for c in single if copy(c) == cp]
+        assert set(fc._CV_FWD_FEATS) <= set().union(*[feats(c) for c in mine if c[11] == "fwd"]), cp
+        assert set(fc._CV_BWD_FEATS) | {"mask_scale"} <= set().union(*[feats(c) for c in mine if c[11] == "bwd"]), cp
+    # each tile, each in-block K split, the cross-block split, the pair kernel and the 256x256 kernel with a ragged M and a ragged OC tile
+    for k in fc.CONV_KINDS:
+        if k != "thin":
+            assert any(kind(c) == k and fc._cv_ragged(c, 1) for c in single), k
+            assert k == "s2" or any(kind(c) == k and fc._cv_ragged(c, 0) for c in single), k
+    # 256x32 through the ladder: 24 channels on the vector epilogue, 6 and 7 on the scalar one, each with mask + statistics on the backward side
+    for ch, cp in ((24, "vec"), (6, "scalar"), (7, "scalar")):
+        assert any(c[4] == ch and kind(c) == "256x32" and copy(c) == cp and not c[15] and {"mask", "stats"} <= feats(c) for c in bwd), ch
+        assert any(c[11] == "fwd" and c[5] == ch and kind(c) == "256x32" and copy(c) == cp for c in single), ch
+    # the scalar epilogue by the channel count and, separately, by alignment alone, on the 64x64 and 128x128 tiles
+    for k in ("64x64 G1", "128x128 G1"):
+        assert any(kind(c) == k and copy(c) == "scalar" and fc.conv_gemm_dims(c)[1] % 8 for c in single), k
+    assert any(kind(c).startswith("64x64") and fc._cv_off_grid_only(c) for c in single) and any(kind(c).startswith("128x128") and fc._cv_off_grid_only(c) for c in single)
+    # the 256x256 kernel: C = 64, OC = 264, M = 330, k = 3 and k = 1 under both k orders, every backward epilogue of the issue, the forward's fp32 output
+    p8 = [c for c in single if kind(c) == "8p"]
+    assert all(fc.conv_gemm_dims(c) == (330, 264) and (c[5] if c[11] == "bwd" else c[4]) == 64 for c in p8)
+    assert {(c[6], dict(c[15])["igemm8p_cmajor"]) for c in p8 if c[11] == "bwd"} == {(3, 0), (3, 1), (1, 0), (1, 1)}
+    assert {"none", "stats", "mask", "mask+stats", "mask+stats+stat_x", "mask+scale", "addend", "addend+mask+stats+stat_x", "accumulate",
+            "accumulate+mask+stats"} <= {c[12] for c in p8 if c[11] == "bwd"}
+    assert any(c[11] == "fwd" and "out_f32" in feats(c) for c in p8)
+    refused = [c for c in single if dict(c[15]).get("conv_tile") == 7 and kind(c) != "8p"]
+    assert len(refused) == 1 and not fc.igemm8p_ok(fc.conv_problem(refused[0])[0]) and fc.conv_route(refused[0]) == ("64x64", 1, "scalar")
+    # the cross-block split at 2, 3 and 8 copies asked, with mask + statistics + stat_x and with an addend; one case with fewer k-tiles than copies
+    xk = [c for c in bwd if kind(c) == "xk"]
+    assert {dict(c[15])["xk"] for c in xk} == {2, 3, 8} and any({"mask", "stats", "stat_x"} <= feats(c) for c in xk) and any("addend" in feats(c) for c in xk)
+    assert any(fc.conv_k_tiles(fc.conv_problem(c)[0]) < dict(c[15])["xk"] for c in xk)
+    # the parity-class kernel: the three tap lattices, both 256-pixel maps, both layer widths, every epilogue operand, each with its generic twin
+    s2 = [c for c in bwd if kind(c) == "s2"]
+    assert {(c[6], c[8]) for c in s2} == {(3, 1), (5, 2), (2, 0)} and {c[1:4] for c in s2} == {(1, 16, 16), (2, 8, 16)} and {c[5] for c in s2} == {64, 128}
+    assert {"mask", "stats", "stat_x", "addend", "mask_scale", "accumulate"} <= set().union(*[feats(c) for c in s2])
+    assert all(fc.conv_route(c, True)[:2] == ("64x64", 1) for c in s2)
+    # the pair kernel: dw and dbias given, mask + statistics on the data-gradient half
+    assert any(kind(c) == "pair" and c[13] == "dx+dw+dbias" and {"mask", "stats"} <= feats(c) for c in bwd)
+    # the thin kernel: OC 6 and 7, C 32 / 64 / 256, MASK 0 / 1 / 2, with and without accumulate, each with the generic kernels as twin
+    thin = [c for c in bwd if kind(c) == "thin"]
+    assert {c[5] for c in thin} == {6, 7} and {c[4] for c in thin} == {32, 64, 256} and all(c[6] == 1 for c in thin)
+    assert any("accumulate" in feats(c) for c in thin) and any("mask_is_x" in feats(c) for c in thin) and any("mask" in feats(c) and "mask_is_x" not in feats(c) for c in thin)
+    assert all(fc.conv_route(c, True)[0] != "thin" for c in thin)
+    # every view kind for every tensor role
+    for side in ("fwd", "bwd"):
+        for role in fc.CONV_ROLES[side]:
+            assert {fc._cv_view_kind(c, role) for c in single} >= set(fc.CONV_VIEWS), role
+    # the grouped entry points, one launch each, in every dtype they take
+    assert {c[10] for c in cases if c[11] == "multi"} == {"bf16", "f32"} and {c[10] for c in cases if c[11] == "group"} == {"bf16", "f32", "f16"}
+    assert all(fc.conv_group_is_one_launch(c) for c in cases if c[11] in ("multi", "group"))
+    # mask draws need no margin, but forward ReLU cases do: they exist in every dtype
+    assert {c[10] for c in single if c[11] == "fwd" and "relu" in feats(c)} == {"f32", "bf16", "f16"}
+
+
+def test_mirrored_conv_plan_reproduces_the_recorded_table():
+    """the mirrored bna_plan (and through it conv_plan, conv_is_vec, conv_k_tiles, conv_blocks, conv_takes_128, igemm8p_ok) against
+    tests/golden/bna_supported.json: all 3780 rows under all nine knob sets, with no scratch registered (the cross-block split is unreachable,
+    as in tests/test_conv_plan_cpu.py, whose sweep and knob sets these are)"""
+    import json
+    from tests import test_conv_plan_cpu as tp
+    with open(tp.GOLDEN) as f:
+        gold = json.load(f)
+    rows = tp.rows()
+    assert len(rows) == 3780 and len(tp.KNOB_SETS) == 9 and gold["knob_sets"] == [n for n, _ in tp.KNOB_SETS]
+    for name, knobs in tp.KNOB_SETS:
+        kn = dict(fc.CONV_KNOBS)
+        kn.update(knobs)
+        got = []
+        for N, HW, C, OC, k, dt in rows:
+            a, _ = fc.conv_problem(_conv_point(N, HW, HW, C, OC, k, 1, k // 2, ("f32", "bf16")[dt], "fwd", "bias+residual+relu+stats"), kn)
+            got.append("1" if kn["no_bna"] != 1 and fc.bna_plan(a, kn, False)[0] != "none" else "0")
+        diff = [(r, w, g) for r, w, g in zip(rows, gold["answers"][name], got) if w != g]
+        assert not diff, "%s: %d rows differ from the recorded answers, first (N, HW, C, OC, k, dtype), recorded, mirrored: %s" % (name, len(diff), diff[:8])
+
+
 def test_mirrored_predicates_at_known_points():
     """the shapes the fixed tests and the model use, whose path is known from the dispatchers' comments"""
     assert fc.bn_rowgeom(64) == (256, 16) and fc.bn_rowgeom(1024) == (256, 1) and fc.bn_rowgeom(2048) == (512, 1) and fc.bn_rowgeom(1028) == (257, 1)
@@ -152,6 +255,48 @@ def test_mirrored_predicates_at_known_points():
     assert fc.gconv_wgrad_plan(221, 32, 4) == (288, 37, 6) and fc.gconv_wgrad_plan(20, 32, 4)[2] == 1 and fc.gconv_wgrad_plan(4225, 2048, 4) == (18432, 76, 56)
     assert fc.gconv_grid(4225, 2048, True) == (265, 256, 8, True) and fc.gconv_grid(8 * 64 * 64, 256, True) == (2048, 2048, 1, False)
     assert fc.gconv_grid(257 * 257, 256, False) == (4129, 4096, 1, True) and fc.gconv_grid(257 * 257, 32, False) == (517, 517, 1, False)
+    # csrc/conv.hip's own comments.  The cross-block split's table (igemm_xk_copies): 8x8x512 -> 512 3x3 at batch 8 is 64 tiles of 72 k-tiles
+    # and takes four copies, 16x16x1024 -> 256 (128 tiles, 144 k-tiles) too, 16x16x256 -> 256 (128 tiles, 36 k-tiles) keeps the in-block
+    # split; "9 k-tiles on 8 copies: per = 2 -> 5 copies"; fp32 and a context without scratch never split
+    kn = dict(fc.CONV_KNOBS)
+    xk = lambda *a_: fc.conv_problem(_conv_point(*a_), kn)[0]
+    a = xk(8, 8, 8, 512, 512, 3, 1, 1, "bf16", "fwd")
+    assert (fc.conv_blocks(a, 64, 64), fc.conv_k_tiles(a)) == (64, 72) and fc.igemm_xk_copies(a, kn, True) == 4 and fc.igemm_xk_copies(a, kn, False) == 0
+    assert fc.conv_plan(a, kn, True) == ("xk", 4, False) and fc.conv_plan(a, kn, False) == ("64x64", 4, False)
+    assert fc.igemm_xk_copies(xk(8, 16, 16, 1024, 256, 3, 1, 1, "bf16", "fwd"), kn, True) == 4 and fc.igemm_xk_copies(xk(8, 16, 16, 256, 256, 3, 1, 1, "bf16", "fwd"), kn, True) == 0
+    assert fc.igemm_xk_copies(xk(8, 8, 8, 512, 512, 3, 1, 1, "f32", "fwd"), kn, True) == 0
+    assert fc.igemm_xk_copies(xk(2, 9, 11, 64, 72, 3, 1, 1, "bf16", "fwd"), dict(kn, xk=8), True) == 5          # 9 k-tiles
+    # the ladder: "the decoder's 32x32x1536 -> 512 3x3 forward" at batch 8 is exactly 256 blocks of 128x128 with 216 k-tiles: two wave groups;
+    # "512 [blocks] at 64x64x256 -> 256": the plain 128x128 tile; a layer with at most 32 output channels: 256x32
+    assert fc.conv_plan(xk(8, 32, 32, 1536, 512, 3, 1, 1, "bf16", "fwd"), kn, True) == ("128x128", 2, False)
+    assert fc.conv_plan(xk(8, 32, 32, 1536, 512, 3, 1, 1, "bf16", "fwd"), dict(kn, no_ksplit128=1), True) == ("128x128", 1, False)
+    assert fc.conv_plan(xk(8, 64, 64, 256, 256, 3, 1, 1, "bf16", "fwd"), kn, True) == ("128x128", 1, False)
+    assert fc.conv_plan(xk(8, 64, 64, 256, 6, 1, 1, 0, "bf16", "fwd"), kn, True) == ("256x32", 1, False)
+    # the 256x256 kernel from 160 blocks with at least 16 k-tiles of 64, or 96 blocks with 144: 128x128x256 -> 256 3x3 at batch 8 is 512 x 1 blocks
+    big = xk(8, 128, 128, 256, 256, 3, 1, 1, "bf16", "fwd")
+    assert fc.igemm8p_ok(big) and fc.conv_plan(big, kn, True) == ("8p", 1, False) and fc.conv_plan(big, dict(kn, igemm8p_min_blocks=0), True)[0] == "128x128"
+    assert not fc.igemm8p_ok(xk(8, 128, 128, 96, 256, 3, 1, 1, "bf16", "fwd")) and not fc.igemm8p_ok(xk(8, 128, 128, 256, 256, 3, 1, 1, "f32", "fwd"))
+    # the parity-class kernel (S2_CASES of tests/test_gpu_conv_fuzz.py): 3x3 stride 2 on 2 x 16 x 16 x 64; a 1x1 only under the knob -1; not at
+    # 2 x 8 x 8 (128 input pixels: 32 rows per class), not with dilation, and not when the knob says 1
+    s2 = lambda *a_, **kw: fc.igemm_s2_ok(fc.conv_problem(_conv_point(*a_), kn)[0], dict(kn, **kw))
+    assert s2(2, 16, 16, 64, 64, 3, 2, 1, "bf16", "bwd") and s2(2, 16, 32, 64, 128, 5, 2, 2, "bf16", "bwd") and s2(2, 16, 16, 64, 128, 2, 2, 0, "f32", "bwd")
+    assert not s2(8, 32, 32, 512, 1024, 1, 2, 0, "bf16", "bwd") and s2(8, 32, 32, 512, 1024, 1, 2, 0, "bf16", "bwd", no_s2_dgrad=-1)
+    assert not s2(2, 8, 8, 64, 64, 3, 2, 1, "bf16", "bwd") and not s2(2, 16, 16, 64, 64, 3, 2, 1, "bf16", "bwd", no_s2_dgrad=1) and not s2(2, 16, 16, 64, 64, 3, 1, 1, "bf16", "bwd")
+    # the thin backward: "8x128x128x256 -> 6 ... 4 channel chunks x 128 pixel chunks": 8 channels per thread, 32 pixel slots, 1024 pixels per block
+    a, w = fc.conv_problem(_conv_point(8, 128, 128, 256, 6, 1, 1, 0, "bf16", "bwd", arm="dx+dw+dbias"), kn)
+    assert fc.thin_bwd_ok(a, w) and fc.thin_bwd_geometry(a, w, kn) == (8, 32, 1024, 0) and w.C // 64 == 4
+    assert not fc.thin_bwd_ok(*fc.conv_problem(_conv_point(8, 128, 128, 256, 6, 1, 1, 0, "bf16", "bwd", "addend", "dx+dw"), kn))
+    assert not fc.thin_bwd_ok(*fc.conv_problem(_conv_point(8, 128, 128, 96, 6, 1, 1, 0, "bf16", "bwd", arm="dx+dw"), kn))          # C no power of two
+    assert not fc.thin_bwd_ok(*fc.conv_problem(_conv_point(8, 128, 128, 256, 9, 1, 1, 0, "bf16", "bwd", arm="dx+dw"), kn))
+    # the pair: "16x16 / 8x8 layers" pair, "from ~1000 dgrad tiles on" (pair_max 768) they do not, nor without dw, nor at OC <= 32
+    pairs = lambda *a_, **kw: fc.conv_bwd_pairs(*fc.conv_problem(_conv_point(*a_, **kw), kn), kn)
+    assert pairs(8, 16, 16, 256, 256, 3, 1, 1, "bf16", "bwd", arm="dx+dw") and pairs(8, 8, 8, 512, 512, 3, 1, 1, "bf16", "bwd", arm="dx+dw+dbias")
+    assert not pairs(8, 64, 64, 128, 128, 3, 1, 1, "bf16", "bwd", arm="dx+dw") and not pairs(8, 16, 16, 256, 256, 3, 1, 1, "bf16", "bwd")
+    assert not pairs(8, 16, 16, 24, 256, 3, 1, 1, "bf16", "bwd", arm="dx+dw")
+    # the epilogue's vec_ok: OC % 8, and every operand's slice on the 16-byte grid
+    vk = lambda views, oc=72, dt="bf16": fc.conv_epilogue_vec_ok(fc.conv_problem(_conv_point(2, 9, 11, oc, 64, 3, 1, 1, dt, "bwd", "addend+mask+stats+stat_x", views=views), kn)[0])
+    assert vk("") and vk("mask:ld8 addend:bs statx:ld+bs16") and not vk("mask:ld4") and not vk("addend:ld4") and not vk("statx:ld4") and not vk("dx:ld4")
+    assert vk("mask:ld4", dt="f32") and not vk("mask:ld2", dt="f32") and not vk("", oc=20)
 
 
 def test_window_cases():
