@@ -311,8 +311,9 @@ __global__ __launch_bounds__(256) void wce_bwd_kernel(const float* __restrict__ 
                                                       float* __restrict__ da, float* __restrict__ db) {
   const long long total = (long long)N * HW;
   const float den_w = res[1] > 0.f ? res[1] : 1.f, inv_den = 1.f / den_w;
-  // (one head divides, two heads multiply by the reciprocal: the two forms the single and the pair entry points have always had)
-  const float ga = NH == 1 ? wa * (up_a ? up_a[0] : 1.f) / den_w : wa * (up_a ? up_a[0] : 1.f) * inv_den;
+  // (both forms multiply by the reciprocal, so a head of the pair carries the single call's bits; the single form used to divide, which differed
+  // from the pair in the last bit wherever the denominator is no power of two)
+  const float ga = wa * (up_a ? up_a[0] : 1.f) * inv_den;
   const float gb = NH == 1 ? 0.f : wb * (up_b ? up_b[0] : 1.f) * inv_den;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
     const long long lab = labels[idx];

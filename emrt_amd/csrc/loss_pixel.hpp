@@ -26,7 +26,8 @@ __device__ __forceinline__ PixelStats pixel_stats(const float* __restrict__ lp, 
 __device__ __forceinline__ float pixel_ce(const float* __restrict__ lp, int C, long long HW, long long lab, const PixelStats& s, float& pr) {
   const float picked = (lab >= 0 && lab < C) ? lp[lab * HW] : 0.f;
   pr = __expf(picked - s.mx) / s.den;
-  return logf(s.den) + s.mx - picked;
+  // (mx - picked first: it is small and exact for logits of any common offset, where logf(den) + mx rounded at the offset's magnitude -- 3e-5 at 1000)
+  return logf(s.den) + (s.mx - picked);
 }
 __device__ __forceinline__ float pixel_ce(const float* __restrict__ lp, int C, long long HW, long long lab) {
   float pr;

@@ -4,6 +4,9 @@
 csrc/msda.hip by plan, build and layout (tests/test_gpu_msda_fuzz.py; tests/msda_reference.py), the written-out case list of the sweep of
 csrc/gconv.hip by group shape, launch plan and view (tests/test_gpu_gconv_fuzz.py), the written-out case list of the sweep of the dense
 convolution's fused epilogues through every tile and backward path of csrc/conv.hip and csrc/igemm8p.hpp (tests/test_gpu_conv_epilogue_fuzz.py),
+the written-out case lists of the sweeps of the loss kernels (csrc/loss.hip, csrc/loss_pixel.hpp, csrc/loss_ext/loss_ext.hip;
+tests/test_gpu_loss_fuzz.py) and of the optimizer half of csrc/optim.hip with emrt_segmentation_areas (tests/test_gpu_step_fuzz.py; inputs,
+float64 references and bounds of both: tests/loss_step_reference.py),
 and the dispatchers' shape predicates restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
 entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
 seed or a range cannot silently empty one.
@@ -491,6 +494,123 @@ Regime -> case ids (regime_table() renders this text; the CPU test compares):
   conv              inputs: ordinary                                   conv2212-{0,1,2,3,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,26,27,28,29,30,31,32,33,34,35,36,37,38,39,40,41,42,43,44,45,46,48,49,50,51,52,54,55,56,57,58,60,61,62,63,64,65,67,68,69,70,71,72,73,74,75,77,78,79,80,82,83,84,85,86,87,88,89,90,92,93,94,95,96,97,98,99,100,101,102,103,104,105,107,108,109,110,111,112,113,114,115,116,117,118,119,120,121,122,123,124}
   conv              inputs: corner                                     conv2212-{4,53,59,81}
   conv              inputs: lastpixel                                  conv2212-{5,47,66,76,91,106}
+  loss              family: ce                                         loss-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,14}
+  loss              family: wce                                        loss-{15,16,17,18,19,20,21,22,23,24,25,26,27,28}
+  loss              family: ohem                                       loss-{29,30,31,32,33,34,35,36,37,38,39,40,41,42,43,44}
+  loss              family: dice                                       loss-{45,46,47,48,49,50,51,52,53,54,55,56}
+  loss              form: single                                       loss-{0,2,4,6,8,10,11,13,14,15,17,19,21,23,25,27,29,31,33,35,37,38,40,41,43,45,47,49,51,53,54,55}
+  loss              form: pair                                         loss-{1,3,5,7,9,12,16,18,20,22,24,26,28,30,32,34,36,39,42,44,46,48,50,52,56}
+  loss              C = 1                                              loss-{0,15,45}
+  loss              C = 2                                              loss-{1,14,16,28,29,42,44,46,56}
+  loss              C = 3                                              loss-{2,17,30,41,43,47}
+  loss              C = 6                                              loss-{3,5,13,18,27,31,34,40,54,55}
+  loss              C = 7                                              loss-{4,19,20,32,50}
+  loss              C = 8                                              loss-{6,21,33,48}
+  loss              C = 9                                              loss-{7,22,35,49}
+  loss              C = 16                                             loss-{8,23,36,51}
+  loss              C = 17                                             loss-{9,24,37,52}
+  loss              C = 19                                             loss-{10,25,38,53}
+  loss              C = 150                                            loss-{11,12,26,39}
+  loss              dice: whole class chunks (C % 8 == 0)              loss-{48,51}
+  loss              dice: several chunks, ragged last                  loss-{49,52,53}
+  loss              1 pixel                                            loss-{0,15,29,45}
+  loss              15 pixels                                          loss-{1,16,30,46}
+  loss              255 pixels                                         loss-{2,6,17,21,31,36,47,51}
+  loss              256 pixels                                         loss-{3,18,32,48}
+  loss              257 pixels                                         loss-{4,19,33,49}
+  loss              a block spans two images (N >= 2, HW % 256 != 0)   loss-{5,7,20,23,34,35,41,42,50,55}
+  loss              several images inside one block                    loss-{6,8,12,13,21,22,27,36,37,40,51,52,54}
+  loss              ce: the forward grid strides                       loss-{14}
+  loss              wce: the forward grid strides                      loss-{28}
+  loss              ohem: the forward grid strides                     loss-{44}
+  loss              dice: the forward grid strides                     loss-{56}
+  loss              ohem: the digit histograms' grid strides           loss-{43,44}
+  loss              second trip: wce_bwd_kernel plain, single          loss-{14}
+  loss              second trip: wce_bwd_kernel weighted, pair         loss-{28}
+  loss              second trip: ohem_bwd_kernel                       loss-{44}
+  loss              second trip: dice_bwd_kernel                       loss-{56}
+  loss              labels: none                                       loss-{0,2,9,15,18,25,29,32,45,48}
+  loss              labels: tenth                                      loss-{1,3,5,6,7,8,11,12,14,16,17,19,20,21,23,26,28,30,31,34,35,36,37,39,41,42,43,44,46,47,49,50,51,55,56}
+  loss              labels: all                                        loss-{13,27,40,54}
+  loss              labels: allbut1                                    loss-{4,22,33,52}
+  loss              labels: oneclass                                   loss-{10,24,38,53}
+  loss              ignore index 255                                   loss-{0,1,2,4,5,7,8,10,11,13,14,15,16,18,19,20,22,23,24,26,27,28,29,30,32,33,34,36,37,38,39,40,41,42,43,44,45,46,48,49,50,52,53,54,55,56}
+  loss              ignore index -100                                  loss-{3,9,17,25,31,47}
+  loss              ignore index inside [0, C)                         loss-{6,12,21,35,51}
+  loss              logits: ordinary                                   loss-{0,1,2,4,5,10,11,13,14,15,16,18,19,20,26,27,28,29,30,31,33,34,39,40,43,45,46,48,49,50,54,56}
+  loss              logits: confident                                  loss-{3,17,25,32,35,47}
+  loss              logits: shift+                                     loss-{6,22,36,51}
+  loss              logits: shift-                                     loss-{7,21,38,55}
+  loss              logits: wide                                       loss-{8,12,23,37,52}
+  loss              logits: constant                                   loss-{9,24,41,53}
+  loss              logits: grid                                       loss-{42,44}
+  loss              class weights: random                              loss-{15,16,18,20,21,22,23,25,26,27,28,47,50,54}
+  loss              class weights: onezero                             loss-{17,24,52}
+  loss              class weights: zeropresent                         loss-{19,55}
+  loss              head weights (1, 0.4)                              loss-{0,1,2,4,5,6,8,9,10,11,13,14,15,16,17,19,20,21,23,24,25,26,27,28,29,30,31,33,34,35,37,38,39,40,41,42,43,44,45,46,47,49,50,51,53,54,55,56}
+  loss              one negative head weight                           loss-{3,12,22,32,48}
+  loss              one head weight zero                               loss-{7,18,36,52}
+  loss              upstream scalar given                              loss-{1,5,10,12,18,20,23,28,32,34,38,44,48,50}
+  loss              upstream NULL                                      loss-{0,2,3,4,6,7,8,9,11,13,14,15,16,17,19,21,22,24,25,26,27,29,30,31,33,35,36,37,39,40,41,42,43,45,46,47,49,51,52,53,54,55,56}
+  loss              ohem: min_kept = 0                                 loss-{29,40}
+  loss              dice: smooth 0                                     loss-{48,49}
+  step              entry: clip                                        step-{0,1,2,3,4,5,6,7,8,9,10,11}
+  step              entry: sgd                                         step-{12,13,14,15,16,17,18,19,20,21,22,23,24,25}
+  step              entry: sgd_sched                                   step-{26,27,28}
+  step              entry: adamw                                       step-{29,30,31,32,33,34,35,36,37,38,39}
+  step              n = 1                                              step-{0,12,29}
+  step              n = 3                                              step-{1,10,13,30}
+  step              n = 4                                              step-{2,14,31}
+  step              n = 5                                              step-{3,15,28,32}
+  step              1023 quads                                         step-{4,7,9,16,17,22,33,37}
+  step              1024 quads                                         step-{5,8,18,19,24,26,27,34}
+  step              1025 quads                                         step-{6,20,21,23,35,36,38}
+  step              tail of 0                                          step-{2,4,8,14,16,20,24,31,34,36}
+  step              tail of 1                                          step-{0,3,5,12,15,17,23,27,28,29,32,37,38}
+  step              tail of 2                                          step-{6,9,18,22,35}
+  step              tail of 3                                          step-{1,7,10,11,13,19,21,25,26,30,33,39}
+  step              clip: the partial sums' grid strides               step-{11}
+  step              sgd: stream_update's grid strides                  step-{25}
+  step              adamw: stream_update's grid strides                step-{39}
+  step              ranges: none                                       step-{12,29}
+  step              ranges: whole                                      step-{13,14,27,30}
+  step              ranges: quad16                                     step-{16,17,26,33}
+  step              ranges: inquad                                     step-{18,31}
+  step              ranges: intail                                     step-{15,21,32,39}
+  step              ranges: border                                     step-{19,25,35}
+  step              ranges: r32                                        step-{20,34}
+  step              ranges: adjacent                                   step-{22,36}
+  step              ranges: empty                                      step-{23,37}
+  step              ranges: past                                       step-{24,28,38}
+  step              mirror: none                                       step-{12,15,17,20,24,27,29,31,34,37}
+  step              mirror: bf16                                       step-{13,16,19,21,23,25,26,30,33,36,38}
+  step              mirror: fp16                                       step-{14,18,22,28,32,35,39}
+  step              sgd_nt = 0                                         step-{13,17,21,22,27,31,34,38}
+  step              sgd_nt = 1                                         step-{12,14,15,16,18,19,20,23,24,25,26,28,29,30,32,33,35,36,37,39}
+  step              clip kind: below                                   step-{1,6}
+  step              clip kind: above                                   step-{0,5,7,11}
+  step              clip kind: zero                                    step-{2,8}
+  step              clip kind: negative                                step-{3,9}
+  step              clip kind: zerograd                                step-{4,10}
+  step              step NULL                                          step-{22,27,37}
+  step              clip_state NULL                                    step-{19,27,35}
+  step              lr_out NULL                                        step-{14,27,36}
+  areas             1 class                                            areas-{0,1}
+  areas             2 classes                                          areas-{2,3}
+  areas             19 classes                                         areas-{4,5,6,10}
+  areas             256 classes                                        areas-{7,8,9}
+  areas             labels: int32                                      areas-{0,4,7}
+  areas             labels: int64                                      areas-{1,5,8}
+  areas             labels: uint8                                      areas-{2,3,6,9,10}
+  areas             uint8 at byte offset 0                             areas-{2,9}
+  areas             uint8 at byte offset 1                             areas-{3,6,10}
+  areas             n = 1                                              areas-{0,8}
+  areas             n = 4095                                           areas-{1,5,9}
+  areas             n = 4096                                           areas-{2,6,7}
+  areas             n = 4097                                           areas-{3,4}
+  areas             the grid strides (n > 1024 x 4096)                 areas-{10}
+  areas             ignore index inside [0, ncls)                      areas-{1,3,8,9}
+  areas             ignore index outside [0, ncls)                     areas-{0,2,4,5,6,7,10}
 
 Not reachable through the wrappers, on purpose:
   * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
@@ -505,6 +625,9 @@ Not reachable through the wrappers, on purpose:
     parity-class kernel has no ragged M tile (M / 4 is a multiple of 64 by its own condition) and, like the cross-block split and the pair
     kernel, no scalar epilogue (the host sends those problems elsewhere); the thin kernel takes neither stat_x nor an addend (thin_bwd_ok).
     The weight-gradient kernels' own plan space belongs to tests/test_gpu_wgrad_group.py and the WG8 cases of tests/test_gpu_conv_fuzz.py.
+  * loss: a label outside [0, C) that is not the ignore index is outside the contract (include/emrt_hip_loss.h) and loss_in_domain refuses
+    it; the Dice entry points stop at 64 classes, so C = 150 runs in the other three families; the 64-bit branch of pixel_of needs 2^32 pixels.
+  * step: the learning-rate schedules (tests/test_gpu_adamw.py::test_schedules_on_the_device) and emrt_pack_weights stay out.
 """
 import random
 
@@ -2258,20 +2381,420 @@ CONV_REGIMES = [("%s, %s epilogue" % (k, cp), _cv_l(lambda c, k_, cp_: _cv_kind(
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the losses: emrt_softmax_ce_* / emrt_wce_* / emrt_ohem_ce_* (csrc/loss.hip), emrt_lx_dice_ce_* (csrc/loss_ext/loss_ext.hip), all on the pixel
+# core of csrc/loss_pixel.hpp (tests/test_gpu_loss_fuzz.py; inputs and float64 references: tests/loss_step_reference.py).  Written out like
+# the gconv list.  The host arithmetic below carries the names the C++ has.
+# ---------------------------------------------------------------------------------------------------------------------------------
+LOSS_LONG_MAX_ELEMS = 2 * 1025 * 1024          # logits of one head, for the four cases that send a backward kernel round its loop twice
+LOSS_FAMILIES = ("ce", "wce", "ohem", "dice")
+LOSS_FORMS = ("single", "pair")
+LOSS_LABELS = ("none", "tenth", "all", "allbut1", "oneclass")          # which pixels carry the ignore index (oneclass: a tenth, the rest one class)
+LOSS_LOGITS = ("ordinary", "confident", "shift+", "shift-", "wide", "constant", "grid")
+LOSS_CW = ("none", "random", "onezero", "zeropresent")
+LOSS_FWD_BLOCKS, LOSS_BWD_BLOCKS, LOSS_HIST_BLOCKS = 1024, 4096, 128          # wce_forward / ohem_forward: loss.hip:359,388; wce_backward / ohem_backward: 372,406; OH_HIST_BLOCKS: 25,391
+LX_MAX_BLOCKS, LX_BWD_BLOCKS, LX_CHUNK, LX_HEAD, LX_MAX_CLASSES = 1024, 4096, 8, 3, 64          # loss_ext.hip:41-44, EMRT_LX_MAX_CLASSES
+
+
+def stream_grid(npix, cap):
+    """grid of a streaming launch: one thread per pixel, capped.  loss_pixel.hpp:56-59"""
+    g = (npix + 255) // 256
+    return cap if g > cap else 1 if g < 1 else g
+
+
+def shape_ok(N, C, H, W):
+    """loss_pixel.hpp:61"""
+    return N >= 1 and C >= 1 and H >= 1 and W >= 1 and N * H * W < (1 << 31)
+
+
+def lx_chunks(C):
+    """loss_ext.hip:48"""
+    return (C + LX_CHUNK - 1) // LX_CHUNK
+
+
+def lx_stride(C):
+    """floats per block of the Dice forward's workspace.  loss_ext.hip:49"""
+    return LX_HEAD + lx_chunks(C) * 3 * LX_CHUNK
+
+
+def loss_npix(c):
+    return c[3] * c[5] * c[6]
+
+
+def loss_grids(c):
+    """(forward grid, backward grid, histogram grid or None) of a case's family: wce_forward / wce_backward / ohem_forward / ohem_backward
+    (loss.hip:359,372,388,391,406), dice_forward / dice_backward (loss_ext.hip:296,313)"""
+    n = loss_npix(c)
+    if c[1] == "dice":
+        return stream_grid(n, LX_MAX_BLOCKS), stream_grid(n, LX_BWD_BLOCKS), None
+    return stream_grid(n, LOSS_FWD_BLOCKS), stream_grid(n, LOSS_BWD_BLOCKS), (stream_grid(n, LOSS_HIST_BLOCKS) if c[1] == "ohem" else None)
+
+
+def loss_depth(npix, grid):
+    """pixels one thread of a grid-stride loop takes at most: the fp32 additions in front of the block's reduction"""
+    return _ceil_div(npix, grid * 256)
+
+
+def loss_in_domain(c):
+    """the EMRT_REQUIRE / LX_REQUIRE lines of the entry points; a label pattern outside LOSS_LABELS (a label outside [0, C) that is not the
+    ignore index: include/emrt_hip_loss.h puts it outside the contract) is refused here"""
+    _, fam, form, N, C, H, W, ign, labels, logits, cw, hw, up, thresh, min_kept, dice, _, _ = c
+    if fam not in LOSS_FAMILIES or form not in LOSS_FORMS or labels not in LOSS_LABELS or logits not in LOSS_LOGITS or cw not in LOSS_CW:
+        return False
+    if not shape_ok(N, C, H, W) or len(hw) != 2:
+        return False
+    if 0 <= ign < C and labels == "none":          # the ignored class's own pixels are ignored: "none ignored" cannot be drawn
+        return False
+    if fam in ("ce", "ohem") and cw != "none":
+        return False
+    if fam == "ohem" and not (min_kept >= 0 and thresh == thresh):
+        return False
+    if fam == "dice":
+        cew, dw, smooth = dice
+        if not (1 <= C <= LX_MAX_CLASSES and cew >= 0 and dw >= 0 and (cew > 0 or dw > 0) and smooth >= 0):
+            return False
+    return True
+
+
+_HW1, _HWN, _HWZ = (1.0, 0.4), (1.0, -0.4), (0.0, 0.4)
+_D1 = (1.0, 1.0, 1.0)
+# (family, form, N, C, H, W, ignore index, label pattern, logit pattern, class weights, head weights, upstream scalar given, thresh, min_kept,
+#  Dice's (ce_weight, dice_weight, smooth), what the row is there for)
+_LOSS_ROWS = (
+    ("ce", "single", 1, 1, 1, 1, 255, "none", "ordinary", "none", _HW1, False, 0, 0, None, "one pixel of one class: p = 1, loss 0"),
+    ("ce", "pair", 1, 2, 3, 5, 255, "tenth", "ordinary", "none", _HW1, True, 0, 0, None, "15 pixels: fewer than a wave"),
+    ("ce", "single", 1, 3, 15, 17, 255, "none", "ordinary", "none", _HW1, False, 0, 0, None, "255 pixels, none ignored"),
+    ("ce", "pair", 1, 6, 16, 16, -100, "tenth", "confident", "none", _HWN, False, 0, 0, None, "256 pixels: exactly one block; ignore index -100; a negative head weight"),
+    ("ce", "single", 1, 7, 1, 257, 255, "allbut1", "ordinary", "none", _HW1, False, 0, 0, None, "257 pixels, one of them labelled"),
+    ("ce", "pair", 2, 6, 33, 31, 255, "tenth", "ordinary", "none", _HW1, True, 0, 0, None, "two images of 1023 pixels: block 3 spans both (pixel_of)"),
+    ("ce", "single", 3, 8, 5, 17, 3, "tenth", "shift+", "none", _HW1, False, 0, 0, None, "class 3 is the ignore index; logits + 1000; three images inside one block"),
+    ("ce", "pair", 2, 9, 33, 31, 255, "tenth", "shift-", "none", _HWZ, False, 0, 0, None, "logits - 1000; a head of weight zero: its gradient is all zeros"),
+    ("ce", "single", 2, 16, 9, 7, 255, "tenth", "wide", "none", _HW1, False, 0, 0, None, "own-class logit 60 and 120 below the maximum: p tiny, and exactly 0 in fp32"),
+    ("ce", "pair", 1, 17, 11, 13, -100, "none", "constant", "none", _HW1, False, 0, 0, None, "constant map: p = 1 / 17 everywhere"),
+    ("ce", "single", 1, 19, 8, 9, 255, "oneclass", "ordinary", "none", _HW1, True, 0, 0, None, "one class present"),
+    ("ce", "single", 1, 150, 6, 7, 255, "tenth", "ordinary", "none", _HW1, False, 0, 0, None, "150 classes: the long class loop"),
+    ("ce", "pair", 2, 150, 5, 5, 7, "tenth", "wide", "none", _HWN, True, 0, 0, None, "150 classes, wide logits, class 7 ignored"),
+    ("ce", "single", 2, 6, 9, 7, 255, "all", "ordinary", "none", _HW1, False, 0, 0, None, "every pixel ignored: loss 0, gradient 0"),
+    ("ce", "single", 1, 2, 1025, 1024, 255, "tenth", "ordinary", "none", _HW1, False, 0, 0, None, "1 049 600 pixels: wce_bwd_kernel<1, false> goes round its loop twice"),
+    ("wce", "single", 1, 1, 1, 1, 255, "none", "ordinary", "random", _HW1, False, 0, 0, None, "one pixel, one weighted class"),
+    ("wce", "pair", 1, 2, 3, 5, 255, "tenth", "ordinary", "random", _HW1, False, 0, 0, None, "15 pixels"),
+    ("wce", "single", 1, 3, 5, 51, -100, "tenth", "confident", "onezero", _HW1, False, 0, 0, None, "255 pixels; one class of weight zero"),
+    ("wce", "pair", 1, 6, 16, 16, 255, "none", "ordinary", "random", _HWZ, True, 0, 0, None, "256 pixels, none ignored, a head of weight zero"),
+    ("wce", "single", 1, 7, 257, 1, 255, "tenth", "ordinary", "zeropresent", _HW1, False, 0, 0, None, "weight zero on every class present: loss 0, gradient 0"),
+    ("wce", "pair", 2, 7, 33, 31, 255, "tenth", "ordinary", "random", _HW1, True, 0, 0, None, "a block spans two images"),
+    ("wce", "single", 3, 8, 5, 17, 0, "tenth", "shift-", "random", _HW1, False, 0, 0, None, "class 0 is the ignore index; logits - 1000"),
+    ("wce", "pair", 2, 9, 7, 9, 255, "allbut1", "shift+", "random", _HWN, False, 0, 0, None, "one labelled pixel, logits + 1000"),
+    ("wce", "single", 2, 16, 33, 31, 255, "tenth", "wide", "random", _HW1, True, 0, 0, None, "16 classes, wide logits"),
+    ("wce", "pair", 1, 17, 9, 11, 255, "oneclass", "constant", "onezero", _HW1, False, 0, 0, None, "17 classes, constant map, one class present"),
+    ("wce", "single", 1, 19, 12, 10, -100, "none", "confident", "random", _HW1, False, 0, 0, None, "19 classes, ignore index -100 and no pixel carries it"),
+    ("wce", "pair", 1, 150, 4, 9, 255, "tenth", "ordinary", "random", _HW1, False, 0, 0, None, "150 weighted classes"),
+    ("wce", "single", 2, 6, 8, 8, 255, "all", "ordinary", "random", _HW1, False, 0, 0, None, "every pixel ignored"),
+    ("wce", "pair", 1, 2, 1025, 1024, 255, "tenth", "ordinary", "random", _HW1, True, 0, 0, None, "1 049 600 pixels: wce_bwd_kernel<2, true> goes round its loop twice"),
+    ("ohem", "single", 1, 2, 1, 1, 255, "none", "ordinary", "none", _HW1, False, 0.7, 0, None, "one pixel, min_kept 0"),
+    ("ohem", "pair", 1, 3, 3, 5, 255, "tenth", "ordinary", "none", _HW1, False, 0.7, 5, None, "15 pixels"),
+    ("ohem", "single", 1, 6, 15, 17, -100, "tenth", "ordinary", "none", _HW1, False, 0.7, 100, None, "255 pixels, ignore index -100"),
+    ("ohem", "pair", 1, 7, 16, 16, 255, "none", "confident", "none", _HWN, True, 0.7, 100, None, "256 confident pixels: the k-th smallest p is the threshold"),
+    ("ohem", "single", 1, 8, 257, 1, 255, "allbut1", "ordinary", "none", _HW1, False, 0.7, 1, None, "one labelled pixel: min_kept reaches their number"),
+    ("ohem", "pair", 2, 6, 33, 31, 255, "tenth", "ordinary", "none", _HW1, True, 0.7, 500, None, "a block spans two images"),
+    ("ohem", "single", 2, 9, 33, 31, 4, "tenth", "confident", "none", _HW1, False, 0.7, 500, None, "class 4 is the ignore index"),
+    ("ohem", "pair", 3, 16, 5, 17, 255, "tenth", "shift+", "none", _HWZ, False, 0.7, 50, None, "16 classes, logits + 1000, a head of weight zero"),
+    ("ohem", "single", 2, 17, 9, 7, 255, "tenth", "wide", "none", _HW1, False, 0.7, 30, None, "17 classes; stored p of exactly 0 sorts first"),
+    ("ohem", "single", 1, 19, 8, 9, 255, "oneclass", "shift-", "none", _HW1, True, 0.5, 20, None, "19 classes, one present, logits - 1000"),
+    ("ohem", "pair", 1, 150, 6, 7, 255, "tenth", "ordinary", "none", _HW1, False, 0.7, 10, None, "150 classes"),
+    ("ohem", "single", 2, 6, 9, 7, 255, "all", "ordinary", "none", _HW1, False, 0.7, 0, None, "every pixel ignored"),
+    ("ohem", "single", 2, 3, 33, 31, 255, "tenth", "constant", "none", _HW1, False, 0.1, 10, None, "every pixel tied at p = 1 / 3 > thresh: the threshold is their p, nothing is kept"),
+    ("ohem", "pair", 2, 2, 33, 31, 255, "tenth", "grid", "none", _HW1, False, 0.1, 900, None, "logits on a grid of 0.5: min_kept inside a tie group"),
+    ("ohem", "single", 1, 3, 200, 180, 255, "tenth", "ordinary", "none", _HW1, False, 0.7, 5000, None, "36 000 pixels: the digit histograms' 128 blocks stride"),
+    ("ohem", "pair", 1, 2, 1025, 1024, 255, "tenth", "grid", "none", _HW1, True, 0.6, 300000, None, "1 049 600 pixels: ohem_bwd_kernel goes round its loop twice; every forward grid strides"),
+    ("dice", "single", 1, 1, 1, 1, 255, "none", "ordinary", "none", _HW1, False, 0, 0, _D1, "one pixel of one class"),
+    ("dice", "pair", 1, 2, 3, 5, 255, "tenth", "ordinary", "none", _HW1, False, 0, 0, _D1, "15 pixels"),
+    ("dice", "single", 1, 3, 15, 17, -100, "tenth", "confident", "random", _HW1, False, 0, 0, (1.5, 0.75, 1.0), "255 pixels, class weights, unequal loss weights"),
+    ("dice", "pair", 1, 8, 16, 16, 255, "none", "ordinary", "none", _HWN, True, 0, 0, (1.0, 1.0, 0.0), "8 classes: exactly one chunk; smooth 0"),
+    ("dice", "single", 1, 9, 1, 257, 255, "tenth", "ordinary", "none", _HW1, False, 0, 0, (1.0, 1.0, 0.0), "9 classes: a second chunk of one class; smooth 0"),
+    ("dice", "pair", 2, 7, 33, 31, 255, "tenth", "ordinary", "random", _HW1, True, 0, 0, _D1, "a block spans two images"),
+    ("dice", "single", 3, 16, 5, 17, 2, "tenth", "shift+", "none", _HW1, False, 0, 0, _D1, "16 classes: two full chunks; class 2 ignored; logits + 1000"),
+    ("dice", "pair", 2, 17, 9, 7, 255, "allbut1", "wide", "onezero", _HWZ, False, 0, 0, _D1, "17 classes: three chunks, the last of one class; one labelled pixel"),
+    ("dice", "single", 1, 19, 8, 9, 255, "oneclass", "constant", "none", _HW1, False, 0, 0, (0.5, 2.0, 1.0), "19 classes, constant map, one class present"),
+    ("dice", "single", 2, 6, 9, 7, 255, "all", "ordinary", "random", _HW1, False, 0, 0, _D1, "every pixel ignored"),
+    ("dice", "single", 2, 6, 33, 31, 255, "tenth", "shift-", "zeropresent", _HW1, False, 0, 0, _D1, "total class weight zero: CE 0, the Dice term alone"),
+    ("dice", "pair", 1, 2, 1025, 1024, 255, "tenth", "ordinary", "none", _HW1, False, 0, 0, _D1, "1 049 600 pixels: dice_bwd_kernel goes round its loop twice (LX_BWD_BLOCKS)"),
+)
+
+
+def loss_cases(seed=2313):
+    """(id, family, form, N, C, H, W, ignore index, labels, logits, class weights, head weights, upstream, thresh, min_kept, dice, why, seed)"""
+    return [("loss-%d" % i,) + row + (seed + i,) for i, row in enumerate(_LOSS_ROWS)]
+
+
+def _ls_bwd_twice(c):
+    return loss_npix(c) > loss_grids(c)[1] * 256
+
+
+LOSS_REGIMES = [("family: %s" % f, (lambda f_: lambda c: c[1] == f_)(f)) for f in LOSS_FAMILIES] + [
+    ("form: %s" % f, (lambda f_: lambda c: c[2] == f_)(f)) for f in LOSS_FORMS] + [
+    ("C = %d" % k, (lambda k_: lambda c: c[4] == k_)(k)) for k in (1, 2, 3, 6, 7, 8, 9, 16, 17, 19, 150)] + [
+    ("dice: whole class chunks (C % 8 == 0)", lambda c: c[1] == "dice" and c[4] % LX_CHUNK == 0),
+    ("dice: several chunks, ragged last", lambda c: c[1] == "dice" and lx_chunks(c[4]) > 1 and c[4] % LX_CHUNK != 0),
+] + [("%d pixel%s" % (k, "s" if k > 1 else ""), (lambda k_: lambda c: loss_npix(c) == k_)(k)) for k in (1, 15, 255, 256, 257)] + [
+    ("a block spans two images (N >= 2, HW % 256 != 0)", lambda c: c[3] >= 2 and (c[5] * c[6]) % 256 != 0 and loss_npix(c) > 256),
+    ("several images inside one block", lambda c: c[3] >= 2 and loss_npix(c) <= 256),
+] + [("%s: the forward grid strides" % f, (lambda f_: lambda c: c[1] == f_ and loss_npix(c) > loss_grids(c)[0] * 256)(f)) for f in LOSS_FAMILIES] + [
+    ("ohem: the digit histograms' grid strides", lambda c: c[1] == "ohem" and loss_npix(c) > loss_grids(c)[2] * 256),
+    ("second trip: wce_bwd_kernel plain, single", lambda c: c[1] == "ce" and c[2] == "single" and _ls_bwd_twice(c)),
+    ("second trip: wce_bwd_kernel weighted, pair", lambda c: c[1] == "wce" and c[2] == "pair" and c[10] != "none" and _ls_bwd_twice(c)),
+    ("second trip: ohem_bwd_kernel", lambda c: c[1] == "ohem" and _ls_bwd_twice(c)),
+    ("second trip: dice_bwd_kernel", lambda c: c[1] == "dice" and _ls_bwd_twice(c)),
+] + [("labels: %s" % p, (lambda p_: lambda c: c[8] == p_)(p)) for p in LOSS_LABELS] + [
+    ("ignore index 255", lambda c: c[7] == 255),
+    ("ignore index -100", lambda c: c[7] == -100),
+    ("ignore index inside [0, C)", lambda c: 0 <= c[7] < c[4]),
+] + [("logits: %s" % p, (lambda p_: lambda c: c[9] == p_)(p)) for p in LOSS_LOGITS] + [
+    ("class weights: %s" % p, (lambda p_: lambda c: c[10] == p_)(p)) for p in LOSS_CW[1:]] + [
+    ("head weights (1, 0.4)", lambda c: c[11] == _HW1),
+    ("one negative head weight", lambda c: min(c[11]) < 0),
+    ("one head weight zero", lambda c: 0.0 in c[11]),
+    ("upstream scalar given", lambda c: c[12]),
+    ("upstream NULL", lambda c: not c[12]),
+    ("ohem: min_kept = 0", lambda c: c[1] == "ohem" and c[14] == 0),
+    ("dice: smooth 0", lambda c: c[1] == "dice" and c[15][2] == 0.0),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the optimizer half of csrc/optim.hip: emrt_grad_clip_scale, emrt_sgd_momentum_step(_sched), emrt_adamw_step through stream_update
+# (tests/test_gpu_step_fuzz.py).
+# ---------------------------------------------------------------------------------------------------------------------------------
+STEP_LONG_MAX_ELEMS = 4 * (8192 * 256 + 1) + 3          # one quad past stream_update's 8192 blocks, plus a 3-element tail
+STEP_ENTRIES = ("clip", "sgd", "sgd_sched", "adamw")
+STEP_LAYOUTS = ("none", "whole", "quad16", "inquad", "intail", "border", "r32", "adjacent", "empty", "past")
+STEP_MIRRORS = ("none", "bf16", "fp16")
+STEP_CLIPS = ("below", "above", "zero", "negative", "zerograd")
+STEP_NULLS = ("step", "clip_state", "lr_out")
+STEP_MAX_RANGES = 32
+
+
+def clip_grid(n):
+    """emrt_grad_clip_scale, optim.hip:292-294"""
+    return min(max((n // 4 + 255) // 256, 1), 2048)
+
+
+def step_grid(n):
+    """launch_step, optim.hip:338-340"""
+    return min(max((n // 4 + 255) // 256, 1), 8192)
+
+
+def step_body_tail(n):
+    """(n4, tail): quads of the vector body, elements of the scalar tail in block 0.  stream_update, optim.hip:77,124; sqnorm_partial_kernel:30,35"""
+    return n // 4, n - n // 4 * 4
+
+
+def clip_depth(n):
+    """fp32 additions in front of one thread's wave_sum in sqnorm_partial_kernel (optim.hip:31-35): four per quad, one for a tail element"""
+    n4, tail = step_body_tail(n)
+    return 4 * _ceil_div(n4, clip_grid(n) * 256) + (1 if tail else 0)
+
+
+def fill_step_args_refuses(aligned16, mirror, mirror_aligned8, mirror_dtype, nranges, ranges_given):
+    """the refusals of fill_step_args (optim.hip:323-326) for non-null buffers -> the reason or None"""
+    if mirror and mirror_dtype not in (1, 2):          # EMRT_BF16, EMRT_F16
+        return "the parameter mirror is bf16 or fp16"
+    if not aligned16 or (mirror and not mirror_aligned8):
+        return "buffers must be 16-byte aligned"
+    if nranges < 0 or nranges > STEP_MAX_RANGES or (nranges != 0 and not ranges_given):
+        return "0..32 lr-mult ranges"
+    return None
+
+
+def step_ranges(layout, n):
+    """the lr-mult ranges [(r0, r1)] of a layout name at n elements.  quad16: all sixteen (start offset, end offset) pairs of the quad pre-test
+    `i + 3 >= r0 && i < r1` (optim.hip:104), one range each, two quads apart"""
+    n4, tail = step_body_tail(n)
+    if layout == "none":
+        return []
+    if layout == "whole":
+        return [(0, n)]
+    if layout == "quad16":
+        return [(32 * (4 * a + b) + 8 + a, 32 * (4 * a + b) + 20 + b) for a in range(4) for b in range(4)]
+    if layout == "inquad":
+        return [(41, 43)] if n >= 44 else [(1, min(3, n))]
+    if layout == "intail":
+        return [(n4 * 4 + (1 if tail == 3 else 0), n)]
+    if layout == "border":
+        return [(n4 * 4 - 2, n4 * 4 + 2)]
+    if layout == "r32":
+        return [(16 * i + 1 + i % 4, 16 * i + 6 + i % 3) for i in range(32)]
+    if layout == "adjacent":
+        return [(8, 13), (13, 22)]
+    if layout == "empty":
+        return [(9, 9)]
+    if layout == "past":
+        return [(n, n + 8), (n - 2, n + 5)]
+    raise ValueError(layout)
+
+
+def step_selected(layout, n):
+    """sorted element indices inside the union of the ranges, clipped to [0, n)"""
+    sel = set()
+    for r0, r1 in step_ranges(layout, n):
+        sel.update(range(max(r0, 0), min(r1, n)))
+    return sorted(sel)
+
+
+def step_in_domain(c):
+    _, entry, n, layout, mirror, nt, clip, nulls, _, _ = c
+    if entry not in STEP_ENTRIES or layout not in STEP_LAYOUTS or mirror not in STEP_MIRRORS or nt not in (0, 1) or n < 1:
+        return False
+    if any(x not in STEP_NULLS for x in nulls):
+        return False
+    if entry == "clip":
+        return clip in STEP_CLIPS and layout == "none" and mirror == "none" and not nulls
+    if clip != "":
+        return False
+    r = step_ranges(layout, n)
+    if len(r) > STEP_MAX_RANGES or any(r0 < 0 for r0, _ in r):
+        return False
+    if layout == "quad16" and n < 32 * 15 + 24:
+        return False
+    if layout == "intail" and step_body_tail(n)[1] == 0:
+        return False
+    if layout == "border" and (n < 4 or step_body_tail(n)[1] < 2):
+        return False
+    return True
+
+
+# (entry point, n, range layout, mirror, sgd_nt, clip kind, which of step / clip_state / lr_out are NULL, what the row is there for)
+_STEP_ROWS = (
+    ("clip", 1, "none", "none", 1, "above", (), "one element: the tail alone"),
+    ("clip", 3, "none", "none", 1, "below", (), "three tail elements, norm below clip: scale exactly 1"),
+    ("clip", 4, "none", "none", 1, "zero", (), "one quad, clip = 0: scale 1"),
+    ("clip", 5, "none", "none", 1, "negative", (), "a quad and a tail element, clip < 0: scale 1"),
+    ("clip", 4092, "none", "none", 1, "zerograd", (), "1023 quads, all-zero gradient: norm 0, scale 1"),
+    ("clip", 4097, "none", "none", 1, "above", (), "1024 quads + 1: four full blocks and one tail element"),
+    ("clip", 4102, "none", "none", 1, "below", (), "1025 quads + 2"),
+    ("clip", 4095, "none", "none", 1, "above", (), "1023 quads + 3"),
+    ("clip", 4096, "none", "none", 1, "zero", (), "1024 quads, clip = 0"),
+    ("clip", 4094, "none", "none", 1, "negative", (), "1023 quads + 2, clip < 0"),
+    ("clip", 3, "none", "none", 1, "zerograd", (), "an all-zero tail"),
+    ("clip", 4 * (2048 * 256 + 1) + 3, "none", "none", 1, "above", (), "2 097 159 elements: sqnorm_partial_kernel's 2048 blocks stride"),
+    ("sgd", 1, "none", "none", 1, "", (), "one element: no vector body"),
+    ("sgd", 3, "whole", "bf16", 0, "", (), "three tail elements, all inside the range"),
+    ("sgd", 4, "whole", "fp16", 1, "", ("lr_out",), "one quad, lr_out NULL"),
+    ("sgd", 5, "intail", "none", 1, "", (), "the one tail element is the range"),
+    ("sgd", 4092, "quad16", "bf16", 1, "", (), "1023 quads; every start / end offset of the quad pre-test"),
+    ("sgd", 4093, "quad16", "none", 0, "", (), "1023 quads + 1, plain loads"),
+    ("sgd", 4098, "inquad", "fp16", 1, "", (), "1024 quads + 2; a range inside one quad"),
+    ("sgd", 4099, "border", "bf16", 1, "", ("clip_state",), "1024 quads + 3; a range across the body / tail border; clip_state NULL"),
+    ("sgd", 4100, "r32", "none", 1, "", (), "1025 quads; 32 ranges"),
+    ("sgd", 4103, "intail", "bf16", 0, "", (), "1025 quads + 3; a range inside the tail"),
+    ("sgd", 4094, "adjacent", "fp16", 0, "", ("step",), "1023 quads + 2; two adjacent ranges; step NULL"),
+    ("sgd", 4101, "empty", "bf16", 1, "", (), "1025 quads + 1; an empty range"),
+    ("sgd", 4096, "past", "none", 1, "", (), "1024 quads; a range starting at n and one running past it"),
+    ("sgd", STEP_LONG_MAX_ELEMS, "border", "bf16", 1, "", (), "8 388 615 elements: stream_update<1>'s 8192 blocks stride"),
+    ("sgd_sched", 4099, "quad16", "bf16", 1, "", (), "the schedule-driven entry point through the same kernel"),
+    ("sgd_sched", 4097, "whole", "none", 0, "", STEP_NULLS, "step, clip_state and lr_out all NULL"),
+    ("sgd_sched", 5, "past", "fp16", 1, "", (), "five elements, a range past n"),
+    ("adamw", 1, "none", "none", 1, "", (), "one element"),
+    ("adamw", 3, "whole", "bf16", 1, "", (), "three tail elements"),
+    ("adamw", 4, "inquad", "none", 0, "", (), "one quad, a range inside it"),
+    ("adamw", 5, "intail", "fp16", 1, "", (), "the one tail element is the range"),
+    ("adamw", 4095, "quad16", "bf16", 1, "", (), "1023 quads + 3; every start / end offset"),
+    ("adamw", 4096, "r32", "none", 0, "", (), "1024 quads; 32 ranges"),
+    ("adamw", 4102, "border", "fp16", 1, "", ("clip_state",), "1025 quads + 2; across the border; clip_state NULL"),
+    ("adamw", 4100, "adjacent", "bf16", 1, "", ("lr_out",), "1025 quads; adjacent ranges; lr_out NULL"),
+    ("adamw", 4093, "empty", "none", 1, "", ("step",), "1023 quads + 1; an empty range; step NULL"),
+    ("adamw", 4101, "past", "bf16", 0, "", (), "1025 quads + 1; ranges at and past n"),
+    ("adamw", STEP_LONG_MAX_ELEMS, "intail", "fp16", 1, "", (), "8 388 615 elements: stream_update<2>'s 8192 blocks stride; a range inside the tail"),
+)
+
+
+def step_cases(seed=2414):
+    """(id, entry, n, layout, mirror, sgd_nt, clip kind, nulls, why, seed)"""
+    return [("step-%d" % i,) + row + (seed + i,) for i, row in enumerate(_STEP_ROWS)]
+
+
+def _st_quads(c):
+    return step_body_tail(c[2])[0]
+
+
+STEP_REGIMES = [("entry: %s" % e, (lambda e_: lambda c: c[1] == e_)(e)) for e in STEP_ENTRIES] + [
+    ("n = %d" % k, (lambda k_: lambda c: c[2] == k_)(k)) for k in (1, 3, 4, 5)] + [
+    ("%d quads" % q, (lambda q_: lambda c: _st_quads(c) == q_)(q)) for q in (1023, 1024, 1025)] + [
+    ("tail of %d" % t, (lambda t_: lambda c: step_body_tail(c[2])[1] == t_)(t)) for t in (0, 1, 2, 3)] + [
+    ("clip: the partial sums' grid strides", lambda c: c[1] == "clip" and _st_quads(c) > clip_grid(c[2]) * 256),
+    ("sgd: stream_update's grid strides", lambda c: c[1] == "sgd" and _st_quads(c) > step_grid(c[2]) * 256),
+    ("adamw: stream_update's grid strides", lambda c: c[1] == "adamw" and _st_quads(c) > step_grid(c[2]) * 256),
+] + [("ranges: %s" % p, (lambda p_: lambda c: c[1] != "clip" and c[3] == p_)(p)) for p in STEP_LAYOUTS] + [
+    ("mirror: %s" % p, (lambda p_: lambda c: c[1] != "clip" and c[4] == p_)(p)) for p in STEP_MIRRORS] + [
+    ("sgd_nt = %d" % k, (lambda k_: lambda c: c[1] != "clip" and c[5] == k_)(k)) for k in (0, 1)] + [
+    ("clip kind: %s" % p, (lambda p_: lambda c: c[6] == p_)(p)) for p in STEP_CLIPS] + [
+    ("%s NULL" % p, (lambda p_: lambda c: p_ in c[7])(p)) for p in STEP_NULLS]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# emrt_segmentation_areas (csrc/optim.hip; tests/test_gpu_step_fuzz.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+AREAS_LONG_MAX_ELEMS = 1024 * 4096 + 1
+AREAS_LTYPES = (0, 1, 2)          # label_is_int64: 0 = int32, 1 = int64, 2 = uint8
+
+
+def areas_grid(n):
+    """emrt_segmentation_areas, optim.hip:276-277: sixteen labels per thread, at most 1024 blocks"""
+    return min((n + 256 * 16 - 1) // (256 * 16), 1024)
+
+
+def areas_in_domain(c):
+    _, ncls, ltype, offset, n, ignore, _, _ = c
+    return 1 <= ncls <= 256 and ltype in AREAS_LTYPES and n >= 1 and offset in (0, 1) and (offset == 0 or ltype == 2)
+
+
+# (classes, label type, byte offset of the uint8 labels, n, ignore index, what the row is there for)
+_AREAS_ROWS = (
+    (1, 0, 0, 1, 255, "one class, one pixel"),
+    (1, 1, 0, 4095, 0, "one class and it is the ignore index: nothing counts"),
+    (2, 2, 0, 4096, 255, "uint8 labels, exactly one block's share"),
+    (2, 2, 1, 4097, 1, "uint8 at an odd byte offset, a second block of one pixel, class 1 ignored"),
+    (19, 0, 0, 4097, 255, "19 classes, int32"),
+    (19, 1, 0, 4095, -1, "int64 labels, a negative ignore index that the labels carry"),
+    (19, 2, 1, 4096, 255, "uint8 at an odd byte offset"),
+    (256, 0, 0, 4096, 300, "256 classes: the whole LDS table; the ignore index above every class"),
+    (256, 1, 0, 1, 255, "256 classes, one pixel, class 255 ignored"),
+    (256, 2, 0, 4095, 255, "256 classes in uint8: every byte value is a class, 255 ignored"),
+    (19, 2, 1, AREAS_LONG_MAX_ELEMS, 255, "4 194 305 pixels: the 1024 blocks stride"),
+)
+
+
+def areas_cases(seed=2515):
+    """(id, classes, label type, byte offset, n, ignore index, why, seed)"""
+    return [("areas-%d" % i,) + row + (seed + i,) for i, row in enumerate(_AREAS_ROWS)]
+
+
+AREAS_REGIMES = [("%d class%s" % (k, "es" if k > 1 else ""), (lambda k_: lambda c: c[1] == k_)(k)) for k in (1, 2, 19, 256)] + [
+    ("labels: %s" % nm, (lambda t_: lambda c: c[2] == t_)(t)) for t, nm in ((0, "int32"), (1, "int64"), (2, "uint8"))] + [
+    ("uint8 at byte offset %d" % o, (lambda o_: lambda c: c[2] == 2 and c[3] == o_)(o)) for o in (0, 1)] + [
+    ("n = %d" % k, (lambda k_: lambda c: c[4] == k_)(k)) for k in (1, 4095, 4096, 4097)] + [
+    ("the grid strides (n > 1024 x 4096)", lambda c: c[4] > areas_grid(c[4]) * 4096),
+    ("ignore index inside [0, ncls)", lambda c: 0 <= c[5] < c[1]),
+    ("ignore index outside [0, ncls)", lambda c: not 0 <= c[5] < c[1]),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 CASES = {
     "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
     "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
     "mha": mha_cases(), "msda": msda_cases(), "gconv": gconv_cases(), "conv": conv_cases(),
+    "loss": loss_cases(), "step": step_cases(), "areas": areas_cases(),
 }
 REGIMES = {
     "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
     "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
     "mha": MHA_REGIMES, "msda": MSDA_REGIMES, "gconv": GCONV_REGIMES, "conv": CONV_REGIMES,
+    "loss": LOSS_REGIMES, "step": STEP_REGIMES, "areas": AREAS_REGIMES,
 }
 IN_DOMAIN = {
     "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
     "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
     "mha": mha_in_domain, "msda": msda_in_domain, "gconv": gconv_in_domain, "conv": conv_in_domain,
+    "loss": loss_in_domain, "step": step_in_domain, "areas": areas_in_domain,
 }
 
 
@@ -2281,7 +2804,14 @@ REGIME_MIN = {("maxpool", "k = 7"): 1, ("msda", "dref on a band pyramid (GRAD_GL
               ("gconv", "grid-stride: forward, no statistics"): 1, ("gconv", "grid-stride: forward with statistics"): 1, ("gconv", "grid-stride: dgrad"): 1,
               # conv: one case each shows that a refused kernel's problem reaches the ladder's own kernel (the issue asks for exactly one)
               ("conv", "8p asked, refused by igemm8p_ok: the ladder's kernel"): 1, ("conv", "thin shape refused by thin_bwd_ok"): 1,
-              ("conv", "xk: fewer k-tiles than the copies asked for"): 1}
+              ("conv", "xk: fewer k-tiles than the copies asked for"): 1,
+              # loss / step / areas: one case each above the ordinary size cap sends a kernel round its grid-stride loop a second time
+              ("loss", "ce: the forward grid strides"): 1, ("loss", "wce: the forward grid strides"): 1, ("loss", "ohem: the forward grid strides"): 1,
+              ("loss", "dice: the forward grid strides"): 1, ("loss", "second trip: wce_bwd_kernel plain, single"): 1,
+              ("loss", "second trip: wce_bwd_kernel weighted, pair"): 1, ("loss", "second trip: ohem_bwd_kernel"): 1,
+              ("loss", "second trip: dice_bwd_kernel"): 1,
+              ("step", "clip: the partial sums' grid strides"): 1, ("step", "sgd: stream_update's grid strides"): 1,
+              ("step", "adamw: stream_update's grid strides"): 1, ("areas", "the grid strides (n > 1024 x 4096)"): 1}
 
 
 def regime_hits(op):

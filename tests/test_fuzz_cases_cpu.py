@@ -64,6 +64,142 @@ def test_case_sizes_stay_small():
             assert fc.conv_gemm_dims(c)[0] * fc.conv_gemm_dims(c)[1] * (c[6] * c[6] * (c[4] if c[11] == "fwd" else c[5])) <= 60000000, c[0]      # multiply-adds of the float64 reference
 
 
+def test_loss_step_and_areas_case_sizes():
+    """the seven cases that send a loss backward kernel or an optimizer kernel round its grid-stride loop a second time (and the one areas
+    case past its 1024 blocks) have caps of their own; everything else stays below MAX_ELEMS"""
+    long_cases = []
+    for c in fc.CASES["loss"]:
+        elems, hits = c[3] * c[4] * c[5] * c[6], fc._ls_bwd_twice(c)
+        assert elems <= (fc.LOSS_LONG_MAX_ELEMS if hits else fc.MAX_ELEMS), c[0]
+        long_cases += [c[0]] if elems > fc.MAX_ELEMS else []
+    assert len(long_cases) == 4
+    for c in fc.CASES["step"]:
+        hits = fc._st_quads(c) > (fc.clip_grid(c[2]) if c[1] == "clip" else fc.step_grid(c[2])) * 256
+        assert c[2] <= (fc.STEP_LONG_MAX_ELEMS if hits else fc.MAX_ELEMS), c[0]
+        long_cases += [c[0]] if c[2] > fc.MAX_ELEMS else []
+    assert len(long_cases) == 7 and fc.STEP_LONG_MAX_ELEMS == 8388615 and fc.LOSS_LONG_MAX_ELEMS == 2 * 1049600
+    big = [c for c in fc.CASES["areas"] if c[4] > fc.MAX_ELEMS]
+    assert len(big) == 1 and big[0][4] == fc.AREAS_LONG_MAX_ELEMS and all(c[4] <= 4097 for c in fc.CASES["areas"] if c is not big[0])
+
+
+def test_loss_sweep_covers_what_it_was_written_for():
+    """one assertion per gap the sweep was written to close in csrc/loss.hip, csrc/loss_pixel.hpp and csrc/loss_ext/loss_ext.hip"""
+    cases = fc.CASES["loss"]
+    assert fc.loss_cases() == cases and 50 <= len(cases) <= 64 and [c[0] for c in cases] == ["loss-%d" % i for i in range(len(cases))]
+    fam = lambda f: [c for c in cases if c[1] == f]
+    # each backward kernel goes round its loop a second time once, at 1 x 2 x 1025 x 1024, and there alone
+    twice = [c for c in cases if fc._ls_bwd_twice(c)]
+    assert [(c[1], c[2], c[10] != "none") for c in twice] == [("ce", "single", False), ("wce", "pair", True), ("ohem", "pair", False), ("dice", "pair", False)]
+    assert all(c[3:7] == (1, 2, 1025, 1024) and fc.loss_depth(fc.loss_npix(c), fc.loss_grids(c)[1]) == 2 for c in twice)
+    # the forward grids (1024 blocks) stride in every family, the OHEM histograms (128 blocks) in a case of ordinary size too
+    for f in fc.LOSS_FAMILIES:
+        assert any(fc.loss_npix(c) > 262144 and fc.loss_grids(c)[0] == 1024 for c in fam(f)), f
+    assert any(32768 < fc.loss_npix(c) <= fc.MAX_ELEMS // c[4] and fc.loss_grids(c)[2] == 128 for c in fam("ohem"))
+    # class counts, in every family that takes them (the Dice entry points stop at 64 classes)
+    for f in ("ce", "wce", "ohem"):
+        assert {1, 2, 3, 6, 7, 8, 9, 16, 17, 19, 150} - {c[4] for c in fam(f)} <= {1, 2, 3, 6, 7, 8, 9} and {16, 17, 19, 150} <= {c[4] for c in fam(f)}, f
+    assert {1, 2, 8, 9, 16, 17, 19} <= {c[4] for c in fam("dice")} and {fc.lx_chunks(c[4]) for c in fam("dice")} == {1, 2, 3}
+    assert {1, 2, 3, 6, 7, 8, 9, 16, 17, 19, 150} == {c[4] for c in cases}
+    # pixel counts around a block, below a wave, and a block across two images of odd size, in every family
+    for f in fc.LOSS_FAMILIES:
+        assert {1, 15, 255, 256, 257} <= {fc.loss_npix(c) for c in fam(f)}, f
+        assert any(c[3] >= 2 and (c[5] * c[6]) % 2 == 1 and c[5] * c[6] > 256 for c in fam(f)), f
+        assert {"none", "tenth", "all", "allbut1", "oneclass"} == {c[8] for c in fam(f)}, f
+        assert {255, -100} <= {c[7] for c in fam(f)} and any(0 <= c[7] < c[4] for c in fam(f)), f
+        assert {"ordinary", "confident", "shift+", "shift-", "wide", "constant"} <= {c[9] for c in fam(f)}, f
+        assert any(min(c[11]) < 0 for c in fam(f)) and any(0.0 in c[11] for c in fam(f)) and any(c[12] for c in fam(f)), f
+    for f in ("wce", "dice"):
+        assert {"random", "onezero", "zeropresent"} <= {c[10] for c in fam(f)}, f
+    assert any(c[9] == "grid" for c in fam("ohem")) and {0, 1} <= {c[14] for c in fam("ohem")}
+    # a label outside [0, C) that is not the ignore index is outside the contract: no pattern draws one, and a row that names one is refused
+    assert not fc.loss_in_domain(cases[5][:8] + ("outside",) + cases[5][9:])
+    assert not fc.loss_in_domain(cases[45][:4] + (65,) + cases[45][5:]) and not fc.loss_in_domain(cases[2][:7] + (1,) + cases[2][8:])
+
+
+def test_step_sweep_covers_what_it_was_written_for():
+    cases = fc.CASES["step"]
+    assert fc.step_cases() == cases and 30 <= len(cases) <= 44
+    upd = [c for c in cases if c[1] != "clip"]
+    ns = {c[2] for c in cases}
+    assert {1, 3, 4, 5} <= ns and {4 * q + t for q in (1023, 1024, 1025) for t in range(4)} <= ns
+    for e in ("clip", "sgd", "adamw"):
+        assert {1, 3, 4, 5} <= {c[2] for c in cases if c[1] == e}, e
+    assert [c[2] for c in cases if c[1] == "clip" and c[2] > fc.MAX_ELEMS] == [4 * (2048 * 256 + 1) + 3]
+    assert [(c[1], c[2]) for c in upd if c[2] > fc.MAX_ELEMS] == [("sgd", 4 * (8192 * 256 + 1) + 3), ("adamw", 4 * (8192 * 256 + 1) + 3)]
+    assert {c[3] for c in upd} == set(fc.STEP_LAYOUTS) and {c[6] for c in cases if c[1] == "clip"} == set(fc.STEP_CLIPS)
+    for e in ("sgd", "adamw"):
+        mine = [c for c in upd if c[1] == e]
+        assert {c[3] for c in mine} == set(fc.STEP_LAYOUTS) and {c[4] for c in mine} == set(fc.STEP_MIRRORS) and {c[5] for c in mine} == {0, 1}, e
+        assert set(fc.STEP_NULLS) <= {x for c in mine + [c for c in upd if c[1] == "sgd_sched"] for x in c[7]}, e
+    # the quad pre-test: all sixteen (start offset, end offset) pairs, each range with untouched quads on both sides
+    r = fc.step_ranges("quad16", 4092)
+    assert {(r0 % 4, r1 % 4) for r0, r1 in r} == {(a, b) for a in range(4) for b in range(4)} and len(r) == 16
+    assert all(r[i][1] + 8 <= r[i + 1][0] for i in range(15))
+    assert fc.step_ranges("inquad", 4098) == [(41, 43)] and fc.step_ranges("intail", 4103) == [(4101, 4103)] and fc.step_ranges("border", 4099) == [(4094, 4098)]
+    assert len(fc.step_ranges("r32", 4100)) == 32 and fc.step_ranges("past", 4096) == [(4096, 4104), (4094, 4101)] and fc.step_selected("past", 4096) == [4094, 4095]
+    assert fc.step_selected("empty", 4101) == [] and fc.step_selected("adjacent", 4094) == list(range(8, 22))
+    assert fc.step_selected("intail", 5) == [4] and fc.step_selected("inquad", 4) == [1, 2]
+    # the refusals the GPU test provokes
+    assert fc.fill_step_args_refuses(False, False, True, 0, 0, False) and fc.fill_step_args_refuses(True, True, True, 0, 0, False)
+    assert fc.fill_step_args_refuses(True, False, True, 0, 33, True) and fc.fill_step_args_refuses(True, False, True, 0, 32, True) is None
+    assert fc.fill_step_args_refuses(True, True, False, 1, 0, False) and fc.fill_step_args_refuses(True, True, True, 2, 1, False)
+
+
+def test_areas_sweep_covers_what_it_was_written_for():
+    cases = fc.CASES["areas"]
+    assert fc.areas_cases() == cases
+    assert {c[1] for c in cases} == {1, 2, 19, 256} and {c[2] for c in cases} == {0, 1, 2} and {c[3] for c in cases if c[2] == 2} == {0, 1}
+    assert {1, 4095, 4096, 4097, 1024 * 4096 + 1} == {c[4] for c in cases}
+    assert any(0 <= c[5] < c[1] for c in cases) and any(c[5] >= c[1] for c in cases) and any(c[5] < 0 for c in cases)
+    from tests import loss_step_reference as R
+    for c in cases[:-1]:          # predictions and labels on both sides of [0, ncls), the ignore index among the labels
+        pred, label = R.areas_inputs(c)
+        assert c[4] < 64 or (pred.min() < 0 and pred.max() >= c[1] and (label.astype("int64") == c[5]).any() == (c[2] != 2 or 0 <= c[5] <= 255)), c[0]
+        assert c[4] < 64 or c[2] == 2 and c[1] == 256 or label.astype("int64").max() >= c[1], c[0]
+
+
+def test_restated_loss_and_step_grids_at_known_points():
+    """computed by hand from csrc/loss_pixel.hpp, csrc/loss.hip, csrc/loss_ext/loss_ext.hip and csrc/optim.hip"""
+    assert [fc.stream_grid(n, 1024) for n in (0, 1, 256, 257, 262144, 262145, 327680)] == [1, 1, 1, 2, 1024, 1024, 1024]
+    assert fc.stream_grid(1048576, 4096) == 4096 and fc.loss_depth(1048576, 4096) == 1 and fc.loss_depth(1048577, 4096) == 2
+    assert fc.stream_grid(32768, 128) == 128 and fc.loss_depth(32769, 128) == 2 and fc.loss_depth(5 * 256 * 256, 1024) == 2
+    assert fc.shape_ok(1, 1, 1, 1) and not fc.shape_ok(1, 1, 1, 2 ** 31) and fc.shape_ok(1, 1, 1, 2 ** 31 - 1) and not fc.shape_ok(0, 1, 1, 1)
+    assert [fc.lx_chunks(c) for c in (1, 8, 9, 16, 17, 64)] == [1, 1, 2, 2, 3, 8] and fc.lx_stride(6) == 27 and fc.lx_stride(17) == 75
+    ohem = [c for c in fc.CASES["loss"] if c[1] == "ohem" and fc.loss_npix(c) == 36000][0]
+    assert fc.loss_grids(ohem) == (141, 141, 128)
+    assert [fc.clip_grid(n) for n in (1, 4099, 2097152, 2097159)] == [1, 4, 2048, 2048] and fc.clip_depth(2097152) == 4 and fc.clip_depth(2097159) == 9
+    assert fc.clip_depth(3) == 1 and fc.clip_depth(4096) == 4
+    assert [fc.step_grid(n) for n in (3, 4099, 8388608, 8388615)] == [1, 4, 8192, 8192] and fc.step_body_tail(4099) == (1024, 3) and fc.step_body_tail(3) == (0, 3)
+    assert [fc.areas_grid(n) for n in (1, 4096, 4097, 1024 * 4096, 1024 * 4096 + 1)] == [1, 1, 2, 1024, 1024]
+
+
+def test_loss_and_step_input_conditions_hold_in_float64():
+    """what the exact comparisons of the GPU tests rest on, from the float64 references alone: no non-ignored pixel of an OHEM case other
+    than the k-th (the tie and constant cases: other than its exact ties) within 1e-5 of the threshold; with range_mult = 0 every element
+    outside the ranges of a step case moves by more than 4 ulp of itself"""
+    from tests import loss_step_reference as R
+    from tests.test_gpu_ohem import assert_input_margin, INF
+    branches = set()
+    for c in fc.CASES["loss"]:
+        if c[1] != "ohem":
+            continue
+        x = R.loss_inputs(c)
+        for z in (x["la"], x["lb"]):
+            r = R.ohem_reference(c, z, x["labels"])
+            assert_input_margin(r, tied_with_kth=r["tied"])
+            nv = int(r["valid"].sum())
+            branches.add("keep-all" if r["threshold"] == INF else "thresh" if r["threshold"] == c[13] else "k-th")
+            if c[9] == "grid":
+                pv = r["p"][r["valid"]]
+                assert int((pv == r["threshold"]).sum()) >= 3 or r["threshold"] == c[13], c[0]
+    assert branches == {"keep-all", "thresh", "k-th"}
+    for c in fc.CASES["step"]:
+        if c[1] != "clip":
+            worst, outside = R.step_condition(c)
+            assert worst > 1.0, "%s: an element outside the ranges moves by %.3g x 4 ulp" % (c[0], worst)
+            assert outside == c[2] - len(fc.step_selected(c[3], c[2]))
+
+
 def test_mha_sweep_covers_what_it_was_written_for():
     """every length of the list without dropout; dropout at p in {0.1, 0.5} on both sides of the LDS threshold of the VALU backward and at the
     lengths the sweep was asked to hold; ordinary inputs under dropout (no probability underflows there: kept == read back > 0)"""
