@@ -8,32 +8,32 @@ import ctypes
 import keyword
 import os
 import re
+from collections import namedtuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip.h")
 # EMRT_HIP_LIB: a differently built copy of the same library (developer experiments: tools/exp builds one with -DEMRT_8P_PROBES)
 LIB_PATH = os.environ.get("EMRT_HIP_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip.so")
 
-# The second library (include/emrt_hip_augment.h: vertical flip and colour distortion).  The ABI of emrt_hip.h is frozen, so its entry points
-# and its descriptor stay out of parse_header() / parse_structs() / struct() above and get a binding of their own: augment_lib(), augment_struct().
-AUG_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_augment.h")
-AUG_LIB_PATH = os.environ.get("EMRT_HIP_AUGMENT_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_augment.so")
+# The libraries beside libemrt_hip.so.  The ABI of emrt_hip.h is frozen, and so is each side header once it has shipped, so every later feature got
+# a library and a header of its own: bound from that header by side_lib(name), each loaded only when something asks for it.
+# slot: the module attribute that holds the loaded library (below); env: overrides the path; prefix: of <prefix>_version / _last_error
+SideLibrary = namedtuple("SideLibrary", "header path slot env prefix what")
 
-# The third library (include/emrt_hip_sampler.h: the label index and the class-aware redraw of the scene sampler), for the same reason: sampler_lib().
-SMP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_sampler.h")
-SMP_LIB_PATH = os.environ.get("EMRT_HIP_SAMPLER_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_sampler.so")
 
-# The fourth library (include/emrt_hip_loss.h: cross entropy + Dice in one pass), for the same reason: loss_lib().
-LOSS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_loss.h")
-LOSS_LIB_PATH = os.environ.get("EMRT_HIP_LOSS_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_loss.so")
+def _side(stem, slot, env, prefix, what):
+    return SideLibrary(os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_%s.h" % stem),
+                       os.environ.get(env) or os.path.join(_HERE, "csrc", "libemrt_hip_%s.so" % stem), slot, env, prefix, what)
 
-# The fifth library (include/emrt_hip_tta.h: flip and rotation test-time augmentation of whole-scene inference), for the same reason: tta_lib().
-TTA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_tta.h")
-TTA_LIB_PATH = os.environ.get("EMRT_HIP_TTA_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_tta.so")
 
-# The sixth library (include/emrt_hip_mstta.h: scale as one more axis of that window-level augmentation), for the same reason: mst_lib().
-MST_HEADER = os.path.join(os.path.dirname(_HERE), "include", "emrt_hip_mstta.h")
-MST_LIB_PATH = os.environ.get("EMRT_HIP_MSTTA_LIB") or os.path.join(_HERE, "csrc", "libemrt_hip_mstta.so")
+SIDE_LIBRARIES = {
+    "augment": _side("augment", "_AUG_LIB", "EMRT_HIP_AUGMENT_LIB", "emrt_aug", "the device augmentation"),      # vertical flip and colour distortion
+    "sampler": _side("sampler", "_SMP_LIB", "EMRT_HIP_SAMPLER_LIB", "emrt_smp", "the class-aware scene sampler"),      # DATA.SCENE_SAMPLING.MODE "class"
+    "loss": _side("loss", "_LOSS_LIB", "EMRT_HIP_LOSS_LIB", "emrt_lx", "the Dice + cross-entropy loss"),      # TRAIN.LOSS "DiceCrossEntropyLoss"
+    "tta": _side("tta", "_TTA_LIB", "EMRT_HIP_TTA_LIB", "emrt_tta", "the test-time augmentation of whole-scene inference"),      # tta other than "none"
+    "mstta": _side("mstta", "_MST_LIB", "EMRT_HIP_MSTTA_LIB", "emrt_mst", "the multi-scale test-time augmentation of whole-scene inference"),      # tta_scales
+}
+AUG_HEADER, SMP_HEADER, LOSS_HEADER, TTA_HEADER, MST_HEADER = (row.header for row in SIDE_LIBRARIES.values())      # (the stand-ins of the tests parse them)
 
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
@@ -126,19 +126,44 @@ def parse_structs(path=HEADER):
     return structs
 
 
-_STRUCTS = {}      # name -> the one ctypes.Structure subclass of that header struct
+_STRUCTS = {}      # header path -> {name: the one ctypes.Structure subclass of that header struct}
+
+
+def _struct_of(header, name):
+    h = os.path.basename(header)
+    if header not in _STRUCTS:
+        _STRUCTS[header] = {
+            sname: type(sname, (ctypes.Structure,), {"_fields_": [(member_name(sname, m), _ctype_of(t) * n if n else _ctype_of(t)) for t, m, n in members],
+                                                     "__doc__": "%s of include/%s" % (sname, h)})
+            for sname, members in parse_structs(header).items()}
+    if name not in _STRUCTS[header]:
+        raise EmrtHipError("%s declares no struct %s" % (h, name))
+    return _STRUCTS[header][name]
 
 
 def struct(name):
     """The ctypes.Structure subclass of a descriptor struct of the header, generated once: (struct(n) * k) is the same array type in every
     module.  Pointer members are c_void_p (None, an int address or data_ptr() all assign)."""
-    if not _STRUCTS:
-        for sname, members in parse_structs().items():
-            fields = [(member_name(sname, m), _ctype_of(t) * n if n else _ctype_of(t)) for t, m, n in members]
-            _STRUCTS[sname] = type(sname, (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s of include/emrt_hip.h" % sname})
-    if name not in _STRUCTS:
-        raise EmrtHipError("emrt_hip.h declares no struct %s" % name)
-    return _STRUCTS[name]
+    return _struct_of(HEADER, name)
+
+
+def augment_struct(name):
+    """The same for a descriptor struct of include/emrt_hip_augment.h."""
+    return _struct_of(AUG_HEADER, name)
+
+
+def _bind(obj, dll, path, header):
+    """Gives obj a `_raw_<name>` ctypes function for every prototype of the header; -> the prototypes.  A symbol the library lacks raises."""
+    protos = parse_header(header)
+    for name, (ret, args) in protos.items():
+        try:
+            fn = getattr(dll, name)
+        except AttributeError:
+            raise EmrtHipError("%s does not export %s declared in %s" % (os.path.basename(path), name, os.path.basename(header)))
+        fn.argtypes = [_ctype_of(t) for t, _ in args]
+        fn.restype = ctypes.c_char_p if ret == "const char*" else (ctypes.c_size_t if ret == "size_t" else ctypes.c_int)
+        setattr(obj, "_raw_" + name, fn)
+    return protos
 
 
 class _Lib:
@@ -155,20 +180,7 @@ class _Lib:
         self._rec = None
         self.empty_pair_ms = 0.0
         self.replay_total_ms = 0.0
-        self.protos = parse_header()
-        for name, (ret, args) in self.protos.items():
-            try:
-                fn = getattr(self._dll, name)
-            except AttributeError:
-                raise EmrtHipError("libemrt_hip.so does not export %s declared in emrt_hip.h" % name)
-            fn.argtypes = [_ctype_of(t) for t, _ in args]
-            if ret == "const char*":
-                fn.restype = ctypes.c_char_p
-            elif ret == "size_t":
-                fn.restype = ctypes.c_size_t
-            else:
-                fn.restype = ctypes.c_int
-            setattr(self, "_raw_" + name, fn)
+        self.protos = _bind(self, self._dll, LIB_PATH, HEADER)
 
     def last_error(self):
         return self._raw_emrt_last_error().decode("utf-8", "replace")
@@ -280,47 +292,24 @@ def lib():
     return _LIB
 
 
-# ---- libemrt_hip_augment.so -------------------------------------------------------------------------------------------------------------------
-
-_AUG_STRUCTS = {}
-
-
-def augment_struct(name):
-    """The ctypes.Structure subclass of a descriptor struct of include/emrt_hip_augment.h, generated once (as struct() does for emrt_hip.h)."""
-    if not _AUG_STRUCTS:
-        for sname, members in parse_structs(AUG_HEADER).items():
-            fields = [(member_name(sname, m), _ctype_of(t) * n if n else _ctype_of(t)) for t, m, n in members]
-            _AUG_STRUCTS[sname] = type(sname, (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s of include/emrt_hip_augment.h" % sname})
-    if name not in _AUG_STRUCTS:
-        raise EmrtHipError("emrt_hip_augment.h declares no struct %s" % name)
-    return _AUG_STRUCTS[name]
-
+# ---- the side libraries ---------------------------------------------------------------------------------------------------------------------------
 
 class _ExtLib:
-    """A library beside libemrt_hip.so (augment_lib(), sampler_lib(), loss_lib(), tta_lib(), mst_lib()), bound from its own header: call / query / last_error as _Lib, with the
+    """A library beside libemrt_hip.so (a row of SIDE_LIBRARIES), bound from its own header: call / query / last_error as _Lib, with the
     library's own `<prefix>_last_error` string and its `<prefix>_version` checked to be 1.  No fallback: a missing library or symbol raises."""
 
     def __init__(self, path, header, prefix, what):
-        so, h = os.path.basename(path), os.path.basename(header)
         if not os.path.exists(path):
             raise EmrtHipError(
                 "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU/PyTorch fallback for %s)" % (path, what))
         import torch  # noqa: F401      (torch first, for the reason given in _Lib.__init__)
         self._dll = ctypes.CDLL(path)
-        self.protos = parse_header(header)
-        for name, (ret, args) in self.protos.items():
-            try:
-                fn = getattr(self._dll, name)
-            except AttributeError:
-                raise EmrtHipError("%s does not export %s declared in %s" % (so, name, h))
-            fn.argtypes = [_ctype_of(t) for t, _ in args]
-            fn.restype = ctypes.c_char_p if ret == "const char*" else (ctypes.c_size_t if ret == "size_t" else ctypes.c_int)
-            setattr(self, "_raw_" + name, fn)
+        self.protos = _bind(self, self._dll, path, header)
         self._last_error = getattr(self, "_raw_%s_last_error" % prefix)
         version = getattr(self, "_raw_%s_version" % prefix)()
         if version != 1:
-            raise EmrtHipError("%s has version %d, this binding expects 1" % (so, version))
+            raise EmrtHipError("%s has version %d, this binding expects 1" % (os.path.basename(path), version))
 
     def last_error(self):
         return self._last_error().decode("utf-8", "replace")
@@ -340,59 +329,32 @@ class _ExtLib:
         return getattr(self, "_raw_" + name)(*args)
 
 
-_AUG_LIB = None
+# The loaded side libraries, one module attribute per row (its `slot`): None until somebody asks for that library.  The tests put their stand-ins here.
+_AUG_LIB = _SMP_LIB = _LOSS_LIB = _TTA_LIB = _MST_LIB = None
+
+
+def side_lib(name):
+    row, slots = SIDE_LIBRARIES[name], globals()
+    if slots[row.slot] is None:
+        slots[row.slot] = _ExtLib(row.path, row.header, row.prefix, row.what)
+    return slots[row.slot]
 
 
 def augment_lib():
-    global _AUG_LIB
-    if _AUG_LIB is None:
-        _AUG_LIB = _ExtLib(AUG_LIB_PATH, AUG_HEADER, "emrt_aug", "the device augmentation")
-    return _AUG_LIB
-
-
-# ---- libemrt_hip_sampler.so (include/emrt_hip_sampler.h: class-aware tile origins; loaded only when DATA.SCENE_SAMPLING.MODE is "class") -------
-
-_SMP_LIB = None
+    return side_lib("augment")
 
 
 def sampler_lib():
-    global _SMP_LIB
-    if _SMP_LIB is None:
-        _SMP_LIB = _ExtLib(SMP_LIB_PATH, SMP_HEADER, "emrt_smp", "the class-aware scene sampler")
-    return _SMP_LIB
-
-
-# ---- libemrt_hip_loss.so (include/emrt_hip_loss.h: cross entropy + Dice; loaded only when TRAIN.LOSS is "DiceCrossEntropyLoss") ----------------
-
-_LOSS_LIB = None
+    return side_lib("sampler")
 
 
 def loss_lib():
-    global _LOSS_LIB
-    if _LOSS_LIB is None:
-        _LOSS_LIB = _ExtLib(LOSS_LIB_PATH, LOSS_HEADER, "emrt_lx", "the Dice + cross-entropy loss")
-    return _LOSS_LIB
-
-
-# ---- libemrt_hip_tta.so (include/emrt_hip_tta.h: window-level flips and rotations; loaded only when a scene is predicted with tta other than "none") ----
-
-_TTA_LIB = None
+    return side_lib("loss")
 
 
 def tta_lib():
-    global _TTA_LIB
-    if _TTA_LIB is None:
-        _TTA_LIB = _ExtLib(TTA_LIB_PATH, TTA_HEADER, "emrt_tta", "the test-time augmentation of whole-scene inference")
-    return _TTA_LIB
-
-
-# ---- libemrt_hip_mstta.so (include/emrt_hip_mstta.h: window-level scales, with or without flips and rotations; loaded only when a scene is predicted with tta_scales) ----
-
-_MST_LIB = None
+    return side_lib("tta")
 
 
 def mst_lib():
-    global _MST_LIB
-    if _MST_LIB is None:
-        _MST_LIB = _ExtLib(MST_LIB_PATH, MST_HEADER, "emrt_mst", "the multi-scale test-time augmentation of whole-scene inference")
-    return _MST_LIB
+    return side_lib("mstta")

@@ -1,10 +1,6 @@
-"""Builds emrt_amd/csrc/libemrt_hip.so and, beside it, emrt_amd/csrc/libemrt_hip_augment.so (csrc/augment_ext/*.hip: the entry points of
-include/emrt_hip_augment.h, kept out of the first library because its ABI is frozen) and emrt_amd/csrc/libemrt_hip_sampler.so
-(csrc/sampler_ext/*.hip: include/emrt_hip_sampler.h, for the same reason) with hipcc for gfx950, in-tree.  GROUPS is the table of the three;
-EXTRA_GROUPS holds the library added next, emrt_amd/csrc/libemrt_hip_loss.so (csrc/loss_ext/*.hip: include/emrt_hip_loss.h), and MORE_GROUPS the
-ones after it: emrt_amd/csrc/libemrt_hip_tta.so (csrc/tta_ext/*.hip: include/emrt_hip_tta.h).  all_groups() is those five rows, pinned by the tests
-of the fifth library; LATER_GROUPS holds what came after them, emrt_amd/csrc/libemrt_hip_mstta.so (csrc/mstta_ext/*.hip:
-include/emrt_hip_mstta.h), and every_group() is every row: what build(), _headers() and source_digest() walk.
+"""Builds emrt_amd/csrc/libemrt_hip.so and the libraries beside it with hipcc for gfx950, in-tree.  LIBRARIES is the one table of them, in
+build order: a row per library with its short name, its path, the directory of its sources and objects, the sources and the public header
+under include/ (each side library is a library of its own because the ABI of the headers before it is frozen).  library(name) looks a row up.
 
 What is rebuilt is decided by CONTENT: every object and the library carry a `<file>.inputs` stamp with the sha256 of the sources, headers,
 compiler path and flags they were built from; "reused" therefore means "built from exactly these inputs", on whatever machine.
@@ -13,6 +9,7 @@ hipcc cross-compiles without a GPU, so this runs in the build container as the "
 import os
 import subprocess
 import sys
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,34 +17,27 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libemrt_hip.so")
 SOURCES = ["conv.hip", "norm.hip", "msda.hip", "attn.hip", "spatial.hip", "loss.hip", "optim.hip", "elementwise.hip", "gconv.hip", "augment.hip", "scene.hip"]
 HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip.h")      # the public C-ABI: csrc/common.hpp includes it, so it is an input of every object
-AUG_DIR = os.path.join(CSRC, "augment_ext")
-AUG_LIB = os.path.join(CSRC, "libemrt_hip_augment.so")
-AUG_SOURCES = ["augment_ext.hip"]
-AUG_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_augment.h")      # includes emrt_hip.h; the sources include csrc/augment_map.hpp
-SMP_DIR = os.path.join(CSRC, "sampler_ext")
-SMP_LIB = os.path.join(CSRC, "libemrt_hip_sampler.so")
-SMP_SOURCES = ["sampler_ext.hip"]
-SMP_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_sampler.h")      # includes emrt_hip.h; the sources include csrc/philox.hpp
-# one row per library: (library, the directory of its sources and objects, sources, public header)
-GROUPS = [(LIB, CSRC, SOURCES, HEADER), (AUG_LIB, AUG_DIR, AUG_SOURCES, AUG_HEADER), (SMP_LIB, SMP_DIR, SMP_SOURCES, SMP_HEADER)]
-LOSS_DIR = os.path.join(CSRC, "loss_ext")
-LOSS_LIB = os.path.join(CSRC, "libemrt_hip_loss.so")
-LOSS_SOURCES = ["loss_ext.hip"]
-LOSS_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_loss.h")      # the sources include csrc/common.hpp and csrc/loss_pixel.hpp
-# the rows behind the first three, same form and same rules (GROUPS itself stays the table of the three libraries the sampler's tests pin)
-EXTRA_GROUPS = [(LOSS_LIB, LOSS_DIR, LOSS_SOURCES, LOSS_HEADER)]
-TTA_DIR = os.path.join(CSRC, "tta_ext")
-TTA_LIB = os.path.join(CSRC, "libemrt_hip_tta.so")
-TTA_SOURCES = ["tta_ext.hip"]
-TTA_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_tta.h")      # the sources include csrc/common.hpp and csrc/scene_norm.hpp
-# the rows behind those (EXTRA_GROUPS is pinned at one row by the loss library's tests, as GROUPS is at three)
-MORE_GROUPS = [(TTA_LIB, TTA_DIR, TTA_SOURCES, TTA_HEADER)]
-MST_DIR = os.path.join(CSRC, "mstta_ext")
-MST_LIB = os.path.join(CSRC, "libemrt_hip_mstta.so")
-MST_SOURCES = ["mstta_ext.hip"]
-MST_HEADER = os.path.join(os.path.dirname(HERE), "include", "emrt_hip_mstta.h")      # the sources include csrc/common.hpp and csrc/scene_norm.hpp
-# the rows behind all_groups() (MORE_GROUPS is pinned at one row and all_groups() at the three tables above by the tta library's tests)
-LATER_GROUPS = [(MST_LIB, MST_DIR, MST_SOURCES, MST_HEADER)]
+Library = namedtuple("Library", "name lib dir sources header")
+
+
+def _side(name):
+    """The row of a side library: csrc/<name>_ext/<name>_ext.hip -> csrc/libemrt_hip_<name>.so, declared in include/emrt_hip_<name>.h"""
+    return Library(name, os.path.join(CSRC, "libemrt_hip_%s.so" % name), os.path.join(CSRC, name + "_ext"), [name + "_ext.hip"],
+                   os.path.join(os.path.dirname(HERE), "include", "emrt_hip_%s.h" % name))
+
+
+# what build(), _headers() and source_digest() walk, in this order (the digest depends on it)
+LIBRARIES = [Library("main", LIB, CSRC, SOURCES, HEADER)] + [_side(n) for n in ("augment", "sampler", "loss", "tta", "mstta")]
+
+
+def library(name):
+    """The row of LIBRARIES with that short name."""
+    for row in LIBRARIES:
+        if row.name == name:
+            return row
+    raise KeyError("no library %r: LIBRARIES has %s" % (name, ", ".join(r.name for r in LIBRARIES)))
+
+
 # (the include path is relative to csrc/, where hipcc runs: the flags are hashed, and an absolute path would tie the digest to one checkout)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result", "-I../../include"]
 
@@ -87,37 +77,27 @@ def _fresh(target, digest):
         return False
 
 
-def all_groups():
-    """Every library's row: GROUPS, then EXTRA_GROUPS, then MORE_GROUPS."""
-    return GROUPS + EXTRA_GROUPS + MORE_GROUPS
-
-
-def every_group():
-    """Every library's row: all_groups(), then LATER_GROUPS."""
-    return all_groups() + LATER_GROUPS
-
-
 def _headers():
     """csrc/*.hpp and the public headers: inputs of every object of every library."""
-    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [g[3] for g in every_group()]
+    return [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".hpp")] + [row.header for row in LIBRARIES]
 
 
 def source_digest():
-    """Content hash of everything the libraries are built from: the sources of every row of every_group(), csrc/*.hpp, include/*.h, the compiler
+    """Content hash of everything the libraries are built from: the sources of every row of LIBRARIES, csrc/*.hpp, include/*.h, the compiler
     path and the flags."""
-    return _digest([os.path.join(d, s) for _, d, sources, _ in every_group() for s in sources] + _headers(), [_hipcc()] + FLAGS)
+    return _digest([os.path.join(row.dir, s) for row in LIBRARIES for s in row.sources] + _headers(), [_hipcc()] + FLAGS)
 
 
 LAST_BUILD = {"mode": None, "digest": None, "compiled": [], "linked": []}      # what the last build() call did: "compiled" | "linked" | "reused"
 
 
 def build(force=False, verbose=True):
-    """Builds every library of every_group(); -> the path of libemrt_hip.so (the others are AUG_LIB, SMP_LIB, LOSS_LIB, TTA_LIB and MST_LIB).  Only the objects whose inputs
-    changed are compiled, and only the libraries that hold one of them are linked again."""
+    """Builds every library of LIBRARIES; -> the path of libemrt_hip.so (the others are library(name).lib).  Only the objects whose inputs changed
+    are compiled, and only the libraries that hold one of them are linked again."""
     hipcc = _hipcc()
     hdrs = _headers()
-    objs, jobs = {g[0]: [] for g in every_group()}, []
-    for lib, d, sources, _ in every_group():
+    objs, jobs = {row.lib: [] for row in LIBRARIES}, []
+    for _, lib, d, sources, _ in LIBRARIES:
         for src in sources:
             s = os.path.join(d, src)
             o = os.path.join(d, src.replace(".hip", ".o"))
@@ -152,7 +132,7 @@ def build(force=False, verbose=True):
                     print("[emrt_amd.build] compiled", os.path.basename(done), flush=True)
     total = source_digest()
     linked = LAST_BUILD["linked"] = []
-    for lib, _, _, _ in every_group():
+    for lib in objs:
         if force or any(j[3] == lib for j in jobs) or not (os.path.exists(lib) and os.path.exists(_stamp(lib))):
             if os.path.exists(_stamp(lib)):
                 os.remove(_stamp(lib))

@@ -1,8 +1,10 @@
 // libemrt_hip_mstta.so: multi-scale test-time augmentation around the model call of whole-scene inference: scale as one more
 // axis of tta_ext's window-level augmentation.  The public interface, the resampling rule and the contract are described in
 // include/emrt_hip_mstta.h.  A library of its own because the ABIs of the other five headers are pinned; EMRT_REQUIRE / check_launch are
-// ../common.hpp's, the normalisation is ../scene_norm.hpp's.  The variant maps and the softmax are restated from tta_ext/tta_ext.hip, which
-// stays as it is.
+// ../common.hpp's, the normalisation is ../scene_norm.hpp's.  What this library has in common with tta_ext/tta_ext.hip is
+// ../window_variants.hpp's: the variant codes with their validation and decoding, the tiles of a launch's bounding box and the tile
+// constants.  The kernels are this file's own; the write-out loop of the crop and the softmax of the accumulation are the same text as in that
+// file, and a change to either is made in both.
 //
 // Two kernels:
 //   crop:       a block owns a 32 x 32 tile of one window.  It works out the taps and weights of the tile's rows and columns once (64 threads),
@@ -17,17 +19,13 @@
 //               owns a pixel: no atomics, the same bits in every run.
 #include "../common.hpp"
 #include "../scene_norm.hpp"
+#include "../window_variants.hpp"
 #include "../../../include/emrt_hip_mstta.h"
 
 thread_local char emrt::g_err[512] = {0};      // this library's own message (EMRT_REQUIRE / check_launch write it): emrt_mst_last_error
 
 namespace emrt {
 namespace {
-
-struct MstCodes {
-  int G;
-  int code[EMRT_MST_MAX_VARIANTS];
-};
 
 // n footprints of fh x fw native pixels at (y0, x0), each resampled to / from a window of ch x cw
 struct MstArgs {
@@ -36,23 +34,14 @@ struct MstArgs {
 };
 
 // -> null, or why the call is refused (codes: HOST int[G]; origins_yx: HOST int[n][2])
-const char* fill_args(MstArgs& a, MstCodes& k, const int* origins_yx, int n, const int* codes, int G, int C, int H, int W, int fh, int fw, int ch,
+const char* fill_args(MstArgs& a, VariantCodes& k, const int* origins_yx, int n, const int* codes, int G, int C, int H, int W, int fh, int fw, int ch,
                       int cw) {
-  if (G < 1 || G > EMRT_MST_MAX_VARIANTS) return "G must be 1..8";
-  if (n < 1 || (long long)n * G > EMRT_MST_MAX_IMAGES) return "n >= 1 and n * G <= 64";
+  if (const char* why = check_variant_counts(G, n)) return why;
   if (H < 1 || W < 1) return "H and W must be positive";
   const int e = EMRT_MST_MAX_EDGE, r = EMRT_MST_MAX_RATIO;
   if (fh < 1 || fh > e || fw < 1 || fw > e || ch < 1 || ch > e || cw < 1 || cw > e) return "fh, fw, ch, cw must be 1..2048";
   if (fh > r * ch || ch > r * fh || fw > r * cw || cw > r * fw) return "a footprint and its window differ by more than 4 times";
-  k.G = G;
-  for (int g = 0; g < EMRT_MST_MAX_VARIANTS; ++g) k.code[g] = 0;
-  for (int g = 0; g < G; ++g) {
-    if (codes[g] < 0 || codes[g] > 7) return "codes must be 0..7";
-    for (int h = 0; h < g; ++h)
-      if (codes[h] == codes[g]) return "a code is repeated";
-    if ((codes[g] & 4) && ch != cw) return "a transposing code (4..7) needs ch == cw";
-    k.code[g] = codes[g];
-  }
+  if (const char* why = fill_variant_codes(k, codes, G, ch, cw)) return why;
   a.n = n; a.C = C; a.H = H; a.W = W; a.fh = fh; a.fw = fw; a.ch = ch; a.cw = cw;
   for (int j = 0; j < EMRT_MST_MAX_IMAGES; ++j) a.y0[j] = a.x0[j] = 0;
   for (int j = 0; j < n; ++j) {
@@ -84,11 +73,7 @@ __device__ __forceinline__ float mst_blend(float a, float b, float c, float d, f
 }
 
 // ---- crop ----------------------------------------------------------------------------------------------------------------------------------
-constexpr int CT = 32;                       // tile edge
-constexpr int CROW = CT + 1;                 // words per LDS row: a column walk (33 words apart) touches every bank once
-constexpr int CPLANE = CT * CROW + 11;       // words per channel plane; + 11 spreads the three channels of a pixel
-
-__global__ __launch_bounds__(256) void mst_crop_windows_kernel(const unsigned char* __restrict__ scene, float* __restrict__ batch, MstArgs a, MstCodes k,
+__global__ __launch_bounds__(256) void mst_crop_windows_kernel(const unsigned char* __restrict__ scene, float* __restrict__ batch, MstArgs a, VariantCodes k,
                                                                SceneNorm nm) {
   __shared__ float s[3 * CPLANE];
   __shared__ int t0[2 * CT], t1[2 * CT];      // taps of the tile's rows [0, CT) and columns [CT, 2 CT), in the footprint
@@ -125,8 +110,8 @@ __global__ __launch_bounds__(256) void mst_crop_windows_kernel(const unsigned ch
   __syncthreads();
   const long long plane = (long long)a.ch * a.cw;
   for (int g = 0; g < k.G; ++g) {
-    const int code = k.code[g];
-    const bool t = (code & 4) != 0, fv = (code & 2) != 0, fh = (code & 1) != 0;
+    const Variant m = decode_variant(k.code[g]);
+    const bool t = m.t, fv = m.fv, fh = m.fh;
     float* vb = batch + (long long)(j * k.G + g) * 3 * plane;
     for (int i = threadIdx.x; i < th * tw; i += 256) {
       int r, px;      // the lanes run along the variant's x: the tile's columns, or its rows when the variant is transposed
@@ -142,16 +127,9 @@ __global__ __launch_bounds__(256) void mst_crop_windows_kernel(const unsigned ch
 }
 
 // ---- accumulate ----------------------------------------------------------------------------------------------------------------------------
-constexpr int AT = 16;                       // tile edge: 256 pixels, one per thread
-constexpr int ACH = 8;                       // classes per chunk
-
-struct MstTiles {
-  int x0, y0, nx;                            // the tiles of one launch: origin (a multiple of AT) and tiles per row of the footprints' bounding box
-};
-
 template <bool SMALL>
 __global__ __launch_bounds__(256) void mst_window_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ final,
-                                                                    float* __restrict__ count, MstArgs a, MstCodes k, MstTiles tl) {
+                                                                    float* __restrict__ count, MstArgs a, VariantCodes k, BoxTiles tl) {
   const int by = blockIdx.x / tl.nx, bx = blockIdx.x - by * tl.nx;
   const int tx0 = tl.x0 + bx * AT, ty0 = tl.y0 + by * AT;
   const int x = tx0 + (threadIdx.x & (AT - 1)), y = ty0 + threadIdx.x / AT;          // the pixel this thread owns
@@ -175,8 +153,8 @@ __global__ __launch_bounds__(256) void mst_window_accumulate_kernel(const float*
     mst_tap(yy, a.fh, a.ch, cy0, cy1, wy);
     mst_tap(xx, a.fw, a.cw, cx0, cx1, wx);
     for (int g = 0; g < k.G; ++g) {
-      const int code = k.code[g];
-      const bool t = (code & 4) != 0, fv = (code & 2) != 0, fh = (code & 1) != 0;
+      const Variant m = decode_variant(k.code[g]);
+      const bool t = m.t, fv = m.fv, fh = m.fh;
       const float* lp = logits + (long long)(j * k.G + g) * a.C * plane;
       // the inverse of the variant: window pixel (cy, cx) is the variant's (my, mx), or (mx, my) when it is transposed (ch == cw)
       const int my0 = fv ? a.ch - 1 - cy0 : cy0, my1 = fv ? a.ch - 1 - cy1 : cy1;
@@ -253,7 +231,7 @@ extern "C" int emrt_mst_crop_windows_u8(const unsigned char* scene, float* batch
                                         double stdinv1, double stdinv2, void* stream) {
   EMRT_REQUIRE(scene && batch && origins_yx && codes, "null pointer");
   MstArgs a;
-  MstCodes k;
+  VariantCodes k;
   const char* why = fill_args(a, k, origins_yx, n, codes, G, 3, H, W, fh, fw, ch, cw);
   EMRT_REQUIRE(!why, why);
   const SceneNorm nm = {{mean0, mean1, mean2}, {stdinv0, stdinv1, stdinv2}};
@@ -267,20 +245,12 @@ extern "C" int emrt_mst_window_accumulate(const float* logits, float* final, flo
   EMRT_REQUIRE(logits && final && count && origins_yx && codes, "null pointer");
   EMRT_REQUIRE(C >= 1 && C <= EMRT_MST_MAX_CLASSES, "C must be 1..256");
   MstArgs a;
-  MstCodes k;
+  VariantCodes k;
   const char* why = fill_args(a, k, origins_yx, n, codes, G, C, H, W, fh, fw, ch, cw);
   EMRT_REQUIRE(!why, why);
   // the tiles of the footprints' bounding box: the rest of the scene is not touched by this launch
-  int x_lo = a.x0[0], x_hi = a.x0[0], y_lo = a.y0[0], y_hi = a.y0[0];
-  for (int j = 1; j < n; ++j) {
-    x_lo = a.x0[j] < x_lo ? a.x0[j] : x_lo; x_hi = a.x0[j] > x_hi ? a.x0[j] : x_hi;
-    y_lo = a.y0[j] < y_lo ? a.y0[j] : y_lo; y_hi = a.y0[j] > y_hi ? a.y0[j] : y_hi;
-  }
-  MstTiles tl;
-  tl.x0 = x_lo / AT * AT;
-  tl.y0 = y_lo / AT * AT;
-  tl.nx = (x_hi + fw - tl.x0 + AT - 1) / AT;
-  const long long tiles = (long long)tl.nx * ((y_hi + fh - tl.y0 + AT - 1) / AT);
+  BoxTiles tl;
+  const long long tiles = fill_box_tiles(tl, a.y0, a.x0, n, fh, fw);
   EMRT_REQUIRE(tiles < (1ll << 31), "the footprints span too many tiles");
   if (C <= ACH)
     hipLaunchKernelGGL(mst_window_accumulate_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, logits, final, count, a, k, tl);

@@ -1,6 +1,9 @@
 // libemrt_hip_tta.so: flip and rotation test-time augmentation around the model call of whole-scene inference.  The public
 // interface, the variant codes and the contract are described in include/emrt_hip_tta.h.  A library of its own because the ABIs of the other four
 // headers are pinned; WindowArgs / fill_windows / EMRT_REQUIRE are ../common.hpp's, the normalisation is ../scene_norm.hpp's (scene.hip's text).
+// What this library has in common with mstta_ext/mstta_ext.hip is ../window_variants.hpp's: the variant codes with their validation and decoding,
+// the tiles of a launch's bounding box and the tile constants.  The kernels are this file's own; the write-out loop of the crop and the softmax
+// of the accumulation are the same text as in that file, and a change to either is made in both.
 //
 // Two kernels:
 //   crop:       a block owns a 32 x 32 tile of one window.  It reads the tile's bytes row by row (each row one contiguous run of at most 96 bytes),
@@ -16,6 +19,7 @@
 //               added to the value `final` held one after the other by the one thread that owns the pixel: no atomics, the same bits in every run.
 #include "../common.hpp"
 #include "../scene_norm.hpp"
+#include "../window_variants.hpp"
 #include "../../../include/emrt_hip_tta.h"
 
 thread_local char emrt::g_err[512] = {0};      // this library's own message (EMRT_REQUIRE / check_launch write it): emrt_tta_last_error
@@ -23,33 +27,14 @@ thread_local char emrt::g_err[512] = {0};      // this library's own message (EM
 namespace emrt {
 namespace {
 
-struct TtaCodes {
-  int G;
-  int code[EMRT_TTA_MAX_VARIANTS];
-};
-
 // -> null, or why the codes (HOST int[G]) are refused for n windows of ch x cw
-const char* fill_codes(TtaCodes& k, const int* codes, int G, int n, int ch, int cw) {
-  if (G < 1 || G > EMRT_TTA_MAX_VARIANTS) return "G must be 1..8";
-  if (n < 1 || (long long)n * G > EMRT_TTA_MAX_IMAGES) return "n >= 1 and n * G <= 64";
-  k.G = G;
-  for (int g = 0; g < EMRT_TTA_MAX_VARIANTS; ++g) k.code[g] = 0;
-  for (int g = 0; g < G; ++g) {
-    if (codes[g] < 0 || codes[g] > 7) return "codes must be 0..7";
-    for (int h = 0; h < g; ++h)
-      if (codes[h] == codes[g]) return "a code is repeated";
-    if ((codes[g] & 4) && ch != cw) return "a transposing code (4..7) needs ch == cw";
-    k.code[g] = codes[g];
-  }
-  return nullptr;
+const char* fill_codes(VariantCodes& k, const int* codes, int G, int n, int ch, int cw) {
+  const char* why = check_variant_counts(G, n);
+  return why ? why : fill_variant_codes(k, codes, G, ch, cw);
 }
 
 // ---- crop ----------------------------------------------------------------------------------------------------------------------------------
-constexpr int CT = 32;                       // tile edge
-constexpr int CROW = CT + 1;                 // words per LDS row: a column walk (33 words apart) touches every bank once
-constexpr int CPLANE = CT * CROW + 11;       // words per channel plane; + 11 spreads the three channels of a pixel, stored by neighbouring lanes
-
-__global__ __launch_bounds__(256) void tta_crop_windows_kernel(const unsigned char* __restrict__ scene, float* __restrict__ batch, WindowArgs a, TtaCodes k,
+__global__ __launch_bounds__(256) void tta_crop_windows_kernel(const unsigned char* __restrict__ scene, float* __restrict__ batch, WindowArgs a, VariantCodes k,
                                                                SceneNorm nm) {
   __shared__ float s[3 * CPLANE];
   const int tiles_x = (a.cw + CT - 1) / CT;
@@ -67,8 +52,8 @@ __global__ __launch_bounds__(256) void tta_crop_windows_kernel(const unsigned ch
   __syncthreads();
   const long long plane = (long long)a.ch * a.cw;
   for (int g = 0; g < k.G; ++g) {
-    const int code = k.code[g];
-    const bool t = (code & 4) != 0, fv = (code & 2) != 0, fh = (code & 1) != 0;
+    const Variant m = decode_variant(k.code[g]);
+    const bool t = m.t, fv = m.fv, fh = m.fh;
     float* vb = batch + (long long)(j * k.G + g) * 3 * plane;
     for (int i = threadIdx.x; i < th * tw; i += 256) {
       int r, px;      // the lanes run along the variant's x: the tile's columns, or its rows when the variant is transposed
@@ -84,17 +69,11 @@ __global__ __launch_bounds__(256) void tta_crop_windows_kernel(const unsigned ch
 }
 
 // ---- accumulate ----------------------------------------------------------------------------------------------------------------------------
-constexpr int AT = 16;                       // tile edge: 256 pixels, one per thread
-constexpr int AROW = AT + 1;
-constexpr int ACH = 8;                       // classes per chunk
-
-struct TtaTiles {
-  int x0, y0, nx;                            // the tiles of one launch: origin (a multiple of AT) and tiles per row of the windows' bounding box
-};
+constexpr int AROW = AT + 1;                 // words per row of the LDS stage of a transposing code
 
 template <bool SMALL>
 __global__ __launch_bounds__(256) void tta_window_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ final,
-                                                                    float* __restrict__ count, WindowArgs a, TtaCodes k, TtaTiles tl) {
+                                                                    float* __restrict__ count, WindowArgs a, VariantCodes k, BoxTiles tl) {
   __shared__ float s[ACH * AT * AROW];
   const int by = blockIdx.x / tl.nx, bx = blockIdx.x - by * tl.nx;
   const int tx0 = tl.x0 + bx * AT, ty0 = tl.y0 + by * AT;
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(256) void tta_window_accumulate_kernel(const float*
     const bool cov2 = inside2 && (unsigned)yy2 < (unsigned)a.ch && (unsigned)xx2 < (unsigned)a.cw;
     if (cov) hits += (float)k.G;
     for (int g = 0; g < k.G; ++g) {
-      const int code = k.code[g];
+      const int code = k.code[g];      // (decoded in place: through decode_variant() this kernel's registers are allocated differently)
       const bool t = (code & 4) != 0, fv = (code & 2) != 0, fh = (code & 1) != 0;
       const float* lp = logits + (long long)(j * k.G + g) * a.C * plane;
       // the inverse of the variant: window pixel (yy, xx) is the variant's (fy, fx), or (fx, fy) when it is transposed
@@ -209,7 +188,7 @@ extern "C" int emrt_tta_crop_windows_u8(const unsigned char* scene, float* batch
                                         double stdinv2, void* stream) {
   EMRT_REQUIRE(scene && batch && origins_yx && codes, "null pointer");
   EMRT_REQUIRE(H >= 1 && W >= 1 && ch >= 1 && cw >= 1, "H, W, ch, cw must be positive");
-  TtaCodes k;
+  VariantCodes k;
   const char* why = fill_codes(k, codes, G, n, ch, cw);
   EMRT_REQUIRE(!why, why);
   WindowArgs a;
@@ -226,22 +205,14 @@ extern "C" int emrt_tta_window_accumulate(const float* logits, float* final, flo
   EMRT_REQUIRE(logits && final && count && origins_yx && codes, "null pointer");
   EMRT_REQUIRE(C >= 1 && C <= EMRT_TTA_MAX_CLASSES, "C must be 1..256");
   EMRT_REQUIRE(H >= 1 && W >= 1 && ch >= 1 && cw >= 1, "H, W, ch, cw must be positive");
-  TtaCodes k;
+  VariantCodes k;
   const char* why = fill_codes(k, codes, G, n, ch, cw);
   EMRT_REQUIRE(!why, why);
   WindowArgs a;
   EMRT_REQUIRE(fill_windows(a, origins_yx, n, C, H, W, ch, cw) == 0, "1..64 windows inside the image");
   // the tiles of the windows' bounding box: the rest of the scene is not touched by this launch
-  int x_lo = a.x0[0], x_hi = a.x0[0], y_lo = a.y0[0], y_hi = a.y0[0];
-  for (int j = 1; j < n; ++j) {
-    x_lo = a.x0[j] < x_lo ? a.x0[j] : x_lo; x_hi = a.x0[j] > x_hi ? a.x0[j] : x_hi;
-    y_lo = a.y0[j] < y_lo ? a.y0[j] : y_lo; y_hi = a.y0[j] > y_hi ? a.y0[j] : y_hi;
-  }
-  TtaTiles tl;
-  tl.x0 = x_lo / AT * AT;
-  tl.y0 = y_lo / AT * AT;
-  tl.nx = (x_hi + cw - tl.x0 + AT - 1) / AT;
-  const long long tiles = (long long)tl.nx * ((y_hi + ch - tl.y0 + AT - 1) / AT);
+  BoxTiles tl;
+  const long long tiles = fill_box_tiles(tl, a.y0, a.x0, n, ch, cw);
   EMRT_REQUIRE(tiles < (1ll << 31), "the windows span too many tiles");
   if (C <= ACH)
     hipLaunchKernelGGL(tta_window_accumulate_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, logits, final, count, a, k, tl);

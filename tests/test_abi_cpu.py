@@ -270,6 +270,27 @@ def test_dtype_refusals_name_the_entry_point(built, name):
         assert "dtype must be" not in text and "inference-only" not in text, text
 
 
+def test_the_one_table_of_libraries(built):
+    """build_ext.LIBRARIES is the six libraries in build order, _lib.SIDE_LIBRARIES the five beside the first under the same names; every library
+    and its stamp exist, every stamp is the one digest, and every public header is an input of every object."""
+    from emrt_amd import _lib, build_ext
+    assert [os.path.basename(row.lib) for row in build_ext.LIBRARIES] == [
+        "libemrt_hip.so", "libemrt_hip_augment.so", "libemrt_hip_sampler.so", "libemrt_hip_loss.so", "libemrt_hip_tta.so", "libemrt_hip_mstta.so"]
+    assert build_ext.LIBRARIES[0][1:] == (build_ext.LIB, build_ext.CSRC, build_ext.SOURCES, build_ext.HEADER) and _lib.HEADER == build_ext.HEADER
+    assert [row.name for row in build_ext.LIBRARIES[1:]] == list(_lib.SIDE_LIBRARIES)
+    digest = build_ext.source_digest()
+    for row in build_ext.LIBRARIES:
+        assert build_ext.library(row.name) is row and all(os.path.exists(os.path.join(row.dir, s)) for s in row.sources)
+        with open(row.lib + ".inputs") as f:
+            assert os.path.exists(row.lib) and f.read().strip() == digest, row.lib
+        assert row.header in build_ext._headers()
+    for name, side in _lib.SIDE_LIBRARIES.items():
+        assert (side.header, side.path) == (build_ext.library(name).header, os.environ.get(side.env) or build_ext.library(name).lib)
+        assert hasattr(_lib, side.slot) and [s.slot for s in _lib.SIDE_LIBRARIES.values()].count(side.slot) == 1
+    with pytest.raises(KeyError):
+        build_ext.library("nope")
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from emrt_amd import _lib
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

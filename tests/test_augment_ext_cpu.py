@@ -380,7 +380,7 @@ def test_replay_aug_has_the_promised_distribution():
 def built():
     from emrt_amd import build_ext
     build_ext.build(verbose=False)
-    return build_ext.AUG_LIB
+    return build_ext.library("augment").lib
 
 
 def test_second_library_exports_exactly_what_its_header_declares(built):
@@ -442,7 +442,7 @@ def test_loader_of_the_second_library(built, monkeypatch, tmp_path):
     A = _lib.augment_lib()
     assert A.query("emrt_aug_version") == 1 and A.query("emrt_aug_workspace_bytes", 17) == 17 * 8
     assert A.query("emrt_aug_workspace_bytes", 0) == 0 and "B must be positive" in A.last_error()
-    monkeypatch.setattr(_lib, "AUG_LIB_PATH", str(tmp_path / "nope.so"))
+    monkeypatch.setitem(_lib.SIDE_LIBRARIES, "augment", _lib.SIDE_LIBRARIES["augment"]._replace(path=str(tmp_path / "nope.so")))
     monkeypatch.setattr(_lib, "_AUG_LIB", None)
     with pytest.raises(_lib.EmrtHipError, match="not found"):
         _lib.augment_lib()

@@ -302,14 +302,12 @@ def test_third_library_exports_exactly_what_its_header_declares(built):
     from emrt_amd import _lib
     protos = _lib.parse_header(_lib.SMP_HEADER)
     assert sorted(protos) == ["emrt_smp_class_redraw", "emrt_smp_last_error", "emrt_smp_row_counts", "emrt_smp_version"]
-    out = subprocess.run(["nm", "-D", "--defined-only", built.SMP_LIB], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", built.library("sampler").lib], capture_output=True, text=True, check=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     assert {n for n in exported if n.startswith("emrt_")} == set(protos)
     assert not set(protos) & (set(_lib.parse_header()) | set(_lib.parse_header(_lib.AUG_HEADER)))          # nothing is declared twice
     assert len(_lib.parse_header()) == 109 and len(_lib.parse_header(_lib.AUG_HEADER)) == 6                # the other two headers are untouched
     assert [len(a) for _, a in (protos["emrt_smp_row_counts"], protos["emrt_smp_class_redraw"])] == [12, 22]
-    assert [os.path.basename(g[0]) for g in built.GROUPS] == ["libemrt_hip.so", "libemrt_hip_augment.so", "libemrt_hip_sampler.so"]
-    assert all(os.path.exists(g[0]) and os.path.exists(g[0] + ".inputs") for g in built.GROUPS)
     assert _lib.SMP_HEADER in built._headers() and os.path.join(built.CSRC, "philox.hpp") in built._headers()
 
 
@@ -318,7 +316,7 @@ def test_loader_of_the_third_library(built, monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_SMP_LIB", None)
     S = _lib.sampler_lib()
     assert S.query("emrt_smp_version") == 1 and S is _lib.sampler_lib() and sorted(S.protos) == sorted(_lib.parse_header(_lib.SMP_HEADER))
-    monkeypatch.setattr(_lib, "SMP_LIB_PATH", str(tmp_path / "nope.so"))
+    monkeypatch.setitem(_lib.SIDE_LIBRARIES, "sampler", _lib.SIDE_LIBRARIES["sampler"]._replace(path=str(tmp_path / "nope.so")))
     monkeypatch.setattr(_lib, "_SMP_LIB", None)
     with pytest.raises(_lib.EmrtHipError, match="not found"):
         _lib.sampler_lib()
@@ -336,7 +334,7 @@ def test_philox_is_written_once():
 def test_build_rebuilds_only_the_third_library_when_its_source_changes(built):
     """Content stamps (tests/test_abi_cpu.py) with the third group: a touched source is "reused"; one more byte in it compiles that one object
     and links that one library, and the recorded digest follows.  The source is put back and rebuilt before the test ends."""
-    src = os.path.join(built.SMP_DIR, built.SMP_SOURCES[0])
+    src = os.path.join(built.library("sampler").dir, built.library("sampler").sources[0])
     assert os.path.dirname(src).endswith("sampler_ext")
     os.utime(src, None)
     built.build(verbose=False)
@@ -349,8 +347,8 @@ def test_build_rebuilds_only_the_third_library_when_its_source_changes(built):
         assert built.source_digest() != before
         built.build(verbose=False)
         assert built.LAST_BUILD["compiled"] == ["sampler_ext.hip"] and built.LAST_BUILD["linked"] == ["libemrt_hip_sampler.so"]
-        for g in built.GROUPS:
-            with open(g[0] + ".inputs") as f:
+        for row in built.LIBRARIES:
+            with open(row.lib + ".inputs") as f:
                 assert f.read().strip() == built.source_digest() == built.LAST_BUILD["digest"]
     finally:
         with open(src, "wb") as f:

@@ -229,18 +229,13 @@ def test_fourth_library_exports_exactly_what_its_header_declares(built):
     from emrt_amd import _lib
     protos = _lib.parse_header(_lib.LOSS_HEADER)
     assert sorted(protos) == sorted(LX + ("emrt_lx_dice_ce_workspace_bytes", "emrt_lx_last_error", "emrt_lx_version"))
-    out = subprocess.run(["nm", "-D", "--defined-only", built.LOSS_LIB], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", built.library("loss").lib], capture_output=True, text=True, check=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     assert {n for n in exported if n.startswith("emrt_")} == set(protos)
     others = [_lib.parse_header(), _lib.parse_header(_lib.AUG_HEADER), _lib.parse_header(_lib.SMP_HEADER)]
     assert [len(o) for o in others] == [109, 6, 4]                           # the three pinned headers are untouched
     assert not set(protos) & set().union(*others)                            # nothing is declared twice
     assert [len(protos[n][1]) for n in LX] == [15, 15, 21, 21]
-    assert [os.path.basename(g[0]) for g in built.GROUPS] == ["libemrt_hip.so", "libemrt_hip_augment.so", "libemrt_hip_sampler.so"]
-    assert [os.path.basename(g[0]) for g in built.EXTRA_GROUPS] == ["libemrt_hip_loss.so"]
-    assert os.path.exists(built.LOSS_LIB) and os.path.exists(built.LOSS_LIB + ".inputs")
-    with open(built.LOSS_LIB + ".inputs") as f:
-        assert f.read().strip() == built.source_digest()
     assert _lib.LOSS_HEADER in built._headers() and os.path.join(built.CSRC, "loss_pixel.hpp") in built._headers()
 
 
@@ -259,7 +254,7 @@ def test_loader_of_the_fourth_library(built, monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_LOSS_LIB", None)
     X = _lib.loss_lib()
     assert X.query("emrt_lx_version") == 1 and X is _lib.loss_lib() and sorted(X.protos) == sorted(_lib.parse_header(_lib.LOSS_HEADER))
-    monkeypatch.setattr(_lib, "LOSS_LIB_PATH", str(tmp_path / "nope.so"))
+    monkeypatch.setitem(_lib.SIDE_LIBRARIES, "loss", _lib.SIDE_LIBRARIES["loss"]._replace(path=str(tmp_path / "nope.so")))
     monkeypatch.setattr(_lib, "_LOSS_LIB", None)
     with pytest.raises(_lib.EmrtHipError, match="not found"):
         _lib.loss_lib()

@@ -87,7 +87,7 @@ def test_sixth_library_exports_exactly_what_its_header_declares(built):
     from emrt_amd import _lib
     protos = _lib.parse_header(_lib.MST_HEADER)
     assert sorted(protos) == sorted(ENTRY + ("emrt_mst_last_error", "emrt_mst_version"))
-    out = subprocess.run(["nm", "-D", "--defined-only", built.MST_LIB], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", built.library("mstta").lib], capture_output=True, text=True, check=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     assert {n for n in exported if n.startswith("emrt_")} == set(protos)
     assert [len(protos[n][1]) for n in ENTRY] == [19, 15]
@@ -96,19 +96,10 @@ def test_sixth_library_exports_exactly_what_its_header_declares(built):
               _lib.parse_header(_lib.TTA_HEADER)]
     assert [len(o) for o in others] == [109, 6, 4, 7, 4]                     # the five pinned headers are untouched
     assert not set(protos) & set().union(*others)
-    assert [os.path.basename(g[0]) for g in built.GROUPS] == ["libemrt_hip.so", "libemrt_hip_augment.so", "libemrt_hip_sampler.so"]
-    assert [os.path.basename(g[0]) for g in built.EXTRA_GROUPS] == ["libemrt_hip_loss.so"]
-    assert [os.path.basename(g[0]) for g in built.MORE_GROUPS] == ["libemrt_hip_tta.so"]
-    assert built.all_groups() == built.GROUPS + built.EXTRA_GROUPS + built.MORE_GROUPS
-    assert [os.path.basename(g[0]) for g in built.LATER_GROUPS] == ["libemrt_hip_mstta.so"]
-    assert built.every_group() == built.all_groups() + built.LATER_GROUPS
-    digest = built.source_digest()
-    for lib, _, _, header in built.every_group():                            # every library's stamp is the one digest
-        with open(lib + ".inputs") as f:
-            assert os.path.exists(lib) and f.read().strip() == digest, lib
-        assert header in built._headers()
-    text = open(os.path.join(built.MST_DIR, "mstta_ext.hip")).read()
-    assert "atomicAdd" not in text and "__hip_atomic" not in text and "scene_norm.hpp\"" in text and "float normalise_f32(" not in text
+    assert _lib.MST_HEADER in built._headers()
+    for path in (os.path.join(built.library("mstta").dir, "mstta_ext.hip"), os.path.join(built.CSRC, "window_variants.hpp")):
+        text = open(path).read()
+        assert "atomicAdd" not in text and "__hip_atomic" not in text and "scene_norm.hpp\"" in text and "float normalise_f32(" not in text, path
     assert "float normalise_f32(" in open(os.path.join(built.CSRC, "scene_norm.hpp")).read()
 
 
@@ -118,7 +109,7 @@ def test_loader_of_the_sixth_library(built, monkeypatch, tmp_path):
     T = _lib.mst_lib()
     assert T.query("emrt_mst_version") == 1 and T is _lib.mst_lib() and sorted(T.protos) == sorted(_lib.parse_header(_lib.MST_HEADER))
     assert T.last_error() == "" or isinstance(T.last_error(), str)
-    monkeypatch.setattr(_lib, "MST_LIB_PATH", str(tmp_path / "nope.so"))
+    monkeypatch.setitem(_lib.SIDE_LIBRARIES, "mstta", _lib.SIDE_LIBRARIES["mstta"]._replace(path=str(tmp_path / "nope.so")))
     monkeypatch.setattr(_lib, "_MST_LIB", None)
     with pytest.raises(_lib.EmrtHipError, match="not found"):
         _lib.mst_lib()

@@ -74,31 +74,46 @@ def test_fifth_library_exports_exactly_what_its_header_declares(built):
     from emrt_amd import _lib
     protos = _lib.parse_header(_lib.TTA_HEADER)
     assert sorted(protos) == sorted(ENTRY + ("emrt_tta_last_error", "emrt_tta_version"))
-    out = subprocess.run(["nm", "-D", "--defined-only", built.TTA_LIB], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", built.library("tta").lib], capture_output=True, text=True, check=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
     assert {n for n in exported if n.startswith("emrt_")} == set(protos)
     others = [_lib.parse_header(), _lib.parse_header(_lib.AUG_HEADER), _lib.parse_header(_lib.SMP_HEADER), _lib.parse_header(_lib.LOSS_HEADER)]
     assert [len(o) for o in others] == [109, 6, 4, 7]                        # the four pinned headers are untouched
     assert not set(protos) & set().union(*others)
     assert [len(protos[n][1]) for n in ENTRY] == [17, 13]
-    assert [os.path.basename(g[0]) for g in built.GROUPS] == ["libemrt_hip.so", "libemrt_hip_augment.so", "libemrt_hip_sampler.so"]
-    assert [os.path.basename(g[0]) for g in built.EXTRA_GROUPS] == ["libemrt_hip_loss.so"]
-    assert [os.path.basename(g[0]) for g in built.MORE_GROUPS] == ["libemrt_hip_tta.so"]
-    assert built.all_groups() == built.GROUPS + built.EXTRA_GROUPS + built.MORE_GROUPS
-    assert os.path.exists(built.TTA_LIB) and os.path.exists(built.TTA_LIB + ".inputs")
-    with open(built.TTA_LIB + ".inputs") as f:
-        assert f.read().strip() == built.source_digest()
     assert _lib.TTA_HEADER in built._headers() and os.path.join(built.CSRC, "scene_norm.hpp") in built._headers()
 
 
 def test_normalisation_is_written_once():
-    """normalise_u8 lives in csrc/scene_norm.hpp; scene.hip and tta_ext.hip include it and neither restates it"""
+    """normalise_u8 lives in csrc/scene_norm.hpp; scene.hip, tta_ext.hip and window_variants.hpp include it and none restates it"""
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "emrt_amd", "csrc")
     assert "float normalise_u8(" in open(os.path.join(csrc, "scene_norm.hpp")).read()
-    for f in ("scene.hip", os.path.join("tta_ext", "tta_ext.hip")):
+    for f in ("scene.hip", os.path.join("tta_ext", "tta_ext.hip"), "window_variants.hpp"):
         text = open(os.path.join(csrc, f)).read()
-        assert "scene_norm.hpp\"" in text and "float normalise_u8(" not in text, f
-    assert "atomicAdd" not in open(os.path.join(csrc, "tta_ext", "tta_ext.hip")).read()
+        assert "scene_norm.hpp\"" in text and "float normalise_u8(" not in text and "float normalise_f32(" not in text, f
+        assert f == "scene.hip" or ("atomicAdd" not in text and "__hip_atomic" not in text), f
+
+
+def test_what_the_two_window_libraries_share_is_written_once(built):
+    """The variant codes with their refusals and decoding, the tile constants and the box tiles live in csrc/window_variants.hpp (an input of
+    every object); tta_ext.hip and mstta_ext.hip include it and neither restates any of it.  (The kernels' write-out loop and softmax are still
+    each file's own: the same text in both, see the header's comment.)"""
+    shared = os.path.join(built.CSRC, "window_variants.hpp")
+    assert shared in built._headers()
+    owned = ("struct VariantCodes", '"G must be 1..8"', '"n >= 1 and n * G <= 64"', '"codes must be 0..7"', '"a code is repeated"',
+             '"a transposing code (4..7) needs ch == cw"', "Variant decode_variant(", "struct BoxTiles", "long long fill_box_tiles(", "x_lo", "constexpr int CT =",
+             "constexpr int CROW =", "constexpr int CPLANE =", "constexpr int AT =", "constexpr int ACH =", "static_assert(EMRT_TTA_MAX_VARIANTS == EMRT_MST_MAX_VARIANTS")
+    text = open(shared).read()
+    for s in owned:
+        assert s in text, s
+    for name in ("tta", "mstta"):
+        row = built.library(name)
+        text = open(os.path.join(row.dir, row.sources[0])).read()
+        assert "../window_variants.hpp\"" in text, name
+        for s in owned + ("struct TtaCodes", "struct MstCodes", "struct TtaTiles", "struct MstTiles"):
+            assert s not in text, (name, s)
+        for s in ("VariantCodes k", "BoxTiles tl", "fill_box_tiles(", "check_variant_counts(", "fill_variant_codes(", "decode_variant("):
+            assert s in text, (name, s)
 
 
 def test_loader_of_the_fifth_library(built, monkeypatch, tmp_path):
@@ -106,7 +121,7 @@ def test_loader_of_the_fifth_library(built, monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_TTA_LIB", None)
     T = _lib.tta_lib()
     assert T.query("emrt_tta_version") == 1 and T is _lib.tta_lib() and sorted(T.protos) == sorted(_lib.parse_header(_lib.TTA_HEADER))
-    monkeypatch.setattr(_lib, "TTA_LIB_PATH", str(tmp_path / "nope.so"))
+    monkeypatch.setitem(_lib.SIDE_LIBRARIES, "tta", _lib.SIDE_LIBRARIES["tta"]._replace(path=str(tmp_path / "nope.so")))
     monkeypatch.setattr(_lib, "_TTA_LIB", None)
     with pytest.raises(_lib.EmrtHipError, match="not found"):
         _lib.tta_lib()
