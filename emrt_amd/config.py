@@ -97,8 +97,11 @@ _DEFAULTS = {
              "DATA_PATH": "/home/ssd3/wutianyi/datasets/pascal_context", "CROP_SIZE": (480, 480), "NUM_CLASSES": 60,
              "NUM_WORKERS": 0,
              # not in the reference's tree: RandomVerticalFlip and RandomDistort (hue off) after the Potsdam / Vaihingen chain's horizontal flip
-             # (transforms.get_transforms); the ranges are the reference's ADE20K values.  The defaults leave every chain as it was.
-             "AUGMENT": {"VFLIP_PROB": 0.0,
+             # (transforms.get_transforms); the ranges are the reference's ADE20K values.  ROT90_PROB: with that probability a sample is turned by
+             # 1, 2 or 3 quarter turns (uniform) between the two, RandomRot90; square DATA.CROP_SIZE only; 0.75 makes the four rotations equally
+             # likely and, with the chain's horizontal flip at 0.5, all eight elements of D4 (what --tta d4 averages over).
+             # The defaults leave every chain as it was.
+             "AUGMENT": {"VFLIP_PROB": 0.0, "ROT90_PROB": 0.0,
                          "DISTORT": {"ENABLE": False, "BRIGHTNESS_RANGE": 0.4, "CONTRAST_RANGE": 0.4, "SATURATION_RANGE": 0.4,
                                      "BRIGHTNESS_PROB": 0.5, "CONTRAST_PROB": 0.5, "SATURATION_PROB": 0.5}},
              # not in the reference's tree, --data scenes only (datasets.SceneSampler): where the tiles are cut.  "uniform": every origin equally

@@ -1,6 +1,7 @@
 // Philox4x32-10 and the draws made from its words, shared by every kernel that takes a random decision on the device: emrt_scene_draw
-// (augment.hip), emrt_aug_scene_draw (augment_ext/augment_ext.hip) and emrt_smp_class_redraw (sampler_ext/sampler_ext.hip).  One text, so the
-// three libraries cannot drift apart: a sample's blocks are numbered across all of them (include/emrt_hip_sampler.h lists who owns which).
+// (augment.hip), emrt_aug_scene_draw (augment_ext/augment_ext.hip), emrt_smp_class_redraw (sampler_ext/sampler_ext.hip) and emrt_rot_scene_batch
+// (rot_ext/rot_ext.hip).  One text, so the libraries cannot drift apart: a sample's blocks are numbered across all of them (include/emrt_hip_rot.h
+// lists who owns which).
 //
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's constants):
 //   key = (key64 low word, key64 high word);  counter = (step low word, step high word, rank * B + b, j),  j = the sample's j-th 128-bit block

@@ -2009,3 +2009,19 @@ def aug_tiles(src, samples, out_size, mean, stdinv, img_pad, label_pad, label_lu
            (ctypes.c_double * 3)(*[float(v) for v in stdinv]), (ctypes.c_float * 3)(*[float(v) for v in img_pad]), int(label_pad), lut,
            P(out), 3 * OH * OW, P(lab), P(ws), nws, c.stream)
     return out, lab
+
+
+def rot_batch(images, labels, turns):
+    """RandomRot90 as a post-pass over a finished batch, in place (csrc/rot_ext: emrt_rot_batch of libemrt_hip_rot.so): images fp32 [B, 3, n, n] and
+    labels int64 [B, n, n] (or None), contiguous; sample b is turned by turns[b] in 0..3 quarter turns counter-clockwise, np.rot90's.  A batch
+    whose turns are all 0 launches nothing."""
+    c = ctx()
+    B, n = int(images.shape[0]), int(images.shape[-1])
+    if images.dtype != torch.float32 or tuple(images.shape) != (B, 3, n, n) or not images.is_contiguous():
+        raise ValueError("rot_batch: images must be contiguous fp32 [B, 3, n, n], got %s %r" % (images.dtype, tuple(images.shape)))
+    if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B, n, n) or not labels.is_contiguous()):
+        raise ValueError("rot_batch: labels must be contiguous int64 %r, got %s %r" % ((B, n, n), labels.dtype, tuple(labels.shape)))
+    if len(turns) != B:
+        raise ValueError("rot_batch: %d turns for a batch of %d" % (len(turns), B))
+    _lib.rot_lib().call("emrt_rot_batch", P(images), P(labels), (ctypes.c_int * B)(*[int(k) for k in turns]), B, n, c.stream)
+    return images, labels

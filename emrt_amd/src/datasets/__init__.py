@@ -237,13 +237,23 @@ class DeviceTileLoader(TileLoader):
             with Image.open(image_path) as im:
                 W, H = im.size
             job.append((image_path, label_path, self.device_plan.plan(H, W)))
+        turns = None
+        if self.device_plan.rot is not None:      # RotPlan(base, turn): the base plans go the usual way, the turns follow the batch to _deliver
+            job, turns = [(ip, lp, p.base) for ip, lp, p in job], [p.turn for _, _, p in job]
         sizes = {self.device_plan.out_size(p.H, p.W) for _, _, p in job}
         if len(sizes) != 1:
             raise ValueError("DeviceTileLoader: the samples of a batch have different output sizes %s (np.stack needs one)" % sorted(sizes))
-        return job
+        return job if turns is None else (job, turns)
 
     def _batch(self, job):
-        """Decoded uint8 sources of one batch packed into one (pinned) buffer -> (buffer, [(img_off, lab_off, SamplePlan)], (OH, OW))."""
+        """Decoded uint8 sources of one batch packed into one (pinned) buffer -> (buffer, [(img_off, lab_off, SamplePlan)], (OH, OW)); with
+        RandomRot90 in the chain the batch's turns are a fourth element."""
+        if self.device_plan.rot is not None:
+            job, turns = job
+            return self._batch_of(job) + (turns,)
+        return self._batch_of(job)
+
+    def _batch_of(self, job):
         total = sum(4 * p.H * p.W for _, _, p in job)
         buf = torch.empty(total, dtype=torch.uint8, pin_memory=self.pin)
         a = buf.numpy()
@@ -262,14 +272,18 @@ class DeviceTileLoader(TileLoader):
 
     def _deliver(self, b):
         from ... import functional as F
-        buf, samples, out_size = b
         dp = self.device_plan
+        buf, samples, out_size = b[:3]
         dev = torch.device(self.device)
         with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
             src = buf.to(dev, non_blocking=True)
             if dp.extended:      # RandomVerticalFlip / RandomDistort in the chain: the second library's entry point
-                return F.aug_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut, distort=dp.distort is not None)
-            return F.augment_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut)
+                out = F.aug_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut, distort=dp.distort is not None)
+            else:
+                out = F.augment_tiles(src, samples, out_size, dp.mean, dp.stdinv, dp.img_pad, dp.label_pad, self.lut)
+            if dp.rot is not None:      # RandomRot90 in the chain: the finished batch is turned in place (libemrt_hip_rot.so), on the same stream
+                F.rot_batch(out[0], out[1], b[3])
+            return out
 
 
 # ---- whole scenes resident in device memory (train.py --data scenes) -----------------------------------------------------------
@@ -488,7 +502,11 @@ class SceneSampler:
     nothing else.  MODE "class" (needs num_classes): the constructor builds the bank's label index (SceneBank.class_index) and the class
     thresholds and uploads them, and fill() puts ONE launch of the third library, emrt_smp_class_redraw (include/emrt_hip_sampler.h), between the
     draw and the sample launch: it moves a share PROB of the windows onto a pixel of a drawn class and leaves every other decision alone.
-    sampler.class_table then holds (class, pixel share, sampling probability) per class; class_names, when given, name the log lines."""
+    sampler.class_table then holds (class, pixel share, sampling probability) per class; class_names, when given, name the log lines.
+
+    With RandomRot90 in the chain (DATA.AUGMENT.ROT90_PROB) fill() appends ONE launch of libemrt_hip_rot.so, emrt_rot_scene_batch, after the sample
+    launch on the same stream: it draws every sample's turn from Philox block 5 of the same key and counter and turns the batch in place;
+    sampler.turns (int32 [B]) then holds the batch's turns.  The other chains never touch that library."""
 
     def __init__(self, bank, transforms, batch_size, seed, rank=0, tile=None, sampling=None, num_classes=None, class_names=None):
         self.bank, self.plan = bank, DevicePlan(list(transforms))
@@ -543,6 +561,8 @@ class SceneSampler:
             self._probs = (ctypes.c_double * 3)(*[float(getattr(d, n + "_prob")) if d is not None else 0.0 for n in names])
             self._ws_bytes = 8 * self.batch_size          # = emrt_aug_workspace_bytes(B); the entry point checks it
             self._ws = torch.zeros(self.batch_size, dtype=torch.int64, device=bank.device)
+        self.rot_prob = float(dp.rot.prob) if dp.rot is not None else 0.0      # (DevicePlan has checked the square crop and the range)
+        self.turns = torch.zeros(self.batch_size, dtype=torch.int32, device=bank.device) if dp.rot is not None else None
         mode = "uniform" if sampling is None else sampling["MODE"]
         if mode not in ("uniform", "class"):
             raise ValueError("scenes: SCENE_SAMPLING.MODE must be 'uniform' or 'class', got %r" % (mode,))
@@ -617,6 +637,7 @@ class SceneSampler:
                    ctypes.cast(self._pad, ctypes.c_void_p), int(self.plan.label_pad),
                    None if self._lut is None else ctypes.cast(self._lut, ctypes.c_void_p), Fn.P(images), 3 * OH * OW, Fn.P(labels),
                    Fn.P(self._ws), self._ws_bytes, c.stream)
+            self._rot(Fn, c, key, images, labels)
             return
         L = Fn._L()
         L.call("emrt_scene_draw", Fn.P(c.step_counter), Fn.P(scenes_dev), Fn.P(cum_dev), ctypes.cast(scenes_host, ctypes.c_void_p),
@@ -628,6 +649,14 @@ class SceneSampler:
                Fn.P(self.draws), B, th, tw, OH, OW, ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._stdinv, ctypes.c_void_p),
                ctypes.cast(self._pad, ctypes.c_void_p), int(self.plan.label_pad),
                None if self._lut is None else ctypes.cast(self._lut, ctypes.c_void_p), Fn.P(images), 3 * OH * OW, Fn.P(labels), c.stream)
+        self._rot(Fn, c, key, images, labels)
+
+    def _rot(self, Fn, c, key, images, labels):
+        """emrt_rot_scene_batch on the batch the sample launch just wrote, on the same stream; nothing without RandomRot90 in the chain."""
+        if self.plan.rot is None:
+            return
+        _lib.rot_lib().call("emrt_rot_scene_batch", Fn.P(c.step_counter), key, self.rank, self.batch_size, self.crop[0], self.rot_prob, Fn.P(images),
+                            Fn.P(labels), Fn.P(self.turns), c.stream)
 
 
 class SceneVal(Dataset):

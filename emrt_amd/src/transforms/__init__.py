@@ -110,6 +110,32 @@ class RandomVerticalFlip:
         return (img,) if label is None else (img, label)
 
 
+class RandomRot90:
+    """Not in the reference: with probability `prob` the sample is turned by k quarter turns, k uniform over 1, 2, 3, counter-clockwise in array
+    coordinates -- np.rot90(img, k, axes=(0, 1)), image and label alike.  The only exact rotation: no resampling, no padding, no label
+    interpolation.  Square samples only (DATA.AUGMENT.ROT90_PROB)."""
+
+    def __init__(self, prob=0.75):
+        self.prob = prob
+
+    def draw(self):
+        """The turn k in 0..3: one Python `random.random()` and, only if that passes, one `random.randrange(3)` for k - 1 (the CPU chain and
+        DevicePlan.plan both draw it here)."""
+        if random.random() < self.prob:
+            return 1 + random.randrange(3)
+        return 0
+
+    def __call__(self, img, label=None):
+        k = self.draw()
+        if k:
+            if img.shape[0] != img.shape[1]:
+                raise ValueError("RandomRot90: a quarter turn needs a square sample, got %dx%d (h x w)" % (img.shape[0], img.shape[1]))
+            img = np.rot90(img, k, axes=(0, 1))
+            if label is not None:
+                label = np.rot90(label, k, axes=(0, 1))
+        return (img,) if label is None else (img, label)
+
+
 class RandomDistort:
     """transforms.py:588-681 with functional.py:76-96: brightness, contrast and saturation through PIL's ImageEnhance on the image truncated to
     uint8, in a shuffled order, each with its own probability and a factor drawn from [1 - range, 1 + range].  The label is untouched.
@@ -280,6 +306,9 @@ SamplePlan = namedtuple("SamplePlan", "H W h w off_y off_x flip")
 # ... of a chain with RandomVerticalFlip / RandomDistort (emrt_aug_tiles of the second library): SamplePlan's fields, the vertical flip, and the
 # applied colour ops [(op name, factor)] in application order.
 AugSamplePlan = namedtuple("AugSamplePlan", "H W h w off_y off_x flip vflip ops")
+# ... of a chain with RandomRot90: `base` is the SamplePlan / AugSamplePlan of the same chain without it, `turn` the quarter turns (0..3) of the
+# post-pass (emrt_rot_batch of libemrt_hip_rot.so) over the batch that the base plans produce.
+RotPlan = namedtuple("RotPlan", "base turn")
 
 
 class DevicePlan:
@@ -288,14 +317,18 @@ class DevicePlan:
     [Normalize] (LoveDA: output size = source size).  Any other op or order raises, naming the op: nothing is skipped or left to the CPU.
     The first chain may carry RandomVerticalFlip and / or RandomDistort, in that order, between RandomHorizontalFlip and Normalize
     (DATA.AUGMENT): `extended` is then True, plan() returns an AugSamplePlan and the loaders call the second library (functional.aug_tiles).
+    RandomRot90 may follow those, before RandomDistort: plan() then returns RotPlan(base, turn) with the plan above as `base`, and the loaders
+    turn the finished batch (functional.rot_batch); `extended` keeps its meaning.
 
     plan(H, W) draws one sample's random decisions with the draw helpers the CPU transforms themselves call (ResizeStepScaling.draw,
-    RandomPaddingCrop.draw, RandomHorizontalFlip.draw, RandomVerticalFlip.draw, RandomDistort.draw), in the chain's order and under its
+    RandomPaddingCrop.draw, RandomHorizontalFlip.draw, RandomVerticalFlip.draw, RandomRot90.draw, RandomDistort.draw), in the chain's order and under its
     conditions, so a seeded run makes the same decisions on either path and leaves np.random / random in the same state."""
 
     _HEAD = (ResizeStepScaling, RandomPaddingCrop, RandomHorizontalFlip)
     CHAINS = (_HEAD + (Normalize,), (Normalize,), _HEAD + (RandomVerticalFlip, Normalize), _HEAD + (RandomDistort, Normalize),
-              _HEAD + (RandomVerticalFlip, RandomDistort, Normalize))
+              _HEAD + (RandomVerticalFlip, RandomDistort, Normalize),
+              _HEAD + (RandomRot90, Normalize), _HEAD + (RandomVerticalFlip, RandomRot90, Normalize), _HEAD + (RandomRot90, RandomDistort, Normalize),
+              _HEAD + (RandomVerticalFlip, RandomRot90, RandomDistort, Normalize))
 
     def __init__(self, transforms):
         transforms = list(transforms)
@@ -313,18 +346,25 @@ class DevicePlan:
             raise ValueError("device transforms: Normalize needs 3 channels, got mean %r std %r" % (norm.mean, norm.std))
         self.mean = np.asarray(norm.mean, dtype=np.float64)
         self.stdinv = 1.0 / np.asarray(norm.std, dtype=np.float64)          # as Normalize computes it
-        self.scaling = self.crop = self.flip = self.vflip = self.distort = None
+        self.scaling = self.crop = self.flip = self.vflip = self.rot = self.distort = None
         self.img_pad, self.label_pad = np.zeros(3, np.float32), 255
         if len(transforms) >= 4:
             self.scaling, self.crop, self.flip = transforms[:3]
             for t in transforms[3:-1]:
                 if isinstance(t, RandomVerticalFlip):
                     self.vflip = t
+                elif isinstance(t, RandomRot90):
+                    self.rot = t
                 else:
                     self.distort = t
             chh, cw = self.crop.size()
             if chh <= 0 or cw <= 0:
                 raise ValueError("device transforms: RandomPaddingCrop size must be positive, got %r" % (self.crop.crop_size,))
+            if self.rot is not None:
+                if chh != cw:
+                    raise ValueError("device transforms: RandomRot90 needs a square crop, got %dx%d (h x w)" % (chh, cw))
+                if not 0.0 <= float(self.rot.prob) <= 1.0:
+                    raise ValueError("device transforms: RandomRot90 prob must lie in [0, 1], got %r" % (self.rot.prob,))
             pad = np.asarray(self.crop.img_padding_value, dtype=np.float32).reshape(-1)
             if pad.size != 3:
                 raise ValueError("device transforms: img_padding_value needs 3 channels, got %r" % (self.crop.img_padding_value,))
@@ -351,24 +391,30 @@ class DevicePlan:
         return (H, W) if self.crop is None else self.crop.size()
 
     def plan(self, H, W):
-        """Draw one H x W sample's decisions -> SamplePlan (AugSamplePlan for an extended chain)."""
+        """Draw one H x W sample's decisions -> SamplePlan (AugSamplePlan for an extended chain; RotPlan around either for a chain with
+        RandomRot90, whose turn is drawn in chain order, between the vertical flip and the distortion)."""
         if self.scaling is None:
             return SamplePlan(H, W, H, W, 0, 0, 0)
         h, w = ResizeStepScaling.resized(self.scaling.draw(), H, W)
         off = self.crop.draw(h, w) or (0, 0)
         flip = self.flip.draw()
-        if not self.extended:
-            return SamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip))
         vflip = self.vflip.draw() if self.vflip is not None else False
-        ops = self.distort.draw() if self.distort is not None else []
-        return AugSamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip), int(vflip), tuple((n, float(f)) for n, f in ops))
+        turn = self.rot.draw() if self.rot is not None else 0
+        if not self.extended:
+            base = SamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip))
+        else:
+            ops = self.distort.draw() if self.distort is not None else []
+            base = AugSamplePlan(H, W, h, w, int(off[0]), int(off[1]), int(flip), int(vflip), tuple((n, float(f)) for n, f in ops))
+        return base if self.rot is None else RotPlan(base, int(turn))
 
 
 def _augment(config, name, chain):
     """DATA.AUGMENT on a dataset's chain: RandomVerticalFlip and RandomDistort (hue off) go after the flip and before Normalize, the order of
-    the reference's ADE20K chain.  A chain without RandomHorizontalFlip (LoveDA's) has no place for them: the key is refused by name."""
+    the reference's ADE20K chain; RandomRot90 (ROT90_PROB; not in the reference) goes between the two.  A chain without RandomHorizontalFlip
+    (LoveDA's) has no place for them: the key is refused by name.  ROT90_PROB with a non-square DATA.CROP_SIZE is refused by name too."""
     aug = config.DATA.AUGMENT
-    wanted = [k for k, on in (("DATA.AUGMENT.VFLIP_PROB", aug.VFLIP_PROB > 0), ("DATA.AUGMENT.DISTORT.ENABLE", bool(aug.DISTORT.ENABLE))) if on]
+    wanted = [k for k, on in (("DATA.AUGMENT.VFLIP_PROB", aug.VFLIP_PROB > 0), ("DATA.AUGMENT.DISTORT.ENABLE", bool(aug.DISTORT.ENABLE)),
+                              ("DATA.AUGMENT.ROT90_PROB", aug.ROT90_PROB > 0)) if on]
     if not wanted:
         return chain
     at = next((i for i, t in enumerate(chain) if isinstance(t, RandomHorizontalFlip)), None)
@@ -378,12 +424,25 @@ def _augment(config, name, chain):
     extra = []
     if aug.VFLIP_PROB > 0:
         extra.append(RandomVerticalFlip(prob=aug.VFLIP_PROB))
+    if aug.ROT90_PROB > 0:
+        check_rot90(config)
+        extra.append(RandomRot90(prob=aug.ROT90_PROB))
     if aug.DISTORT.ENABLE:
         d = aug.DISTORT
         extra.append(RandomDistort(brightness_range=d.BRIGHTNESS_RANGE, brightness_prob=d.BRIGHTNESS_PROB, contrast_range=d.CONTRAST_RANGE,
                                    contrast_prob=d.CONTRAST_PROB, saturation_range=d.SATURATION_RANGE, saturation_prob=d.SATURATION_PROB,
                                    hue_prob=0))
     return chain[:at + 1] + extra + chain[at + 1:]
+
+
+def check_rot90(config):
+    """DATA.AUGMENT.ROT90_PROB > 0 needs a square DATA.CROP_SIZE and a probability in [0, 1]: refused by name otherwise (the chain builder and
+    train.py's start-up both call this)."""
+    p, crop = config.DATA.AUGMENT.ROT90_PROB, tuple(config.DATA.CROP_SIZE)
+    if not 0 <= p <= 1:
+        raise ValueError("DATA.AUGMENT.ROT90_PROB must lie in [0, 1], got %r" % (p,))
+    if p > 0 and (len(crop) != 2 or crop[0] != crop[1]):
+        raise ValueError("DATA.AUGMENT.ROT90_PROB is set, but DATA.CROP_SIZE is %r: a quarter turn needs a square crop (w == h)" % (crop,))
 
 
 def get_transforms(config):

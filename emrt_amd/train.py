@@ -156,6 +156,11 @@ def main(argv=None):
     if config.DATA.SCENE_SAMPLING.MODE == "class" and args.data != "scenes":
         raise SystemExit("[train] DATA.SCENE_SAMPLING.MODE 'class' needs --data scenes (the classes are drawn from the label maps of the resident "
                          "scenes; --data %s has none)" % args.data)
+    try:          # said at start-up, before a process group or a model exists: DATA.AUGMENT.ROT90_PROB needs a square DATA.CROP_SIZE
+        from .src.transforms import check_rot90
+        check_rot90(config)
+    except ValueError as e:
+        raise SystemExit("[train] %s" % e)
     rank, local_rank, nranks = init_process_group()
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)

@@ -19,7 +19,7 @@
  * cum and thr are formed by the caller from counts; P is the caller's choice (emrt_amd: exp((1 - f_c) / T), or explicit weights).
  *
  * The redraw of sample b.  Philox4x32-10 with key and counter exactly as emrt_scene_draw: key = the words of `key`, counter = (low, high word
- * of *step_counter, rank * B + b, j).  Blocks j = 0..4 belong to the draw kernels, 5..7 stay free for them, this library uses 8 and 9:
+ * of *step_counter, rank * B + b, j).  Blocks j = 0..4 belong to the draw kernels, 5 to emrt_rot_scene_batch (emrt_hip_rot.h), 6 and 7 stay free, this library uses 8 and 9:
  *   block 8, word 0:    class mode iff word * 2^-32 < prob (float64); otherwise the row is left as it is
  *   block 8, word 1:    cls = the number of c with word >= thr[c], at most the last class with pixels
  *   block 8, words 2-3: k = the high half of value * n_cls (n_cls = cum[cls][R]): the k-th pixel of that class in bank order
