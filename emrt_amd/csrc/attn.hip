@@ -7,6 +7,7 @@
 // 110x110x32 per block is < 1 us of VALU work and the kernel is bound by its launch and its few global accesses.
 // Probabilities (pre-dropout) are saved in fp32 for the backward pass.
 #include "common.hpp"
+#include "drop_hash.hpp"
 
 using namespace emrt;
 
@@ -310,12 +311,7 @@ __device__ __forceinline__ uint4 mha_frag_t(const T* sXt, int dt, int s, int lan
   const uint2 lo = *reinterpret_cast<const uint2*>(row), hi = *reinterpret_cast<const uint2*>(row + 16);
   return make_uint4(lo.x, lo.y, hi.x, hi.y);
 }
-// four 16-bit uniforms for (row, quad of 4 consecutive columns); keep iff u16 >= thr
-__device__ __forceinline__ void mha_drop4(unsigned long long seed, unsigned salt, unsigned group, uint32_t (&h)[2]) {
-  h[0] = mix32((group ^ (uint32_t)seed) + salt * 0x9E3779B9U);      // (the salt in the first round: see common.hpp drop_quad)
-  h[1] = mix32(h[0] ^ (uint32_t)(seed >> 32) ^ (salt * 0x85EBCA6BU));
-}
-__device__ __forceinline__ bool mha_keep4(const uint32_t (&h)[2], int e, uint32_t thr) { return ((h[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= thr; }
+// (mha_drop4 / mha_keep4, the four 16-bit uniforms of a row's quad of columns: drop_hash.hpp)
 
 template <class T>
 __global__ __launch_bounds__(64 * MHA_TILES) void mha_fwd_mfma_kernel(MhaArgs a) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include "drop_hash.hpp"      // mix32, uniform01, drop_quad / drop_words8 / mha_drop4: the hashes behind every dropout mask
 #include "../../include/emrt_hip.h"      // the public C-ABI: every definition under csrc/ is compiled against its prototype and its descriptor structs
 
 #define EMRT_F32 0
@@ -319,42 +320,7 @@ __device__ __forceinline__ void block_tree_sum_f64(const double (&a)[K], double 
   }
 }
 
-// counter-based RNG for dropout: one 32-bit hash of (seed, salt, index).  keep iff u >= p.
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ float uniform01(uint64_t seed, uint32_t salt, uint64_t idx) {
-  uint32_t a = mix32((uint32_t)idx ^ (uint32_t)seed);
-  uint32_t b = mix32((uint32_t)(idx >> 32) ^ (uint32_t)(seed >> 32) ^ (salt * 0x9E3779B9U));
-  uint32_t h = mix32(a ^ (b + 0x9E3779B9U + (a << 6) + (a >> 2)));
-  return (float)(h >> 8) * (1.0f / 16777216.0f);
-}
-
-// Element-mode dropout (nn.Dropout on token tensors: the stand-alone kernels and the LayerNorm kernels that apply a branch's dropout themselves):
-// the kernels move 4 consecutive elements per lane, so ONE 64-bit draw per aligned quad of the flat index gives their four 16-bit uniforms --
-// 2 hash rounds per 4 elements where uniform01() needs 12 (the hash was most of the VALU work of the LayerNorm kernels: 14 + 14 launches a step).
-// keep iff u16 >= p * 65536.  Every kernel that must agree on a mask calls these two functions with the same (seed, salt, quad index).
-// The salt (one per dropout site) enters the FIRST round: every word of the draw -- hence every element of the quad -- differs between two sites
-// that share the step's seed and the flat index (round 5 kept it out of h[0]: elements 0 and 1 of every quad had the same mask at every site).
-__device__ __forceinline__ void drop_quad(uint64_t seed, uint32_t salt, uint64_t quad, uint32_t (&h)[2]) {
-  h[0] = mix32(((uint32_t)quad ^ (uint32_t)seed) + salt * 0x9E3779B9U);
-  h[1] = mix32(h[0] ^ (uint32_t)(quad >> 32) ^ (uint32_t)(seed >> 32) ^ (salt * 0x85EBCA6BU));
-}
-__device__ __forceinline__ bool drop_quad_keep(const uint32_t (&h)[2], int e, uint32_t thr) { return ((h[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= thr; }
-__device__ __forceinline__ uint32_t drop_thr16(float p) { return (uint32_t)(p * 65536.f); }
-
-// Dropout inside a GEMM epilogue (conv.hip: linear1 -> ReLU -> Dropout of the FFN): the per-element hash above costs ~45 VALU instructions
-// per element, which on a GEMM's critical path cost more than the separate dropout launch it replaced.  Here ONE group of
-// 8 consecutive channels of a row draws four 32-bit words = eight 16-bit uniforms (~4 instructions per element); keep iff u16 >= p * 65536.
-// The backward never re-derives this mask: the consumer's data gradient masks with (stored output > 0) (functional.conv2d: drop_rec).
-__device__ __forceinline__ void drop_words8(uint64_t seed, uint32_t salt, uint32_t group, uint32_t (&h)[4]) {
-  h[0] = mix32((group ^ (uint32_t)seed) + salt * 0x9E3779B9U);      // (the salt in the first round: see drop_quad)
-  h[1] = mix32(h[0] ^ (uint32_t)(seed >> 32) ^ (salt * 0x85EBCA6BU));
-  h[2] = mix32(h[1] + 0x9E3779B9U + (h[0] << 6));
-  h[3] = mix32(h[2] ^ 0x85EBCA6BU ^ (h[1] >> 2));
-}
-__device__ __forceinline__ bool drop_keep8(const uint32_t (&h)[4], int e, uint32_t thr) { return ((h[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= thr; }
+// (the dropout hashes -- mix32, uniform01, drop_quad, drop_words8 and their kin -- are drop_hash.hpp: one text for the kernels and the host model)
 
 // Flat index -> coordinates for the grid-stride elementwise kernels.  idx = ((i3 * D2 + i2) * D1 + i1) * D0 + i0.
 // A 64-bit division is ~100 VALU instructions on gfx950 (no 64-bit divider, quarter-rate 32x32 multiplies): three of them per 16-byte vector

@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const T* __restrict__ 
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
     float v[4];
     Vec4<T>::load(x + i * 4, v);
-    if (mode == 0) {      // one draw per quad of elements (common.hpp: drop_quad)
+    if (mode == 0) {      // one draw per quad of elements (drop_hash.hpp: drop_quad)
       uint32_t h[2];
       drop_quad(sd, salt, (unsigned long long)i, h);
       const uint32_t thr = drop_thr16(p);

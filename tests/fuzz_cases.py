@@ -6,7 +6,10 @@ csrc/gconv.hip by group shape, launch plan and view (tests/test_gpu_gconv_fuzz.p
 convolution's fused epilogues through every tile and backward path of csrc/conv.hip and csrc/igemm8p.hpp (tests/test_gpu_conv_epilogue_fuzz.py),
 the written-out case lists of the sweeps of the loss kernels (csrc/loss.hip, csrc/loss_pixel.hpp, csrc/loss_ext/loss_ext.hip;
 tests/test_gpu_loss_fuzz.py) and of the optimizer half of csrc/optim.hip with emrt_segmentation_areas (tests/test_gpu_step_fuzz.py; inputs,
-float64 references and bounds of both: tests/loss_step_reference.py),
+float64 references and bounds of both: tests/loss_step_reference.py), the written-out case lists of the kernels that draw a dropout mask
+(emrt_dropout_fwd / emrt_mask_bwd: tests/test_gpu_dropout_fuzz.py; the LayerNorm kernels with a fused branch dropout:
+tests/test_gpu_norm_fuzz.py; emrt_conv2d_drop: tests/test_gpu_conv_epilogue_fuzz.py -- every mask held to tests/dropout_reference.py, the host
+model of csrc/drop_hash.hpp) and of the small streaming kernels of csrc/elementwise.hip (tests/test_gpu_elementwise_fuzz.py),
 and the dispatchers' shape predicates restated in Python.  No GPU and no library import: tests/test_fuzz_cases_cpu.py checks on any machine that every case lies inside its
 entry point's accepted domain (no case is an expected refusal) and that every regime below keeps at least two cases, so a later edit of a
 seed or a range cannot silently empty one.
@@ -611,6 +614,165 @@ Regime -> case ids (regime_table() renders this text; the CPU test compares):
   areas             the grid strides (n > 1024 x 4096)                 areas-{10}
   areas             ignore index inside [0, ncls)                      areas-{1,3,8,9}
   areas             ignore index outside [0, ncls)                     areas-{0,2,4,5,6,7,10}
+  dropout           element mode                                       drop-{0,1,2,3,4,5,6,7,8,9,10,11}
+  dropout           channel mode                                       drop-{12,13,14,15,16,17,18,19,20}
+  dropout           element: n = 4                                     drop-{0,1}
+  dropout           element: n = 1020                                  drop-{2,3,4}
+  dropout           element: n = 1024                                  drop-{5,6,7}
+  dropout           element: n = 1028                                  drop-{8,9,10}
+  dropout           element: the second trip (n > 8192 x 1024)         drop-{11}
+  dropout           channel: N > 1, hw = 1                             drop-{12,13,14}
+  dropout           channel: N > 1, hw = 25                            drop-{15,16,17,18}
+  dropout           channel: C = 4                                     drop-{12,15}
+  dropout           channel: C = 64                                    drop-{13,16,19,20}
+  dropout           channel: C = 100                                   drop-{14,17,18}
+  dropout           channel: C hw % 1024 != 0                          drop-{12,13,14,15,16,17,18}
+  dropout           p = 0                                              drop-{0,5,19}
+  dropout           p = 2^-17 (threshold 0)                            drop-{2,8,14}
+  dropout           p = 0.1                                            drop-{3,6,13,17}
+  dropout           p = 0.5                                            drop-{1,7,9,11,12,15,16,20}
+  dropout           p = 0.999                                          drop-{4,10,18}
+  dropout           backward arm: mask                                 drop-{1,2,4,6,7,9,11,12,14,15,16,17,18}
+  dropout           backward arm: mask+relu                            drop-{3,6,8,9,10,13,15,17,20}
+  dropout           backward arm: relu                                 drop-{0,5,19}
+  dropout           backward arm: stored                               drop-{1,4,6,8}
+  dropout           channel mode, backward with relu_out               drop-{13,15,17,20}
+  dropout           seed 0                                             drop-{2,7,12,17}
+  dropout           seed with the top bit set                          drop-{3,8,13,18}
+  dropout           salt 0                                             drop-{7,15}
+  layernorm_drop    C = 12                                             lnd-{0,1}
+  layernorm_drop    C = 100                                            lnd-{2,3}
+  layernorm_drop    C = 256                                            lnd-{4,5,6,7}
+  layernorm_drop    C = 260                                            lnd-{8,9,10}
+  layernorm_drop    C = 1000                                           lnd-{11,12,13}
+  layernorm_drop    C = 1024                                           lnd-{14,15,16}
+  layernorm_drop    rows % 4 != 0                                      lnd-{0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16}
+  layernorm_drop    rows = 1                                           lnd-{0,3,10,13}
+  layernorm_drop    form ln(a+b)                                       lnd-{0,4,8,13,15}
+  layernorm_drop    form ln(a+b,post)                                  lnd-{1,5,11,16}
+  layernorm_drop    form ln(a+b,qpos)                                  lnd-{2,6,10,12}
+  layernorm_drop    form ln(a+b,addend)                                lnd-{3,7,9,14}
+  layernorm_drop    p = 0.1                                            lnd-{1,3,4,6,9,11,13,15}
+  layernorm_drop    p = 0.5                                            lnd-{0,2,5,7,8,10,12,14,16}
+  layernorm_drop    backward under the default knobs                   lnd-{0,1,2,3,4,8,10,11,13,14}
+  layernorm_drop    backward under ln_bwd_rows                         lnd-{6,7,9,12,16}
+  layernorm_drop    backward under ln_bwd_max_blocks                   lnd-{5,6,12,15}
+  layernorm_drop    backward blocks loop under the block cap           lnd-{5,6,12,15}
+  layernorm_drop    several backward blocks                            lnd-{2,4,5,6,7,8,9,11,12,14,15,16}
+  conv_drop         M = 1                                              cdrop-{0,1}
+  conv_drop         M = 63                                             cdrop-{2,3}
+  conv_drop         M = 64                                             cdrop-{4,5,11}
+  conv_drop         M = 65                                             cdrop-{6,7}
+  conv_drop         M = 114                                            cdrop-{8,9,10}
+  conv_drop         C = 8                                              cdrop-{0,2,5,10}
+  conv_drop         C = 64                                             cdrop-{1,4,6,8}
+  conv_drop         C = 264                                            cdrop-{3,7,9,11}
+  conv_drop         OC = 8                                             cdrop-{0,4,7}
+  conv_drop         OC = 72                                            cdrop-{1,3,8,11}
+  conv_drop         OC = 96                                            cdrop-{2,6,10}
+  conv_drop         OC = 1024                                          cdrop-{5,9}
+  conv_drop         ldout == OC                                        cdrop-{0,1,2,4,5,6,8,11}
+  conv_drop         ldout > OC (a slice of a wider buffer)             cdrop-{3,7,9,10}
+  conv_drop         ldin > C                                           cdrop-{5,8}
+  conv_drop         ragged last M tile                                 cdrop-{0,1,2,3,6,7,8,9,10}
+  conv_drop         several M tiles                                    cdrop-{6,7,8,9,10}
+  conv_drop         several N tiles                                    cdrop-{1,2,3,5,6,8,9,10,11}
+  conv_drop         ragged last N tile                                 cdrop-{0,1,2,3,4,6,7,8,10,11}
+  conv_drop         p = 0.1                                            cdrop-{1,3,5,6,9,11}
+  conv_drop         p = 0.5                                            cdrop-{0,2,4,7,8,10}
+  elementwise       kernel: add, f32                                   ew-{0,3,6,9,12,15,18,21,24,27,30}
+  elementwise       kernel: add, bf16                                  ew-{1,4,7,10,13,16,19,22,25,28,31,33}
+  elementwise       kernel: add, f16                                   ew-{2,5,8,11,14,17,20,23,26,29,32}
+  elementwise       kernel: add_f32row, f32                            ew-{34,37,40,43,46,49,52,55,58,61,64}
+  elementwise       kernel: add_f32row, bf16                           ew-{35,38,41,44,47,50,53,56,59,62,65,67}
+  elementwise       kernel: add_f32row, f16                            ew-{36,39,42,45,48,51,54,57,60,63,66}
+  elementwise       kernel: levels, f32                                ew-{68,71,74,77,80,83,86,89,92,95,98}
+  elementwise       kernel: levels, bf16                               ew-{69,72,75,78,81,84,87,90,93,96,99,101}
+  elementwise       kernel: levels, f16                                ew-{70,73,76,79,82,85,88,91,94,97,100}
+  elementwise       kernel: add3d, f32                                 ew-{102,105,108,111,114,117,120,123,126,129,132,135,138,141}
+  elementwise       kernel: add3d, bf16                                ew-{103,106,109,112,115,118,121,124,127,130,133,136,139,142,144}
+  elementwise       kernel: add3d, f16                                 ew-{104,107,110,113,116,119,122,125,128,131,134,137,140,143}
+  elementwise       kernel: acc3d, f32                                 ew-{145,148,151,154,157,160,163,166,169,172,175,178}
+  elementwise       kernel: acc3d, bf16                                ew-{146,149,152,155,158,161,164,167,170,173,176,179,181}
+  elementwise       kernel: acc3d, f16                                 ew-{147,150,153,156,159,162,165,168,171,174,177,180}
+  elementwise       kernel: concat, f32                                ew-{182,185,188,191,194,197,200,203,206,209}
+  elementwise       kernel: concat, bf16                               ew-{183,186,189,192,195,198,201,204,207,210,212}
+  elementwise       kernel: concat, f16                                ew-{184,187,190,193,196,199,202,205,208,211}
+  elementwise       kernel: split, f32                                 ew-{213,216,219,222,225,228,231,234,237,240}
+  elementwise       kernel: split, bf16                                ew-{214,217,220,223,226,229,232,235,238,241,243}
+  elementwise       kernel: split, f16                                 ew-{215,218,221,224,227,230,233,236,239,242}
+  elementwise       kernel: cast_to, bf16                              ew-{244,245,246,247}
+  elementwise       kernel: cast_to, f16                               ew-{248,249,250,251,252}
+  elementwise       kernel: cast_from, bf16                            ew-{253,254,255,256,261}
+  elementwise       kernel: cast_from, f16                             ew-{257,258,259,260}
+  elementwise       kernel: sigmoid_fwd, f32                           ew-{262,263,264,265}
+  elementwise       kernel: sigmoid_bwd, f32                           ew-{266,267,268,269}
+  elementwise       kernel: memcpy, f32                                ew-{270,271,272,273,274,275,276}
+  elementwise       second trip: add                                   ew-{33}
+  elementwise       second trip: add_f32row                            ew-{67}
+  elementwise       second trip: levels                                ew-{101}
+  elementwise       second trip: add3d                                 ew-{144}
+  elementwise       second trip: acc3d                                 ew-{181}
+  elementwise       second trip: concat                                ew-{212}
+  elementwise       second trip: split                                 ew-{243}
+  elementwise       second trip: cast_to                               ew-{252}
+  elementwise       second trip: cast_from                             ew-{261}
+  elementwise       second trip: sigmoid_fwd                           ew-{265}
+  elementwise       second trip: sigmoid_bwd                           ew-{269}
+  elementwise       second trip: memcpy                                ew-{276}
+  elementwise       1 lane                                             ew-{0,1,2,34,35,36,68,69,70,102,103,104,145,146,147,182,183,184,213,214,215,244,248,253,257,262,266}
+  elementwise       255 lanes                                          ew-{3,4,5,6,7,8,9,10,11,12,13,14,37,38,39,40,41,42,43,44,45,46,47,48,92,93,94,105,106,107,114,115,116,117,118,119,120,121,122,123,124,125,126,127,128,129,130,131,148,149,150,157,158,159,160,161,162,163,164,165,166,167,168,203,204,205,234,235,236,246,250,255,259}
+  elementwise       256 lanes                                          ew-{15,16,17,18,19,20,21,22,23,49,50,51,52,53,54,55,56,57,95,96,97,108,109,110,151,152,153,206,207,208,237,238,239}
+  elementwise       257 lanes                                          ew-{24,25,26,27,28,29,30,31,32,58,59,60,61,62,63,64,65,66,98,99,100,111,112,113,154,155,156,209,210,211,240,241,242,247,251,256,260,263,267}
+  elementwise       add: period == n                                   ew-{0,1,2,3,4,5,15,16,17,24,25,26,34,35,36,37,38,39,49,50,51,58,59,60}
+  elementwise       add: period 4                                      ew-{6,7,8,27,28,29,40,41,42,61,62,63}
+  elementwise       add: period divides n                              ew-{9,10,11,18,19,20,43,44,45,52,53,54}
+  elementwise       add: period does not divide n                      ew-{12,13,14,21,22,23,30,31,32,46,47,48,55,56,57,64,65,66}
+  elementwise       levels: L = 1                                      ew-{68,69,70,71,72,73,95,96,97}
+  elementwise       levels: L = 2                                      ew-{74,75,76,77,78,79,92,93,94}
+  elementwise       levels: L = 3                                      ew-{80,81,82,83,84,85,98,99,100,101}
+  elementwise       levels: L = 4                                      ew-{86,87,88,89,90,91}
+  elementwise       levels: a level of one row                         ew-{68,69,70,74,75,76,77,78,79,80,81,82,83,84,85,86,87,88,89,90,91,98,99,100,101}
+  elementwise       levels: the last level of one row                  ew-{74,75,76,80,81,82,86,87,88,98,99,100}
+  elementwise       levels: C = 4                                      ew-{68,69,70,83,84,85,86,87,88,92,93,94,95,96,97,98,99,100,101}
+  elementwise       levels: C = 100                                    ew-{71,72,73,74,75,76,89,90,91}
+  elementwise       levels: C = 256                                    ew-{77,78,79,80,81,82}
+  elementwise       add3d: operand 0 a slab, the others dense          ew-{114,115,116}
+  elementwise       add3d: operand 0 a slice, the others dense         ew-{117,118,119}
+  elementwise       add3d: operand 1 a slab, the others dense          ew-{120,121,122}
+  elementwise       add3d: operand 1 a slice, the others dense         ew-{123,124,125}
+  elementwise       add3d: operand 2 a slab, the others dense          ew-{126,127,128}
+  elementwise       add3d: operand 2 a slice, the others dense         ew-{129,130,131}
+  elementwise       acc3d: operand 0 a slab, the others dense          ew-{157,158,159}
+  elementwise       acc3d: operand 0 a slice, the others dense         ew-{160,161,162}
+  elementwise       acc3d: operand 1 a slab, the others dense          ew-{163,164,165}
+  elementwise       acc3d: operand 1 a slice, the others dense         ew-{166,167,168}
+  elementwise       add3d: every operand strided                       ew-{132,133,134,135,136,137,138,139,140,141,142,143}
+  elementwise       acc3d: every operand strided                       ew-{169,170,171,172,173,174,175,176,177,178,179,180}
+  elementwise       add3d: B = 1                                       ew-{102,103,104,111,112,113,138,139,140}
+  elementwise       acc3d: B = 1                                       ew-{145,146,147,154,155,156,175,176,177}
+  elementwise       add3d: rows = 1                                    ew-{102,103,104,141,142,143}
+  elementwise       acc3d: rows = 1                                    ew-{145,146,147,178,179,180}
+  elementwise       concat: 1 part                                     ew-{182,183,184,185,186,187}
+  elementwise       concat: 4 parts                                    ew-{188,189,190,191,192,193,194,195,196}
+  elementwise       concat: 8 parts                                    ew-{197,198,199,200,201,202}
+  elementwise       split: 1 part                                      ew-{213,214,215,216,217,218}
+  elementwise       split: 4 parts                                     ew-{219,220,221,222,223,224,225,226,227}
+  elementwise       split: 8 parts                                     ew-{228,229,230,231,232,233}
+  elementwise       concat / split: a part of one token first          ew-{188,189,190,197,198,199,209,210,211,219,220,221,228,229,230,240,241,242}
+  elementwise       concat / split: a part of one token last           ew-{191,192,193,200,201,202,206,207,208,212,222,223,224,231,232,233,237,238,239,243}
+  elementwise       concat / split: a part of one token in the middle  ew-{194,195,196,200,201,202,225,226,227,231,232,233}
+  elementwise       concat / split: B = 1                              ew-{182,183,184,188,189,190,197,198,199,206,207,208,209,210,211,212,213,214,215,219,220,221,228,229,230,237,238,239,240,241,242,243}
+  elementwise       concat / split: B = 3                              ew-{185,186,187,191,192,193,194,195,196,200,201,202,203,204,205,216,217,218,222,223,224,225,226,227,231,232,233,234,235,236}
+  elementwise       concat / split: C = 4                              ew-{182,183,184,191,192,193,197,198,199,203,204,205,206,207,208,209,210,211,212,213,214,215,222,223,224,228,229,230,234,235,236,237,238,239,240,241,242,243}
+  elementwise       concat / split: C = 64                             ew-{185,186,187,188,189,190,194,195,196,200,201,202,216,217,218,219,220,221,225,226,227,231,232,233}
+  elementwise       cast: n = 1                                        ew-{244,248,253,257}
+  elementwise       cast: n = 3                                        ew-{245,249,254,258}
+  elementwise       cast: n = 255                                      ew-{246,250,255,259}
+  elementwise       cast: n = 257                                      ew-{247,251,256,260}
+  elementwise       memcpy: the copy kernel                            ew-{270,271,276}
+  elementwise       memcpy: a size that is no multiple of 16           ew-{272,273}
+  elementwise       memcpy: misaligned pointers                        ew-{274,275}
 
 Not reachable through the wrappers, on purpose:
   * functional.pyramid_tokens_to_maps passes align_corners=True to both pyramid entry points (the model's only use), so the pyramid sweep
@@ -620,14 +782,18 @@ Not reachable through the wrappers, on purpose:
     of the sweep; FINALIZE and the band kinds do not exist for the (1, 4) build (see MSDA_REGIMES).
   * gconv: emrt_gconv2d has no dilation and no kernel size but 3; maps of 2^31 pixels and more are refused (check_common).  The refusals
     are one separate test without a launch (tests/test_gpu_gconv_fuzz.py).
-  * conv: the dropout epilogue (emrt_conv2d_drop) and the BatchNorm operand transform (emrt_conv2d_bna) have their own tests and stay out of
-    the sweep (bna_plan is mirrored only to hold conv_plan to the recorded table); mode 1 of emrt_conv2d is not what the model runs.  The
+  * conv: the BatchNorm operand transform (emrt_conv2d_bna) has its own tests and stays out of the sweep (bna_plan is mirrored only to hold
+    conv_plan to the recorded table); the dropout epilogue (emrt_conv2d_drop) is the op conv_drop; mode 1 of emrt_conv2d is not what the model runs.  The
     parity-class kernel has no ragged M tile (M / 4 is a multiple of 64 by its own condition) and, like the cross-block split and the pair
     kernel, no scalar epilogue (the host sends those problems elsewhere); the thin kernel takes neither stat_x nor an addend (thin_bwd_ok).
     The weight-gradient kernels' own plan space belongs to tests/test_gpu_wgrad_group.py and the WG8 cases of tests/test_gpu_conv_fuzz.py.
   * loss: a label outside [0, C) that is not the ignore index is outside the contract (include/emrt_hip_loss.h) and loss_in_domain refuses
     it; the Dice entry points stop at 64 classes, so C = 150 runs in the other three families; the 64-bit branch of pixel_of needs 2^32 pixels.
   * step: the learning-rate schedules (tests/test_gpu_adamw.py::test_schedules_on_the_device) and emrt_pack_weights stay out.
+  * dropout / conv_drop: emrt_conv2d_drop refuses an output it cannot store in whole 16-byte chunks (conv_drop_vec_ok), so no case has one; no
+    statistic is taken on the device -- the model's are checked on the CPU (tests/test_dropout_reference_cpu.py), the device is held to the model.
+  * elementwise: the 64-bit index branches (n4 | period4 > 2^32 in the add kernels, unravel3 in add3d / acc3d / concat) need more than 2^32
+    elements and stay unexercised; emrt_colsum_acc and emrt_colsum_levels_multi are reductions of csrc/norm.hip and not part of this sweep.
 """
 import random
 
@@ -2778,23 +2944,388 @@ AREAS_REGIMES = [("%d class%s" % (k, "es" if k > 1 else ""), (lambda k_: lambda 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the kernels that draw a dropout mask, each held to the host model of csrc/drop_hash.hpp (tests/dropout_reference.py) bit for bit:
+# emrt_dropout_fwd / emrt_mask_bwd (tests/test_gpu_dropout_fuzz.py), the LayerNorm kernels with a fused branch dropout
+# (tests/test_gpu_norm_fuzz.py) and emrt_conv2d_drop (tests/test_gpu_conv_epilogue_fuzz.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+DROP_LONG_MAX_ELEMS = 4 * (8192 * 256 + 1)          # one quad past ew_grid's 8192 blocks: the second trip round the grid-stride loop
+DROP_PS = (0.0, 2.0 ** -17, 0.1, 0.5, 0.999)          # 0: identity; 2^-17: threshold 0, nothing dropped, the scale still applied
+DROP_ARMS = ("mask", "mask+relu", "relu", "stored")          # emrt_mask_bwd: seed + mask alone; seed + relu_out; relu_out alone (p = 0); seed == NULL,
+DROP_DTYPES = ("both", "f32", "bf16")                        # p > 0 (relu_out is emrt_conv2d_drop's stored output: both masks)
+DROP_SEEDS = (0x0123456789abcdef, 7, 0, 0xfedcba9876543210, 1234 * 0x9E3779B97F4A7C15 % (1 << 63))
+
+
+def ew_grid(quads):
+    """ew_grid (csrc/elementwise.hip): blocks of 256 lanes, at most 8192"""
+    return min(max(_ceil_div(quads, 256), 1), 8192)
+
+
+def drop_n(c):
+    """elements of a dropout case: n (element mode) or N hw C (channel mode)"""
+    return c[2][0] if c[1] == "element" else c[2][0] * c[2][1] * c[2][2]
+
+
+def drop_in_domain(c):
+    _, mode, dims, p, arms, dtypes, _, _, _ = c
+    n = drop_n(c)
+    if mode not in ("element", "channel") or n < 4 or n % 4 != 0 or not 0.0 <= p < 1.0 or dtypes not in DROP_DTYPES:
+        return False
+    if mode == "channel" and (dims[1] < 1 or dims[2] < 1):
+        return False
+    for arm in arms:          # (emrt_mask_bwd: p == 0 or a seed or relu_out)
+        if arm not in DROP_ARMS or (arm == "relu") != (p == 0.0):
+            return False
+    return True
+
+
+# (mode, dims, p, arms of emrt_mask_bwd, dtypes, salt, what the row is there for).  element: dims = (n,); channel: dims = (N, hw, C)
+_DROP_ROWS = (
+    ("element", (4,), 0.0, ("relu",), "both", 1, "one quad, p = 0: the forward is the identity bit for bit, the backward the ReLU mask alone"),
+    ("element", (4,), 0.5, ("mask", "stored"), "both", 2, "one quad, one lane"),
+    ("element", (1020,), 2.0 ** -17, ("mask",), "both", 3, "255 quads, threshold 0: nothing dropped, every element scaled by 1 / (1 - 2^-17)"),
+    ("element", (1020,), 0.1, ("mask+relu",), "both", 4, "255 quads"),
+    ("element", (1020,), 0.999, ("mask", "stored"), "both", 5, "255 quads, almost everything dropped, scale 1000"),
+    ("element", (1024,), 0.0, ("relu",), "both", 6, "one block exactly, p = 0"),
+    ("element", (1024,), 0.1, ("mask", "mask+relu", "stored"), "both", 7, "one block exactly, every arm of the backward with a mask"),
+    ("element", (1024,), 0.5, ("mask",), "both", 0, "one block exactly, salt 0"),
+    ("element", (1028,), 2.0 ** -17, ("mask+relu", "stored"), "both", 1000, "257 quads: one lane of a second block, threshold 0"),
+    ("element", (1028,), 0.5, ("mask", "mask+relu"), "both", 0xFFFFFFFF, "257 quads, the largest salt"),
+    ("element", (1028,), 0.999, ("mask+relu",), "both", 11, "257 quads, p = 0.999"),
+    ("element", (DROP_LONG_MAX_ELEMS,), 0.5, ("mask",), "bf16", 12, "8 388 612 elements: both kernels go round their grid-stride loop a second time"),
+    ("channel", (3, 1, 4), 0.5, ("mask",), "both", 5, "hw = 1, C = 4: three quads, each an image"),
+    ("channel", (2, 1, 64), 0.1, ("mask+relu",), "both", 6, "hw = 1"),
+    ("channel", (2, 1, 100), 2.0 ** -17, ("mask",), "both", 7, "p = 2^-17: a plane drops only below 2^-17, nothing here; the scale still applied"),
+    ("channel", (2, 25, 4), 0.5, ("mask", "mask+relu"), "both", 0, "C = 4: every quad is one pixel; salt 0"),
+    ("channel", (4, 25, 64), 0.5, ("mask",), "both", 9, "C hw = 1600: a block of 1024 elements spans two images"),
+    ("channel", (3, 25, 100), 0.1, ("mask", "mask+relu"), "both", 10, "C = 100, C hw = 2500: blocks and quads cut across pixels' ends differently in every image"),
+    ("channel", (40, 25, 100), 0.999, ("mask",), "both", 11, "p = 0.999, compared in float32: 4000 planes, a handful kept"),
+    ("channel", (2, 16, 64), 0.0, ("relu",), "both", 12, "C hw = 1024: an image per block; p = 0"),
+    ("channel", (5, 16, 64), 0.5, ("mask+relu",), "both", 13, "C hw = 1024: an image per block"),
+)
+
+
+def drop_cases():
+    """(id, mode, dims, p, arms, dtypes, salt, why, seed word of the device): the seed words go round DROP_SEEDS, nothing is drawn"""
+    return [("drop-%d" % i,) + row + (DROP_SEEDS[i % len(DROP_SEEDS)],) for i, row in enumerate(_DROP_ROWS)]
+
+
+DROP_REGIMES = [("%s mode" % m, (lambda m_: lambda c: c[1] == m_)(m)) for m in ("element", "channel")] + [
+    ("element: n = %d" % n, (lambda n_: lambda c: c[1] == "element" and c[2][0] == n_)(n)) for n in (4, 1020, 1024, 1028)] + [
+    ("element: the second trip (n > 8192 x 1024)", lambda c: c[1] == "element" and c[2][0] // 4 > ew_grid(c[2][0] // 4) * 256),
+    ("channel: N > 1, hw = 1", lambda c: c[1] == "channel" and c[2][0] > 1 and c[2][1] == 1),
+    ("channel: N > 1, hw = 25", lambda c: c[1] == "channel" and c[2][0] > 1 and c[2][1] == 25),
+] + [("channel: C = %d" % k, (lambda k_: lambda c: c[1] == "channel" and c[2][2] == k_)(k)) for k in (4, 64, 100)] + [
+    ("channel: C hw % 1024 != 0", lambda c: c[1] == "channel" and (c[2][1] * c[2][2]) % 1024 != 0),
+    ("p = 0", lambda c: c[3] == 0.0), ("p = 2^-17 (threshold 0)", lambda c: c[3] == 2.0 ** -17),
+] + [("p = %g" % p, (lambda p_: lambda c: c[3] == p_)(p)) for p in (0.1, 0.5, 0.999)] + [
+    ("backward arm: %s" % a, (lambda a_: lambda c: a_ in c[4])(a)) for a in DROP_ARMS] + [
+    ("channel mode, backward with relu_out", lambda c: c[1] == "channel" and "mask+relu" in c[4]),
+    ("seed 0", lambda c: c[8] == 0), ("seed with the top bit set", lambda c: c[8] >> 63 == 1), ("salt 0", lambda c: c[6] == 0)]
+
+
+# ---- emrt_layernorm_fwd / _bwd with drop_p > 0 -------------------------------------------------------------------------------------
+LND_FORMS = ("a+b", "a+b,post", "a+b,qpos", "a+b,addend")          # qpos: layer_norm(q_pos=) also writes q = out + pos; addend: identity_from (dz_addend)
+LND_CS = (12, 100, 256, 260, 1000, 1024)
+
+
+def lnd_in_domain(case):
+    _, B, L, C, form, p, salt, max_blocks, rows_knob, _, _ = case
+    return C % 4 == 0 and 12 <= C <= 1024 and B * L >= 1 and form in LND_FORMS and 0.0 < p < 1.0 and max_blocks >= 0 and rows_knob >= 0 and salt >= 0
+
+
+# (B, L, C, form, p, salt, ln_bwd_max_blocks, ln_bwd_rows, what the row is there for)
+_LND_ROWS = (
+    (1, 1, 12, "a+b", 0.5, 5, 0, 0, "one row of three quads"),
+    (3, 7, 12, "a+b,post", 0.1, 6, 0, 0, "21 rows of 12: eight rows share a 256-lane pass"),
+    (2, 37, 100, "a+b,qpos", 0.5, 7, 0, 0, "C = 100: 25 quads a row, rows % 4 = 2"),
+    (1, 1, 100, "a+b,addend", 0.1, 8, 0, 0, "one row, with the identity's addend"),
+    (3, 23, 256, "a+b", 0.1, 11, 0, 0, "C = 256, 69 rows: two backward blocks of 64 rows"),
+    (2, 65, 256, "a+b,post", 0.5, 12, 2, 0, "C = 256 under ln_bwd_max_blocks = 2: every backward block loops over its rows"),
+    (1, 131, 256, "a+b,qpos", 0.1, 1, 3, 8, "C = 256 under ln_bwd_rows = 8, ln_bwd_max_blocks = 3"),
+    (2, 33, 256, "a+b,addend", 0.5, 2, 0, 5, "C = 256 under ln_bwd_rows = 5: 14 blocks of 5 rows, the last of one"),
+    (1, 43, 260, "a+b", 0.5, 0, 0, 0, "C = 260: a ragged second pass of one quad; salt 0"),
+    (3, 9, 260, "a+b,addend", 0.1, 1000, 0, 7, "C = 260 under ln_bwd_rows = 7"),
+    (1, 1, 260, "a+b,qpos", 0.5, 13, 0, 0, "one row of C = 260"),
+    (2, 51, 1000, "a+b,post", 0.1, 14, 0, 0, "C = 1000: 250 quads, a ragged fourth pass"),
+    (1, 35, 1000, "a+b,qpos", 0.5, 15, 2, 3, "C = 1000 under ln_bwd_rows = 3, ln_bwd_max_blocks = 2"),
+    (1, 1, 1000, "a+b", 0.1, 16, 0, 0, "one row of C = 1000"),
+    (3, 11, 1024, "a+b,addend", 0.5, 17, 0, 0, "C = 1024: four whole passes"),
+    (1, 67, 1024, "a+b", 0.1, 18, 2, 0, "C = 1024 under ln_bwd_max_blocks = 2"),
+    (2, 3, 1024, "a+b,post", 0.5, 0xFFFFFFFF, 0, 4, "C = 1024 under ln_bwd_rows = 4; the largest salt"),
+)
+
+
+def lnd_cases(seed=2717):
+    """(id, B, L, C, form, p, salt, ln_bwd_max_blocks, ln_bwd_rows, why, seed)"""
+    return [("lnd-%d" % i,) + row + (seed + i,) for i, row in enumerate(_LND_ROWS)]
+
+
+LND_REGIMES = [("C = %d" % k, (lambda k_: lambda c: c[3] == k_)(k)) for k in LND_CS] + [
+    ("rows % 4 != 0", lambda c: (c[1] * c[2]) % 4 != 0), ("rows = 1", lambda c: c[1] * c[2] == 1),
+] + [("form ln(%s)" % f, (lambda f_: lambda c: c[4] == f_)(f)) for f in LND_FORMS] + [
+    ("p = %g" % p, (lambda p_: lambda c: c[5] == p_)(p)) for p in (0.1, 0.5)] + [
+    ("backward under the default knobs", lambda c: c[7] == 0 and c[8] == 0),
+    ("backward under ln_bwd_rows", lambda c: c[8] > 0),
+    ("backward under ln_bwd_max_blocks", lambda c: c[7] > 0),
+    ("backward blocks loop under the block cap", lambda c: ln_bwd_blocks(c[1] * c[2], c[3], c[8], c[7])[1]),
+    ("several backward blocks", lambda c: ln_bwd_blocks(c[1] * c[2], c[3], c[8], c[7])[0] > 1)]
+
+
+# ---- emrt_conv2d_drop: dropout(relu(x w + bias)) drawn in the 64x64 tile's epilogue ------------------------------------------------
+CDROP_MS = (1, 63, 64, 65, 114)
+CDROP_CS = (8, 64, 264)
+CDROP_OCS = (8, 72, 96, 1024)
+
+
+def conv_drop_vec_ok(M, C, ldin, OC, ldout, esz, in_al=True, out_al=True):
+    """Mirrors what emrt_conv2d_drop asks (csrc/conv.hip): conv_is_vec of the input and conv_plan's vec_out of the output; anything else is refused"""
+    epc = 16 // esz
+    vec_in = C % epc == 0 and ldin % epc == 0 and (M * ldin) % epc == 0 and in_al
+    vec_out = out_al and ldout % epc == 0 and (M * ldout) % epc == 0 and OC % 8 == 0
+    return vec_in and vec_out
+
+
+def cdrop_in_domain(c):
+    _, M, C, ldin, OC, ldout, p, _, _, _ = c
+    if not (M > 0 and C > 0 and OC > 0 and OC % 8 == 0 and M * OC < 1 << 32 and 0.0 < p < 1.0 and ldin >= C and ldout >= OC):
+        return False
+    return all(conv_drop_vec_ok(M, C, ldin, OC, ldout, esz) for esz in (4, 2))          # every case runs in fp32 and in bf16
+
+
+# (M, C, ldin, OC, ldout, p, salt, what the row is there for)
+_CDROP_ROWS = (
+    (1, 8, 8, 8, 8, 0.5, 5, "one row, one group of 8"),
+    (1, 64, 64, 72, 72, 0.1, 6, "one row of nine groups"),
+    (63, 8, 8, 96, 96, 0.5, 7, "one ragged M tile, two N tiles (the second of 32 columns)"),
+    (63, 264, 264, 72, 80, 0.1, 8, "ldout > OC: rows of 80 hold a slice of 72"),
+    (64, 64, 64, 8, 8, 0.5, 0, "one whole M tile, an N tile of one group; salt 0"),
+    (64, 8, 16, 1024, 1024, 0.1, 11, "sixteen N tiles; ldin > C"),
+    (65, 64, 64, 96, 96, 0.1, 12, "a second M tile of one row"),
+    (65, 264, 264, 8, 24, 0.5, 13, "ldout = 3 OC"),
+    (114, 64, 72, 72, 72, 0.5, 14, "114 rows, ldin > C: OC = 72 makes (m * OC + n0) >> 3 differ from (m * ldout + n0) >> 3 only where ldout != OC"),
+    (114, 264, 264, 1024, 1032, 0.1, 1000, "114 x 1024 in rows of 1032"),
+    (114, 8, 8, 96, 128, 0.5, 0xFFFFFFFF, "ldout = 128 > OC = 96; the largest salt"),
+    (64, 264, 264, 72, 72, 0.1, 15, "K = 264: five k-tiles in bf16, a ragged last one"),
+)
+
+
+def cdrop_cases(seed=2818):
+    """(id, M, C, ldin, OC, ldout, p, salt, why, seed)"""
+    return [("cdrop-%d" % i,) + row + (seed + i,) for i, row in enumerate(_CDROP_ROWS)]
+
+
+CDROP_REGIMES = [("M = %d" % k, (lambda k_: lambda c: c[1] == k_)(k)) for k in CDROP_MS] + [
+    ("C = %d" % k, (lambda k_: lambda c: c[2] == k_)(k)) for k in CDROP_CS] + [
+    ("OC = %d" % k, (lambda k_: lambda c: c[4] == k_)(k)) for k in CDROP_OCS] + [
+    ("ldout == OC", lambda c: c[5] == c[4]), ("ldout > OC (a slice of a wider buffer)", lambda c: c[5] > c[4]), ("ldin > C", lambda c: c[3] > c[2]),
+    ("ragged last M tile", lambda c: c[1] % 64 != 0), ("several M tiles", lambda c: c[1] > 64), ("several N tiles", lambda c: c[4] > 64),
+    ("ragged last N tile", lambda c: c[4] % 64 != 0),
+] + [("p = %g" % p, (lambda p_: lambda c: c[6] == p_)(p)) for p in (0.1, 0.5)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the small streaming kernels of csrc/elementwise.hip (tests/test_gpu_elementwise_fuzz.py): emrt_add, emrt_add_f32row,
+# emrt_add_f32row_levels, emrt_add3d, emrt_acc3d, emrt_concat_tokens, emrt_cast, emrt_sigmoid_fwd / _bwd, emrt_memcpy (memcpy_kernel = 1)
+# ---------------------------------------------------------------------------------------------------------------------------------
+EW_TRIP = 8192 * 256 + 1          # quads (lanes) of the one second-trip case of each kernel: one past ew_grid's 8192 blocks of 256
+EW_LONG_MAX_ELEMS = 4 * EW_TRIP
+EW_MEMCPY_TRIP = 2048 * 256 * 16 + 16          # bytes: copy16_kernel's grid stops at 2048 blocks
+EW_KERNELS = ("add", "add_f32row", "levels", "add3d", "acc3d", "concat", "split", "cast_to", "cast_from", "sigmoid_fwd", "sigmoid_bwd", "memcpy")
+EW_DTYPES = ("f32", "bf16", "f16")
+EW_VIEWS = ("dense", "slab", "slice")          # slab: tokens [:, s:s + n] of [B, Lv, C]; slice: channels [c0:c0 + C] of a wider map
+
+
+def ew_lanes(c):
+    """lanes (quads, or elements of the scalar kernels, or 16-byte words of the copy) a case's grid-stride loop covers"""
+    k, s = c[1], c[3]
+    if k in ("add", "add_f32row"):
+        return s[0] // 4
+    if k == "levels":
+        return sum(s[0]) * s[1] // 4
+    if k in ("add3d", "acc3d"):
+        return s[0] * s[1] * s[2] // 4
+    if k in ("concat", "split"):
+        return s[0] * s[1] * sum(s[2]) // 4
+    if k == "memcpy":
+        return s[0] // 16
+    return s[0]
+
+
+def ew_second_trip(c):
+    if c[1] == "memcpy":
+        return c[3][0] % 16 == 0 and c[3][1] == 0 and ew_lanes(c) > 2048 * 256
+    return ew_lanes(c) > ew_grid(ew_lanes(c)) * 256
+
+
+def ew_in_domain(c):
+    _, k, d, s, _, _ = c
+    if k not in EW_KERNELS:
+        return False
+    if d not in (EW_DTYPES if k not in ("sigmoid_fwd", "sigmoid_bwd", "memcpy") else ("f32",)):
+        return False
+    if k in ("cast_to", "cast_from"):
+        return d in ("bf16", "f16") and s[0] >= 1
+    if k in ("add", "add_f32row"):
+        n, period = s
+        return n > 0 and n % 4 == 0 and period > 0 and period % 4 == 0 and period <= n
+    if k == "levels":
+        sizes, C = s
+        return 1 <= len(sizes) <= 4 and all(x > 0 for x in sizes) and C > 0 and C % 4 == 0
+    if k in ("add3d", "acc3d"):
+        B, rows, cols = s[:3]
+        return B > 0 and rows > 0 and cols > 0 and cols % 4 == 0 and all(v in EW_VIEWS for v in s[3:]) and len(s) == (6 if k == "add3d" else 5)
+    if k in ("concat", "split"):
+        B, C, parts = s
+        return B > 0 and C > 0 and C % 4 == 0 and 1 <= len(parts) <= 8 and all(x > 0 for x in parts)
+    if k == "memcpy":
+        return s[0] > 0 and s[1] in (0, 4, 8)
+    return s[0] >= 1
+
+
+def _ew_rows():
+    """(kernel, dtype, shape, what the row is there for); shape per kernel: add / add_f32row (n, period); levels ((rows of each level), C);
+    add3d (B, rows, cols, view of a, of b, of out); acc3d (B, rows, cols, view of dst, of src); concat / split (B, C, (tokens of each part));
+    cast_to / cast_from (n,); sigmoid_* (n,); memcpy (bytes, byte offset of both pointers off a 16-byte boundary)"""
+    rows = []
+    every = lambda k, s, why: rows.extend((k, d, s, why) for d in EW_DTYPES)
+    for k in ("add", "add_f32row"):
+        every(k, (4, 4), "one lane: period == n == 4")
+        every(k, (1020, 1020), "255 quads, period == n")
+        every(k, (1020, 4), "255 quads, period 4: every quad reads the same one")
+        every(k, (1020, 340), "255 quads, a period that divides n")
+        every(k, (1020, 16), "255 quads, a period that does not divide n")
+        every(k, (1024, 1024), "256 quads, period == n")
+        every(k, (1024, 256), "256 quads, a period that divides n")
+        every(k, (1024, 48), "256 quads, a period that does not divide n")
+        every(k, (1028, 1028), "257 quads, period == n")
+        every(k, (1028, 4), "257 quads, period 4")
+        every(k, (1028, 24), "257 quads, a period that does not divide n")
+        rows.append((k, "bf16", (EW_LONG_MAX_ELEMS, 4000), "the second trip; a period that does not divide n"))
+    every("levels", ((1,), 4), "L = 1, one row, one lane")
+    every("levels", ((7,), 100), "L = 1")
+    every("levels", ((5, 1), 100), "L = 2, the last level of one row")
+    every("levels", ((1, 9), 256), "L = 2, the first level of one row")
+    every("levels", ((3, 9, 1), 256), "L = 3, the last level of one row")
+    every("levels", ((4, 1, 6), 4), "L = 3, the middle level of one row")
+    every("levels", ((1, 6, 2, 1), 4), "L = 4, first and last level of one row")
+    every("levels", ((64, 1, 17, 3), 100), "L = 4, C = 100")
+    every("levels", ((200, 55), 4), "255 quads")
+    every("levels", ((256,), 4), "256 quads")
+    every("levels", ((1, 255, 1), 4), "257 quads")
+    rows.append(("levels", "bf16", ((2097000, 1, 152), 4), "the second trip: 2 097 153 rows of one quad, a level of one row in the middle"))
+    for k, nv in (("add3d", 3), ("acc3d", 2)):
+        dense = ("dense",) * nv
+        every(k, (1, 1, 4) + dense, "one lane: B = 1, rows = 1")
+        every(k, (3, 5, 68) + dense, "255 quads, all dense")
+        every(k, (2, 8, 64) + dense, "256 quads, all dense")
+        every(k, (1, 257, 4) + dense, "257 quads, B = 1")
+        for i in range(nv):
+            for v in ("slab", "slice"):
+                views = tuple(v if j == i else "dense" for j in range(nv))
+                every(k, (3, 5, 68) + views, "operand %d is a %s, the others dense" % (i, v))
+        every(k, (2, 7, 36) + ("slab", "slice", "slab")[:nv], "every operand strided")
+        every(k, (2, 7, 36) + ("slice", "slab", "slice")[:nv], "every operand strided, the other way round")
+        every(k, (1, 9, 20) + ("slice",) * nv, "B = 1, channel slices")
+        every(k, (3, 1, 12) + ("slab",) * nv, "rows = 1, token slabs")
+        rows.append((k, "bf16", (1, EW_TRIP, 4) + dense, "the second trip"))
+    for k in ("concat", "split"):
+        every(k, (1, 4, (1,)), "one part of one token, one lane")
+        every(k, (3, 64, (7,)), "one part")
+        every(k, (1, 64, (1, 4, 9, 36)), "4 parts, a part of one token first (the pyramid-pooling tokens)")
+        every(k, (3, 4, (36, 9, 4, 1)), "4 parts, a part of one token last")
+        every(k, (3, 64, (5, 1, 3, 2)), "4 parts, a part of one token in the middle")
+        every(k, (1, 4, (1, 2, 3, 4, 5, 6, 7, 8)), "8 parts, a part of one token first")
+        every(k, (3, 64, (2, 1, 2, 1, 3, 1, 2, 1)), "8 parts, parts of one token in the middle and last")
+        every(k, (3, 4, (50, 35)), "255 quads")
+        every(k, (1, 4, (255, 1)), "256 quads")
+        every(k, (1, 4, (1, 256)), "257 quads")
+        rows.append((k, "bf16", (1, 4, (2097152, 1)), "the second trip; the last part is the one token past the grid"))
+    for k in ("cast_to", "cast_from"):
+        for d in ("bf16", "f16"):
+            for n in (1, 3, 255, 257):
+                rows.append((k, d, (n,), "n = %d (no multiple-of-4 rule)" % n))
+        rows.append((k, "f16" if k == "cast_to" else "bf16", (EW_TRIP,), "the second trip"))
+    for k in ("sigmoid_fwd", "sigmoid_bwd"):
+        rows.append((k, "f32", (1,), "one element"))
+        rows.append((k, "f32", (257,), "a second block of one element"))
+        rows.append((k, "f32", (2443,), "the grid over [-30, 30] and +-100"))
+        rows.append((k, "f32", (EW_TRIP,), "the second trip"))
+    rows.append(("memcpy", "f32", (16, 0), "16 bytes: one lane"))
+    rows.append(("memcpy", "f32", (4096 + 16, 0), "257 lanes"))
+    rows.append(("memcpy", "f32", (24, 0), "a size that is no multiple of 16: the runtime's copy"))
+    rows.append(("memcpy", "f32", (4096 + 8, 0), "4104 bytes: the runtime's copy"))
+    rows.append(("memcpy", "f32", (32, 4), "pointers 4 bytes off a 16-byte boundary: the runtime's copy"))
+    rows.append(("memcpy", "f32", (4096, 8), "pointers 8 bytes off: the runtime's copy"))
+    rows.append(("memcpy", "f32", (EW_MEMCPY_TRIP, 0), "8 388 624 bytes: copy16_kernel's 2048 blocks stride"))
+    return rows
+
+
+def ew_cases(seed=2919):
+    """(id, kernel, dtype, shape, why, seed)"""
+    return [("ew-%d" % i,) + row + (seed + i,) for i, row in enumerate(_ew_rows())]
+
+
+def _ew_is(k):
+    return lambda c: c[1] == k
+
+
+def _ew_period(kind):
+    def pred(c):
+        if c[1] not in ("add", "add_f32row") or ew_second_trip(c):
+            return False
+        n, period = c[3]
+        return {"== n": period == n, "4": period == 4 and n > 4, "divides n": 4 < period < n and n % period == 0, "does not divide n": n % period != 0}[kind]
+    return pred
+
+
+EW_REGIMES = [("kernel: %s, %s" % (k, d), (lambda k_, d_: lambda c: c[1] == k_ and c[2] == d_)(k, d)) for k in EW_KERNELS for d in EW_DTYPES
+              if not (k in ("sigmoid_fwd", "sigmoid_bwd", "memcpy") and d != "f32") and not (k in ("cast_to", "cast_from") and d == "f32")] + [
+    ("second trip: %s" % k, (lambda k_: lambda c: c[1] == k_ and ew_second_trip(c))(k)) for k in EW_KERNELS] + [
+    ("%d lane%s" % (q, "s" if q > 1 else ""), (lambda q_: lambda c: c[1] != "memcpy" and ew_lanes(c) == q_)(q)) for q in (1, 255, 256, 257)] + [
+    ("add: period %s" % kd, _ew_period(kd)) for kd in ("== n", "4", "divides n", "does not divide n")] + [
+    ("levels: L = %d" % l, (lambda l_: lambda c: c[1] == "levels" and len(c[3][0]) == l_)(l)) for l in (1, 2, 3, 4)] + [
+    ("levels: a level of one row", lambda c: c[1] == "levels" and 1 in c[3][0]),
+    ("levels: the last level of one row", lambda c: c[1] == "levels" and len(c[3][0]) > 1 and c[3][0][-1] == 1),
+] + [("levels: C = %d" % k, (lambda k_: lambda c: c[1] == "levels" and c[3][1] == k_)(k)) for k in (4, 100, 256)] + [
+    ("%s: operand %d a %s, the others dense" % (k, i, v),
+     (lambda k_, i_, v_: lambda c: c[1] == k_ and c[3][3 + i_] == v_ and all(x == "dense" for j, x in enumerate(c[3][3:]) if j != i_))(k, i, v))
+    for k, nv in (("add3d", 3), ("acc3d", 2)) for i in range(nv) for v in ("slab", "slice")] + [
+    ("%s: every operand strided" % k, (lambda k_: lambda c: c[1] == k_ and "dense" not in c[3][3:])(k)) for k in ("add3d", "acc3d")] + [
+    ("%s: B = 1" % k, (lambda k_: lambda c: c[1] == k_ and c[3][0] == 1 and not ew_second_trip(c))(k)) for k in ("add3d", "acc3d")] + [
+    ("%s: rows = 1" % k, (lambda k_: lambda c: c[1] == k_ and c[3][1] == 1)(k)) for k in ("add3d", "acc3d")] + [
+    ("%s: %d part%s" % (k, n, "s" if n > 1 else ""), (lambda k_, n_: lambda c: c[1] == k_ and len(c[3][2]) == n_ and not ew_second_trip(c))(k, n))
+    for k in ("concat", "split") for n in (1, 4, 8)] + [
+    ("concat / split: a part of one token %s" % w, (lambda w_: lambda c: c[1] in ("concat", "split") and len(c[3][2]) > 1 and {
+        "first": c[3][2][0] == 1, "last": c[3][2][-1] == 1, "in the middle": 1 in c[3][2][1:-1]}[w_])(w)) for w in ("first", "last", "in the middle")] + [
+    ("concat / split: B = %d" % b, (lambda b_: lambda c: c[1] in ("concat", "split") and c[3][0] == b_)(b)) for b in (1, 3)] + [
+    ("concat / split: C = %d" % k, (lambda k_: lambda c: c[1] in ("concat", "split") and c[3][1] == k_)(k)) for k in (4, 64)] + [
+    ("cast: n = %d" % n, (lambda n_: lambda c: c[1] in ("cast_to", "cast_from") and c[3][0] == n_)(n)) for n in (1, 3, 255, 257)] + [
+    ("memcpy: the copy kernel", lambda c: c[1] == "memcpy" and c[3][0] % 16 == 0 and c[3][1] == 0),
+    ("memcpy: a size that is no multiple of 16", lambda c: c[1] == "memcpy" and c[3][0] % 16 != 0),
+    ("memcpy: misaligned pointers", lambda c: c[1] == "memcpy" and c[3][1] != 0)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 CASES = {
     "batchnorm": bn_cases(), "groupnorm": gn_cases(), "groupnorm_levels": gnl_cases(), "layernorm": ln_cases(),
     "resize": resize_cases(), "maxpool": maxpool_cases(), "adaptive_pool": adaptive_cases(), "pyramid": pyramid_cases(),
     "mha": mha_cases(), "msda": msda_cases(), "gconv": gconv_cases(), "conv": conv_cases(),
     "loss": loss_cases(), "step": step_cases(), "areas": areas_cases(),
+    "dropout": drop_cases(), "layernorm_drop": lnd_cases(), "conv_drop": cdrop_cases(), "elementwise": ew_cases(),
 }
 REGIMES = {
     "batchnorm": BN_REGIMES, "groupnorm": GN_REGIMES, "groupnorm_levels": GNL_REGIMES, "layernorm": LN_REGIMES,
     "resize": RESIZE_REGIMES, "maxpool": MAXPOOL_REGIMES, "adaptive_pool": ADAPTIVE_REGIMES, "pyramid": PYRAMID_REGIMES,
     "mha": MHA_REGIMES, "msda": MSDA_REGIMES, "gconv": GCONV_REGIMES, "conv": CONV_REGIMES,
     "loss": LOSS_REGIMES, "step": STEP_REGIMES, "areas": AREAS_REGIMES,
+    "dropout": DROP_REGIMES, "layernorm_drop": LND_REGIMES, "conv_drop": CDROP_REGIMES, "elementwise": EW_REGIMES,
 }
 IN_DOMAIN = {
     "batchnorm": bn_in_domain, "groupnorm": gn_in_domain, "groupnorm_levels": gnl_in_domain, "layernorm": ln_in_domain,
     "resize": resize_in_domain, "maxpool": maxpool_in_domain, "adaptive_pool": adaptive_in_domain, "pyramid": pyramid_in_domain,
     "mha": mha_in_domain, "msda": msda_in_domain, "gconv": gconv_in_domain, "conv": conv_in_domain,
     "loss": loss_in_domain, "step": step_in_domain, "areas": areas_in_domain,
+    "dropout": drop_in_domain, "layernorm_drop": lnd_in_domain, "conv_drop": cdrop_in_domain, "elementwise": ew_in_domain,
 }
 
 
@@ -2811,7 +3342,10 @@ REGIME_MIN = {("maxpool", "k = 7"): 1, ("msda", "dref on a band pyramid (GRAD_GL
               ("loss", "second trip: wce_bwd_kernel weighted, pair"): 1, ("loss", "second trip: ohem_bwd_kernel"): 1,
               ("loss", "second trip: dice_bwd_kernel"): 1,
               ("step", "clip: the partial sums' grid strides"): 1, ("step", "sgd: stream_update's grid strides"): 1,
-              ("step", "adamw: stream_update's grid strides"): 1, ("areas", "the grid strides (n > 1024 x 4096)"): 1}
+              ("step", "adamw: stream_update's grid strides"): 1, ("areas", "the grid strides (n > 1024 x 4096)"): 1,
+              # dropout / elementwise: one case per kernel above the ordinary size cap, the second trip round its grid-stride loop
+              ("dropout", "element: the second trip (n > 8192 x 1024)"): 1}
+REGIME_MIN.update({("elementwise", "second trip: %s" % k): 1 for k in EW_KERNELS})
 
 
 def regime_hits(op):

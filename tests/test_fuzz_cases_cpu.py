@@ -452,3 +452,55 @@ def test_window_cases():
 def test_the_docstring_table_is_current():
     for line in fc.regime_table().splitlines():
         assert line.rstrip() in fc.__doc__, "tests/fuzz_cases.py: the docstring's regime table is stale; regime_table() gives\n" + fc.regime_table()
+
+
+def test_dropout_elementwise_case_sizes():
+    """one second-trip case per kernel above MAX_ELEMS, at 8192 x 256 + 1 lanes (2048 x 256 + 1 for the copy kernel); everything else small"""
+    big = [c for c in fc.CASES["dropout"] if fc.drop_n(c) > fc.MAX_ELEMS]
+    assert [fc.drop_n(c) for c in big] == [fc.DROP_LONG_MAX_ELEMS] and fc.DROP_LONG_MAX_ELEMS == fc.STEP_LONG_MAX_ELEMS - 3
+    assert {fc.drop_n(c) for c in fc.CASES["dropout"] if c[1] == "element"} == {4, 1020, 1024, 1028, fc.DROP_LONG_MAX_ELEMS}
+    assert {c[3] for c in fc.CASES["dropout"]} == set(fc.DROP_PS)
+    from tests import dropout_reference as dr
+    for c in fc.CASES["dropout"]:          # a channel-mode case that drops at all has planes of both kinds (a wrong plane index cannot hide)
+        if c[1] == "channel" and c[3] >= 0.1:
+            planes = dr.channel_mask(c[8], c[6], c[3], fc.drop_n(c), c[2][1], c[2][2]).reshape(c[2][0], c[2][1], c[2][2])[:, 0]
+            assert 0 < int(planes.sum()) < planes.size, c[0]
+    for c in fc.CASES["layernorm_drop"]:
+        assert c[1] * c[2] * c[3] <= fc.MAX_ELEMS and c[1] * c[2] <= 700
+    assert {c[3] for c in fc.CASES["layernorm_drop"]} == set(fc.LND_CS)
+    for c in fc.CASES["conv_drop"]:
+        assert c[1] * max(c[3], c[5]) <= fc.MAX_ELEMS and c[2] * c[4] <= fc.MAX_ELEMS
+    assert ({c[1] for c in fc.CASES["conv_drop"]}, {c[2] for c in fc.CASES["conv_drop"]}, {c[4] for c in fc.CASES["conv_drop"]}) == (
+        set(fc.CDROP_MS), set(fc.CDROP_CS), set(fc.CDROP_OCS))
+    # a case emrt_conv2d_drop would refuse is no case: an output row that is not whole 16-byte chunks, in either type
+    assert fc.conv_drop_vec_ok(64, 64, 64, 72, 76, 4) and not fc.conv_drop_vec_ok(64, 64, 64, 72, 74, 4) and not fc.conv_drop_vec_ok(64, 64, 64, 72, 76, 2) and not fc.conv_drop_vec_ok(63, 8, 12, 8, 8, 2)
+    assert not fc.cdrop_in_domain(fc.CASES["conv_drop"][0][:5] + (12,) + fc.CASES["conv_drop"][0][6:])
+    trips = {}
+    for c in fc.CASES["elementwise"]:
+        lanes, bytes_ = fc.ew_lanes(c), {"f32": 4, "bf16": 2, "f16": 2}[c[2]]
+        if fc.ew_second_trip(c):
+            assert c[1] not in trips and lanes == (2048 * 256 + 1 if c[1] == "memcpy" else fc.EW_TRIP), c
+            trips[c[1]] = lanes
+        else:
+            assert lanes * 4 <= fc.MAX_ELEMS, c
+    assert sorted(trips) == sorted(fc.EW_KERNELS) and fc.EW_LONG_MAX_ELEMS == fc.DROP_LONG_MAX_ELEMS
+
+
+def test_attention_dropout_cases_leave_nothing_out_of_the_mask_comparison():
+    """tests/test_gpu_mha_fuzz.py compares the device's kept / dropped pattern with the host model except where the float64 reference probability
+    is below 1e-30.  Every dropout case runs all three paths (bf16 as dispatched: the MFMA kernels, staging or re-deriving the probabilities by
+    mha_bwd_split; mha_valu = 1 and fp32: the VALU kernels on either side of mha_bwd_stages_probs), so: each side of each threshold has a dropout
+    case that leaves out nothing, and no case leaves out more than half."""
+    import torch
+    from tests import mha_reference as mr
+    shares = {}
+    for c in fc.CASES["mha"]:
+        if c[5] > 0:
+            for d in mr.DTYPES:
+                q, k = mr.make_inputs(c[4], c[1], c[2], c[3], c[7], d)[:2]
+                shares[(c[0], d)] = float((torch.softmax(mr.scores(q, k), -1) < 1e-30).double().mean())
+    assert len(shares) == 32 and max(shares.values()) <= 0.5
+    for d in mr.DTYPES:
+        for staged in (True, False):
+            assert any(shares[(c[0], d)] == 0.0 for c in fc.CASES["mha"] if c[5] > 0 and fc.mha_bwd_stages_probs(c[3]) == staged), (d, staged)
+    assert max(shares.values()) == 0.0          # today: nothing is left out in any dropout case

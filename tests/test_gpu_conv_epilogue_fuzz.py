@@ -51,6 +51,7 @@ from emrt_amd import functional as Fn                     # noqa: E402
 from emrt_amd import nn as hnn                            # noqa: E402
 from emrt_amd._lib import EmrtHipError                    # noqa: E402
 from emrt_amd.runtime import ctx, F32, BF16, F16          # noqa: E402
+from tests import dropout_reference as dr                 # noqa: E402
 from tests import fuzz_cases as fc                        # noqa: E402
 from tests.hip_utils import init, close_gemm, close_f16, ulp16, Holder      # noqa: E402
 from tests.test_gpu_resnext import _P, _TD, _padded, _whole, _rounded       # noqa: E402
@@ -448,3 +449,60 @@ def test_conv_epilogue_refusals_launch_nothing():
         L.call("emrt_conv2d_dgrad_multi", arr, 2, F32, st)
     torch.cuda.synchronize()
     assert torch.equal(buf, before) and torch.equal(stats, sb)
+
+
+# ---- emrt_conv2d_drop: dropout(relu(x w^T + bias)) with the mask drawn in the 64x64 tile's epilogue ---------------------------------------------
+DROP_SWEEP = fc.CASES["conv_drop"]
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", DROP_SWEEP, ids=[c[0] for c in DROP_SWEEP])
+def test_conv2d_drop_mask_is_the_models(dtype, case):
+    """emrt_conv2d_drop called directly over fuzz_cases.CASES["conv_drop"]: M on both sides of the 64-row tile, one to sixteen N tiles, K of one
+    chunk to several k-tiles, the output dense and as a slice of wider rows (ldout > OC), the input once with ldin > C; pre-activations of both
+    signs.  The mask is the host model's (tests/dropout_reference.py: drop_words8 at (m * OC + n0) >> 3 -- OC, not ldout), bit for bit: an
+    element the model drops is exactly 0; an element it keeps equals relu(x w^T + bias) / (1 - p) in float64 on the rounded operands within
+    close_gemm's bound on relu(linear) times ks, so wherever the kept value stands clear of zero the device's mask is read off the output and
+    must be the model's.  The columns beside the slice and the rows behind it keep their sentinel bits; the inputs are not written."""
+    cid, M, C, ldin, OC, ldout, p, salt, _, seed = case
+    c = init(dtype, seed=seed)
+    td = _TD[dtype]
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, C, generator=g).to(td)
+    w = (torch.randn(OC, C, generator=g) / math.sqrt(C)).to(td)
+    b = torch.randn(OC, generator=g) * 0.3
+    lin = hnn.Linear(C, OC)
+    with torch.no_grad():
+        lin.weight.copy_(w.float())
+        lin.bias.copy_(b)
+    holder = Holder(lin=lin).place()
+    xbuf = torch.full((M + 2, ldin), 1.0e4, dtype=td)          # (what lies beside and behind the input would show in every output)
+    xbuf[:M, :C] = x
+    xd = xbuf.cuda()
+    out = torch.full((M + 2, ldout), SENTINEL, dtype=td, device="cuda")
+    before = (holder.store.packed.clone(), holder.store.master.clone())
+    _lib.lib().call("emrt_conv2d_drop", _P(xd), ctypes.c_void_p(lin.gw.fwd_ptr), _P(out), _P(lin.gw.bias), M, C, ldin, OC, ldout, float(p), c.seed_ptr,
+                    salt, dtype, c.stream)
+    torch.cuda.synchronize()
+    keep = torch.from_numpy(dr.conv_drop_mask(dr.context_seed(seed), salt, p, M, OC))
+    got = out[:M, :OC].cpu()
+    fresh = torch.full((M + 2, ldout), SENTINEL, dtype=td)
+    it = torch.int32 if td == torch.float32 else torch.int16
+    assert torch.equal(out.cpu().view(it)[:, OC:], fresh.view(it)[:, OC:]) and torch.equal(out.cpu().view(it)[M:], fresh.view(it)[M:]), \
+        "%s: written beside the slice (columns >= %d of rows of %d) or behind it" % (cid, OC, ldout)
+    assert bool(torch.isfinite(got.float()).all()), "%s: an element of the slice was not written" % cid
+    assert torch.equal(xd.cpu().view(it), xbuf.view(it)) and torch.equal(holder.store.packed, before[0]) and torch.equal(holder.store.master, before[1])
+    assert bool((got[~keep] == 0).all()), "%s: %d elements the model drops are not 0" % (cid, int((got[~keep] != 0).sum()))
+    r = (x.double() @ w.double().t() + b.double()).clamp_min(0)
+    assert bool((r > 0).any()) and bool((r == 0).any())          # pre-activations of both signs
+    ks = 1.0 / (1.0 - float(torch.tensor(p, dtype=torch.float32)))
+    rms = r.pow(2).mean().sqrt().item()
+    bound = (2e-4 * r + 2e-4 * max(rms, 1e-30)) if dtype == F32 else (2.0 ** -8 * r + 2.0 ** -10 * rms)          # close_gemm's bound on relu(linear)
+    want = torch.where(keep, r * ks, torch.zeros_like(r))
+    err = (got.double() - want).abs()
+    bad = err > bound * ks
+    assert not bool(bad.any()), "%s: %d of %d elements beyond the bound; worst error / bound %.3f; first at %s: got %.6g, want %.6g (model keeps: %s)" % (
+        cid, int(bad.sum()), bad.numel(), (err / (bound * ks)).max().item(), torch.nonzero(bad)[0].tolist(), got[bad][0].item(), want[bad][0].item(),
+        bool(keep[bad][0]))
+    clear = r * ks > 2 * bound * ks          # here a kept value cannot be mistaken for a dropped one: the device's mask, read back
+    assert torch.equal((got != 0)[clear], keep[clear]) and int(clear.sum()) >= max(1, M * OC // 5)          # (about half the pre-activations are positive)

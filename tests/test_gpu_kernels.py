@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 from emrt_amd import functional as Fn          # noqa: E402
 from emrt_amd import nn as hnn                  # noqa: E402
 from emrt_amd.runtime import ctx, F32, BF16, Tape   # noqa: E402
-from tests.hip_utils import close_gemm, init, dev_map, host_map, dev, host, rnd, Holder, close   # noqa: E402
+from tests.hip_utils import close_gemm, init, dev_map, host_map, dev, host, rnd, Holder, close, TOL   # noqa: E402
 
 DTYPES = [F32, BF16]
 
@@ -490,13 +490,22 @@ def test_layer_norm_residual_post(dtype):
     layer_norm_case(dtype, 3, 113, 256, "a+b,post")
 
 
-def layer_norm_case(dtype, B, L, C, form, seed=7, spread=False, dead_row=None, ref=torch.float32):
+def layer_norm_case(dtype, B, L, C, form, seed=7, spread=False, dead_row=None, ref=torch.float32, drop=None):
     """hnn.LayerNorm as ln(a) / ln(a, b) / ln(a, b, post=) (form "a" / "a+b" / "a+b,post") against F.layer_norm + autograd in `ref` precision on
     the rounded operands.  spread: a = (randn * s_c + m_c) * s_r + m_r with per-channel and per-row scales in [0.5, 2] and shifts in [-2, 2]
-    (rows differ in their statistics by far more than any tolerance); dead_row: that row of the LayerNorm input is all zeros."""
-    c = init(dtype)
+    (rows differ in their statistics by far more than any tolerance); dead_row: that row of the LayerNorm input is all zeros.
+    Forms "a+b,qpos" (layer_norm(q_pos=) also writes q = out + pos and sums q's gradient into out's) and "a+b,addend" (identity_from: the
+    gradient of a later tensor t = f(a) + a is summed into dz_a by the backward kernel) run the other two arms of the kernels.
+    drop = (p, salt): the branch dropout drawn inside the kernels.  The mask is NOT read back: it is the host model's
+    (tests/dropout_reference.layernorm_mask: drop_quad at (row * C + c) >> 2 under the context's seed word, here init(dtype, seed)), so the
+    reference branch is round_T(mask * b * ks); out, q, dz_a, dgamma and dbeta come from autograd through it, and dz_b = mask *
+    round_T(dz without the addend) * ks -- the two roundings the kernels document (csrc/norm.hip: "rounded through T exactly as a separate
+    dropout kernel would store it", "the mask is applied to the STORED dz").  An element the model drops must be exactly 0 in dz_b, and where
+    dz stands clear of zero dz_b is non-zero exactly where the model keeps.  The bounds are the same with and without dropout."""
+    c = init(dtype, seed if drop is not None else 0)
     g = torch.Generator().manual_seed(seed)
-    with_b, with_post = form != "a", form == "a+b,post"
+    with_b, with_post, with_q, with_addend = form != "a", form == "a+b,post", form == "a+b,qpos", form == "a+b,addend"
+    assert drop is None or with_b
     if spread:
         s_c, m_c = torch.rand(C, generator=g) * 1.5 + 0.5, torch.rand(C, generator=g) * 4 - 2
         s_r, m_r = torch.rand(B, L, 1, generator=g) * 1.5 + 0.5, torch.rand(B, L, 1, generator=g) * 4 - 2
@@ -508,35 +517,83 @@ def layer_norm_case(dtype, B, L, C, form, seed=7, spread=False, dead_row=None, r
             b.view(B * L, C)[dead_row] = 0.0
             dead[dead_row] = True
         a, b, post = rnd(a), rnd(b), rnd(post)
-        population_floor("ln", (a + b if with_b else a).reshape(B * L, C), (1,), dead)
     else:
         a, b, post = (rnd(torch.randn(B, L, C, generator=g)) for _ in range(3))
+    mask, ks, beff = None, 1.0, b
+    if drop is not None:
+        from tests import dropout_reference as dr
+        p, salt = drop
+        mask = torch.from_numpy(dr.layernorm_mask(dr.context_seed(seed), salt, p, B * L, C)).view(B, L, C)
+        ks = float(dr.keep_scale(p))
+        beff = rnd(torch.where(mask, b * ks, torch.zeros_like(b)))          # the branch as a separate dropout kernel would store it
+        assert 0 < int(mask.sum()) < mask.numel() or mask.numel() < 64
+    if spread:
+        population_floor("ln", (a + beff if with_b else a).reshape(B * L, C), (1,), dead)
     ln = hnn.LayerNorm(C)
     with torch.no_grad():
         ln.weight.copy_(torch.rand(C, generator=g) + 0.5)
         ln.bias.copy_(torch.randn(C, generator=g) * 0.3)
     gam, bet = ln.weight.detach().clone(), ln.bias.detach().clone()
     Holder(ln=ln).place()
-    ar, br_, pr = (leaf(t, ref) for t in (a, b, post))
+    ar, br_, pr = (leaf(t, ref) for t in (a, beff, post))
     gr, ber = leaf(gam, ref), leaf(bet, ref)
-    o = F.layer_norm(ar + br_ if with_b else ar, (C,), gr, ber, 1e-5)
+    zr = ar + br_ if with_b else ar
+    if with_b:
+        zr.retain_grad()
+    o = F.layer_norm(zr, (C,), gr, ber, 1e-5)
     if with_post:
         o = o + pr
     dy = rnd(torch.randn(o.shape, generator=g))
-    o.backward(dy.to(ref))
+    pos = rnd(torch.randn(L, C, generator=g)) if with_q else None
+    dyq = rnd(torch.randn(o.shape, generator=g)) if with_q else None
+    extra = rnd(torch.randn(o.shape, generator=g)) if with_addend else None
+    loss = (o * (dy + dyq if with_q else dy).to(ref)).sum()          # (q = round(out) + pos: its gradient reaches out unchanged)
+    if with_addend:
+        loss = loss + (ar * extra.to(ref)).sum()          # the identity path of t = f(a) + a
+    loss.backward()
     ad, bd, pd = dev(a), dev(b) if with_b else None, dev(post) if with_post else None
+    kw, got_q = {}, []
+    if drop is not None:
+        kw.update(drop_p=drop[0], drop_salt=drop[1])
+    if with_q:
+        kw.update(q_pos=dev(pos), q_bgrad=got_q.append)
+    td = dev(torch.zeros(B, L, C)) if with_addend else None
+    if with_addend:
+        kw.update(identity_from=td)
     tape = Tape()
     c.tape = tape
-    y = ln(ad, bd, post=pd)
+    y = ln(ad, bd, post=pd, **kw)
     c.tape = None
+    y, q = y if with_q else (y, None)
     watched = [t for t in (ad, bd, pd) if t is not None]
     for t in watched:
         tape.watch(t)
     close("ln fwd", host(y), o.detach(), dtype)
-    grads = run_bwd(tape, [(y, dev(dy))], watched)
+    if with_q:
+        close("ln q", host(q), rnd(host(y)) + pos, dtype)
+        assert torch.equal(host(q), rnd(rnd(host(y)) + pos))          # q really is the stored out plus pos, rounded once
+    outs = [(y, dev(dy))] + ([(q, dev(dyq))] if with_q else []) + ([(td, dev(extra))] if with_addend else [])
+    from emrt_amd import _lib
+    _lib.lib().start_record()
+    try:
+        grads = run_bwd(tape, outs, watched)
+    finally:
+        rec = _lib.lib().stop_record()
+    (bwd_args,) = [args for name, args in rec if name == "emrt_layernorm_bwd"]
+    assert (bwd_args[15] is not None) == with_addend and (bwd_args[16] is not None) == with_q, "the backward did not take the addend / q's gradient"
+    if with_q:
+        assert len(got_q) == 1 and torch.equal(host(got_q[0]), dyq)
     close("ln da", host(grads[0]), ar.grad, dtype, 2.0)
-    if with_b:
+    if with_b and drop is None:
         close("ln db", host(grads[1]), br_.grad, dtype, 2.0)
+    elif with_b:
+        dzr = rnd(zr.grad.float())          # dz without the addend, as the kernel stores it
+        db = host(grads[1])
+        close("ln db", db, torch.where(mask, dzr * ks, torch.zeros_like(dzr)), dtype, 2.0)
+        assert bool((db[~mask] == 0).all()), "ln db: %d elements the model drops are not 0" % int((db[~mask] != 0).sum())
+        tol = TOL[dtype]
+        clear = dzr.abs() * ks > 2.0 * (tol["atol"] * 2.0 + tol["rtol"] * dzr.abs() * ks)          # a kept value here cannot have come out as 0
+        assert torch.equal((db != 0)[clear], mask[clear]), "ln db: kept / dropped differs from the model"
     if with_post:
         close("ln dpost", host(grads[2]), pr.grad, dtype)
     sc = math.sqrt(B * L)

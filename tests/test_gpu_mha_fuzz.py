@@ -9,7 +9,9 @@ fuzz_cases.mha_path; bf16 runs three ways -- as dispatched, with mha_valu = 1, w
 the exact values (each kernel is right, not: the kernels agree).  Dropout cases read the device's own dropped probabilities out of the forward
 with one-hot values (ceil(L / 32) tiny launches), per kernel family; kept entries must equal P / (1 - p) to the output's rounding, the
 dropped fraction must be p (floor(65536 p) / 65536 in the MFMA kernels) within 5 standard errors, and o, dq, dk, dv must equal the closed
-form with THAT mask -- which ties the backward's re-derived masks (row pass, column pass, and the VALU kernel's second derivation past
+form with THAT mask (and that mask must be the host model's, tests/dropout_reference.py, bit for bit at every position whose reference
+probability is at least 1e-30: mha_drop4 at ((b M + m) L + i) 32 + (j >> 2) in the MFMA kernels, uniform01 at ((b M + m) L + i) L + j in the
+VALU kernels) -- which ties the backward's re-derived masks (row pass, column pass, and the VALU kernel's second derivation past
 L = 110) to the forward's.  The direct layouts write into wider buffers pre-filled with a NaN bit pattern, two guard rows behind: everything
 outside rows < B L, columns < E stays bit-identical, everything inside is finite.
 
@@ -38,6 +40,7 @@ from emrt_amd import _lib                                                       
 from emrt_amd import functional as Fn                                            # noqa: E402
 from emrt_amd.functional import P                                                # noqa: E402
 from emrt_amd.runtime import ctx, F32, BF16, Tape                                # noqa: E402
+from tests import dropout_reference as dr                                        # noqa: E402
 from tests import fuzz_cases as fc                                               # noqa: E402
 from tests import mha_reference as mr                                            # noqa: E402
 from tests.hip_utils import init                                                 # noqa: E402
@@ -199,7 +202,7 @@ def _ids(cases):
 @pytest.mark.parametrize("case", CASES, ids=_ids(CASES))
 def test_mha_random_shapes(dtype, case):
     cid, B, M, L, regime, p, layout, seed = case
-    c = init(dtype)
+    c = init(dtype, seed if p > 0.0 else 0)          # a dropout case has its own seed word on the device, both halves non-zero
     d = NAME[dtype]
     ins = mr.make_inputs(regime, B, M, L, seed, d)
     q, k, v, dy = (_rows(t, c.tdtype) for t in ins)
@@ -220,6 +223,15 @@ def test_mha_random_shapes(dtype, case):
                     pd = _read_dropped_probs(layout, dtype, q, k, B, M, L, p, salt)
                     mask = (pd > 0).to(F64)
                     Pk = torch.softmax(mr.scores(ins[0], ins[1]), -1) / (1.0 - p)
+                    # kept / dropped against the host model of csrc/drop_hash.hpp, bit for bit (the seed word of init(dtype, seed)); only a position whose
+                    # reference probability is below 1e-30 is left out -- a zero read there is not a drop (the case list has none: the CPU suite checks)
+                    model = torch.from_numpy((dr.mha_mfma_mask if key == 1 else dr.mha_valu_mask)(dr.context_seed(seed), salt, p, B, M, L))
+                    live = Pk * (1.0 - p) >= 1e-30
+                    differ = ((pd > 0) != model) & live
+                    assert not bool(differ.any()), "%s %s path %d: the device keeps / drops %d of %d positions differently from the model; first at %s" % (
+                        cid, arm, key, int(differ.sum()), int(live.sum()), torch.nonzero(differ)[0].tolist())
+                    print("[mha sweep] %s %s path %d: mask equals the model's; %.4f of the positions left out (reference probability < 1e-30)" % (
+                        cid, d, key, 1.0 - live.double().mean().item()))
                     off = ((pd - Pk * mask).abs() / (Pk * _kept_tolerance(ins[0], ins[1], dtype))).max().item()
                     p_eff = int(p * 65536.0) / 65536.0 if key == 1 else p
                     frac = 1.0 - mask.mean().item()

@@ -91,3 +91,20 @@ def test_layer_norm_random_shapes(dtype, case):
 def test_layer_norm_dead_row(dtype, B, L, C, form, row):
     """one all-zero row (with rows % 4 != 0, once the very last row)"""
     layer_norm_case(dtype, B, L, C, form, seed=2303, spread=True, dead_row=row, ref=F64)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", fc.CASES["layernorm_drop"], ids=_ids(fc.CASES["layernorm_drop"]))
+def test_layer_norm_branch_dropout_random_shapes(dtype, case):
+    """LN(a + dropout(b)) with the dropout drawn inside emrt_layernorm_fwd / _bwd, the mask held to the host model of csrc/drop_hash.hpp
+    (tests/dropout_reference.py) instead of being read back: every channel count on both sides of a 256-lane pass, rows % 4 != 0 and one
+    row, the post, q_pos and addend arms, p in {0.1, 0.5}, the backward under its default block shape and under ln_bwd_rows /
+    ln_bwd_max_blocks settings that change which rows a block walks (a block that re-derived another quad's word would mask dz_b wrongly)."""
+    _, B, L, C, form, p, salt, max_blocks, rows_knob, _, seed = case
+    Lb = _lib.lib()
+    old = [(k, Lb.set_tuning(k, v)) for k, v in (("ln_bwd_max_blocks", max_blocks), ("ln_bwd_rows", rows_knob))]
+    try:
+        layer_norm_case(dtype, B, L, C, form, seed=seed, spread=True, ref=F64, drop=(p, salt))
+    finally:
+        for k, v in old:
+            Lb.set_tuning(k, v)
