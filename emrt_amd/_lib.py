@@ -40,6 +40,12 @@ LATER_SIDE_LIBRARIES = {
     "rot": _side("rot", "_ROT_LIB", "EMRT_HIP_ROT_LIB", "emrt_rot", "the quarter turn of the training augmentation"),      # DATA.AUGMENT.ROT90_PROB > 0
 }
 ROT_HEADER = LATER_SIDE_LIBRARIES["rot"].header
+# That dict is pinned to its one row as well (tests/test_rot90_cpu.py).  This one is the open end (build_ext.OPEN_LIBRARIES is the build's half): its
+# test asks that a row is in it and behaves like the others, never that the rows are its whole content, so the next library is one more row here.
+OPEN_SIDE_LIBRARIES = {
+    "bnd": _side("bnd", "_BND_LIB", "EMRT_HIP_BND_LIB", "emrt_bnd", "the boundary-aware scene evaluation"),      # SceneEvaluator(boundary=r)
+}
+BND_HEADER = OPEN_SIDE_LIBRARIES["bnd"].header
 
 _TRACE = bool(int(os.environ.get("EMRT_TRACE", "0")))
 
@@ -301,7 +307,7 @@ def lib():
 # ---- the side libraries ---------------------------------------------------------------------------------------------------------------------------
 
 class _ExtLib:
-    """A library beside libemrt_hip.so (a row of SIDE_LIBRARIES or LATER_SIDE_LIBRARIES), bound from its own header: call / query / last_error as _Lib, with the
+    """A library beside libemrt_hip.so (a row of SIDE_LIBRARIES, LATER_SIDE_LIBRARIES or OPEN_SIDE_LIBRARIES), bound from its own header: call / query / last_error as _Lib, with the
     library's own `<prefix>_last_error` string and its `<prefix>_version` checked to be 1.  No fallback: a missing library or symbol raises."""
 
     def __init__(self, path, header, prefix, what):
@@ -336,11 +342,16 @@ class _ExtLib:
 
 
 # The loaded side libraries, one module attribute per row (its `slot`): None until somebody asks for that library.  The tests put their stand-ins here.
-_AUG_LIB = _SMP_LIB = _LOSS_LIB = _TTA_LIB = _MST_LIB = _ROT_LIB = None
+_AUG_LIB = _SMP_LIB = _LOSS_LIB = _TTA_LIB = _MST_LIB = _ROT_LIB = _BND_LIB = None
+
+
+def side_libraries():
+    """SIDE_LIBRARIES, LATER_SIDE_LIBRARIES and OPEN_SIDE_LIBRARIES as one dict, in the order build_ext.all_libraries() builds them."""
+    return {**SIDE_LIBRARIES, **LATER_SIDE_LIBRARIES, **OPEN_SIDE_LIBRARIES}
 
 
 def side_lib(name):
-    row, slots = (SIDE_LIBRARIES[name] if name in SIDE_LIBRARIES else LATER_SIDE_LIBRARIES[name]), globals()
+    row, slots = side_libraries()[name], globals()
     if slots[row.slot] is None:
         slots[row.slot] = _ExtLib(row.path, row.header, row.prefix, row.what)
     return slots[row.slot]
@@ -368,3 +379,7 @@ def mst_lib():
 
 def rot_lib():
     return side_lib("rot")
+
+
+def bnd_lib():
+    return side_lib("bnd")

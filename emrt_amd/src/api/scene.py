@@ -20,6 +20,10 @@ Both take `tta_scales`, with any `tta`: a sequence of scales in [
 crop / s native pixels where it is cropped from the uint8 scene, and its logits are resampled back where they are accumulated -- two launches of
 libemrt_hip_mstta.so per model call, no scaled scene and no fp32 scene; the result is the mean class probability over every scale, covering
 footprint and variant.  None (the default) takes the paths above untouched and never loads that library.
+
+SceneEvaluator takes `boundary`: a radius r in 1..32 adds, per scene, the launches of libemrt_hip_bnd.so that mark the pixels within r
+of another class in the prediction and in the label map and count the ISPRS eroded-boundary areas and the Boundary IoU areas from them.  None
+(the default) issues what it always issued and never loads that library.
 """
 import ctypes
 from collections import namedtuple
@@ -333,6 +337,23 @@ class ScenePredictor:
         return out
 
 
+BOUNDARY_MAX_RADIUS = 32          # include/emrt_hip_bnd.h EMRT_BND_MAX_RADIUS
+BOUNDARY_SHAPES = {"disk": 0, "square": 1}          # include/emrt_hip_bnd.h EMRT_BND_DISK / EMRT_BND_SQUARE
+
+
+def check_boundary(boundary, shape):
+    """-> (radius or None, shape code); a radius that is no integer in 1..32 and an unknown shape are refused here, before anything is loaded"""
+    if shape not in BOUNDARY_SHAPES:
+        raise ValueError("boundary_shape must be one of %s, got %r" % (", ".join(BOUNDARY_SHAPES), shape))
+    if boundary is None:
+        return None, BOUNDARY_SHAPES[shape]
+    if isinstance(boundary, bool) or not isinstance(boundary, (int, np.integer)):
+        raise ValueError("boundary must be an integer radius in pixels, got %r" % (boundary,))
+    if not 1 <= int(boundary) <= BOUNDARY_MAX_RADIUS:
+        raise ValueError("boundary must be a radius in 1..%d, got %r" % (BOUNDARY_MAX_RADIUS, boundary))
+    return int(boundary), BOUNDARY_SHAPES[shape]
+
+
 class SceneEvaluator:
     """ev = SceneEvaluator(model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None, tta="none")
     tot = ev.evaluate(rank=0, nranks=1)     int64 [3, ncls] on the device: intersect, prediction and label areas of this rank's scenes
@@ -345,10 +366,19 @@ class SceneEvaluator:
     row.  Everything is enqueued on the current stream: no host copy of a pixel, no synchronisation.  Sums, counts, normalised logits and the
     prediction are allocated once per distinct scene shape and reused by every scene of that shape and by every later evaluation.
     crop_size / stride_size are (w, h) as in the configs (VAL.CROP_SIZE, VAL.STRIDE_SIZE); mean / std as transforms.Normalize takes them; tta as
-    ScenePredictor takes it (the argmax is then that of the mean class probability), and tta_scales likewise."""
+    ScenePredictor takes it (the argmax is then that of the mean class probability), and tta_scales likewise.
+
+    boundary=r (1..32), boundary_shape "disk" or "square": after each scene's emrt_segmentation_areas, emrt_bnd_runs and emrt_bnd_band mark the band of
+    the prediction and of the label map (include/emrt_hip_bnd.h; one runs map and two bands per scene shape, reused like the rest) and emrt_bnd_areas
+    counts into
+    ev.boundary_per_scene                   int64 [n_scenes, 2, 3, ncls]: [0] the three areas outside the label's band (the ISPRS eroded protocol),
+                                            [1] those of Boundary IoU; zeroed by evaluate(), rows of other ranks' scenes zero
+    ev.boundary_totals()                    its sum over the scenes, int64 [2, 3, ncls]
+    evaluate() and per_scene are what they are without it: the launches only read the prediction."""
 
     def __init__(self, model, bank, num_classes, crop_size, stride_size, mean, std, ignore_index=255, max_batch=32, scales=None,
-                 flip_horizontal=True, tta="none", tta_scales=None):
+                 flip_horizontal=True, tta="none", tta_scales=None, boundary=None, boundary_shape="disk"):
+        self.boundary, self.boundary_shape = check_boundary(boundary, boundary_shape)
         self.model, self.bank, self.ncls = model, bank, int(num_classes)
         self.crop, self.stride = check_windows(crop_size, stride_size)
         self.scales = None if scales is None else tuple(scales)
@@ -370,6 +400,33 @@ class SceneEvaluator:
         self.tta, self.codes = tta, check_tta(tta, self.crop, self.max_batch, self.scales)
         self.per_scene = torch.empty((len(bank), 3, self.ncls), dtype=torch.int64, device=bank.device)
         self._scratch = {}          # (H, W) -> (sums, counts, normalised logits, prediction)
+        self.boundary_per_scene = None
+        if self.boundary is not None:
+            self.boundary_per_scene = torch.empty((len(bank), 2, 3, self.ncls), dtype=torch.int64, device=bank.device)
+        self._bnd_scratch = {}      # (H, W) -> (runs, the prediction's band, the label's band), uint8 [H, W] each
+
+    def _boundary_buffers(self, H, W):
+        if (H, W) not in self._bnd_scratch:
+            self._bnd_scratch[(H, W)] = tuple(torch.empty((H, W), dtype=torch.uint8, device=self.bank.device) for _ in range(3))
+        return self._bnd_scratch[(H, W)]
+
+    def _count_boundary(self, i, pred, label):
+        """The bands of scene i's prediction (int32) and label map (uint8, where it lies in the bank) and the counts of both protocols: five
+        launches on the current stream.  The runs map is shared: the stream orders the prediction's column pass before the label's row pass."""
+        B, c = _lib.bnd_lib(), ctx()
+        H, W = self.bank.sizes[i]
+        run, band_pred, band_label = self._boundary_buffers(H, W)
+        for m, kind, band in ((pred, 0, band_pred), (label, 2, band_label)):
+            B.call("emrt_bnd_runs", Fn.P(m), kind, H, W, self.boundary, Fn.P(run), c.stream)
+            B.call("emrt_bnd_band", Fn.P(m), kind, Fn.P(run), H, W, self.boundary, self.boundary_shape, Fn.P(band), c.stream)
+        B.call("emrt_bnd_areas", Fn.P(pred), Fn.P(label), Fn.P(band_pred), Fn.P(band_label), H * W, self.ncls, self.ignore_index,
+               Fn.P(self.boundary_per_scene[i]), c.stream)
+
+    def boundary_totals(self):
+        """int64 [2, 3, ncls]: boundary_per_scene summed over this rank's scenes"""
+        if self.boundary is None:
+            raise ValueError("this SceneEvaluator was made without boundary=: there are no boundary counts")
+        return self.boundary_per_scene.sum(0)
 
     def _buffers(self, H, W):
         if (H, W) not in self._scratch:
@@ -407,8 +464,12 @@ class SceneEvaluator:
         L, c = Fn._L(), ctx()
         self.model.eval()
         L.call("emrt_memset", Fn.P(self.per_scene), 0, self.per_scene.numel() * 8, c.stream)
+        if self.boundary is not None:
+            L.call("emrt_memset", Fn.P(self.boundary_per_scene), 0, self.boundary_per_scene.numel() * 8, c.stream)
         for i in range(rank, len(self.bank), nranks):
             pred = self.predict(i)
             _, label = self.bank.scene(i)
             L.call("emrt_segmentation_areas", Fn.P(pred), Fn.P(label), 2, pred.numel(), self.ncls, self.ignore_index, Fn.P(self.per_scene[i]), c.stream)
+            if self.boundary is not None:
+                self._count_boundary(i, pred, label)
         return self.per_scene.sum(0)

@@ -8,7 +8,8 @@ all-reduce of the [3, ncls] int64 areas at the end when WORLD_SIZE > 1 (the refe
 image, val.py:164-170), then mIoU / Acc / Kappa / per-class F1 exactly as val.py:197-209 prints them.
 
 --data scenes evaluates the whole scenes of <DATA.DATA_PATH>/val_images + /val_labels at their own resolution: they are uploaded once as uint8
-(datasets.SceneBank) and api.scene.SceneEvaluator cuts, normalises, predicts and counts them on the device; one more line per scene.
+(datasets.SceneBank) and api.scene.SceneEvaluator cuts, normalises, predicts and counts them on the device; one more line per scene.  With --boundary R it also prints the ISPRS
+metrics on ground truth whose class boundaries are eroded by R pixels and Boundary IoU at that distance.
 """
 import argparse
 import os
@@ -21,7 +22,7 @@ from .config import get_config, update_config
 from .distributed import init_process_group
 from .runtime import BF16, F16, F32
 from .src.api import infer
-from .src.api.scene import TTA_MODES, check_tta_scales, refuse_scales_with_config
+from .src.api.scene import BOUNDARY_SHAPES, TTA_MODES, check_boundary, check_tta_scales, refuse_scales_with_config
 from .src.models import get_model
 from .src.utils import metrics
 
@@ -42,7 +43,22 @@ def parse_args(argv=None):
     p.add_argument("--tta_scales", default=None, type=float, nargs="+", metavar="S",
                    help="with --data scenes: window-level scales in [0.25, 4], e.g. 0.75 1.0 1.25, with any --tta (DESIGN.md 23); the class "
                         "probabilities of all scales and variants are averaged. Not with --multi_scales / VAL.MULTI_SCALES_VAL")
+    p.add_argument("--boundary", default=None, type=int, metavar="R",
+                   help="with --data scenes: also report the metrics on ground truth whose class boundaries are eroded by R pixels (the ISPRS protocol "
+                        "uses a disk of 3) and Boundary IoU at distance R; 1..32 (DESIGN.md 25)")
+    p.add_argument("--boundary_shape", default="disk", choices=list(BOUNDARY_SHAPES),
+                   help="the structuring element of --boundary: a disk (ISPRS) or a square (Chebyshev distance: R erosions by 3x3, as the Boundary IoU "
+                        "reference code)")
     args = p.parse_args(argv)
+    if args.boundary is not None:
+        if args.data != "scenes":
+            p.error("--boundary needs --data scenes: only whole scenes resident on the GPU are evaluated at their boundaries, --data %s is not" % args.data)
+        try:
+            check_boundary(args.boundary, args.boundary_shape)
+        except ValueError as e:
+            p.error("--boundary: %s" % e)
+    elif args.boundary_shape != "disk":
+        p.error("--boundary_shape needs --boundary")
     if args.tta_scales is not None:
         if args.data != "scenes":
             p.error("--tta_scales needs --data scenes: only whole scenes resident on the GPU are evaluated with test-time augmentation, --data %s is not"
@@ -139,17 +155,17 @@ def metric_tuple(tot):
     return miou, acc, kap, class_iou, class_acc, class_f1, float(np.mean(class_f1))
 
 
-def scene_evaluator(model, config, device, multi_scales=False, max_batch=32, tta="none", tta_scales=None):
+def scene_evaluator(model, config, device, multi_scales=False, max_batch=32, tta="none", tta_scales=None, boundary=None, boundary_shape="disk"):
     """The validation bank of a scene tree (<DATA.DATA_PATH>/val_images + /val_labels, uploaded here, labels stored as a `val` Dataset shifts them)
     and the SceneEvaluator over it, from VAL.CROP_SIZE / STRIDE_SIZE / MEAN / STD and TRAIN.IGNORE_INDEX; VAL.SCALE_RATIOS when multi_scales; tta as
-    SceneEvaluator takes it, and tta_scales likewise."""
+    SceneEvaluator takes it, and tta_scales, boundary and boundary_shape likewise."""
     from .src.api.scene import SceneEvaluator
     from .src.datasets import SceneBank
     bank = SceneBank(config.DATA.DATA_PATH, device, label_shift=1 if config.DATA.DATASET == "LoveDA" else 0, sub=("val_images", "val_labels"),
                      shift_on_upload=True)
     return SceneEvaluator(model, bank, config.DATA.NUM_CLASSES, config.VAL.CROP_SIZE, config.VAL.STRIDE_SIZE, list(config.VAL.MEAN), list(config.VAL.STD),
                           ignore_index=config.TRAIN.IGNORE_INDEX, max_batch=max_batch, scales=list(config.VAL.SCALE_RATIOS) if multi_scales else None, tta=tta,
-                          tta_scales=tta_scales)
+                          tta_scales=tta_scales, boundary=boundary, boundary_shape=boundary_shape)
 
 
 def evaluate_scenes(evaluator, rank=0, nranks=1):
@@ -177,6 +193,23 @@ def scene_lines(evaluator, nranks=1):
     return lines
 
 
+def boundary_lines(evaluator, nranks=1):
+    """The four lines of --boundary from evaluator.boundary_totals() (one more all-reduce when nranks > 1): the ISPRS metrics over the pixels
+    outside the label's band with their class F1 scores, and mean Boundary IoU with its class values."""
+    tot = evaluator.boundary_totals()
+    if nranks > 1:
+        torch.distributed.all_reduce(tot)
+    tot = tot.cpu()
+    what = "%s r=%d" % ([k for k, v in BOUNDARY_SHAPES.items() if v == evaluator.boundary_shape][0], evaluator.boundary)
+    miou, acc, _, _, _, cf1, mf1 = metric_tuple(tot[0])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cbiou, mbiou = metrics.mean_iou(tot[1][0], tot[1][1], tot[1][2])
+    return ["[EVAL] Eroded ({}): mIoU: {:.4f}  Acc: {:.4f}  mF1: {:.4f}".format(what, miou, acc, mf1),
+            "[EVAL] Eroded Class F1-score: " + str(np.round(cf1, 4)),
+            "[EVAL] Boundary ({}): mBIoU: {:.4f}".format(what, mbiou),
+            "[EVAL] Boundary Class BIoU: " + str(np.round(cbiou, 4))]
+
+
 def main(argv=None):
     args = parse_args(argv)
     config = update_config(get_config(), args)
@@ -197,7 +230,8 @@ def main(argv=None):
     if args.data == "scenes":           # whole validation scenes resident on the device, evaluated at their own resolution
         if getattr(args, "data_path", None):
             config.DATA.DATA_PATH = args.data_path
-        ev = scene_evaluator(model, config, dev, multi_scales, tta=args.tta, tta_scales=args.tta_scales)
+        ev = scene_evaluator(model, config, dev, multi_scales, tta=args.tta, tta_scales=args.tta_scales, boundary=args.boundary,
+                             boundary_shape=args.boundary_shape)
         images = ev.bank.names
         if rank == 0:
             print("[EVAL] data: %d validation scenes resident on the GPU (%.1f MB)" % (len(ev.bank), ev.bank.nbytes / 1e6), flush=True)
@@ -221,6 +255,8 @@ def main(argv=None):
     if ev is not None:
         cost, miou, acc, kap, ciou, cacc, cf1, mf1 = evaluate_scenes(ev, rank, nranks)
         lines = scene_lines(ev, nranks)
+        if args.boundary is not None:
+            lines += boundary_lines(ev, nranks)
     else:
         cost, miou, acc, kap, ciou, cacc, cf1, mf1 = evaluate(model, images, labels, config, rank, nranks, multi_scales=multi_scales)
         lines = []
